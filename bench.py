@@ -20,6 +20,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -765,6 +766,23 @@ def run_edit(model, cfg, dev, rank, world, dist, batch=4, in_hw=448, out_hw=512,
                         f"{num_timesteps} diffusion steps, batch={batch}"}
 
 
+DUMP_LOGITS_BYTES = 48 << 20       # --dump-outputs stays under 64 MB in all
+
+
+def dump_outputs(d, ids, logits):
+    """The headline decode's outputs as .npy: ids [steps, B] (exact in float64) and the last step's logits (bf16 -> float32, exact).
+    Logits larger than DUMP_LOGITS_BYTES are cut to a fixed, seeded sample of rows, listed in logits_rows.npy."""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "ids.npy"), ids.cpu().numpy().astype(np.float64))
+    lg = logits.float().cpu()
+    rows_max = max(1, DUMP_LOGITS_BYTES // (lg.shape[1] * 4))
+    if lg.shape[0] > rows_max:
+        rows = torch.randperm(lg.shape[0], generator=torch.Generator().manual_seed(0))[:rows_max].sort().values
+        lg = lg[rows]
+        np.save(os.path.join(d, "logits_rows.npy"), rows.numpy().astype(np.float64))
+    np.save(os.path.join(d, "logits.npy"), lg.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-t2i", action="store_true", help="skip the text-to-image leg (configs[2])")
@@ -796,6 +814,10 @@ def main():
                          "[B, vocab] bf16 logits of every step")
     ap.add_argument("--fp8-act", type=int, default=1, help="fp8 leg: 1 = W8A8 (e4m3 activations on the fp8 MFMA) for prefill / flow "
                     "passes, 0 = bf16 activations on the bf16 image of the dequantised weights")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the headline decode computed (rank 0): ids.npy = the token of every timed step "
+                         "[steps, batch] (float64), logits.npy = the last step's logits [rows, vocab] (float32; a fixed sample of rows "
+                         "when the whole array exceeds the size cap, logits_rows.npy names them)")
     ap.add_argument("--cpu-child", default=None, help=argparse.SUPPRESS)      # internal: one pinned arm of the CPU baseline
     args = ap.parse_args()
     if args.cpu_child:
@@ -951,9 +973,11 @@ def main():
             mine = logits_all[rank * B:(rank + 1) * B].float().argmax(-1).cpu()
             assert torch.equal(mine, toks[-1]), "all-gathered logits do not reproduce the generated ids"
 
-        return dict(sess=sess, cache=cache, elapsed=elapsed, gpu_ms=gpu_ms, ctx=ctx, t_prefill=t_prefill, t_prefill_cold=t_cold)
+        return dict(sess=sess, cache=cache, elapsed=elapsed, gpu_ms=gpu_ms, ctx=ctx, t_prefill=t_prefill, t_prefill_cold=t_cold, ids=toks)
 
     leg = decode_leg(model)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, leg["ids"], leg["sess"].logits)
     sess, cache, elapsed, gpu_ms, ctx, t_prefill = (leg[k] for k in ("sess", "cache", "elapsed", "gpu_ms", "ctx", "t_prefill"))
 
     # ---- roofline of the dominant kernel: the weight-streaming skinny GEMM (gemm_skinny_kernel<1,2>:

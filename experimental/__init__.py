@@ -4,5 +4,5 @@ layer engine and the prefill attention on the 32x32x16 matrix instruction.  A pa
 
     python -m experimental.build          ->  experimental/lib/libunimedvl_hip_experimental.so
 
-Nothing in unimedvl_amd imports it; __graft_entry__.build() does not build it (UMV_BUILD_EXPERIMENTAL=1 does); its tests skip when
+Nothing in unimedvl_amd imports it; __graft_entry__.build() builds it alongside the product library; its tests skip when
 the library has not been built."""

@@ -12,24 +12,20 @@ if ROOT not in sys.path:
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
-# GPU tests of experimental/ (kernels that were measured and NOT adopted; nothing in unimedvl_amd/ imports that package).  They cost the
-# round-end GPU suite ~40 % of its time for code that is not the product: opt-in with UMV_TEST_EXPERIMENTAL=1 (+ python -m experimental.build).
+# GPU tests of experimental/ (kernels that were measured and NOT adopted; nothing in unimedvl_amd/ imports that package).  They run with
+# the suite (build() compiles that library too) and carry the `experimental` marker: -m "not experimental" leaves them out.
 EXPERIMENTAL_MODULES = {"test_attn_decode_fused_gpu", "test_attn_prefill32_gpu", "test_decode_engine_gpu", "test_gemm_decode_gpu"}
 
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
-    config.addinivalue_line("markers", "experimental: exercises experimental/ (opt-in: UMV_TEST_EXPERIMENTAL=1)")
+    config.addinivalue_line("markers", "experimental: exercises experimental/ (deselect with -m 'not experimental')")
 
 
 def pytest_collection_modifyitems(config, items):
-    if os.environ.get("UMV_TEST_EXPERIMENTAL", "0") not in ("0", ""):
-        return
-    skip = pytest.mark.skip(reason="experimental/ kernels are opt-in: UMV_TEST_EXPERIMENTAL=1 (and python -m experimental.build)")
     for item in items:
         if item.module.__name__.split(".")[-1] in EXPERIMENTAL_MODULES:
             item.add_marker(pytest.mark.experimental)
-            item.add_marker(skip)
 
 
 def load_golden(name):

@@ -27,14 +27,43 @@ def _ops():
     return ops
 
 
-def _mk(ops, N, K, swiglu, fp8, g, bias=True):
+def _mk(ops, N, K, swiglu, fp8, g, bias=True, keep=None):
     if swiglu:
         gate = (torch.randn(N // 2, K, generator=g) * 0.05).to(BF16).cuda()
         up = (torch.randn(N // 2, K, generator=g) * 0.05).to(BF16).cuda()
+        if keep is not None:
+            keep.update(w=(gate, up), b=None)
         return (ops.PackedLinear.from_gate_up_fp8 if fp8 else ops.PackedLinear.from_gate_up)(gate, up)
     w = (torch.randn(N, K, generator=g) * 0.05).to(BF16).cuda()
     b = torch.randn(N, generator=g).to(BF16).cuda() if bias else None
+    if keep is not None:
+        keep.update(w=w, b=b)
     return (ops.PackedLinear.from_weight_fp8 if fp8 else ops.PackedLinear.from_weight)(w, b)
+
+
+def _reorder_bound(x, src, swiglu, K, out):
+    """Largest |difference| two fp8-weight GEMMs on the same operands may show, per output element, when they sum the K products in
+    different fp32 orders.  Each fp32 sum is within d = K * 2^-24 * sum_k |x_k w'_k| of the exact one a (w' = the dequantised
+    weights, oracle/fp8.py), and each bf16 rounding of the epilogue (gemm_epilogue.h) can land one ulp (<= 2^-7 |value|) apart.
+    Linear: rbf(a + bias), then rbf(. + residual).  SwiGLU: rbf(rbf(silu(g)) * u), g and u possibly rounded to bf16 first; silu is
+    1.1-Lipschitz.  `out` = the larger |output| of the two."""
+    from oracle import fp8
+    xd = x.double().cpu()
+    ulp = 2.0 ** -7
+
+    def acc(w, b=None):
+        wd = fp8.quantize_rows(w.cpu())[2].double()
+        a = xd @ wd.T + (0 if b is None else b.double().cpu())
+        d = 2 * K * 2.0 ** -24 * (xd.abs() @ wd.abs().T)        # the two sums' errors added
+        return a, d
+    if swiglu:
+        (g, dg), (u, du) = acc(src["w"][0]), acc(src["w"][1])
+        dg, du = dg + ulp * (g.abs() + dg), du + ulp * (u.abs() + du)          # optional bf16 rounding of g / u
+        sil = g * torch.sigmoid(g)
+        ds = 1.1 * dg + ulp * (sil.abs() + 1.1 * dg)                            # silu(g) and its rounding
+        return ds * (u.abs() + du) + sil.abs() * du + ulp * out
+    a, d = acc(src["w"], src["b"])
+    return d + ulp * (a.abs() + d) + ulp * out                                  # first rounding, then the residual add's
 
 
 SHAPES = [
@@ -49,10 +78,12 @@ SHAPES = [
 @pytest.mark.parametrize("N,K,swiglu", SHAPES)
 def test_gemm_decode_bit_exact(N, K, swiglu, M, fp8):
     ops = _ops()
-    if fp8 and K % 512 != 0:
-        pytest.skip("umv_gemm_fp8w and the decode image agree bit for bit only when the 8 K slices coincide (K % 512 == 0)")
+    # umv_gemm_fp8w and the decode image agree bit for bit only when the 8 K slices coincide (K % 512 == 0); otherwise the same
+    # products are summed in another order, and the outputs must agree within what that reordering can change (_reorder_bound)
+    sliced = fp8 and K % 512 != 0
     g = torch.Generator().manual_seed(N + K + M)
-    lin = _mk(ops, N, K, swiglu, fp8, g)
+    src = {}
+    lin = _mk(ops, N, K, swiglu, fp8, g, keep=src)
     dl = _xops().DecodeLinear(lin)
     L = dl.layout
     rows = N // 2 if swiglu else N
@@ -61,7 +92,13 @@ def test_gemm_decode_bit_exact(N, K, swiglu, M, fp8):
     res = None if swiglu else torch.randn(M, N, generator=g).to(BF16).cuda()
     ref = ops.gemm(x, lin, residual=res)
     got = _xops().gemm_decode(x, dl, residual=res)
-    assert torch.equal(got, ref)
+    if not sliced:
+        assert torch.equal(got, ref)
+        return
+    assert torch.isfinite(got.float()).all()
+    tol = _reorder_bound(x, src, swiglu, K, torch.maximum(got.double().abs(), ref.double().abs()).cpu())
+    diff = (got.double() - ref.double()).abs().cpu()
+    assert (diff <= tol).all(), f"max |diff| {diff.max():.4g}, worst diff / bound {(diff / tol.clamp_min(1e-30)).max():.3f}"
 
 
 def test_gemm_decode_layouts_for_model_shapes():

@@ -160,7 +160,7 @@ def test_c_abi_exports_every_declared_symbol():
     assert exp_declared == set(xlib.declared_symbols())
     for name in sorted(exp_declared):
         assert not hasattr(lib, name), f"{name} is experimental but exported by the product library"
-    if xlib.available():      # built only on request (python -m experimental.build)
+    if xlib.available():      # built by __graft_entry__.build() / python -m experimental.build
         exp = ctypes.CDLL(xlib.EXP_LIB_PATH)
         for name in sorted(exp_declared):
             assert hasattr(exp, name), f"{name} declared in the experimental header but not exported"
