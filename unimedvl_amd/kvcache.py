@@ -203,8 +203,8 @@ class PagedCache:
     """Block-table KV cache: every layer owns ONE pool of 256-token pages, K [page][kvh][256][hd] and
     V^T [page][kvh][hd][256], that all segments draw from; a segment's context is the list of its pages (`table` on the device).
     A context grows by taking pages - nothing is copied or re-allocated, the pool is shared by short and long requests - and a finished
-    request returns its pages (`release`).  snapshot() shares the pages of the prefix (reference counts; the partially filled last page is
-    copied when the snapshot or the original appends to it).
+    request returns its pages (`release`).  snapshot() shares the pages of the prefix (reference counts); a page either side is about to
+    write while the other still holds it is replaced by a private one first (copy-on-write in ensure_tokens).
 
     Same surface as NaiveCache for the paths that take it: LanguageModel.forward_inference (prefill: umv_qkv_post writes through the
     table, the attention of a paged call runs on the per-wave kernel), decode.DecodeSession (the captured step reads the table from
@@ -256,7 +256,10 @@ class PagedCache:
         self.ensure_tokens([need_cap] * nseg, nkv, hd, device)
 
     def ensure_tokens(self, need, nkv, hd, device):
-        """Pages for need[s] tokens in segment s (committed + the call's new tokens); only segments that grow take pages."""
+        """Pages for need[s] tokens in segment s (committed + the call's new tokens); only segments that grow take pages.  Every page
+        this call makes writable - page indices lens[s] // 256 .. ceil(need[s] / 256) - 1 - is private to this cache afterwards: one
+        still shared with a snapshot (refs > 1) is replaced by a fresh page (copy-on-write; only the partially filled page at lens[s]
+        carries data over, the others hold nothing committed yet).  All or nothing: a refused call takes and changes no page."""
         nseg = len(need)
         if self.pool is None:
             self.pool = _PagePool(self._num_layers, self.pool_pages, nkv, hd, device, nseg, self.max_pages)
@@ -264,29 +267,36 @@ class PagedCache:
             self.nkv, self.hd, self.device = nkv, hd, device
         if nseg != len(self.lens):
             raise ValueError(f"cache holds {len(self.lens)} samples, call has {nseg}")
-        changed = []
+        P = ops.KV_PAGE
         want = 0                              # all-or-nothing: check the reach and the pool before taking a single page
         for s, n in enumerate(need):
             if n > self.cap:
                 raise ValueError(f"segment {s}: {n} tokens exceed the page table's reach of {self.cap} (max_context)")
             pages = self._pages(s)
-            want += max(0, (n + ops.KV_PAGE - 1) // ops.KV_PAGE - len(pages))
-            want += int(n > self.lens[s] and bool(pages) and self.lens[s] % ops.KV_PAGE != 0 and self.pool.refs[pages[-1]] > 1)
+            want += max(0, (n + P - 1) // P - len(pages))
+            if n > self.lens[s]:
+                want += sum(self.pool.refs[p] > 1 for p in pages[self.lens[s] // P:(n + P - 1) // P])
         if want > len(self.pool.free):
             raise RuntimeError(f"paged KV pool exhausted: {want} pages wanted, {len(self.pool.free)} of {self.pool.npages - 1} free "
-                               f"({ops.KV_PAGE} tokens each): raise pool_pages")
+                               f"({P} tokens each): raise pool_pages")
+        changed = []
         for s, n in enumerate(need):
             pages = self._pages(s)
-            # copy-on-write: the last, partially filled page is shared with a snapshot and this call appends to it
-            if n > self.lens[s] and pages and self.lens[s] % ops.KV_PAGE and self.pool.refs[pages[-1]] > 1:
-                old, new = pages[-1], self.pool.alloc()
-                for sl in self.pool.slabs:
-                    sl.k[new].copy_(sl.k[old])
-                    sl.vt[new].copy_(sl.vt[old])
-                self.pool.unref(old)
-                pages[-1] = new
-                changed.append((s, len(pages) - 1, new))
-            while len(pages) * ops.KV_PAGE < n:
+            if n > self.lens[s]:
+                # copy-on-write: a page this call writes is shared with a snapshot (or the snapshot's source)
+                for i in range(self.lens[s] // P, min(len(pages), (n + P - 1) // P)):
+                    old = pages[i]
+                    if self.pool.refs[old] == 1:
+                        continue
+                    new = self.pool.alloc()
+                    if i * P < self.lens[s]:         # the partially filled page: its committed head is this cache's context
+                        for sl in self.pool.slabs:
+                            sl.k[new].copy_(sl.k[old])
+                            sl.vt[new].copy_(sl.vt[old])
+                    self.pool.unref(old)
+                    pages[i] = new
+                    changed.append((s, i, new))
+            while len(pages) * P < n:
                 pages.append(self.pool.alloc())
                 changed.append((s, len(pages) - 1, pages[-1]))
         if changed:
@@ -299,27 +309,34 @@ class PagedCache:
         self.ensure_tokens([0] * nseg, nkv, hd, device)
 
     def release(self, seg):
-        """Return segment `seg`'s pages to the pool (its request is finished) and reset its length."""
+        """Return segment `seg`'s pages to the pool (its request is finished), reset its length and zero its row of the device table:
+        a stray write through the released row lands in page 0, which is never handed out, not in a page another request owns now."""
         for p in self._pages(seg):
             self.pool.unref(p)
         self._pages(seg).clear()
+        self.pool.table[self._seg0 + seg].zero_()
         self.lens[seg] = 0
 
     def pages_in_use(self):
         return self.pool.npages - 1 - len(self.pool.free)
 
     def snapshot(self):
-        """Logical copy sharing every page of the current contexts (reference counted); appends by either side to the shared, partially
-        filled last page copy that one page first (ensure_tokens).  The snapshot has a table of its own over the same pools."""
+        """Logical copy sharing the pages of the current contexts (reference counted): the first ceil(lens[s] / 256) pages of each
+        segment.  Pages past that (a decode horizon taken before a rewind of `lens`) stay with this cache alone.  Appends by either side
+        are isolated: ensure_tokens replaces every shared page the append will write (copy-on-write).  The snapshot has a table of its
+        own over the same pools and allocator; release() its segments to give its pages back."""
         c = PagedCache(self._num_layers, self.pool_pages, self.max_pages * ops.KV_PAGE)
         c.lens = list(self.lens)
         c.nkv, c.hd, c.device = self.nkv, self.hd, self.device
         if self.pool is not None:
             src = self.pool
             c.pool = _PagePool.__new__(_PagePool)
+            c.pool.host_table = [list(self._pages(s)[:(n + ops.KV_PAGE - 1) // ops.KV_PAGE]) for s, n in enumerate(self.lens)]
             c.pool.table = torch.zeros_like(src.table[self._seg0:self._seg0 + len(self.lens)])
-            c.pool.table.copy_(src.table[self._seg0:self._seg0 + len(self.lens)])
-            c.pool.host_table = [list(self._pages(s)) for s in range(len(self.lens))]
+            rows = torch.zeros(c.pool.table.shape, dtype=torch.int32)
+            for s, pages in enumerate(c.pool.host_table):
+                rows[s, :len(pages)] = torch.tensor(pages, dtype=torch.int32)
+            c.pool.table.copy_(rows)
             c.pool.free, c.pool.refs = src.free, src.refs            # ONE allocator: shared lists
             c.pool.npages, c.pool.nkv, c.pool.hd, c.pool.device = src.npages, src.nkv, src.hd, src.device
             c.pool.slabs = []
