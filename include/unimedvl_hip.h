@@ -124,6 +124,29 @@ int umv_quantize_pack_weight_fp8(const uint16_t* w, const uint16_t* w_up, uint8_
 /* M <= 64 only; a->wp = the e4m3 image, a->w_scale = its scales; norm_w / tile_rows unsupported */
 int umv_gemm_fp8w(const umv_gemm_args* a, umv_stream_t stream);
 
+/* ------------------------------------------------------------------ MXFP4 weights (llm_weight_dtype = "fp4"; no reference
+ * counterpart).  Weight-only e2m1 with one E8M0 power-of-two scale per BLOCK of 32 consecutive k of a row (K % 32 == 0):
+ *   s = 2^e, e = the smallest integer with 6 * 2^e >= max|W[block]| (no clipping; the OCP MX rule, which saturates, is not used),
+ *   clamped to [-127, 127], e = 0 for an all-zero block, stored as the byte e + 127;
+ *   q = rne_e2m1(W / s) (ties to the even code), the SIGN KEPT: a negative value that rounds to zero is code 8 (-0).
+ * W' = q * s is exact in bf16, so
+ *   umv_gemm_mxfp4w(x, img)  ==  umv_gemm_bf16(x, pack(W'))   bit for bit   (K % 512 == 0, no split-K, wherever umv_gemm_bf16
+ *                                                                         takes its weight-streaming kernel: not SwiGLU at 33..64
+ *                                                                         rows with K >= 1024, which it runs on a tiled kernel)
+ * Image (umv_packed_weight_mxfp4_bytes; NP = ceil(ceil(N/16) / 2) pairs of 16-row tiles, KT8 = ceil(K/64)):
+ *   codes  C[p][k/64][lane = ((k%32)/8)*16 + n%16][16 B] at byte 0: bytes 0..3 tile 2p k%64 < 32, 4..7 tile 2p k%64 >= 32,
+ *          8..11 tile 2p+1 k%64 < 32, 12..15 tile 2p+1 k%64 >= 32; element k%8 is nibble k%8 of its 4 bytes, low nibble first;
+ *   scales S[p][k/64][n%16][4 B] at byte NP*KT8*1024, in the same (tile, k half) order as the code words.
+ * Padding is code 0 with scale byte 127.  With w_up != NULL, `w`/`w_up` are gate_proj / up_proj [rows=I, K] and the image
+ * interleaves their 16-row tiles (UMV_EPI_SWIGLU), so pair t is (gate tile t, up tile t).  deq / deq_up (optional) receive W'
+ * row-major.  All buffers 16-byte aligned, K <= 65536; weights finite with |W| < 1.75 * 2^127 (from there W' leaves bf16). */
+size_t umv_packed_weight_mxfp4_bytes(int N, int K);
+int umv_quantize_pack_weight_mxfp4(const uint16_t* w, const uint16_t* w_up, uint8_t* packed4, uint16_t* deq, uint16_t* deq_up,
+                                   int rows, int K, umv_stream_t stream);
+/* M <= 64 only; a->wp = the MXFP4 image, a->w_scale = NULL; BIAS, RESIDUAL, SWIGLU, OUT_F32, row_idx and split-K partials as
+ * umv_gemm_bf16; norm_w, th-row tiles and argmax_partial unsupported */
+int umv_gemm_mxfp4w(const umv_gemm_args* a, umv_stream_t stream);
+
 /* W8A8 on the fp8 matrix instruction (v_mfma_scale_f32_16x16x128_f8f6f4) for the MFMA-bound GEMMs of the fp8 mode
  * (M > 64: prefill, flow passes).  Activations are quantised per ROW the way weights are per channel:
  *   sx[m] = smallest 2^e with 448 * 2^e >= max_k |x[m,k]|,  xq = rne_e4m3(x / sx)   (umv_quantize_act_fp8; rows may be

@@ -7,7 +7,7 @@ set -e
 cd "$(dirname "$0")/.."
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 WHAT=${1:-both}
-SRCS="host_error elementwise pack gemm gemm_w4 gemm_fp8mfma attention attention_prefill vision"
+SRCS="host_error elementwise pack gemm gemm_w4 gemm_fp8mfma gemm_mxfp4 attention attention_prefill vision"
 build_and_run() {
   local name=$1 flags=$2 D=unimedvl_amd/lib/san_$1
   mkdir -p $D

@@ -20,7 +20,8 @@ class UniMedVLConfig:
     rms_eps: float = 1e-6
     max_position: int = 32768
     # "bf16" (the reference's precision) or "fp8": weight-only e4m3 with power-of-two channel scales for the LLM
-    # linear layers and lm_head (BASELINE.json configs[4]; include/unimedvl_hip.h umv_quantize_pack_weight_fp8)
+    # linear layers and lm_head (BASELINE.json configs[4]; include/unimedvl_hip.h umv_quantize_pack_weight_fp8), or "fp4": MXFP4
+    # (e2m1, one power-of-two scale per 32 k; umv_quantize_pack_weight_mxfp4) for the linears of both experts, lm_head in e4m3
     llm_weight_dtype: str = "bf16"
     # "fp8" (needs llm_weight_dtype == "fp8"): W8A8 - every LLM forward that is not a one-token decode step rounds the
     # activations of its linear layers per row through e4m3 and runs them on the fp8 matrix instruction

@@ -73,7 +73,7 @@ class ImageGenerator:
             cfg = UniMedVLConfig.from_checkpoint_dir(model_path, max_latent_size=64, vit_max_num_patch_per_side=70)
             device = f"cuda:{self.config['target_gpu_device']}"
             # optional extras over the reference's config keys: "checkpoint_weight_path" overlays a fine-tuned checkpoint on the
-            # base one (eval/vlm/utils.py:71-98); "llm_weight_dtype": "fp8" streams e4m3 LLM weights at decode
+            # base one (eval/vlm/utils.py:71-98); "llm_weight_dtype": "fp8" / "fp4" streams e4m3 / MXFP4 LLM weights at decode
             cfg.llm_weight_dtype = self.config.get("llm_weight_dtype", "bf16")
             get = checkpoint_getter(model_path, all_shapes(cfg), self.config.get("checkpoint_weight_path"),
                                     self.config["use_model_checkpoint"])

@@ -61,9 +61,9 @@ def _req(t, dtype, name):
 class PackedLinear:
     """nn.Linear weight [N,K] (+bias) re-tiled for the MFMA GEMM kernels."""
 
-    __slots__ = ("wp", "bias", "N", "K", "swiglu", "th", "w8", "scale", "w8m")
+    __slots__ = ("wp", "bias", "N", "K", "swiglu", "th", "w8", "scale", "w8m", "w4")
 
-    def __init__(self, wp, bias, N, K, swiglu=False, th=16, w8=None, scale=None):
+    def __init__(self, wp, bias, N, K, swiglu=False, th=16, w8=None, scale=None, w4=None):
         self.wp, self.bias, self.N, self.K, self.swiglu, self.th = wp, bias, N, K, swiglu, th
         # fp8 weights (BASELINE.json configs[4]): w8 = e4m3 image streamed by the decode GEMM (M <= 64), scale = its
         # power-of-two channel scales; wp is then the bf16 image of the SAME dequantised weights for M > 64
@@ -71,6 +71,9 @@ class PackedLinear:
         # optional: the e4m3 image re-tiled for the fp8 matrix instruction; when present, GEMMs with M > 64 rows quantise
         # their activations per row and run W8A8 (enable_fp8_mfma)
         self.w8m = None
+        # MXFP4 weights (llm_weight_dtype="fp4"): w4 = the e2m1 + block-scale image streamed by the decode GEMM (M <= 64); wp is
+        # then the bf16 image of the SAME dequantised weights for M > 64
+        self.w4 = w4
 
     def enable_fp8_mfma(self, keep_bf16=False):
         """Build the fp8-MFMA image from the e4m3 image; the bf16 image of the dequantised weights is dropped unless asked."""
@@ -118,10 +121,38 @@ class PackedLinear:
         lin.w8, lin.scale = w8, scale
         return lin
 
+    @staticmethod
+    def from_weight_mxfp4(w, bias=None):
+        """Quantise an nn.Linear weight to MXFP4 (e2m1, one power-of-two scale per 32 k); see include/unimedvl_hip.h."""
+        lib = _lib.load()
+        w = _req(w.contiguous(), BF16, "weight")
+        N, K = w.shape
+        w4 = torch.empty(lib.umv_packed_weight_mxfp4_bytes(N, K), dtype=torch.uint8, device=w.device)
+        deq = torch.empty_like(w)
+        check(lib.umv_quantize_pack_weight_mxfp4(_p(w), None, _p(w4), _p(deq), None, N, K, _stream()), "umv_quantize_pack_weight_mxfp4")
+        lin = PackedLinear.from_weight(deq, bias)
+        lin.w4 = w4
+        return lin
+
+    @staticmethod
+    def from_gate_up_mxfp4(gate, up):
+        lib = _lib.load()
+        gate = _req(gate.contiguous(), BF16, "gate")
+        up = _req(up.contiguous(), BF16, "up")
+        I, K = gate.shape
+        assert I % 16 == 0, "intermediate size must be a multiple of 16"
+        w4 = torch.empty(lib.umv_packed_weight_mxfp4_bytes(2 * I, K), dtype=torch.uint8, device=gate.device)
+        dg, du = torch.empty_like(gate), torch.empty_like(up)
+        check(lib.umv_quantize_pack_weight_mxfp4(_p(gate), _p(up), _p(w4), _p(dg), _p(du), I, K, _stream()),
+              "umv_quantize_pack_weight_mxfp4")
+        lin = PackedLinear.from_gate_up(dg, du)
+        lin.w4 = w4
+        return lin
+
     def for_decode(self, n_cus=256):
         """A second, decode-only image with th-row tiles such that the number of tiles is a multiple of the
         CU count (exact partition of the weight stream over the chip); returns self when 16 is already fine."""
-        if self.swiglu or self.th != 16 or self.w8 is not None:
+        if self.swiglu or self.th != 16 or self.w8 is not None or self.w4 is not None:
             return self
         best = None
         for th in range(15, 7, -1):
@@ -205,7 +236,8 @@ def gemm(x, lin, out=None, *, M=None, residual=None, act=None, row_idx=None, out
     # which kernel family takes the call (mirrors the branches below exactly, so a dropped image raises instead of crashing)
     use_a8 = act8 and M > 64 and norm_w is None and not out_f32       # fp8 matrix instruction, e4m3 activations
     use_w8 = lin.w8 is not None and M <= 64 and norm_w is None        # weight-streaming kernel on the e4m3 image
-    if lin.wp is None and not use_a8 and not use_w8:
+    use_w4 = lin.w4 is not None and M <= 64 and norm_w is None        # weight-streaming kernel on the MXFP4 image
+    if lin.wp is None and not use_a8 and not use_w8 and not use_w4:
         raise _lib.UmvError(f"this linear only has fp8 images (the bf16 image was dropped by enable_fp8_mfma): M={M} rows with "
                             f"act8={act8}, out_f32={out_f32}, norm_w={'set' if norm_w is not None else 'None'} need the bf16 kernel - "
                             "build the weights with enable_fp8_mfma(keep_bf16=True)")
@@ -223,6 +255,17 @@ def gemm(x, lin, out=None, *, M=None, residual=None, act=None, row_idx=None, out
             ldr=residual.stride(0) if residual is not None else 0, out=out.data_ptr(), ldo=out.stride(0),
             row_idx=row_idx.data_ptr() if row_idx is not None else None, M=M, N=lin.N, K=lin.K, epilogue=flags)
         check(lib.umv_gemm_fp8a8w(C.byref(a8), _stream()), "umv_gemm_fp8a8w")
+        return out
+    if use_w4:
+        a = GemmArgs(
+            x=x.data_ptr(), ldx=x.stride(0), wp=lin.w4.data_ptr(),
+            bias=lin.bias.data_ptr() if (flags & EPI_BIAS) else None,
+            residual=residual.data_ptr() if residual is not None else None,
+            ldr=residual.stride(0) if residual is not None else 0,
+            out=out.data_ptr(), ldo=out.stride(0),
+            row_idx=row_idx.data_ptr() if row_idx is not None else None,
+            M=M, N=lin.N, K=lin.K, epilogue=flags, norm_w=None, norm_eps=norm_eps, tile_rows=0, argmax_partial=amax)
+        check(lib.umv_gemm_mxfp4w(C.byref(a), _stream()), "umv_gemm_mxfp4w")
         return out
     if use_w8:
         a = GemmArgs(
@@ -435,6 +478,9 @@ def gemm_splitk(x, lin, partials, k_splits, *, M=None):
     if lin.w8 is not None:   # e4m3 image: same split, same consumers
         a.wp, a.w_scale = lin.w8.data_ptr(), lin.scale.data_ptr()
         check(lib.umv_gemm_fp8w(C.byref(a), _stream()), "umv_gemm_fp8w")
+    elif lin.w4 is not None and M <= 64:    # MXFP4 image; above 64 rows the bf16 image of W' (the tiled split-K kernel)
+        a.wp = lin.w4.data_ptr()
+        check(lib.umv_gemm_mxfp4w(C.byref(a), _stream()), "umv_gemm_mxfp4w")
     else:
         check(lib.umv_gemm_bf16(C.byref(a), _stream()), "umv_gemm_bf16")
     return partials

@@ -23,19 +23,21 @@ import uuid
 
 import torch
 
-PACK_LAYOUT_VERSION = "umv-pack-1"     # P[n/16][k/32][lane][8] bf16; P8[n/16][k/64][lane][16 B] e4m3 + f32 pow2 scales; P8M fp8-MFMA image
-_LIN_FIELDS = ("wp", "bias", "w8", "scale", "w8m")
+PACK_LAYOUT_VERSION = "umv-pack-1"     # P[n/16][k/32][lane][8] bf16; P8[n/16][k/64][lane][16 B] e4m3 + f32 pow2 scales; P8M fp8-MFMA image;
+                                        # MXFP4 codes + E8M0 block scales in one image (csrc/gemm_mxfp4.hip)
+_LIN_FIELDS = ("wp", "bias", "w8", "scale", "w8m", "w4")
 
 
 def kernel_stamp():
-    """sha256 of PACK_LAYOUT_VERSION + the sources that decide the bytes of a packed image: csrc/pack.hip and the headers it includes
-    (common.h: the bf16 rounding helpers; gemm_internal.h: cvt_fp8x16 behind the deq / w8 images; the public header).  None when a
+    """sha256 of PACK_LAYOUT_VERSION + the sources that decide the bytes of a packed image: csrc/pack.hip, csrc/gemm_mxfp4.hip (the MXFP4
+    packer) and the headers they include (common.h: the bf16 rounding helpers; gemm_internal.h: cvt_fp8x16 behind the deq / w8 images;
+    the public header).  None when a
     source is not there - a cache whose maker cannot be identified is never trusted (and two unknowns never compare equal)"""
     import hashlib
     here = os.path.dirname(os.path.abspath(__file__))
     h = hashlib.sha256(PACK_LAYOUT_VERSION.encode())
     try:
-        for rel in ("csrc/pack.hip", "csrc/common.h", "csrc/gemm_internal.h", "../include/unimedvl_hip.h"):
+        for rel in ("csrc/pack.hip", "csrc/gemm_mxfp4.hip", "csrc/common.h", "csrc/gemm_internal.h", "../include/unimedvl_hip.h"):
             with open(os.path.join(here, rel), "rb") as f:
                 h.update(f.read())
     except OSError:
@@ -128,6 +130,8 @@ class PackStore:
                 raise _lib.UmvError(f"{self.path}: {key}: packed image of {parts['wp'].numel()} elements, {m['N']} x {m['K']} needs {want}")
         if parts["bias"] is not None and parts["bias"].numel() != m["N"]:
             raise _lib.UmvError(f"{self.path}: {key}: bias of {parts['bias'].numel()} for N = {m['N']}")
+        if parts["w4"] is not None and parts["w4"].numel() != _lib.load().umv_packed_weight_mxfp4_bytes(m["N"], m["K"]):
+            raise _lib.UmvError(f"{self.path}: {key}: MXFP4 image of {parts['w4'].numel()} bytes for {m['N']} x {m['K']}")
 
     # ------------------------------------------------------------------ linears
     def linear(self, key, build):
@@ -140,7 +144,7 @@ class PackStore:
             self.t_read += time.time() - t0
             self._check_linear(key, m, parts)
             lin = ops.PackedLinear(parts["wp"], parts["bias"], m["N"], m["K"], swiglu=m["swiglu"], th=m["th"], w8=parts["w8"],
-                                   scale=parts["scale"])
+                                   scale=parts["scale"], w4=parts["w4"])
             lin.w8m = parts["w8m"]
             self.hits += 1
             return lin

@@ -44,12 +44,23 @@ def _tensor(get, device, name):
     return _store(get).tensor(name, lambda: _dev(get(name), device))
 
 
-def _linear(get, device, wname, bname=None, fp8=False):
+def _linear(get, device, wname, bname=None, fp8=False, fp4=False):
     def build():
         w = _dev(get(wname), device)
         b = _dev(get(bname), device) if bname else None
+        if fp4:
+            return ops.PackedLinear.from_weight_mxfp4(w, b)
         return ops.PackedLinear.from_weight_fp8(w, b) if fp8 else ops.PackedLinear.from_weight(w, b)
     return _store(get).linear(wname, build)
+
+
+def check_llm_dtypes(cfg: UniMedVLConfig):
+    """ValueError unless (llm_weight_dtype, llm_act_dtype) is a supported pair: bf16 / fp8 / fp4 weights, bf16 activations, or
+    fp8 activations with fp8 weights (W8A8); W4A8 is not supported"""
+    if cfg.llm_weight_dtype not in ("bf16", "fp8", "fp4"):
+        raise ValueError(f"llm_weight_dtype must be 'bf16', 'fp8' or 'fp4', got {cfg.llm_weight_dtype!r}")
+    if cfg.llm_act_dtype not in ("bf16", "fp8") or (cfg.llm_act_dtype == "fp8" and cfg.llm_weight_dtype != "fp8"):
+        raise ValueError("llm_act_dtype must be 'bf16', or 'fp8' together with llm_weight_dtype='fp8'")
 
 
 class LLMWeights:
@@ -57,17 +68,16 @@ class LLMWeights:
 
     def __init__(self, cfg: UniMedVLConfig, get, device, load_gen=True):
         p = "language_model.model."
-        if cfg.llm_weight_dtype not in ("bf16", "fp8"):
-            raise ValueError(f"llm_weight_dtype must be 'bf16' or 'fp8', got {cfg.llm_weight_dtype!r}")
+        check_llm_dtypes(cfg)
         fp8 = self.fp8 = cfg.llm_weight_dtype == "fp8"
-        if cfg.llm_act_dtype not in ("bf16", "fp8") or (cfg.llm_act_dtype == "fp8" and not fp8):
-            raise ValueError("llm_act_dtype must be 'bf16', or 'fp8' together with llm_weight_dtype='fp8'")
+        # "fp4": MXFP4 for the seven linears of both experts; lm_head stays e4m3 (fused argmax / sampling, 8 bits on the output)
+        fp4 = self.fp4 = cfg.llm_weight_dtype == "fp4"
         self.act8 = cfg.llm_act_dtype == "fp8"
         self.embed = _tensor(get, device, p + "embed_tokens.weight")
         self.und, self.gen = [], []
         for l in range(cfg.layers):
-            self.und.append(self._layer(get, device, p + f"layers.{l}.", "", fp8))
-            self.gen.append(self._layer(get, device, p + f"layers.{l}.", "_moe_gen", fp8) if load_gen else None)
+            self.und.append(self._layer(get, device, p + f"layers.{l}.", "", fp8, fp4))
+            self.gen.append(self._layer(get, device, p + f"layers.{l}.", "_moe_gen", fp8, fp4) if load_gen else None)
             if self.act8:   # W8A8: the fp8-MFMA image replaces the bf16 image of the dequantised weights
                 for lw in (self.und[-1], self.gen[-1]):
                     if lw is not None:
@@ -75,7 +85,7 @@ class LLMWeights:
                             lin.enable_fp8_mfma()
         self.norm = _tensor(get, device, p + "norm.weight")
         self.norm_gen = _tensor(get, device, p + "norm_moe_gen.weight") if load_gen else None
-        self.lm_head = _linear(get, device, "language_model.lm_head.weight", fp8=fp8)
+        self.lm_head = _linear(get, device, "language_model.lm_head.weight", fp8=fp8 or fp4)
         # rotary tables exactly as Qwen2RotaryEmbedding returns them (modeling_qwen2.py:164-184):
         # fp32 outer product, cos/sin, cast to bf16; built on the CPU so the bits match torch's.
         hd = cfg.head_dim
@@ -87,7 +97,7 @@ class LLMWeights:
         self.sin = emb.sin().to(BF16).to(device)
 
     @staticmethod
-    def _layer(get, device, p, suf, fp8=False):
+    def _layer(get, device, p, suf, fp8=False, fp4=False):
         lw = LayerWeights()
         a = p + "self_attn."
         st = _store(get)
@@ -95,16 +105,20 @@ class LLMWeights:
         def build_qkv():
             w = torch.cat([_dev(get(a + f"{n}_proj{suf}.weight"), device) for n in "qkv"], 0)
             b = torch.cat([_dev(get(a + f"{n}_proj{suf}.bias"), device) for n in "qkv"], 0)
+            if fp4:
+                return ops.PackedLinear.from_weight_mxfp4(w, b)
             return ops.PackedLinear.from_weight_fp8(w, b) if fp8 else ops.PackedLinear.from_weight(w, b)
 
         def build_gate_up():
             g = _dev(get(p + f"mlp{suf}.gate_proj.weight"), device)
             u = _dev(get(p + f"mlp{suf}.up_proj.weight"), device)
+            if fp4:
+                return ops.PackedLinear.from_gate_up_mxfp4(g, u)
             return ops.PackedLinear.from_gate_up_fp8(g, u) if fp8 else ops.PackedLinear.from_gate_up(g, u)
         lw.qkv = st.linear(a + f"qkv_proj{suf}", build_qkv)
-        lw.o = _linear(get, device, a + f"o_proj{suf}.weight", fp8=fp8)
+        lw.o = _linear(get, device, a + f"o_proj{suf}.weight", fp8=fp8, fp4=fp4)
         lw.gate_up = st.linear(p + f"mlp{suf}.gate_up_proj", build_gate_up)
-        lw.down = _linear(get, device, p + f"mlp{suf}.down_proj.weight", fp8=fp8)
+        lw.down = _linear(get, device, p + f"mlp{suf}.down_proj.weight", fp8=fp8, fp4=fp4)
         lw.in_norm = _tensor(get, device, p + f"input_layernorm{suf}.weight")
         lw.post_norm = _tensor(get, device, p + f"post_attention_layernorm{suf}.weight")
         lw.q_norm = _tensor(get, device, a + f"q_norm{suf}.weight")
@@ -112,9 +126,10 @@ class LLMWeights:
         return lw
 
     def decode_weight_bytes(self):
-        """bytes one decode step streams: the e4m3 images when llm_weight_dtype == "fp8", else the bf16 ones"""
-        nb = (lambda lin: lin.w8.numel()) if self.fp8 else (lambda lin: lin.nbytes())
-        n = nb(self.lm_head)
+        """bytes one decode step streams: the e4m3 images when llm_weight_dtype == "fp8", the MXFP4 images (block scales included)
+        and the e4m3 lm_head when "fp4", else the bf16 ones"""
+        nb = (lambda lin: lin.w8.numel()) if self.fp8 else (lambda lin: lin.w4.numel()) if self.fp4 else (lambda lin: lin.nbytes())
+        n = self.lm_head.w8.numel() if self.fp4 else nb(self.lm_head)
         for lw in self.und:
             n += nb(lw.qkv) + nb(lw.o) + nb(lw.gate_up) + nb(lw.down)
         return n
