@@ -12,6 +12,12 @@ a real ViT encode + LLM prefill of 8 synthetic 448x448 images and 32-token quest
 full assumed 14B dims (no checkpoint, no network).  Data-parallel: every rank owns its own
 8 samples and a full weight replica; the only collective is one RCCL all-gather of the
 generated token ids.  One JSON line on rank 0 (contract in the task statement).
+
+A plain run does only what the headline figure needs: set up, warm up, time the steps, write
+--dump-outputs, print the line (with the step-level roofline, which is arithmetic on the timed
+step).  --full adds everything else after the headline decode: the dominant / secondary kernel
+rooflines, the ViT, sampled-decode, configs[3], text-to-image, edit, fp8, mixed, VAE, KV-growth
+and load-path legs and the CPU baseline; the --no-<leg> switches leave legs out of a --full run.
 """
 import argparse
 import json
@@ -785,6 +791,9 @@ def dump_outputs(d, ids, logits):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline decode, run every other leg (kernel rooflines, ViT, sampled decode, configs[3], T2I, edit, "
+                         "fp8, mixed, VAE, KV growth, load path, CPU baseline); without it only the headline figure is measured")
     ap.add_argument("--no-t2i", action="store_true", help="skip the text-to-image leg (configs[2])")
     ap.add_argument("--t2i-steps", type=int, default=50)
     ap.add_argument("--no-sampled", action="store_true", help="skip the sampled-decode leg (do_sample=True, temperature 1.0)")
@@ -799,7 +808,7 @@ def main():
     ap.add_argument("--no-vit", action="store_true", help="skip the ViT encode leg (profiling runs of the decode step)")
     ap.add_argument("--no-vae", action="store_true", help="skip the AutoEncoder leg")
     ap.add_argument("--strict-profile", action="store_true",
-                    help="fail instead of reporting traffic: null when profiles/roofline_profile_latest.json was not measured on this library")
+                    help="--full: fail instead of reporting traffic: null when profiles/roofline_profile_latest.json was not measured on this library")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--weights", default="bf16", choices=["bf16", "fp8"],
                     help="fp8: the whole run on e4m3 LLM weights (BASELINE.json configs[4]); the headline value is the bf16 run")
@@ -894,6 +903,8 @@ def main():
         prompt_len = 128 if args.config == "full" else 12
     t_load = time.time()
     want_t2i = not args.no_t2i
+    # the gen expert is built even when no leg uses it: random_getter draws every tensor from ONE seeded stream in load order, and
+    # LLMWeights interleaves the und and gen layers, so leaving it out would change the headline decode's weights
     model = Bagel(cfg, random_getter(cfg, dev, seed=1234), device=dev, visual_gen=want_t2i, visual_und=True)
     torch.cuda.synchronize()
     t_load = time.time() - t_load
@@ -979,10 +990,51 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, leg["ids"], leg["sess"].logits)
     sess, cache, elapsed, gpu_ms, ctx, t_prefill = (leg[k] for k in ("sess", "cache", "elapsed", "gpu_ms", "ctx", "t_prefill"))
+    lw = model.language_model.w
+    ms_per_step = elapsed * 1e3 / args.steps
+    value = world * B * args.steps / elapsed
+    # whole-step algorithmic bytes (weights + KV read/write + logits), for the step-level fraction
+    kv_tok = cfg.layers * 2 * cfg.kv_heads * cfg.head_dim * 2
+    step_bytes = lw.decode_weight_bytes() + B * (ctx + args.warmup + args.steps / 2) * kv_tok + B * kv_tok + B * cfg.vocab * 2
+    step_roofline = {
+        "step_algorithmic_GBps": round(step_bytes / (ms_per_step * 1e-3) / 1e9, 1),
+        "step_frac_of_peak": round(step_bytes / (ms_per_step * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
+        # the other roofline, for completeness (BASELINE.json pairs decode with MFMA): at B rows per weight byte
+        # the MFMA fraction is capped near B / 310 by the HBM roofline
+        "step_mfma_frac_of_2500": round(B * (2 * lw.decode_weight_bytes() / (1 if lw.fp8 else 2)
+                                             + 4 * cfg.layers * cfg.heads * cfg.head_dim * ctx)
+                                        / (ms_per_step * 1e-3) / 2.5e15, 5)}
+    out = {
+        "metric": f"VQA greedy decode tokens/s, UniMedVL-14B (BAGEL-7B-MoT dims), batch {B} x 448x448 per GPU",
+        "value": round(value, 2), "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "bf16" if not lw.fp8 else "bf16 (e4m3 weights, power-of-two channel scales)", "data": "synthetic (random N(0,0.02^2) weights at assumed 14B dims, synthetic images, random token ids)",
+        "config": {"workload": (("configs[3]: medical-report generation, 32 samples per GPU (batch 256 over 8 GPUs), ViT encode + "
+                                 "prefill + long greedy decode" if args.workload == "configs3" else
+                                 "configs[1]: UniMedVL-14B bf16 VQA greedy decode, batch=8 448x448, 1xMI355X") if not lw.fp8 else
+                                "configs[4]-style: UniMedVL-14B fp8-weight VQA greedy decode, batch=8 448x448 per GPU")
+                               if args.config == "full" else "tiny smoke config",
+                   "c1_gather": args.gather if world > 1 else None,
+                   "batch_per_gpu": B, "context_tokens": ctx, "image": f"{img_hw}x{img_hw}", "prompt_tokens": prompt_len,
+                   "parallelism": f"dp{world}", "cpu_binding": cpu_binding, "decode": "hipGraph" if not args.no_graph else "eager",
+                   "prefill_s": round(t_prefill, 3), "prefill_cold_s": round(leg["t_prefill_cold"], 3),
+                   "prefill_images_per_s": round(world * B / t_prefill, 1),
+                   "weights_init_s": round(t_load, 1), "gpu_ms_per_step": round(gpu_ms / args.steps, 4)},
+        # plain run: the step-level figures only; --full replaces this with the audited roofline of the dominant kernel
+        "roofline": {"bound": "hbm", "peak": PEAK_HBM_GBS, "unit": "GB/s", **step_roofline},
+    }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.dist.destroy_process_group()
+    if not args.full:
+        return finish()
 
     # ---- roofline of the dominant kernel: the weight-streaming skinny GEMM (gemm_skinny_kernel<1,2>:
     # the 28 gate/up SwiGLU projections + lm_head of one step), HIP events on the launch stream
-    lw = model.language_model.w
     x = torch.randn((B, cfg.hidden), device=dev).to(torch.bfloat16)
     act = torch.empty((B, cfg.inter), dtype=torch.bfloat16, device=dev)
     logits = torch.empty((B, cfg.vocab), dtype=torch.bfloat16, device=dev)
@@ -1008,9 +1060,6 @@ def main():
     lm_bytes = cfg.vocab * cfg.hidden * wb + B * cfg.hidden * 2 + B * cfg.vocab * 2 + (4 * cfg.vocab if lw.fp8 else 0)
     bytes_per_launch = (cfg.layers * gu_bytes + lm_bytes) / (cfg.layers + 1)
     achieved = bytes_per_launch / (avg_us * 1e-6) / 1e9
-    # whole-step algorithmic bytes (weights + KV read/write + logits), for the step-level fraction
-    kv_tok = cfg.layers * 2 * cfg.kv_heads * cfg.head_dim * 2
-    step_bytes = lw.decode_weight_bytes() + B * (ctx + args.warmup + args.steps / 2) * kv_tok + B * kv_tok + B * cfg.vocab * 2
 
     # ---- the roofline audits itself: tools/roofline_profile.sh (rocprofv3 kernel trace of a 512-step graph decode + separate
     # --pmc FETCH_SIZE / WRITE_SIZE passes, gfx950 x2 correction) writes profiles/roofline_profile_latest.json stamped with the
@@ -1203,8 +1252,6 @@ def main():
         vit["mfma_counters"] = stage_counters("vit")
         vit["roofline"] = mfma_roofline("vit", B * (img_hw // cfg.patch) ** 2, cfg.vit_inter, cfg.vit_hidden, False, "SigLIP fc1 (bias + GELU epilogue not in the timed call)")
 
-    ms_per_step = elapsed * 1e3 / args.steps
-    value = world * B * args.steps / elapsed
     # ---- the reference's DEFAULT decode mode (interactive_vqa_inferencer.py:58-71: do_sample=True, temperature 1.0; bagel.py:1297-1299):
     # same batch / context; the draw is a Gumbel-max over bf16(logit / T) in the lm_head epilogue (umv_gemm_args.sample_temperature), finished by
     # the same step-end kernel as the greedy step.  Never the headline value (BASELINE.json's metric is greedy).
@@ -1218,39 +1265,15 @@ def main():
                    "greedy_ms_per_step": round(ms_per_step, 4)}
         ls = None
         torch.cuda.empty_cache()
-    out = {
-        "metric": f"VQA greedy decode tokens/s, UniMedVL-14B (BAGEL-7B-MoT dims), batch {B} x 448x448 per GPU",
-        "value": round(value, 2), "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "bf16" if not lw.fp8 else "bf16 (e4m3 weights, power-of-two channel scales)", "data": "synthetic (random N(0,0.02^2) weights at assumed 14B dims, synthetic images, random token ids)",
-        "config": {"workload": (("configs[3]: medical-report generation, 32 samples per GPU (batch 256 over 8 GPUs), ViT encode + "
-                                 "prefill + long greedy decode" if args.workload == "configs3" else
-                                 "configs[1]: UniMedVL-14B bf16 VQA greedy decode, batch=8 448x448, 1xMI355X") if not lw.fp8 else
-                                "configs[4]-style: UniMedVL-14B fp8-weight VQA greedy decode, batch=8 448x448 per GPU")
-                               if args.config == "full" else "tiny smoke config",
-                   "c1_gather": args.gather if world > 1 else None,
-                   "batch_per_gpu": B, "context_tokens": ctx, "image": f"{img_hw}x{img_hw}", "prompt_tokens": prompt_len,
-                   "parallelism": f"dp{world}", "cpu_binding": cpu_binding, "decode": "hipGraph" if not args.no_graph else "eager",
-                   "prefill_s": round(t_prefill, 3), "prefill_cold_s": round(leg["t_prefill_cold"], 3),
-                   "prefill_images_per_s": round(world * B / t_prefill, 1),
-                   "weights_init_s": round(t_load, 1), "gpu_ms_per_step": round(gpu_ms / args.steps, 4)},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                     "frac": round(achieved / PEAK_HBM_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                     "kernel": ("gemm_skinny8_kernel" if lw.fp8 else "gemm_skinny_kernel") + ("<1,2,4>" if B <= 16 else "<2,4,2>" if B <= 32 else " / tiled 128x64")
-                               + " (28 gate/up SwiGLU GEMMs + lm_head per step)",
-                     "avg_launch_us": round(avg_us, 2), "avg_launch_us_source": ("in-graph kernel, rocprofv3 average (profiles/roofline_profile_latest.json)"
-                                                                                 if dom is not None else "isolated back-to-back replay, HIP events"),
-                     "avg_launch_us_replay": round(avg_us_replay, 2), "profile_status": prof_status,
-                     "secondary": secondary, "latency_floor_kernels": small,
-                     "algorithmic_bytes_per_launch": int(bytes_per_launch),
-                     "step_algorithmic_GBps": round(step_bytes / (ms_per_step * 1e-3) / 1e9, 1),
-                     "step_frac_of_peak": round(step_bytes / (ms_per_step * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
-                     # the other roofline, for completeness (BASELINE.json pairs decode with MFMA): at B rows per weight byte
-                     # the MFMA fraction is capped near B / 310 by the HBM roofline
-                     "step_mfma_frac_of_2500": round(B * (2 * lw.decode_weight_bytes() / (1 if lw.fp8 else 2)
-                                                          + 4 * cfg.layers * cfg.heads * cfg.head_dim * ctx)
-                                                     / (ms_per_step * 1e-3) / 2.5e15, 5)},
-    }
+    out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                       "frac": round(achieved / PEAK_HBM_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
+                       "kernel": ("gemm_skinny8_kernel" if lw.fp8 else "gemm_skinny_kernel") + ("<1,2,4>" if B <= 16 else "<2,4,2>" if B <= 32 else " / tiled 128x64")
+                                 + " (28 gate/up SwiGLU GEMMs + lm_head per step)",
+                       "avg_launch_us": round(avg_us, 2), "avg_launch_us_source": ("in-graph kernel, rocprofv3 average (profiles/roofline_profile_latest.json)"
+                                                                                   if dom is not None else "isolated back-to-back replay, HIP events"),
+                       "avg_launch_us_replay": round(avg_us_replay, 2), "profile_status": prof_status,
+                       "secondary": secondary, "latency_floor_kernels": small,
+                       "algorithmic_bytes_per_launch": int(bytes_per_launch), **step_roofline}
     if sampled is not None:
         out["decode_sampled"] = sampled
     if vit is not None:
@@ -1374,11 +1397,7 @@ def main():
             out["cpu_baseline"] = {"value": None, "unit": "tokens/s", "cores": torch.get_num_threads(), "kind": "port",
                                    "sample": f"failed: {type(e).__name__}: {e}"}
         out["cpu_baseline"]["host"] = cpu_info()
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if dist is not None:
-        dist.barrier()
-        dist.dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -25,7 +25,7 @@ def _run_bench(*flags):
 
 
 def test_bench_line_contract():
-    d = _run_bench()
+    d = _run_bench("--full")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline"):
         assert key in d, key
@@ -40,6 +40,22 @@ def test_bench_line_contract():
     assert r["bound"] == "hbm" and r["unit"] == "GB/s" and r["peak"] == 8000.0
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3
     assert "t2i" in d and d["t2i"]["images_per_s"] > 0
+
+
+def test_bench_plain_run_is_headline_only():
+    """Without --full the run measures the headline decode and nothing else: the same headline keys, the step-level roofline
+    (arithmetic on the timed step) and no kernel replays or extra legs."""
+    d = _run_bench()
+    assert d["unit"] == "tokens/s" and d["n_gpus"] == 1 and d["steps"] == 6 and d["warmup"] == 2
+    assert d["higher_is_better"] is True and d["scaling"] == "weak" and d["vs_baseline"] is None and d["dtype"] == "bf16"
+    assert d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 8 * 6 / (d["ms_per_step"] * 6e-3)) <= 0.02 * d["value"]
+    assert set(d) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                      "dtype", "data", "config", "roofline"}, sorted(d)
+    r = d["roofline"]
+    assert set(r) == {"bound", "peak", "unit", "step_algorithmic_GBps", "step_frac_of_peak", "step_mfma_frac_of_2500"}, sorted(r)
+    assert r["bound"] == "hbm" and r["unit"] == "GB/s" and r["peak"] == 8000.0 and r["step_algorithmic_GBps"] > 0
+    assert abs(r["step_frac_of_peak"] - r["step_algorithmic_GBps"] / r["peak"]) < 1e-3
 
 
 def test_bench_no_graph_and_flags():
@@ -76,7 +92,7 @@ def test_bench_self_launches_two_ranks(gather):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(PYTHONDONTWRITEBYTECODE="1", UMV_BENCH_BACKEND="gloo", UMV_BENCH_SHARE_GPU="1")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "tiny", "--steps", "6", "--warmup", "2",
-                        "--gather", gather], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--gather", gather, "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]

@@ -5,7 +5,7 @@
 # Everything a step prints lands in gpurun_out/<tag>_session/ (merged back by gpurun).  Steps:
 #   suite                       the round-end GPU suite as the driver runs it (pytest -m gpu -x, 25 slowest tests) + __graft_entry__.smoke()
 #   tests:<pytest args>         e.g. 'tests:tests/test_attn_lazy_gpu.py -k deterministic -s'
-#   bench[:<flags>]             python bench.py <flags> -> <tag>/bench.txt
+#   bench[:<flags>]             python bench.py --full <flags> -> <tag>/bench.txt
 #   decode[:<flags>]            the decode leg only (256 steps): value / ms per step on one line
 #   ab:<VAR=a,b,c>[:<flags>]    the decode leg once per value of an environment knob, e.g. 'ab:UMV_DECODE_NSPLIT=12,24'
 #   env:<K=V ...>               export variables for the steps that follow, e.g. 'env:UMV_DECODE_WSPLIT=4 UMV_DECODE_NSPLIT=6'
@@ -28,7 +28,7 @@ for step in "$@"; do
     suite)   timeout 2400 python -m pytest tests/ -x -q -m gpu --durations=25 2>&1 | tail -70 > $O/suite.txt
              python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; tail -3 $O/suite.txt $O/smoke.txt ;;
     tests)   timeout 2400 python -m pytest $arg -q -m gpu 2>&1 | tail -60 >> $O/tests.txt; tail -3 $O/tests.txt ;;
-    bench)   timeout 1200 python bench.py $arg > $O/bench.txt 2>&1; grep '^{' $O/bench.txt | line ;;
+    bench)   timeout 1200 python bench.py --full $arg > $O/bench.txt 2>&1; grep '^{' $O/bench.txt | line ;;
     decode)  timeout 600 python bench.py $DECODE_ONLY $arg 2>/dev/null | line | tee -a $O/decode.txt ;;
     ab)      var=${arg%%=*}; rest=${arg#*=}; vals=${rest%%:*}; flags=""; [ "$vals" != "$rest" ] && flags=${rest#*:}
              for v in ${vals//,/ }; do echo -n "$var=$v: "; env $var=$v timeout 600 python bench.py $DECODE_ONLY $flags 2>/dev/null | line; done | tee -a $O/ab.txt ;;

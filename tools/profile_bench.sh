@@ -3,6 +3,7 @@
 # usage (inside gpurun): bash tools/profile_bench.sh <tag> [bench args...]
 set -e
 TAG=${1:-prof}; shift || true
+set -- --full "$@"          # every leg of the benchmark, not only the headline decode
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out/$TAG
 rocprofv3 --kernel-trace --stats -d gpurun_out/$TAG -o bench -- python bench.py --no-cpu-baseline "$@" > gpurun_out/$TAG/bench.log 2>&1 || true
