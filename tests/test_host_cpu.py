@@ -353,3 +353,27 @@ def test_attention_prefill_isa_has_no_scratch(tmp_path):
             # the lazy softmax is compiler-visible throughout: no inline asm next to its v_permlane*_swap steps (round 6)
             body = s[s.index(n + ":"):b]
             assert not re.search(r";;#ASMSTART\s+v_", body), f"{n}: inline-asm VALU instruction in a lazy kernel"
+
+
+def test_pack_stamp_hashes_the_include_closure_of_the_packers(monkeypatch):
+    """packstore.kernel_stamp() decides whether a packed weight file may be reused: it must hash exactly what csrc/pack.hip's
+    #include "..." chain reaches - a decode-kernel or tiled-GEMM edit must not throw every packed file away."""
+    import builtins
+    from unimedvl_amd import packstore
+    pkg = os.path.dirname(os.path.abspath(packstore.__file__))
+    closure, todo = set(), [os.path.join(pkg, "csrc", "pack.hip")]
+    while todo:
+        f = os.path.realpath(todo.pop())
+        if f not in closure:
+            closure.add(f)
+            todo += [os.path.join(os.path.dirname(f), inc) for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(f).read(), re.M)]
+    read, real_open = [], builtins.open
+
+    def spy(path, *args, **kwargs):
+        read.append(os.path.realpath(path))
+        return real_open(path, *args, **kwargs)
+    monkeypatch.setattr(builtins, "open", spy)
+    stamp = packstore.kernel_stamp()
+    monkeypatch.undo()
+    assert stamp is not None
+    assert sorted(read) == sorted(closure), (sorted(set(read) - closure), sorted(closure - set(read)))

@@ -379,9 +379,9 @@ def test_gemm_lean_epilogue_bit_identical(ops, tile, w4):
 def test_skinny_full_line_x_staging_bit_identical(ops):
     """The weight-streaming kernels with x in full 128-byte lines (gemm.hip XL, the default: a k-tile pair of 8 rows per load, per-wave
     LDS staging, one piece for M <= 8, two per 16-row tile above) against the fragment-shaped loads they replaced
-    (UMV_SKINNY_XL=0 / UMV_SKINNY8_XL=0): same operands, same MFMAs, same order - every bit must agree.  Rows 1 .. 64, K slices that
+    (UMV_SKINNY_XL=0): same operands, same MFMAs, same order - every bit must agree.  Rows 1 .. 64, K slices that
     start on odd k-tiles (K = 3584 over 3 splits: 38 / 8 waves = 5 tiles per wave), K % 64 != 0, K % 32 != 0, split-K partial sums,
-    SwiGLU, residual, row-indexed x, and the e4m3 kernels."""
+    SwiGLU, residual, row-indexed x, and the e4m3 and MXFP4 images."""
     import subprocess as sp
     code = f"""
 import hashlib, sys, math, torch
@@ -391,10 +391,10 @@ from test_kernel_branches_gpu import rnd, BF16
 def sha(t): return hashlib.sha256(t.cpu().contiguous().view(torch.int16 if t.dtype == BF16 else torch.int32).numpy().tobytes()).hexdigest()[:16]
 for N, K in ((4608, 3584), (3584, 18944), (1000, 1096), (320, 4304), (96, 96)):
     w = rnd((N, K), 2, 1 / math.sqrt(K)); b = rnd((N,), 3)
-    for fp8 in (False, True):
-        if fp8 and K % 64:
+    for fp8 in (False, True, 'fp4'):
+        if (fp8 is True and K % 64) or (fp8 == 'fp4' and K % 32):
             continue
-        lin = (ops.PackedLinear.from_weight_fp8 if fp8 else ops.PackedLinear.from_weight)(w, b)
+        lin = (ops.PackedLinear.from_weight_mxfp4 if fp8 == 'fp4' else ops.PackedLinear.from_weight_fp8 if fp8 else ops.PackedLinear.from_weight)(w, b)
         for M in (1, 7, 8, 9, 16, 17, 32, 33, 64):
             x = rnd((M, K), 10 + M)
             res = rnd((M, N), 4)
@@ -411,8 +411,8 @@ for N, K in ((4608, 3584), (3584, 18944), (1000, 1096), (320, 4304), (96, 96)):
         ops.gemm(xs, lin, out=o, M=10, row_idx=rows)
         print('sha rows', N, K, fp8, sha(o))
 g, u = rnd((1024, 3584), 6, 0.02), rnd((1024, 3584), 7, 0.02)
-for fp8 in (False, True):
-    lin = (ops.PackedLinear.from_gate_up_fp8 if fp8 else ops.PackedLinear.from_gate_up)(g, u)
+for fp8 in (False, True, 'fp4'):
+    lin = (ops.PackedLinear.from_gate_up_mxfp4 if fp8 == 'fp4' else ops.PackedLinear.from_gate_up_fp8 if fp8 else ops.PackedLinear.from_gate_up)(g, u)
     for M in (8, 24, 48):
         print('sha swiglu', fp8, M, sha(ops.gemm(rnd((M, 3584), 8), lin)))
 """
@@ -420,7 +420,7 @@ for fp8 in (False, True):
     for xl in ("0", "default"):
         env = dict(os.environ)
         if xl == "0":
-            env.update(UMV_SKINNY_XL="0", UMV_SKINNY8_XL="0")
+            env.update(UMV_SKINNY_XL="0")
         r = sp.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900, env=env)
         assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
         shas[xl] = [ln for ln in r.stdout.splitlines() if ln.startswith("sha")]

@@ -8,332 +8,28 @@
 // lane, i.e. one 8-byte bf16x4 store per 16x16 tile.
 //
 // Two kernels:
-//   * gemm_skinny  (M <= 64, decode / MoT text rows): HBM-bound weight streaming.
-//     One workgroup = NT n-tiles x all of K; its 8 waves split K and reduce through
-//     LDS (deterministic, no atomics, no inter-workgroup split-K).  Weight fragments
-//     go straight from HBM to VGPRs (no LDS round trip: each byte is used once).
+//   * gemm_skinny  (M <= 64, decode / MoT text rows): HBM-bound weight streaming, the body in gemm_skinny.h; this file has
+//     its bf16 and e4m3 entries (gemm_skinny_kernel, gemm_skinny8_kernel).
 //   * gemm_tiled   (M > 64, prefill / ViT / diffusion): 128x128 workgroup tile,
 //     4 waves of 64x64, W fragments from the packed stream, x staged through LDS.
 #include "common.h"
 #include "../../include/unimedvl_hip.h"
 #include "gemm_epilogue.h"
 #include "gemm_internal.h"
+#include "gemm_skinny.h"
 #include <string.h>
 #include <stdlib.h>
 
-// ----------------------------------------------------------------------------- skinny (M <= 64)
-// Weight streaming, HBM-bound.  One workgroup = NT n-tiles x all of K; its 8 waves take
-// contiguous K slices and reduce through LDS.  Each wave keeps U weight fragments per n-tile
-// in flight (U KiB of contiguous HBM per n-tile) and, when DB, prefetches the next chunk
-// while the MFMAs of the current one issue.  NORM fuses Qwen2RMSNorm (modeling_qwen2.py:89-94)
-// of the x rows into the prologue: the wave holds its whole K slice of x in registers,
-// the row sum of squares is combined across waves through LDS, and the fragments are
-// normalised in place with the reference's two bf16 roundings before feeding the MFMAs.
-#define SK_WAVES 8
-#define SK_XMAX 16   // NORM: K <= 8*16*32 = 4096
-
-template <int MB, int NT, int U, int XL = 0>
-struct SkBuf {
-    bf16x8 w[U][NT];
-    bf16x8 x[U][MB];
-    u32x4 xp[XL ? U / 2 : 1][XL == 1 ? 1 : (XL ? 2 * MB : 1)];     // XL: the x pieces of the chunk's k-tile pairs on their way to LDS
-};
-
-// XL (round 4): x reaches the MFMAs in FULL 128-byte lines.  The plain kernel loads x in fragment shape - per wave instruction
-// 16 rows x 64 bytes, half a line per row - and every workgroup re-reads all of x through L2 -> L1 (at 8 rows that is half the
-// weight bytes, at 32 rows twice them).  Here a wave loads 8 rows x 128 bytes per instruction (a k-tile PAIR of 8 rows, lane L:
-// row L >> 3, chunk (L & 7) ^ (L >> 3)), parks the piece in its own KiB of LDS (lane-linear ds_write_b128: the image is row-major,
-// XOR-swizzled by the row) and reads the B fragments of the two k-tiles back conflict free (lane (r, g), k half h: chunk
-// (4h + g) ^ (r & 7) of row r) - the tiled kernel's full-line staging (SCHED = 3) without the DMA.  Same operands, same MFMAs,
-// same order: bit-identical to the plain kernel.  XL = 2: two pieces per 16-row tile; XL = 1 (M <= 8): one piece, rows 8..15 of a
-// fragment re-read rows 0..7 (their output columns are never stored).  Needs an even U.
+// ----------------------------------------------------------------------------- skinny (M <= 64): gemm_skinny.h
 template <int MB, int NT, int U, bool DB, int NORM, int XL = 0>   // NORM: 0 = off, 8 / 16 = fused RMSNorm keeping that many x rows
 __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(umv_gemm_args a, int KT, int NTT) {
-    extern __shared__ __attribute__((aligned(16))) float red[];  // [SK_WAVES][NT*MB*4][64] (+ norm partials)
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 15, g = lane >> 4;
-    const int nt0 = blockIdx.x * NT;
+    gemm_skinny_body<SkBf16<NT>, MB, U, DB, NORM, XL>(a, KT, NTT, 0);
+}
 
-    const bf16_t* xrow[MB];
-    bool xvalid[MB];
-#pragma unroll
-    for (int mb = 0; mb < MB; ++mb) {
-        int m = mb * 16 + r;
-        xvalid[mb] = m < a.M;
-        int64_t row = xvalid[mb] ? (a.row_idx ? (int64_t)a.row_idx[m] : (int64_t)m) : 0;
-        xrow[mb] = a.x + row * a.ldx;
-    }
-    f32x4 acc[NT][MB];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb) acc[t][mb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    // split-K (a.k_splits > 1): blockIdx.y owns the k-tiles [ks0, ks1) and stores raw fp32 partial sums
-    const int nsplit = a.k_splits > 1 ? a.k_splits : 1;
-    const int kts = (KT + nsplit - 1) / nsplit;
-    const int ks0 = (int)blockIdx.y * kts, ks1 = min(KT, ks0 + kts);
-    const int kt_per = (max(0, ks1 - ks0) + SK_WAVES - 1) / SK_WAVES;
-    const int kt_begin = ks0 + wave * kt_per;
-    const int kt_end = min(ks1, kt_begin + kt_per);
-    // XL works on whole k-tile PAIRS (one 128-byte line of x per row): a slice that starts on an odd k-tile starts one tile early
-    // with that tile's weights masked to zero - an MFMA that adds exact zeros (the x it multiplies is the neighbour wave's, finite).
-    // PRECONDITION of "bit-identical to the plain kernel": x is finite.  Where x holds Inf / NaN in the neighbour's k-tile the masked
-    // product is 0 * Inf = NaN and this wave's partial sum becomes NaN where the plain kernel's would not (the row's final result is
-    // Inf / NaN either way - the neighbour's own product sees the same value; only WHICH of the two non-finite values differs).
-    const int kt_lo = XL != 0 ? (kt_begin & ~1) : kt_begin;
-    const int nk = max(0, kt_end - kt_lo);
-    const int nchunks = (nk + U - 1) / U;
-    // TH = rows per n-tile of the packed image (16 standard; < 16 for the exact-partition decode copies,
-    // whose lanes r >= TH carry no row): tile (nt, kt) holds [g][r < TH][8] = 4*TH*8 elements
-    const int TH = a.tile_rows > 0 ? a.tile_rows : 16;
-    const int tile_elems = 4 * TH * 8;
-    const bool rowlane = r < TH;
-    const bf16_t* wbase[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const bool tv = (nt0 + t) < NTT;
-        wbase[t] = a.wp + ((int64_t)(tv ? nt0 + t : 0) * KT) * tile_elems + (g * TH + (rowlane ? r : 0)) * 8;
-    }
-    static_assert(!XL || (U % 2 == 0 && NORM == 0), "full-line x staging: whole k-tile pairs per chunk, no fused norm");
-    static_assert(XL != 1 || MB == 1, "one-piece staging serves one 16-row tile of at most 8 valid rows");
-    constexpr int XLP = XL == 1 ? 1 : 2 * MB;          // pieces per k-tile pair
-    // XL: this lane's row of each 8-row piece and its 16-byte chunk of the pair's 128 bytes
-    const int xchunk = (lane & 7) ^ ((lane >> 3) & 7);
-    const bf16_t* xprow[XL ? XLP : 1];
-    bool xpvalid[XL ? XLP : 1];
-    if constexpr (XL != 0) {
-#pragma unroll
-        for (int q = 0; q < XLP; ++q) {
-            const int m = q * 8 + (lane >> 3);
-            xpvalid[q] = m < a.M;
-            const int64_t row = xpvalid[q] ? (a.row_idx ? (int64_t)a.row_idx[m] : (int64_t)m) : 0;
-            xprow[q] = a.x + row * a.ldx + xchunk * 8;
-        }
-    }
-    char* xstage = reinterpret_cast<char*>(red) + wave * (U / 2 * XLP * 1024);      // XL: this wave's own staging KiBs
-    auto load_chunk = [&](int c, SkBuf<MB, NT, U, XL>& b) {
-        if constexpr (XL != 0) {
-#pragma unroll
-            for (int pr = 0; pr < U / 2; ++pr) {
-                const int kt = kt_lo + c * U + 2 * pr;
-                const int k = kt * 32 + xchunk * 8;
-#pragma unroll
-                for (int q = 0; q < XLP; ++q)
-                    b.xp[pr][q] = (kt < kt_end && xpvalid[q] && k < a.K) ? *reinterpret_cast<const u32x4*>(xprow[q] + (int64_t)kt * 32)
-                                                                         : (u32x4){0u, 0u, 0u, 0u};
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int kt = kt_lo + c * U + u;
-            const bool ok = kt >= kt_begin && kt < kt_end;
-#pragma unroll
-            for (int t = 0; t < NT; ++t)
-                b.w[u][t] = (ok && rowlane) ? __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(wbase[t] + (int64_t)kt * tile_elems))
-                                            : zero_frag();
-            if (!NORM && XL == 0) {
-                const int k = kt * 32 + g * 8;
-#pragma unroll
-                for (int mb = 0; mb < MB; ++mb) b.x[u][mb] = (ok && xvalid[mb] && k < a.K) ? ldg_frag(xrow[mb] + k) : zero_frag();
-            }
-        }
-    };
-    // XL: the chunk's pieces go through the wave's LDS KiBs and come back as the B fragments the MFMAs take (LDS operations of
-    // one wave execute in order and nobody else touches these bytes: no barrier)
-    auto unstage = [&](SkBuf<MB, NT, U, XL>& b) {
-        if constexpr (XL != 0) {
-#pragma unroll
-            for (int pr = 0; pr < U / 2; ++pr)
-#pragma unroll
-                for (int q = 0; q < XLP; ++q) *reinterpret_cast<u32x4*>(xstage + (pr * XLP + q) * 1024 + lane * 16) = b.xp[pr][q];
-            const int rr = XL == 1 ? (r & 7) : r;
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int mb = 0; mb < MB; ++mb)
-                    b.x[u][mb] = *reinterpret_cast<const bf16x8*>(xstage + (u >> 1) * (XLP * 1024) + (mb * 16 + rr) * 128 +
-                                                                  ((((u & 1) * 4 + g) ^ (rr & 7)) << 4));
-        }
-    };
-    SkBuf<MB, NT, U, XL> b0, b1;
-    if (nchunks > 0) load_chunk(0, b0);
-
-    if constexpr (NORM != 0) {
-        static_assert(!NORM || MB == 1, "fused RMSNorm supports M <= 16");
-        // Stage RMSNorm(x) * norm_w ONCE per workgroup into LDS, already in MFMA B-fragment order:
-        // slot (kt, g, r) holds the 8 bf16 of row r at k = kt*32 + g*8.  MP = rows kept (8 or 16).
-        constexpr int MP = NORM ? NORM : 8;
-        bf16_t* xl = reinterpret_cast<bf16_t*>(red + SK_WAVES * NT * MB * 4 * 64 + SK_WAVES * 16);
-        float* part = red + SK_WAVES * NT * MB * 4 * 64;   // [SK_WAVES][16]
-        const int rr = tid & (MP - 1);
-        constexpr int sh = MP == 8 ? 3 : 4;        // log2(MP)
-        constexpr int XS = MP;                     // 16-byte groups per thread: (4096/32) * 4 * MP / 512
-        const int nslots = KT * 4 * MP;
-        const bool rowok = rr < a.M;
-        const bf16_t* xr = a.x + (rowok ? (a.row_idx ? (int64_t)a.row_idx[rr] : (int64_t)rr) : 0) * a.ldx;
-        // ONE batch of loads per phase: a loop of dependent L2 round trips (7 per pass at K = 3584) costs ~10 us per
-        // workgroup, a batch about one round trip.  Phase 1: x -> registers -> row sums of squares, raw x parked in LDS.
-        {
-            bf16x8 xv[XS];
-#pragma unroll
-            for (int i = 0; i < XS; ++i) {
-                const int sidx = tid + i * SK_WAVES * 64;
-                const int k = (sidx >> (sh + 2)) * 32 + ((sidx >> sh) & 3) * 8;
-                xv[i] = (sidx < nslots && k < a.K && rowok) ? ldg_frag(xr + k) : zero_frag();
-            }
-            float ss = 0.f;
-#pragma unroll
-            for (int i = 0; i < XS; ++i) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    float f = bf2f((bf16_t)xv[i][j]);
-                    ss += f * f;
-                }
-                const int sidx = tid + i * SK_WAVES * 64;
-                if (sidx < nslots) *reinterpret_cast<bf16x8*>(xl + (int64_t)sidx * 8) = xv[i];
-            }
-            // lanes sharing a row: lane & (MP-1)
-            if (MP == 8) ss += __shfl_xor(ss, 8, 64);
-            ss += __shfl_xor(ss, 16, 64);
-            ss += __shfl_xor(ss, 32, 64);
-            if (lane < MP) part[wave * 16 + lane] = ss;
-        }
-        // phase 2: norm_w batch (in flight across the barrier), then normalise the thread's own slots in place
-        bf16x8 wv[XS];
-#pragma unroll
-        for (int i = 0; i < XS; ++i) {
-            const int sidx = tid + i * SK_WAVES * 64;
-            const int k = (sidx >> (sh + 2)) * 32 + ((sidx >> sh) & 3) * 8;
-            wv[i] = (sidx < nslots && k < a.K) ? ldg_frag(a.norm_w + k) : zero_frag();
-        }
-        __syncthreads();
-        float tot = 0.f;
-#pragma unroll
-        for (int w = 0; w < SK_WAVES; ++w) tot += part[w * 16 + rr];
-        const float rstd = rsqrt_ieee(tot / (float)a.K + a.norm_eps);
-#pragma unroll
-        for (int i = 0; i < XS; ++i) {
-            const int sidx = tid + i * SK_WAVES * 64;
-            if (sidx < nslots) {
-                bf16x8 v = *reinterpret_cast<const bf16x8*>(xl + (int64_t)sidx * 8), o;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) o[j] = (short)f2bf(bf2f((bf16_t)wv[i][j]) * rbf(bf2f((bf16_t)v[j]) * rstd));   // two roundings
-                *reinterpret_cast<bf16x8*>(xl + (int64_t)sidx * 8) = o;
-            }
-        }
-        __syncthreads();
-        const int rsel = r & (MP - 1);
-        auto xfrag = [&](int kt) -> bf16x8 {
-            return *reinterpret_cast<const bf16x8*>(xl + ((int64_t)(kt * 4 + g) * MP + rsel) * 8);
-        };
-        for (int c = 0; c < nchunks; c += 2) {
-            if (DB && c + 1 < nchunks) load_chunk(c + 1, b1);
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int kt = min(kt_begin + c * U + u, KT - 1);
-                bf16x8 xf = xfrag(kt);
-#pragma unroll
-                for (int t = 0; t < NT; ++t) acc[t][0] = mfma16(b0.w[u][t], xf, acc[t][0]);
-            }
-            if (c + 1 < nchunks) {
-                if (!DB) load_chunk(c + 1, b1);
-                if (c + 2 < nchunks && DB) load_chunk(c + 2, b0);
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int kt = min(kt_begin + (c + 1) * U + u, KT - 1);
-                    bf16x8 xf = xfrag(kt);
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) acc[t][0] = mfma16(b1.w[u][t], xf, acc[t][0]);
-                }
-                if (c + 2 < nchunks && !DB) load_chunk(c + 2, b0);
-            }
-        }
-    } else {
-        for (int c = 0; c < nchunks; c += 2) {
-            if (DB && c + 1 < nchunks) load_chunk(c + 1, b1);
-            unstage(b0);
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int t = 0; t < NT; ++t)
-#pragma unroll
-                    for (int mb = 0; mb < MB; ++mb) acc[t][mb] = mfma16(b0.w[u][t], b0.x[u][mb], acc[t][mb]);
-            if (c + 1 < nchunks) {
-                if (!DB) load_chunk(c + 1, b1);
-                if (c + 2 < nchunks && DB) load_chunk(c + 2, b0);
-                unstage(b1);
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-#pragma unroll
-                    for (int t = 0; t < NT; ++t)
-#pragma unroll
-                        for (int mb = 0; mb < MB; ++mb) acc[t][mb] = mfma16(b1.w[u][t], b1.x[u][mb], acc[t][mb]);
-                if (c + 2 < nchunks && !DB) load_chunk(c + 2, b0);
-            }
-        }
-    }
-    // cross-wave reduction through LDS
-    if constexpr (XL != 0) __syncthreads();      // the reduction buffer overlays the waves' x staging KiBs: everyone has left the main loop
-    constexpr int E4 = NT * MB;  // f32x4 fragments per lane
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb) {
-            f32x4* dst = reinterpret_cast<f32x4*>(red) + ((wave * E4 + t * MB + mb) * 64 + lane);
-            *dst = acc[t][mb];
-        }
-    __syncthreads();
-    EpiCtx e{a.bias, a.residual, a.ldr, a.out, a.ldo, a.N, a.epilogue};
-    if (nsplit > 1) {   // partial sums: fp32, no bias / activation / residual (the consumer kernel finishes the row)
-        e.out = reinterpret_cast<float*>(a.out) + (int64_t)blockIdx.y * a.split_stride;
-        e.flags = UMV_EPI_OUT_F32;
-    }
-    if (a.epilogue & UMV_EPI_SWIGLU) {
-        // tiles come in (gate, up) pairs; NT is even
-        for (int idx = tid; idx < (NT / 2) * MB * 64; idx += SK_WAVES * 64) {
-            int l = idx & 63;
-            int f = idx >> 6;  // pair*MB + mb
-            int pair = f / MB, mb = f % MB;
-            f32x4 sg = {0, 0, 0, 0}, su = {0, 0, 0, 0};
-#pragma unroll
-            for (int w = 0; w < SK_WAVES; ++w) {
-                sg += reinterpret_cast<f32x4*>(red)[(w * E4 + (2 * pair) * MB + mb) * 64 + l];
-                su += reinterpret_cast<f32x4*>(red)[(w * E4 + (2 * pair + 1) * MB + mb) * 64 + l];
-            }
-            int m = mb * 16 + (l & 15);
-            int ntile = nt0 + 2 * pair;
-            if (m < a.M && ntile < NTT) {
-                int64_t orow = a.row_idx ? (int64_t)a.row_idx[m] : (int64_t)m;
-                int c0 = (ntile >> 1) * 16 + (l >> 4) * 4;
-                float gg[4] = {sg.x, sg.y, sg.z, sg.w}, uu[4] = {su.x, su.y, su.z, su.w};
-                epi_swiglu4(e, orow, c0, a.N / 2, gg, uu);
-            }
-        }
-    } else {
-        for (int idx = tid; idx < E4 * 64; idx += SK_WAVES * 64) {
-            int l = idx & 63;
-            int f = idx >> 6;  // t*MB + mb
-            int t = f / MB, mb = f % MB;
-            f32x4 s = {0, 0, 0, 0};
-#pragma unroll
-            for (int w = 0; w < SK_WAVES; ++w) s += reinterpret_cast<f32x4*>(red)[(w * E4 + f) * 64 + l];
-            int m = mb * 16 + (l & 15);
-            int n0 = (nt0 + t) * TH + (l >> 4) * 4;
-            int nend = min(a.N, (nt0 + t) * TH + TH);            // rows of this tile stop at TH
-            const bool valid = m < a.M && n0 < nend;
-            float fin[4] = {0.f, 0.f, 0.f, 0.f};
-            if (valid) {
-                int64_t orow = a.row_idx ? (int64_t)a.row_idx[m] : (int64_t)m;
-                EpiCtx et = e;
-                et.N = nend;
-                epi_store4(et, orow, n0, s.x, s.y, s.z, s.w, fin);
-            }
-            if (a.argmax_partial && nt0 + t < NTT)   // wave-uniform: greedy argmax rides on the lm_head epilogue
-                epi_argmax_tile(a.argmax_partial, NTT, m, nt0 + t, l, valid, n0, nend, fin, a.sample_temperature, a.sample_seed, a.sample_step);
-        }
-    }
+template <int MB, int NT, int U, bool DB, int NORM>
+static int launch_skinny(const umv_gemm_args& a, int KT, int NTT, hipStream_t s) {
+    return launch_skinny_body<MB, NT, U, 1, NORM>([](auto XL) { return &gemm_skinny_kernel<MB, NT, U, DB, NORM, decltype(XL)::value>; }, a, KT,
+                                                  NTT, s, KT, NTT);
 }
 
 // ----------------------------------------------------------------------------- fp8 weights (decode, BASELINE.json configs[4])
@@ -345,229 +41,19 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(umv_gemm_arg
 //   image: P8[nt][kt8][lane][16 B], lane = g*16 + r; bytes 0..7  <-> W[nt*16 + r][kt8*64 +      g*8 + j]
 //                                                    bytes 8..15 <-> W[nt*16 + r][kt8*64 + 32 + g*8 + j]
 //   scale: f32 [ntt*16] in packed row order (SwiGLU images interleave gate / up 16-row tiles like the bf16 one)
-
-
-template <int MB, int NT, int U, int XL = 0>
-struct SkBuf8 {
-    u32x4 w[U][NT];
-    bf16x8 x[U][2][MB];
-    u32x4 xp[XL ? U : 1][XL == 1 ? 1 : (XL ? 2 * MB : 1)];      // XL: the 8-row x 128-byte x pieces of the chunk's k super-tiles
-};
-
-// Same work decomposition as gemm_skinny_kernel (8 waves split K in contiguous slices, LDS reduce in wave
-// order), over 64-wide k super-tiles; for K % 512 == 0 the slices - and so the fp32 sums - are identical.
-// XL = full-line x staging as in gemm_skinny_kernel (a 64-wide k super-tile is exactly one 128-byte line per row): 1 = M <= 8,
-// one piece per super-tile (rows 8..15 of the fragment re-read rows 0..7: their output columns are never stored), 2 = two pieces
-// per 16-row tile.
+// The weight-streaming body over the e4m3 image (64-k units); for K % 512 == 0 its 8-wave K slices - and so the fp32 sums - are those
+// of gemm_skinny_kernel on W'.  x costs as much L2->L1 traffic as the e4m3 weights at NT = 1 (M = 8 rows x 2 B vs 16 rows x 1 B per k)
+// and is what holds this kernel below the HBM rate: down_proj 18.2 us with these x loads, 12.8 us with x from a constant
+// (tools/skinny_bench.py; rotating the K order per workgroup or pre-packing x in fragment order did not help).
 template <int MB, int NT, int U, int XL = 0>
 __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny8_kernel(umv_gemm_args a, int KT8, int NTT) {
-    extern __shared__ __attribute__((aligned(16))) float red[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 15, g = lane >> 4;
-    const int nt0 = blockIdx.x * NT;
-    const uint8_t* wq = reinterpret_cast<const uint8_t*>(a.wp);
-
-    const bf16_t* xrow[MB];
-    bool xvalid[MB];
-#pragma unroll
-    for (int mb = 0; mb < MB; ++mb) {
-        int m = mb * 16 + r;
-        xvalid[mb] = m < a.M;
-        int64_t row = xvalid[mb] ? (a.row_idx ? (int64_t)a.row_idx[m] : (int64_t)m) : 0;
-        xrow[mb] = a.x + row * a.ldx;
-    }
-    f32x4 acc[NT][MB];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb) acc[t][mb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    const int nsplit = a.k_splits > 1 ? a.k_splits : 1;   // split-K as in gemm_skinny_kernel (over 64-wide super-tiles)
-    const int kts = (KT8 + nsplit - 1) / nsplit;
-    const int ks0 = (int)blockIdx.y * kts, ks1 = min(KT8, ks0 + kts);
-    const int kt_per = (max(0, ks1 - ks0) + SK_WAVES - 1) / SK_WAVES;
-    const int kt_begin = ks0 + wave * kt_per;
-    const int kt_end = min(ks1, kt_begin + kt_per);
-    const int nk = max(0, kt_end - kt_begin);
-    const int nchunks = (nk + U - 1) / U;
-    const uint8_t* wbase[NT];
-    float wscale[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const bool tv = (nt0 + t) < NTT;
-        const int nt = tv ? nt0 + t : 0;
-        wbase[t] = wq + ((int64_t)nt * KT8 * 64 + lane) * 16;
-        wscale[t] = a.w_scale[nt * 16 + r];
-    }
-    // x costs as much L2->L1 traffic as the e4m3 weights at NT = 1 (M = 8 rows x 2 B vs 16 rows x 1 B per k) and is what
-    // holds this kernel below the HBM rate: down_proj 18.2 us with these x loads, 12.8 us with x from a constant
-    // (tools/skinny_bench.py; rotating the K order per workgroup or pre-packing x in fragment order did not help).
-    static_assert(XL != 1 || MB == 1, "one-piece staging serves one 16-row tile of at most 8 valid rows");
-    constexpr int XLP = XL == 1 ? 1 : 2 * MB;        // pieces per k super-tile
-    const int xchunk = (lane & 7) ^ ((lane >> 3) & 7);
-    const bf16_t* xprow[XL ? XLP : 1];
-    bool xpvalid[XL ? XLP : 1];
-    if constexpr (XL != 0) {
-#pragma unroll
-        for (int q = 0; q < XLP; ++q) {
-            const int m = q * 8 + (lane >> 3);
-            xpvalid[q] = m < a.M;
-            const int64_t row = xpvalid[q] ? (a.row_idx ? (int64_t)a.row_idx[m] : (int64_t)m) : 0;
-            xprow[q] = a.x + row * a.ldx + xchunk * 8;
-        }
-    }
-    char* xstage = reinterpret_cast<char*>(red) + wave * (U * XLP * 1024);
-    auto load_chunk = [&](int c, SkBuf8<MB, NT, U, XL>& b) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int kt = kt_begin + c * U + u;
-            const bool ok = kt < kt_end;
-#pragma unroll
-            for (int t = 0; t < NT; ++t)
-                b.w[u][t] = ok ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wbase[t] + (int64_t)kt * 1024)) : (u32x4){0u, 0u, 0u, 0u};
-            if constexpr (XL != 0) {
-                const int k = kt * 64 + xchunk * 8;
-#pragma unroll
-                for (int q = 0; q < XLP; ++q)
-                    b.xp[u][q] = (ok && xpvalid[q] && k < a.K) ? *reinterpret_cast<const u32x4*>(xprow[q] + (int64_t)kt * 64) : (u32x4){0u, 0u, 0u, 0u};
-            } else
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int k = kt * 64 + h * 32 + g * 8;
-#pragma unroll
-                for (int mb = 0; mb < MB; ++mb) b.x[u][h][mb] = (ok && xvalid[mb] && k < a.K) ? ldg_frag(xrow[mb] + k) : zero_frag();
-            }
-        }
-    };
-    auto consume = [&](SkBuf8<MB, NT, U, XL>& b) {
-        if constexpr (XL != 0) {       // pieces -> the wave's own LDS KiBs (row-major, XOR-swizzled by the row) -> B fragments
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int q = 0; q < XLP; ++q) *reinterpret_cast<u32x4*>(xstage + (u * XLP + q) * 1024 + lane * 16) = b.xp[u][q];
-            const int rr = XL == 1 ? (r & 7) : r;
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int mb = 0; mb < MB; ++mb)
-                        b.x[u][h][mb] = *reinterpret_cast<const bf16x8*>(xstage + u * (XLP * 1024) + (mb * 16 + rr) * 128 + (((h * 4 + g) ^ (rr & 7)) << 4));
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            bf16x8 wlo[NT], whi[NT];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) cvt_fp8x16(b.w[u][t], wscale[t], wlo[t], whi[t]);
-#pragma unroll
-            for (int t = 0; t < NT; ++t)
-#pragma unroll
-                for (int mb = 0; mb < MB; ++mb) acc[t][mb] = mfma16(wlo[t], b.x[u][0][mb], acc[t][mb]);
-#pragma unroll
-            for (int t = 0; t < NT; ++t)
-#pragma unroll
-                for (int mb = 0; mb < MB; ++mb) acc[t][mb] = mfma16(whi[t], b.x[u][1][mb], acc[t][mb]);
-        }
-    };
-    SkBuf8<MB, NT, U, XL> b0, b1;
-    if (nchunks > 0) load_chunk(0, b0);
-    for (int c = 0; c < nchunks; c += 2) {
-        if (c + 1 < nchunks) load_chunk(c + 1, b1);
-        consume(b0);
-        if (c + 1 < nchunks) {
-            if (c + 2 < nchunks) load_chunk(c + 2, b0);
-            consume(b1);
-        }
-    }
-    // cross-wave reduction + epilogue: identical to gemm_skinny_kernel (16-row tiles)
-    if constexpr (XL != 0) __syncthreads();      // the reduction buffer overlays the waves' x staging KiBs
-    constexpr int E4 = NT * MB;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb) reinterpret_cast<f32x4*>(red)[(wave * E4 + t * MB + mb) * 64 + lane] = acc[t][mb];
-    __syncthreads();
-    EpiCtx e{a.bias, a.residual, a.ldr, a.out, a.ldo, a.N, a.epilogue};
-    if (nsplit > 1) {
-        e.out = reinterpret_cast<float*>(a.out) + (int64_t)blockIdx.y * a.split_stride;
-        e.flags = UMV_EPI_OUT_F32;
-    }
-    if (a.epilogue & UMV_EPI_SWIGLU) {
-        for (int idx = tid; idx < (NT / 2) * MB * 64; idx += SK_WAVES * 64) {
-            int l = idx & 63;
-            int f = idx >> 6;
-            int pair = f / MB, mb = f % MB;
-            f32x4 sg = {0, 0, 0, 0}, su = {0, 0, 0, 0};
-#pragma unroll
-            for (int w = 0; w < SK_WAVES; ++w) {
-                sg += reinterpret_cast<f32x4*>(red)[(w * E4 + (2 * pair) * MB + mb) * 64 + l];
-                su += reinterpret_cast<f32x4*>(red)[(w * E4 + (2 * pair + 1) * MB + mb) * 64 + l];
-            }
-            int m = mb * 16 + (l & 15);
-            int ntile = nt0 + 2 * pair;
-            if (m < a.M && ntile < NTT) {
-                int64_t orow = a.row_idx ? (int64_t)a.row_idx[m] : (int64_t)m;
-                int c0 = (ntile >> 1) * 16 + (l >> 4) * 4;
-                float gg[4] = {sg.x, sg.y, sg.z, sg.w}, uu[4] = {su.x, su.y, su.z, su.w};
-                epi_swiglu4(e, orow, c0, a.N / 2, gg, uu);
-            }
-        }
-    } else {
-        for (int idx = tid; idx < E4 * 64; idx += SK_WAVES * 64) {
-            int l = idx & 63;
-            int f = idx >> 6;
-            int t = f / MB, mb = f % MB;
-            f32x4 s = {0, 0, 0, 0};
-#pragma unroll
-            for (int w = 0; w < SK_WAVES; ++w) s += reinterpret_cast<f32x4*>(red)[(w * E4 + f) * 64 + l];
-            int m = mb * 16 + (l & 15);
-            int n0 = (nt0 + t) * 16 + (l >> 4) * 4;
-            const bool valid = m < a.M && n0 < a.N;
-            float fin[4] = {0.f, 0.f, 0.f, 0.f};
-            if (valid) {
-                int64_t orow = a.row_idx ? (int64_t)a.row_idx[m] : (int64_t)m;
-                epi_store4(e, orow, n0, s.x, s.y, s.z, s.w, fin);
-            }
-            if (a.argmax_partial && nt0 + t < NTT)
-                epi_argmax_tile(a.argmax_partial, NTT, m, nt0 + t, l, valid, n0, a.N, fin, a.sample_temperature, a.sample_seed, a.sample_step);
-        }
-    }
-}
-
-static int skinny8_xl() {     // UMV_SKINNY8_XL: 0 never, 1 above 8 rows, 2 always (default; A/B only)
-    static const int v = umv_env_int("UMV_SKINNY8_XL", 2);
-    return v;
-}
-
-template <int MB, int NT, int U, int XL>
-static int launch_skinny8_v(const umv_gemm_args& a, int KT8, int NTT, hipStream_t s) {
-    int blocks = (NTT + NT - 1) / NT;
-    size_t lds = (size_t)SK_WAVES * NT * MB * 4 * 64 * sizeof(float);
-    if (XL != 0) {
-        const size_t xl = (size_t)SK_WAVES * U * (XL == 1 ? 1 : 2 * MB) * 1024;
-        if (xl > lds) lds = xl;
-        static bool attr_set[UMV_MAX_DEVICES] = {};
-        if (lds > 64 * 1024 && umv_first_on_device(attr_set))
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny8_kernel<MB, NT, U, XL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-    hipLaunchKernelGGL((gemm_skinny8_kernel<MB, NT, U, XL>), dim3(blocks, a.k_splits > 1 ? a.k_splits : 1), dim3(SK_WAVES * 64), lds, s, a,
-                       KT8, NTT);
-    UMV_LAUNCH_CHECK();
-    return UMV_OK;
+    gemm_skinny_body<SkE4m3<NT>, MB, U, true, 0, XL>(a, KT8, NTT, 0);
 }
 
 template <int MB, int NT, int U>
 static int launch_skinny8(const umv_gemm_args& a, int KT8, int NTT, hipStream_t s) {
-    const bool lines = (a.ldx % 64) == 0 && ((uintptr_t)a.x % 128) == 0;      // rows start on a 128-byte boundary
-    const int mode = skinny8_xl();
-    if (lines && mode && (mode > 1 || a.M > 8)) {
-        if constexpr (MB == 1) {
-            if (a.M <= 8) return launch_skinny8_v<MB, NT, U, 1>(a, KT8, NTT, s);
-        }
-        return launch_skinny8_v<MB, NT, U, 2>(a, KT8, NTT, s);
-    }
-    return launch_skinny8_v<MB, NT, U, 0>(a, KT8, NTT, s);
+    return launch_skinny_body<MB, NT, U, 2, 0>([](auto XL) { return &gemm_skinny8_kernel<MB, NT, U, decltype(XL)::value>; }, a, KT8, NTT, s,
+                                               KT8, NTT);
 }
 
 extern "C" int umv_gemm_fp8w(const umv_gemm_args* ap, umv_stream_t stream) {
@@ -1246,52 +732,6 @@ static int launch_tiled(const umv_gemm_args& a, int KT, int NTT, hipStream_t s) 
     return UMV_OK;
 }
 
-// full-line x staging of the weight-streaming kernels: 2 (default) = always, 1 = above 8 rows only, 0 = never (UMV_SKINNY_XL, A/B only).
-// Measured on MI355X (tools/skinny_bench.py, us, plain -> XL; profiles/r04_skinny_xl.txt): 32 rows qkv 21.3 -> 16.4, o 13.0 -> 9.9,
-// gate/up 59.3 -> 53.3, down 51.0 -> 34.8 (configs[3] decode step 4.445 -> 4.099 ms, 7199 -> 7807 tokens/s); 16 rows 14.3 -> 11.9 /
-// 9.0 -> 8.1 / 48.5 -> 47.2 / 33.5 -> 27.9.  At 8 rows the two-piece form costs gate/up its second resident workgroup (125 -> 142
-// registers: 42.4 -> 45.4 us), the ONE-piece form (rows 0..7 only, 124 registers) wins: gate/up 42.5 -> 41.4 (6.57 TB/s), down
-// 26.0 -> 24.7, qkv 11.4 -> 9.2, headline step 3.161 -> 3.111 ms.
-static int skinny_xl() {
-    static const int v = umv_env_int("UMV_SKINNY_XL", 2);
-    return v;
-}
-
-template <int MB, int NT, int U, bool DB, int NORM>
-static int launch_skinny(const umv_gemm_args& a, int KT, int NTT, hipStream_t s) {
-    int blocks = (NTT + NT - 1) / NT;
-    size_t lds = (size_t)SK_WAVES * NT * MB * 4 * 64 * sizeof(float);
-    if (NORM) lds += SK_WAVES * 16 * sizeof(float) + (size_t)KT * 4 * NORM * 16;
-    const int nsplit = a.k_splits > 1 ? a.k_splits : 1;
-    if constexpr (NORM == 0 && U % 2 == 0) {
-        // (rows that start on a 128-byte boundary, so that a k-tile pair is one cache line; any K, any split)
-        if ((skinny_xl() > 1 || (skinny_xl() == 1 && a.M > 8)) && (a.ldx % 64) == 0 && ((uintptr_t)a.x % 128) == 0) {
-            auto go = [&](auto XLV) {
-                constexpr int XL = decltype(XLV)::value;
-                size_t l2 = lds;
-                const size_t xl = (size_t)SK_WAVES * (U / 2) * (XL == 1 ? 1 : 2 * MB) * 1024;
-                if (xl > l2) l2 = xl;
-                static bool attr_set[UMV_MAX_DEVICES] = {};
-                if (l2 > 64 * 1024 && umv_first_on_device(attr_set))
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_kernel<MB, NT, U, DB, NORM, XL>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2);
-                hipLaunchKernelGGL((gemm_skinny_kernel<MB, NT, U, DB, NORM, XL>), dim3(blocks, nsplit), dim3(SK_WAVES * 64), l2, s, a, KT, NTT);
-            };
-            if constexpr (MB == 1) {
-                if (a.M <= 8) go(std::integral_constant<int, 1>{});
-                else go(std::integral_constant<int, 2>{});
-            } else {
-                go(std::integral_constant<int, 2>{});
-            }
-            UMV_LAUNCH_CHECK();
-            return UMV_OK;
-        }
-    }
-    hipLaunchKernelGGL((gemm_skinny_kernel<MB, NT, U, DB, NORM>), dim3(blocks, nsplit), dim3(SK_WAVES * 64), lds, s,
-                       a, KT, NTT);
-    UMV_LAUNCH_CHECK();
-    return UMV_OK;
-}
 
 // Tile choice from measurements on MI355X (tools/gemm_bench.py, profiles/r01_gemm_tiles_auto.txt).  The 256x256x32
 // 4-buffer tile with the interleaved schedule wins whenever it yields >= ~144 workgroups (885-1120 TF/s on the

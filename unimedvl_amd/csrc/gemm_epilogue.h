@@ -1,5 +1,6 @@
 // Shared GEMM epilogue for libunimedvl_hip (gfx950): bias / activation / SwiGLU / residual with a bf16 rounding
-// exactly where the reference materialises a bf16 tensor (see include/unimedvl_hip.h, umv_gemm_bf16).
+// exactly where the reference materialises a bf16 tensor (see include/unimedvl_hip.h, umv_gemm_bf16).  The weight-streaming
+// GEMM's cross-wave reduction around these pieces is in gemm_skinny.h.
 #pragma once
 #include "common.h"
 #include "../../include/unimedvl_hip.h"
@@ -533,65 +534,5 @@ __device__ __forceinline__ bool epi_wave_tile_lean_any(int kind, const umv_gemm_
         if constexpr (TN % 2 == 0) { epi_wave_tile_lean<TN, TM, 8>(a, acc, wreg, lane, m_wave0, nt_base, bias_tile); return true; }
         return false;
     default: return false;
-    }
-}
-
-// Cross-wave reduction and epilogue of gemm_skinny4_kernel (gemm_mxfp4.hip), the code gemm_skinny8_kernel has inline (kept there
-// as it is: folding it into this call changes that kernel's register allocation): every wave parks its NT x MB accumulator fragments in `red` ([SK waves][NT*MB][64] f32x4), the sums run in wave order 0..NW-1,
-// then bias / activation / residual / SwiGLU or, for split-K (nsplit > 1), the raw fp32 partial sums of split blockIdx.y.
-// The caller has made `red` free (no wave still reads its x staging there).
-template <int NW, int NT, int MB>
-__device__ __forceinline__ void skinny16_reduce_epilogue(const umv_gemm_args& a, float* red, const f32x4 (&acc)[NT][MB], int tid,
-                                                         int lane, int wave, int nt0, int NTT, int nsplit) {
-    constexpr int E4 = NT * MB;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb) reinterpret_cast<f32x4*>(red)[(wave * E4 + t * MB + mb) * 64 + lane] = acc[t][mb];
-    __syncthreads();
-    EpiCtx e{a.bias, a.residual, a.ldr, a.out, a.ldo, a.N, a.epilogue};
-    if (nsplit > 1) {
-        e.out = reinterpret_cast<float*>(a.out) + (int64_t)blockIdx.y * a.split_stride;
-        e.flags = UMV_EPI_OUT_F32;
-    }
-    if (a.epilogue & UMV_EPI_SWIGLU) {
-        for (int idx = tid; idx < (NT / 2) * MB * 64; idx += NW * 64) {
-            int l = idx & 63;
-            int f = idx >> 6;
-            int pair = f / MB, mb = f % MB;
-            f32x4 sg = {0, 0, 0, 0}, su = {0, 0, 0, 0};
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                sg += reinterpret_cast<f32x4*>(red)[(w * E4 + (2 * pair) * MB + mb) * 64 + l];
-                su += reinterpret_cast<f32x4*>(red)[(w * E4 + (2 * pair + 1) * MB + mb) * 64 + l];
-            }
-            int m = mb * 16 + (l & 15);
-            int ntile = nt0 + 2 * pair;
-            if (m < a.M && ntile < NTT) {
-                int64_t orow = a.row_idx ? (int64_t)a.row_idx[m] : (int64_t)m;
-                int c0 = (ntile >> 1) * 16 + (l >> 4) * 4;
-                float gg[4] = {sg.x, sg.y, sg.z, sg.w}, uu[4] = {su.x, su.y, su.z, su.w};
-                epi_swiglu4(e, orow, c0, a.N / 2, gg, uu);
-            }
-        }
-    } else {
-        for (int idx = tid; idx < E4 * 64; idx += NW * 64) {
-            int l = idx & 63;
-            int f = idx >> 6;
-            int t = f / MB, mb = f % MB;
-            f32x4 s = {0, 0, 0, 0};
-#pragma unroll
-            for (int w = 0; w < NW; ++w) s += reinterpret_cast<f32x4*>(red)[(w * E4 + f) * 64 + l];
-            int m = mb * 16 + (l & 15);
-            int n0 = (nt0 + t) * 16 + (l >> 4) * 4;
-            const bool valid = m < a.M && n0 < a.N;
-            float fin[4] = {0.f, 0.f, 0.f, 0.f};
-            if (valid) {
-                int64_t orow = a.row_idx ? (int64_t)a.row_idx[m] : (int64_t)m;
-                epi_store4(e, orow, n0, s.x, s.y, s.z, s.w, fin);
-            }
-            if (a.argmax_partial && nt0 + t < NTT)
-                epi_argmax_tile(a.argmax_partial, NTT, m, nt0 + t, l, valid, n0, a.N, fin, a.sample_temperature, a.sample_seed, a.sample_step);
-        }
     }
 }

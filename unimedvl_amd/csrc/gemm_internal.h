@@ -1,5 +1,6 @@
 // Pieces shared by the tiled GEMM kernels of libunimedvl_hip (gemm.hip, gemm_w4.hip): the workgroup -> tile order, the
-// instruction slots of the interleaved schedules, and the launcher of the 4-wave kernels.  Internal to csrc/.
+// instruction slots of the interleaved schedules, the launcher of the 4-wave kernels, and the environment knobs of every GEMM
+// launcher.  The weight-streaming decode GEMM is gemm_skinny.h, the weight formats' conversions quant.h.  Internal to csrc/.
 #pragma once
 #include "common.h"
 #include "../../include/unimedvl_hip.h"
@@ -63,19 +64,3 @@ static inline int umv_tile_superblock(int mblocks, int BM, int K) {
 int umv_gemm_lean_epilogue(const umv_gemm_args& a);      // gemm.hip: >= 0 = the lean epilogue kind of this call, -1 = general
 bool umv_gemm_w4_can_take(const umv_gemm_args& a, int KT, int NTT);
 int umv_gemm_w4_launch(const umv_gemm_args& a, int KT, int NTT, int cfg, int gn, hipStream_t s);
-
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_hw;
-// 16 e4m3 values x one power-of-two scale -> 16 bf16 (exact: an e4m3 value times 2^e is a bf16 value)
-__device__ __forceinline__ void cvt_fp8x16(u32x4 q, float scale, bf16x8& lo, bf16x8& hi) {
-    union { bf16x2_hw h[4]; bf16x8 v; } a, b;
-    a.h[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q.x, scale, false);
-    a.h[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q.x, scale, true);
-    a.h[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q.y, scale, false);
-    a.h[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q.y, scale, true);
-    b.h[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q.z, scale, false);
-    b.h[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q.z, scale, true);
-    b.h[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q.w, scale, false);
-    b.h[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q.w, scale, true);
-    lo = a.v;
-    hi = b.v;
-}

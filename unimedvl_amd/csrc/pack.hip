@@ -5,12 +5,13 @@
 //          interleaved, umv_pack_weight_swiglu_bf16); Q[n/th][k/32][g][r < th][8] = the same with th-row tiles for the decode GEMM
 //   e4m3   P8[n/16][k/64][lane][16 B] + one power-of-two fp32 scale per output channel (umv_quantize_pack_weight_fp8), and the
 //          K = 128 image of the scaled fp8 MFMA made from it (umv_repack_weight_fp8_mfma)
+//   MXFP4  C[pair of 16-row tiles][k/64][lane][16 B] e2m1 codes, then E8M0 scales per 32 k (umv_quantize_pack_weight_mxfp4)
 //
-// This file (with PACK_LAYOUT_VERSION) is what unimedvl_amd/packstore.py stamps its on-disk cache of packed images with: an edit here
-// invalidates the cache, an edit of a GEMM / attention / vision kernel does not.
+// This file and the headers it includes (with PACK_LAYOUT_VERSION) are what unimedvl_amd/packstore.py stamps its on-disk cache of
+// packed images with: an edit here invalidates the cache, an edit of a GEMM / attention / vision kernel does not.
 #include "common.h"
 #include "../../include/unimedvl_hip.h"
-#include "gemm_internal.h"
+#include "quant.h"
 #include <stdlib.h>
 
 // ----------------------------------------------------------------------------- bf16 images
@@ -228,3 +229,115 @@ extern "C" int umv_repack_weight_fp8_mfma(const uint8_t* packed8, uint8_t* out, 
     return UMV_OK;
 }
 
+// ----------------------------------------------------------------------------- MXFP4 images
+// e2m1 codes with one E8M0 power-of-two scale per 32 consecutive k of a row (decode GEMM: gemm_mxfp4.hip).
+// Format (include/unimedvl_hip.h): s = 2^e, e the smallest integer with 6 * 2^e >= max|W[block]| (6 = the largest e2m1 value, so
+// nothing is clipped), clamped to [-127, 127], e = 0 for an all-zero block; q = rne_e2m1(W / s) with the sign kept (a negative value
+// that rounds to zero is code 8, -0); W' = q * s is exact in bf16.
+//
+// Image (one buffer, NP = ceil(ceil(N/16) / 2) pairs of 16-row tiles, KT8 = ceil(K/64)):
+//   codes  C[p][kt8][lane = g*16 + r][16 B]   bytes  0..3  <-> tile 2p,   row r, k = kt8*64 +      g*8 + j  (nibble j of the 4 bytes,
+//                                             bytes  4..7  <-> tile 2p,   row r, k = kt8*64 + 32 + g*8 + j   low nibble first)
+//                                             bytes  8..11 <-> tile 2p+1, row r, k = kt8*64 +      g*8 + j
+//                                             bytes 12..15 <-> tile 2p+1, row r, k = kt8*64 + 32 + g*8 + j
+//   scales S[p][kt8][r][4 B] at byte NP*KT8*1024: E8M0 of (tile 2p, k block 2*kt8), (2p, 2*kt8+1), (2p+1, 2*kt8), (2p+1, 2*kt8+1)
+// One lane load of 16 B covers two n-tiles x 64 k: a wave's unit of work along k is 64, as for the e4m3 image, so the 8-wave K
+// partition is the bf16 kernel's.  Padding rows / k are zero codes with scale byte 127.  SwiGLU images interleave the gate and up
+// 16-row tiles like the bf16 one, so a pair is (gate tile t, up tile t).
+//
+// One workgroup (256 threads) per tile pair: block scales into LDS and the image, then the codes (+ optional W' in bf16, converted
+// by the decode kernel's instruction).  LDS: 32 rows x 2*KT8 scale bytes.
+__global__ __launch_bounds__(256) void quantize_pack_mxfp4_kernel(const bf16_t* __restrict__ w, const bf16_t* __restrict__ w2,
+                                                                  uint8_t* __restrict__ img, bf16_t* __restrict__ deq,
+                                                                  bf16_t* __restrict__ deq2, int rows, int K, int KT8, int NTT, int NP) {
+    extern __shared__ uint8_t sexp[];       // [2 tiles][16 rows][2*KT8]
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const bool inter = w2 != nullptr;
+    const int KB = 2 * KT8;
+    // which source row a (tile of this pair, row) is, or -1
+    auto src_row = [&](int i, int r, const bf16_t*& src, bf16_t*& dq) -> int {
+        const int t = 2 * p + i;
+        src = (inter && (t & 1)) ? w2 : w;
+        dq = (inter && (t & 1)) ? deq2 : deq;
+        const int n = (inter ? (t >> 1) : t) * 16 + r;
+        return (t < NTT && n < rows) ? n : -1;
+    };
+    uint8_t* scales = img + (int64_t)NP * KT8 * 1024;
+    for (int idx = tid; idx < 32 * KB; idx += 256) {      // one thread per (tile, row, 32-k block)
+        const int kb = idx % KB, rr = idx / KB, i = rr >> 4, r = rr & 15;
+        const bf16_t* src;
+        bf16_t* dq;
+        const int n = src_row(i, r, src, dq);
+        uint32_t amax = 0;
+        if (n >= 0 && kb * 32 < K) {
+            const u32x4* q = reinterpret_cast<const u32x4*>(src + (int64_t)n * K + kb * 32);    // K % 32 == 0: 64 aligned bytes
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const u32x4 x = q[v];
+                const uint32_t wd[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) amax = max(amax, max(wd[j] & 0x7FFFu, (wd[j] >> 16) & 0x7FFFu));
+            }
+        }
+        const uint32_t sb = mxfp4_scale_byte(amax);
+        sexp[rr * KB + kb] = (uint8_t)sb;
+        scales[((int64_t)p * KT8 + (kb >> 1)) * 64 + r * 4 + i * 2 + (kb & 1)] = (uint8_t)sb;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < KT8 * 64; idx += 256) {      // one thread per (kt8, lane) 16-byte group
+        const int lane = idx & 63, kt8 = idx >> 6;
+        const int r = lane & 15, g = lane >> 4;
+        uint32_t o[4];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const bf16_t* src;
+            bf16_t* dq;
+            const int n = src_row(i, r, src, dq);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int kb = kt8 * 2 + h;
+                const int k0 = kb * 32 + g * 8;
+                const uint32_t sb = sexp[(i * 16 + r) * KB + kb];
+                uint32_t word = 0;
+                if (n >= 0 && k0 < K) {
+                    const u32x4 x = *reinterpret_cast<const u32x4*>(src + (int64_t)n * K + k0);
+                    const uint32_t wd[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        word |= e2m1_code((uint16_t)(wd[j] & 0xFFFFu), (int)sb - 127) << (8 * j);
+                        word |= e2m1_code((uint16_t)(wd[j] >> 16), (int)sb - 127) << (8 * j + 4);
+                    }
+                    if (dq) {
+                        const bf16x8 d = cvt_fp4x8(word, e8m0_scale(sb));
+                        *reinterpret_cast<bf16x8*>(dq + (int64_t)n * K + k0) = d;
+                    }
+                }
+                o[2 * i + h] = word;
+            }
+        }
+        *reinterpret_cast<u32x4*>(img + (((int64_t)p * KT8 + kt8) * 64 + lane) * 16) = (u32x4){o[0], o[1], o[2], o[3]};
+    }
+}
+
+extern "C" size_t umv_packed_weight_mxfp4_bytes(int N, int K) {
+    if (N <= 0 || K <= 0) return 0;
+    const size_t np = ((size_t)(N + 15) / 16 + 1) / 2, kt8 = (size_t)(K + 63) / 64;
+    return np * kt8 * (1024 + 64);
+}
+
+extern "C" int umv_quantize_pack_weight_mxfp4(const uint16_t* w, const uint16_t* w_up, uint8_t* packed4, uint16_t* deq,
+                                              uint16_t* deq_up, int rows, int K, umv_stream_t stream) {
+    UMV_CHECK(w && packed4 && rows > 0 && K > 0, UMV_ERR_ARG, "quantize_pack_weight_mxfp4: bad args");
+    UMV_CHECK((K % 32) == 0 && K <= 65536, UMV_ERR_ARG, "quantize_pack_weight_mxfp4: K (%d) must be a multiple of 32 (the block) and <= 65536",
+              K);
+    UMV_CHECK(!w_up || (rows % 16) == 0, UMV_ERR_ARG, "quantize_pack_weight_mxfp4: SwiGLU image needs I %% 16 == 0 (I=%d)", rows);
+    UMV_CHECK(!(deq_up && !w_up), UMV_ERR_ARG, "quantize_pack_weight_mxfp4: deq_up without w_up");
+    UMV_CHECK(((uintptr_t)w | (uintptr_t)w_up | (uintptr_t)deq | (uintptr_t)deq_up | (uintptr_t)packed4) % 16 == 0, UMV_ERR_ARG,
+              "quantize_pack_weight_mxfp4: every buffer must be 16-byte aligned");
+    const int NTT = (w_up ? 2 : 1) * ((rows + 15) / 16), NP = (NTT + 1) / 2, KT8 = (K + 63) / 64;
+    const size_t lds = (size_t)32 * 2 * KT8;
+    hipLaunchKernelGGL(quantize_pack_mxfp4_kernel, dim3(NP), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)w, (const bf16_t*)w_up,
+                       packed4, (bf16_t*)deq, (bf16_t*)deq_up, rows, K, KT8, NTT, NP);
+    UMV_LAUNCH_CHECK();
+    return UMV_OK;
+}

@@ -24,20 +24,21 @@ import uuid
 import torch
 
 PACK_LAYOUT_VERSION = "umv-pack-1"     # P[n/16][k/32][lane][8] bf16; P8[n/16][k/64][lane][16 B] e4m3 + f32 pow2 scales; P8M fp8-MFMA image;
-                                        # MXFP4 codes + E8M0 block scales in one image (csrc/gemm_mxfp4.hip)
+                                        # MXFP4 codes + E8M0 block scales in one image (csrc/pack.hip)
+# the sources that decide the bytes of a packed image: the packers and what their #include chain reaches
+PACK_SOURCES = ("csrc/pack.hip", "csrc/quant.h", "csrc/common.h", "../include/unimedvl_hip.h")
 _LIN_FIELDS = ("wp", "bias", "w8", "scale", "w8m", "w4")
 
 
 def kernel_stamp():
-    """sha256 of PACK_LAYOUT_VERSION + the sources that decide the bytes of a packed image: csrc/pack.hip, csrc/gemm_mxfp4.hip (the MXFP4
-    packer) and the headers they include (common.h: the bf16 rounding helpers; gemm_internal.h: cvt_fp8x16 behind the deq / w8 images;
-    the public header).  None when a
+    """sha256 of PACK_LAYOUT_VERSION + PACK_SOURCES: csrc/pack.hip (every packer) and the headers it includes (quant.h: the e4m3 / MXFP4
+    conversions behind the deq / w8 / w4 images; common.h: the bf16 rounding helpers; the public header).  None when a
     source is not there - a cache whose maker cannot be identified is never trusted (and two unknowns never compare equal)"""
     import hashlib
     here = os.path.dirname(os.path.abspath(__file__))
     h = hashlib.sha256(PACK_LAYOUT_VERSION.encode())
     try:
-        for rel in ("csrc/pack.hip", "csrc/gemm_mxfp4.hip", "csrc/common.h", "csrc/gemm_internal.h", "../include/unimedvl_hip.h"):
+        for rel in PACK_SOURCES:
             with open(os.path.join(here, rel), "rb") as f:
                 h.update(f.read())
     except OSError:
