@@ -146,6 +146,13 @@ int umv_quantize_pack_weight_mxfp4(const uint16_t* w, const uint16_t* w_up, uint
 /* M <= 64 only; a->wp = the MXFP4 image, a->w_scale = NULL; BIAS, RESIDUAL, SWIGLU, OUT_F32, row_idx and split-K partials as
  * umv_gemm_bf16; norm_w, th-row tiles and argmax_partial unsupported */
 int umv_gemm_mxfp4w(const umv_gemm_args* a, umv_stream_t stream);
+/* M > 64: the MFMA-tiled GEMM on the SAME MXFP4 image (a->wp), a->w_scale = NULL, K % 32 == 0 - an fp4 linear then needs no bf16 image
+ * of W'.  BIAS, RESIDUAL, SWIGLU, OUT_F32, row_idx as umv_gemm_bf16; with k_splits > 1 (M <= 128) raw fp32 partials over umv_gemm_bf16's
+ * K ranges (ceil(K/32 / k_splits) k-tiles of 32 per split, an empty range writes zeros).  One accumulator chain per output over k in
+ * ascending 32-wide steps on v_mfma_f32_16x16x32_bf16:
+ *   umv_gemm_mxfp4t(x, img)  ==  umv_gemm_bf16(x, pack(W'))   bit for bit, every M > 64, split-K partials included
+ * norm_w, argmax_partial, th-row tiles and M <= 64 are UMV_ERR_UNSUPPORTED */
+int umv_gemm_mxfp4t(const umv_gemm_args* a, umv_stream_t stream);
 
 /* W8A8 on the fp8 matrix instruction (v_mfma_scale_f32_16x16x128_f8f6f4) for the MFMA-bound GEMMs of the fp8 mode
  * (M > 64: prefill, flow passes).  Activations are quantised per ROW the way weights are per channel:

@@ -72,6 +72,19 @@ static void bad_arguments() {
     EXPECT_ERR(umv_gemm_mxfp4w(&g, nullptr));
     g.w_scale = nullptr; g.argmax_partial = (uint64_t*)dummyl;  // lm_head stays e4m3
     EXPECT_ERR(umv_gemm_mxfp4w(&g, nullptr));
+    EXPECT_ERR(umv_gemm_mxfp4t(nullptr, nullptr));
+    std::memset(&g, 0, sizeof g);
+    EXPECT_ERR(umv_gemm_mxfp4t(&g, nullptr));                  // null x / wp / out
+    g.x = dummy16; g.wp = dummy16; g.out = dummy16; g.M = 65; g.N = 16; g.K = 48;      // K % 32 != 0
+    EXPECT_ERR(umv_gemm_mxfp4t(&g, nullptr));
+    g.K = 64; g.M = 64;                                         // the tiled kernel starts at 65 rows
+    EXPECT_ERR(umv_gemm_mxfp4t(&g, nullptr));
+    g.M = 65; g.w_scale = dummyf;                               // the scales are part of the image
+    EXPECT_ERR(umv_gemm_mxfp4t(&g, nullptr));
+    g.w_scale = nullptr; g.norm_w = dummy16;                    // no fused norm
+    EXPECT_ERR(umv_gemm_mxfp4t(&g, nullptr));
+    g.norm_w = nullptr; g.argmax_partial = (uint64_t*)dummyl;   // lm_head stays e4m3
+    EXPECT_ERR(umv_gemm_mxfp4t(&g, nullptr));
     std::memset(&g, 0, sizeof g);
     EXPECT_ERR(umv_gemm_fp8a8w(nullptr, nullptr));
     umv_gemm8_args g8;

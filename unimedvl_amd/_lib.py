@@ -88,6 +88,7 @@ _SIGS = {
     "umv_quantize_pack_weight_mxfp4": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                                  C.c_void_p]),
     "umv_gemm_mxfp4w": (C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
+    "umv_gemm_mxfp4t": (C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
     "umv_residual_rmsnorm_bf16": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                             C.c_int, C.c_float, C.c_void_p]),
     "umv_rmsnorm_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,

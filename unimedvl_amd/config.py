@@ -23,6 +23,10 @@ class UniMedVLConfig:
     # linear layers and lm_head (BASELINE.json configs[4]; include/unimedvl_hip.h umv_quantize_pack_weight_fp8), or "fp4": MXFP4
     # (e2m1, one power-of-two scale per 32 k; umv_quantize_pack_weight_mxfp4) for the linears of both experts, lm_head in e4m3
     llm_weight_dtype: str = "bf16"
+    # False (needs llm_weight_dtype == "fp4"): the fp4 linears carry no bf16 image of their dequantised weights - prefill, the flow passes
+    # and 65..128-row decode steps run the tiled GEMM on the MXFP4 image (umv_gemm_mxfp4t; same bits, 10.6 GB resident for the whole engine,
+    # 65..128-sample decode steps 4-7 % faster, prefill GEMMs 1.2-2.0x slower: DESIGN.md section 5.1)
+    llm_fp4_keep_bf16: bool = True
     # "fp8" (needs llm_weight_dtype == "fp8"): W8A8 - every LLM forward that is not a one-token decode step rounds the
     # activations of its linear layers per row through e4m3 and runs them on the fp8 matrix instruction
     # (umv_gemm_fp8a8w); decode steps keep bf16 activations on the e4m3 weight stream

@@ -115,8 +115,9 @@ class DecodeSession:
             # makes the exact-partition copy of the o_proj weights unnecessary)
             # 65..128 rows: the same scheme on the 128 x 128 MFMA tile (umv_gemm_bf16 routes k_splits > 1 there above 64 rows):
             # without it down_proj is 14 workgroups of 256 x 256 (151 us); bf16 weights only (the e4m3 image is an M <= 64 layout)
-            # MXFP4 weights take both branches: up to 64 rows the split partials of umv_gemm_mxfp4w, 65..128 rows the bf16 image of
-            # the dequantised weights that every fp4 linear carries (ops.gemm_splitk routes by rows)
+            # MXFP4 weights take both branches: up to 64 rows the split partials of umv_gemm_mxfp4w; 65..128 rows the same K ranges on
+            # the tiled MXFP4 kernel (umv_gemm_mxfp4t) when the linears carry no bf16 image of their dequantised weights
+            # (llm_fp4_keep_bf16=False), else umv_gemm_bf16 on that image - ops.gemm_splitk routes by rows and by what the linear holds
             sk = "3,4,4" if B <= 64 else ("6,8,8" if B <= 128 and not getattr(w, "fp8", False) else "0")
         self.sk = (1, 1, 1) if sk in ("0", "") else tuple(max(1, int(v)) for v in sk.split(","))
         if len(self.sk) != 3 or any(v > 64 for v in self.sk):

@@ -98,6 +98,8 @@ class VQAInferencer:
             # optional extras over the reference's config keys: "checkpoint_weight_path" overlays a fine-tuned checkpoint on the
             # base one (eval/vlm/utils.py:71-98); "llm_weight_dtype": "fp8" / "fp4" streams e4m3 / MXFP4 LLM weights at decode
             cfg.llm_weight_dtype = self.config.get("llm_weight_dtype", "bf16")
+            # "llm_fp4_keep_bf16": False (with "fp4") keeps only the MXFP4 images of the LLM linears: every row count runs on them
+            cfg.llm_fp4_keep_bf16 = bool(self.config.get("llm_fp4_keep_bf16", True))
             get = checkpoint_getter(model_path, all_shapes(cfg), self.config.get("checkpoint_weight_path"),
                                     self.config["use_model_checkpoint"])
             # fast path (not a reference key; the counterpart of its one-time ema_bf16.safetensors conversion,

@@ -71,9 +71,17 @@ class PackedLinear:
         # optional: the e4m3 image re-tiled for the fp8 matrix instruction; when present, GEMMs with M > 64 rows quantise
         # their activations per row and run W8A8 (enable_fp8_mfma)
         self.w8m = None
-        # MXFP4 weights (llm_weight_dtype="fp4"): w4 = the e2m1 + block-scale image streamed by the decode GEMM (M <= 64); wp is
-        # then the bf16 image of the SAME dequantised weights for M > 64
+        # MXFP4 weights (llm_weight_dtype="fp4"): w4 = the e2m1 + block-scale image, streamed by the decode GEMM (M <= 64) and read by
+        # the tiled MXFP4 GEMM above that; wp is then either the bf16 image of the SAME dequantised weights (M > 64 runs on it when it is
+        # there: bit-identical) or None (keep_bf16=False / drop_bf16: the linear stands on its 4-bit image alone)
         self.w4 = w4
+
+    def drop_bf16(self):
+        """Release the bf16 image of the dequantised weights of an fp4 linear: M > 64 then runs the tiled GEMM on the MXFP4 image."""
+        if self.w4 is None:
+            raise _lib.UmvError("drop_bf16 needs MXFP4 weights (from_weight_mxfp4 / from_gate_up_mxfp4)")
+        self.wp = None
+        return self
 
     def enable_fp8_mfma(self, keep_bf16=False):
         """Build the fp8-MFMA image from the e4m3 image; the bf16 image of the dequantised weights is dropped unless asked."""
@@ -122,12 +130,16 @@ class PackedLinear:
         return lin
 
     @staticmethod
-    def from_weight_mxfp4(w, bias=None):
-        """Quantise an nn.Linear weight to MXFP4 (e2m1, one power-of-two scale per 32 k); see include/unimedvl_hip.h."""
+    def from_weight_mxfp4(w, bias=None, keep_bf16=True):
+        """Quantise an nn.Linear weight to MXFP4 (e2m1, one power-of-two scale per 32 k); see include/unimedvl_hip.h.
+        keep_bf16=False: no bf16 image of the dequantised weights is built (not even as scratch)."""
         lib = _lib.load()
         w = _req(w.contiguous(), BF16, "weight")
         N, K = w.shape
         w4 = torch.empty(lib.umv_packed_weight_mxfp4_bytes(N, K), dtype=torch.uint8, device=w.device)
+        if not keep_bf16:
+            check(lib.umv_quantize_pack_weight_mxfp4(_p(w), None, _p(w4), None, None, N, K, _stream()), "umv_quantize_pack_weight_mxfp4")
+            return PackedLinear(None, None if bias is None else bias.contiguous(), N, K, w4=w4)
         deq = torch.empty_like(w)
         check(lib.umv_quantize_pack_weight_mxfp4(_p(w), None, _p(w4), _p(deq), None, N, K, _stream()), "umv_quantize_pack_weight_mxfp4")
         lin = PackedLinear.from_weight(deq, bias)
@@ -135,13 +147,17 @@ class PackedLinear:
         return lin
 
     @staticmethod
-    def from_gate_up_mxfp4(gate, up):
+    def from_gate_up_mxfp4(gate, up, keep_bf16=True):
         lib = _lib.load()
         gate = _req(gate.contiguous(), BF16, "gate")
         up = _req(up.contiguous(), BF16, "up")
         I, K = gate.shape
         assert I % 16 == 0, "intermediate size must be a multiple of 16"
         w4 = torch.empty(lib.umv_packed_weight_mxfp4_bytes(2 * I, K), dtype=torch.uint8, device=gate.device)
+        if not keep_bf16:
+            check(lib.umv_quantize_pack_weight_mxfp4(_p(gate), _p(up), _p(w4), None, None, I, K, _stream()),
+                  "umv_quantize_pack_weight_mxfp4")
+            return PackedLinear(None, None, 2 * I, K, swiglu=True, w4=w4)
         dg, du = torch.empty_like(gate), torch.empty_like(up)
         check(lib.umv_quantize_pack_weight_mxfp4(_p(gate), _p(up), _p(w4), _p(dg), _p(du), I, K, _stream()),
               "umv_quantize_pack_weight_mxfp4")
@@ -187,7 +203,7 @@ class PackedLinear:
         return PackedLinear(wp, None, 2 * I, K, swiglu=True)
 
     def nbytes(self):
-        return self.wp.numel() * 2
+        return self.wp.numel() * 2 if self.wp is not None else self.w4.numel()
 
 
 def gemm(x, lin, out=None, *, M=None, residual=None, act=None, row_idx=None, out_f32=False, use_bias=True,
@@ -237,7 +253,12 @@ def gemm(x, lin, out=None, *, M=None, residual=None, act=None, row_idx=None, out
     use_a8 = act8 and M > 64 and norm_w is None and not out_f32       # fp8 matrix instruction, e4m3 activations
     use_w8 = lin.w8 is not None and M <= 64 and norm_w is None        # weight-streaming kernel on the e4m3 image
     use_w4 = lin.w4 is not None and M <= 64 and norm_w is None        # weight-streaming kernel on the MXFP4 image
-    if lin.wp is None and not use_a8 and not use_w8 and not use_w4:
+    use_w4t = lin.w4 is not None and lin.wp is None and M > 64 and norm_w is None and amax is None    # tiled kernel on the MXFP4 image
+    if lin.wp is None and lin.w4 is not None and not use_w4 and not use_w4t:
+        raise _lib.UmvError(f"this linear only has its fp4 (MXFP4) image (built with keep_bf16=False / drop_bf16): M={M} rows with "
+                            f"norm_w={'set' if norm_w is not None else 'None'}, argmax_partial={'set' if amax is not None else 'None'} need "
+                            "the bf16 kernel - build the weights with keep_bf16=True (llm_fp4_keep_bf16=True)")
+    if lin.wp is None and not use_a8 and not use_w8 and not use_w4 and not use_w4t:
         raise _lib.UmvError(f"this linear only has fp8 images (the bf16 image was dropped by enable_fp8_mfma): M={M} rows with "
                             f"act8={act8}, out_f32={out_f32}, norm_w={'set' if norm_w is not None else 'None'} need the bf16 kernel - "
                             "build the weights with enable_fp8_mfma(keep_bf16=True)")
@@ -256,7 +277,7 @@ def gemm(x, lin, out=None, *, M=None, residual=None, act=None, row_idx=None, out
             row_idx=row_idx.data_ptr() if row_idx is not None else None, M=M, N=lin.N, K=lin.K, epilogue=flags)
         check(lib.umv_gemm_fp8a8w(C.byref(a8), _stream()), "umv_gemm_fp8a8w")
         return out
-    if use_w4:
+    if use_w4 or use_w4t:
         a = GemmArgs(
             x=x.data_ptr(), ldx=x.stride(0), wp=lin.w4.data_ptr(),
             bias=lin.bias.data_ptr() if (flags & EPI_BIAS) else None,
@@ -265,7 +286,10 @@ def gemm(x, lin, out=None, *, M=None, residual=None, act=None, row_idx=None, out
             out=out.data_ptr(), ldo=out.stride(0),
             row_idx=row_idx.data_ptr() if row_idx is not None else None,
             M=M, N=lin.N, K=lin.K, epilogue=flags, norm_w=None, norm_eps=norm_eps, tile_rows=0, argmax_partial=amax)
-        check(lib.umv_gemm_mxfp4w(C.byref(a), _stream()), "umv_gemm_mxfp4w")
+        if use_w4t:
+            check(lib.umv_gemm_mxfp4t(C.byref(a), _stream()), "umv_gemm_mxfp4t")
+        else:
+            check(lib.umv_gemm_mxfp4w(C.byref(a), _stream()), "umv_gemm_mxfp4w")
         return out
     if use_w8:
         a = GemmArgs(
@@ -478,9 +502,12 @@ def gemm_splitk(x, lin, partials, k_splits, *, M=None):
     if lin.w8 is not None:   # e4m3 image: same split, same consumers
         a.wp, a.w_scale = lin.w8.data_ptr(), lin.scale.data_ptr()
         check(lib.umv_gemm_fp8w(C.byref(a), _stream()), "umv_gemm_fp8w")
-    elif lin.w4 is not None and M <= 64:    # MXFP4 image; above 64 rows the bf16 image of W' (the tiled split-K kernel)
+    elif lin.w4 is not None and M <= 64:    # MXFP4 image, weight-streaming kernel
         a.wp = lin.w4.data_ptr()
         check(lib.umv_gemm_mxfp4w(C.byref(a), _stream()), "umv_gemm_mxfp4w")
+    elif lin.w4 is not None and lin.wp is None:   # 65..128 rows without a bf16 image of W': the tiled kernel on the MXFP4 image (same partials)
+        a.wp = lin.w4.data_ptr()
+        check(lib.umv_gemm_mxfp4t(C.byref(a), _stream()), "umv_gemm_mxfp4t")
     else:
         check(lib.umv_gemm_bf16(C.byref(a), _stream()), "umv_gemm_bf16")
     return partials

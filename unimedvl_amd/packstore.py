@@ -224,6 +224,8 @@ class PackStore:
 def attach(get, model_path, device, cfg, source_files, enabled=True, extra_tag=""):
     """Give the checkpoint getter `get` a PackStore for `<model_path>/ema_packed_<dtypes>.safetensors`."""
     from . import shapes
+    if cfg.llm_weight_dtype == "fp4" and not getattr(cfg, "llm_fp4_keep_bf16", True):
+        extra_tag = "-standalone" + extra_tag      # fp4 linears without their bf16 images: a file of its own (no wp stored for them)
     tag = f"w-{cfg.llm_weight_dtype}_a-{cfg.llm_act_dtype}{extra_tag}"
     try:
         expected = shapes.all_shapes(cfg)

@@ -44,12 +44,12 @@ def _tensor(get, device, name):
     return _store(get).tensor(name, lambda: _dev(get(name), device))
 
 
-def _linear(get, device, wname, bname=None, fp8=False, fp4=False):
+def _linear(get, device, wname, bname=None, fp8=False, fp4=False, keep_bf16=True):
     def build():
         w = _dev(get(wname), device)
         b = _dev(get(bname), device) if bname else None
         if fp4:
-            return ops.PackedLinear.from_weight_mxfp4(w, b)
+            return ops.PackedLinear.from_weight_mxfp4(w, b, keep_bf16=keep_bf16)
         return ops.PackedLinear.from_weight_fp8(w, b) if fp8 else ops.PackedLinear.from_weight(w, b)
     return _store(get).linear(wname, build)
 
@@ -61,6 +61,8 @@ def check_llm_dtypes(cfg: UniMedVLConfig):
         raise ValueError(f"llm_weight_dtype must be 'bf16', 'fp8' or 'fp4', got {cfg.llm_weight_dtype!r}")
     if cfg.llm_act_dtype not in ("bf16", "fp8") or (cfg.llm_act_dtype == "fp8" and cfg.llm_weight_dtype != "fp8"):
         raise ValueError("llm_act_dtype must be 'bf16', or 'fp8' together with llm_weight_dtype='fp8'")
+    if not cfg.llm_fp4_keep_bf16 and cfg.llm_weight_dtype != "fp4":
+        raise ValueError("llm_fp4_keep_bf16=False needs llm_weight_dtype='fp4' (it drops the bf16 images of the fp4 linears)")
 
 
 class LLMWeights:
@@ -73,11 +75,13 @@ class LLMWeights:
         # "fp4": MXFP4 for the seven linears of both experts; lm_head stays e4m3 (fused argmax / sampling, 8 bits on the output)
         fp4 = self.fp4 = cfg.llm_weight_dtype == "fp4"
         self.act8 = cfg.llm_act_dtype == "fp8"
+        # fp4 without the bf16 images of the dequantised weights (llm_fp4_keep_bf16=False): M > 64 runs on the MXFP4 images too
+        keep = self.fp4_keep_bf16 = bool(cfg.llm_fp4_keep_bf16) or not fp4
         self.embed = _tensor(get, device, p + "embed_tokens.weight")
         self.und, self.gen = [], []
         for l in range(cfg.layers):
-            self.und.append(self._layer(get, device, p + f"layers.{l}.", "", fp8, fp4))
-            self.gen.append(self._layer(get, device, p + f"layers.{l}.", "_moe_gen", fp8, fp4) if load_gen else None)
+            self.und.append(self._layer(get, device, p + f"layers.{l}.", "", fp8, fp4, keep))
+            self.gen.append(self._layer(get, device, p + f"layers.{l}.", "_moe_gen", fp8, fp4, keep) if load_gen else None)
             if self.act8:   # W8A8: the fp8-MFMA image replaces the bf16 image of the dequantised weights
                 for lw in (self.und[-1], self.gen[-1]):
                     if lw is not None:
@@ -97,7 +101,7 @@ class LLMWeights:
         self.sin = emb.sin().to(BF16).to(device)
 
     @staticmethod
-    def _layer(get, device, p, suf, fp8=False, fp4=False):
+    def _layer(get, device, p, suf, fp8=False, fp4=False, keep_bf16=True):
         lw = LayerWeights()
         a = p + "self_attn."
         st = _store(get)
@@ -106,19 +110,19 @@ class LLMWeights:
             w = torch.cat([_dev(get(a + f"{n}_proj{suf}.weight"), device) for n in "qkv"], 0)
             b = torch.cat([_dev(get(a + f"{n}_proj{suf}.bias"), device) for n in "qkv"], 0)
             if fp4:
-                return ops.PackedLinear.from_weight_mxfp4(w, b)
+                return ops.PackedLinear.from_weight_mxfp4(w, b, keep_bf16=keep_bf16)
             return ops.PackedLinear.from_weight_fp8(w, b) if fp8 else ops.PackedLinear.from_weight(w, b)
 
         def build_gate_up():
             g = _dev(get(p + f"mlp{suf}.gate_proj.weight"), device)
             u = _dev(get(p + f"mlp{suf}.up_proj.weight"), device)
             if fp4:
-                return ops.PackedLinear.from_gate_up_mxfp4(g, u)
+                return ops.PackedLinear.from_gate_up_mxfp4(g, u, keep_bf16=keep_bf16)
             return ops.PackedLinear.from_gate_up_fp8(g, u) if fp8 else ops.PackedLinear.from_gate_up(g, u)
         lw.qkv = st.linear(a + f"qkv_proj{suf}", build_qkv)
-        lw.o = _linear(get, device, a + f"o_proj{suf}.weight", fp8=fp8, fp4=fp4)
+        lw.o = _linear(get, device, a + f"o_proj{suf}.weight", fp8=fp8, fp4=fp4, keep_bf16=keep_bf16)
         lw.gate_up = st.linear(p + f"mlp{suf}.gate_up_proj", build_gate_up)
-        lw.down = _linear(get, device, p + f"mlp{suf}.down_proj.weight", fp8=fp8, fp4=fp4)
+        lw.down = _linear(get, device, p + f"mlp{suf}.down_proj.weight", fp8=fp8, fp4=fp4, keep_bf16=keep_bf16)
         lw.in_norm = _tensor(get, device, p + f"input_layernorm{suf}.weight")
         lw.post_norm = _tensor(get, device, p + f"post_attention_layernorm{suf}.weight")
         lw.q_norm = _tensor(get, device, a + f"q_norm{suf}.weight")
