@@ -243,7 +243,7 @@ print('OK')
 
 @pytest.mark.parametrize("tile", [266, 268, 384, 270])
 def test_full_line_x_staging_bit_identical(ops, tile):
-    """The default staging of the interleaved tiles (gemm.hip SCHED = 3: x in full 128-byte lines through an XOR-swizzled row-major
+    """The default staging of the interleaved tiles (gemm_tiled.h SCHED = 3: x in full 128-byte lines through an XOR-swizzled row-major
     ring, k-step pairs) against the half-line staging it replaced (UMV_GEMM_XLINE=0): the same MFMAs on the same operands in the
     same order, so every output bit must agree - full tiles, ragged M / N, K that is not a multiple of 64 or of 32 (zero-filled
     tail chunks), an odd number of k-steps, K shorter than the prologue, row-indexed A / C and the SwiGLU epilogue."""

@@ -195,6 +195,56 @@ __device__ __forceinline__ void epi_swiglu4(const EpiCtx& e, int64_t orow, int c
     }
 }
 
+// ----------------------------------------------------------------------------- direct wave-tile epilogue
+// Every lane stores its own 4 columns per row: the form of fp32 outputs (split-K partials, OUT_F32) in the tiled kernels, whose
+// bf16 outputs leave through LDS (below).  Compile-time accumulator indices: a runtime-indexed acc[][] would be demoted to scratch.
+template <int TN, int TM>
+__device__ __forceinline__ void epi_wave_tile_direct(const EpiCtx& e, f32x4 (&acc)[TN][TM], int lane, int m_wave0, int M,
+                                                     const int32_t* __restrict__ row_idx, int nt_base, int NTT) {
+    const int r = lane & 15, g = lane >> 4;
+    if (e.flags & UMV_EPI_SWIGLU) {
+        static_for<0, TM>([&](auto J) {
+            constexpr int j = decltype(J)::value;
+            const int m = m_wave0 + j * 16 + r;
+            if (m < M) {
+                const int64_t orow = row_idx ? (int64_t)row_idx[m] : (int64_t)m;
+                static_for<0, TN / 2>([&](auto P) {
+                    constexpr int p = decltype(P)::value;
+                    const int ntile = nt_base + 2 * p;
+                    if (ntile < NTT) {
+                        const int c0 = (ntile >> 1) * 16 + g * 4;
+                        float gg[4] = {acc[2 * p][j].x, acc[2 * p][j].y, acc[2 * p][j].z, acc[2 * p][j].w};
+                        float uu[4] = {acc[2 * p + 1][j].x, acc[2 * p + 1][j].y, acc[2 * p + 1][j].z, acc[2 * p + 1][j].w};
+                        epi_swiglu4(e, orow, c0, e.N / 2, gg, uu);
+                    }
+                });
+            }
+        });
+        return;
+    }
+    // column groups outside, rows inside: the bias of a column group is loaded once (8 bytes), not once per row
+    int64_t orow[TM];
+    bool mok[TM];
+#pragma unroll
+    for (int j = 0; j < TM; ++j) {
+        const int m = m_wave0 + j * 16 + r;
+        mok[j] = m < M;
+        orow[j] = (mok[j] && row_idx) ? (int64_t)row_idx[m] : (int64_t)m;
+    }
+    static_for<0, TN>([&](auto T) {
+        constexpr int t = decltype(T)::value;
+        const int n0 = (nt_base + t) * 16 + g * 4;
+        if (n0 < e.N) {
+            float b4[4] = {0.f, 0.f, 0.f, 0.f};
+            if (e.flags & UMV_EPI_BIAS) epi_bias4(e, n0, b4);
+            static_for<0, TM>([&](auto J) {
+                constexpr int j = decltype(J)::value;
+                if (mok[j]) epi_store4(e, orow[j], n0, acc[t][j].x, acc[t][j].y, acc[t][j].z, acc[t][j].w, nullptr, b4);
+            });
+        }
+    });
+}
+
 // ----------------------------------------------------------------------------- wave-tile epilogue through LDS
 // The MFMA accumulator layout gives a lane 4 consecutive columns of one row: stored directly, a wave's store instruction
 // covers 16 rows x 32 bytes - 16 partial cache lines, and TN*TM such instructions per wave (the store tail of a 256 x 256
@@ -215,16 +265,12 @@ __device__ __forceinline__ int epi_swz(int chunk, int row) {
     else return (chunk + row) % CH;
 }
 
-// L32: the accumulators come from 32x32x16 MFMAs, renamed by the caller into f32x4 quads acc[t][j] that hold, for this lane, row
-// (j >> 1) * 32 + (lane & 31) and columns t * 16 + (2 * (j & 1) + (lane >> 5)) * 4 .. + 3 of the wave tile (quad q of the 32 x 32
-// tile (u, v) is acc[2u + (q >> 1)][2v + (q & 1)]); otherwise the 16x16x32 layout: row j * 16 + (lane & 15), columns
-// t * 16 + (lane >> 4) * 4 .. + 3.  Only the lane -> (row, column group) map differs; arithmetic and roundings are the same.
-template <bool L32>
-__device__ __forceinline__ int epi_row_of(int j, int lane) { return L32 ? (j >> 1) * 32 + (lane & 31) : j * 16 + (lane & 15); }
-template <bool L32>
-__device__ __forceinline__ int epi_grp_of(int j, int lane) { return L32 ? 2 * (j & 1) + (lane >> 5) : (lane >> 4); }
+// accumulator layout of v_mfma_f32_16x16x32_bf16: acc[t][j] holds, for this lane, row j * 16 + (lane & 15) and columns
+// t * 16 + (lane >> 4) * 4 .. + 3 of the wave tile
+__device__ __forceinline__ int epi_row_of(int j, int lane) { return j * 16 + (lane & 15); }
+__device__ __forceinline__ int epi_grp_of(int lane) { return lane >> 4; }
 
-template <int TN, int TM, bool L32 = false>
+template <int TN, int TM>
 __device__ __forceinline__ void epi_wave_tile_lds(const EpiCtx& e, f32x4 (&acc)[TN][TM], char* wreg, int lane, int m_wave0, int M,
                                                   const int32_t* __restrict__ row_idx, int nt_base, int NTT,
                                                   const bf16_t* bias_tile = nullptr,   // LDS copy of bias[nt_base*16 ..], zero past N
@@ -233,7 +279,7 @@ __device__ __forceinline__ void epi_wave_tile_lds(const EpiCtx& e, f32x4 (&acc)[
     float sxr[TM];
 #pragma unroll
     for (int j = 0; j < TM; ++j) {
-        const int m = m_wave0 + epi_row_of<L32>(j, lane);
+        const int m = m_wave0 + epi_row_of(j, lane);
         sxr[j] = sx ? sx[m < M ? m : M - 1] : 1.f;
     }
     auto finish = [&](auto CHC, int col_base, int n_out) {
@@ -287,7 +333,7 @@ __device__ __forceinline__ void epi_wave_tile_lds(const EpiCtx& e, f32x4 (&acc)[
             constexpr int p = decltype(P)::value;
             static_for<0, TM>([&](auto J) {
                 constexpr int j = decltype(J)::value;
-                const int row = epi_row_of<L32>(j, lane), g = epi_grp_of<L32>(j, lane);
+                const int row = epi_row_of(j, lane), g = epi_grp_of(lane);
                 float v[4];
                 const float gg[4] = {acc[2 * p][j].x, acc[2 * p][j].y, acc[2 * p][j].z, acc[2 * p][j].w};
                 const float uu[4] = {acc[2 * p + 1][j].x, acc[2 * p + 1][j].y, acc[2 * p + 1][j].z, acc[2 * p + 1][j].w};
@@ -314,42 +360,34 @@ __device__ __forceinline__ void epi_wave_tile_lds(const EpiCtx& e, f32x4 (&acc)[
         constexpr int CH = 2 * TN;
         static_for<0, TN>([&](auto T) {
             constexpr int t = decltype(T)::value;
-            // the column group of a quad depends on the lane alone (16x16x32) or on the lane and the parity of j (32x32x16):
-            // bias / scales of the one or two groups this lane meets in column tile t
-            constexpr int NG = L32 ? 2 : 1;
-            float b4[NG][4], s4[NG][4];
-#pragma unroll
-            for (int gi = 0; gi < NG; ++gi) {
-                const int g = epi_grp_of<L32>(gi, lane);
-                const int n0 = (nt_base + t) * 16 + g * 4;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { b4[gi][q] = 0.f; s4[gi][q] = 1.f; }
-                if (e.flags & UMV_EPI_BIAS) {
-                    if (bias_tile) {
-                        const u32x2 pk = *reinterpret_cast<const u32x2*>(bias_tile + t * 16 + g * 4);
-                        b4[gi][0] = __uint_as_float(pk.x << 16); b4[gi][1] = __uint_as_float(pk.x & 0xFFFF0000u);
-                        b4[gi][2] = __uint_as_float(pk.y << 16); b4[gi][3] = __uint_as_float(pk.y & 0xFFFF0000u);
-                    } else if (n0 < e.N) {
-                        epi_bias4(e, n0, b4[gi]);
-                    }
+            // bias / scales of the column group this lane holds in column tile t
+            const int g = epi_grp_of(lane);
+            const int n0 = (nt_base + t) * 16 + g * 4;
+            float b4[4] = {0.f, 0.f, 0.f, 0.f}, s4[4] = {1.f, 1.f, 1.f, 1.f};
+            if (e.flags & UMV_EPI_BIAS) {
+                if (bias_tile) {
+                    const u32x2 pk = *reinterpret_cast<const u32x2*>(bias_tile + t * 16 + g * 4);
+                    b4[0] = __uint_as_float(pk.x << 16); b4[1] = __uint_as_float(pk.x & 0xFFFF0000u);
+                    b4[2] = __uint_as_float(pk.y << 16); b4[3] = __uint_as_float(pk.y & 0xFFFF0000u);
+                } else if (n0 < e.N) {
+                    epi_bias4(e, n0, b4);
                 }
-                if (sw) {
+            }
+            if (sw) {
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) s4[gi][q] = sw[min(n0 + q, e.N - 1)];
-                }
+                for (int q = 0; q < 4; ++q) s4[q] = sw[min(n0 + q, e.N - 1)];
             }
             static_for<0, TM>([&](auto J) {
                 constexpr int j = decltype(J)::value;
-                constexpr int gi = L32 ? (j & 1) : 0;
-                const int row = epi_row_of<L32>(j, lane), g = epi_grp_of<L32>(j, lane);
+                const int row = epi_row_of(j, lane);
                 float v[4] = {acc[t][j].x, acc[t][j].y, acc[t][j].z, acc[t][j].w};
                 if (sw) {
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) v[q] = v[q] * s4[gi][q] * sxr[j];
+                    for (int q = 0; q < 4; ++q) v[q] = v[q] * s4[q] * sxr[j];
                 }
                 if (e.flags & UMV_EPI_BIAS) {
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) v[q] += b4[gi][q];
+                    for (int q = 0; q < 4; ++q) v[q] += b4[q];
                 }
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = rbf(v[q]);

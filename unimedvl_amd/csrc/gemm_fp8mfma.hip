@@ -16,11 +16,9 @@
 #include "common.h"
 #include "../../include/unimedvl_hip.h"
 #include "gemm_epilogue.h"
-#include <stdlib.h>
+#include "gemm_internal.h"
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
-typedef __attribute__((address_space(3))) void* lds8_ptr_t;
-__device__ __attribute__((aligned(16))) const uint32_t g_zero_page8[4] = {0, 0, 0, 0};
 
 // ----------------------------------------------------------------------------- activations: per-row e4m3
 __device__ __forceinline__ float act_pow2_scale(float amax) {   // smallest 2^e with 448 * 2^e >= amax (1 for a zero row)
@@ -94,11 +92,7 @@ extern "C" int umv_quantize_act_fp8(const uint16_t* x, int64_t ldx, const int32_
 
 // ----------------------------------------------------------------------------- the GEMM
 // inline-asm building blocks of the hand-ordered k-step (free functions: clang rejects asm operands naming the enclosing
-// function's locals from inside a generic lambda)
-template <int OFF>
-__device__ __forceinline__ void lds_read16(u32x4& dst, uint32_t addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
+// function's locals from inside a generic lambda); the fragment reads are umv_lds_read128
 __device__ __forceinline__ void mfma8_asm(f32x4& c, const i32x8& a, const i32x8& b, int one) {   // scales 2^0 on both operands
     asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %3 op_sel_hi:[0,0,0]" : "+v"(c) : "v"(a), "v"(b), "v"(one));
 }
@@ -108,13 +102,6 @@ __device__ __forceinline__ void lds_wait() {   // at most N of the LDS reads iss
 }
 __device__ __forceinline__ i32x8 frag8(const u32x4& lo, const u32x4& hi) {
     return (i32x8){(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
-}
-
-// piece p of n_pieces goes behind MFMA floor((2p + 1) * span / (2 * n_pieces)) of the step's first `span` MFMAs
-__host__ __device__ constexpr int dma_slot8(int i, int span, int n_pieces) {
-    for (int p = 0; p < n_pieces; ++p)
-        if (((2 * p + 1) * span) / (2 * n_pieces) == i) return p;
-    return -1;
 }
 
 template <int WN, int WM, int TN, int TM, int NBUF>
@@ -131,19 +118,8 @@ __global__ __launch_bounds__(WN * WM * 64) void gemm_tiled8_kernel(umv_gemm8_arg
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, g = lane >> 4;
     const int wn = wave % WN, wm = wave / WN;
-    const int nwg = mblocks * nblocks;
-    int bid = blockIdx.x;
-    {   // XCD-aware order, as gemm_tiled_kernel
-        const int q = nwg / 8, rem = nwg % 8, xcd = bid % 8, idx = bid / 8;
-        bid = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + idx;
-    }
-    int mblk, nblk;   // strips of gn n-blocks, n-block within the strip fastest (see gemm_tiled_kernel)
-    {
-        const int per = mblocks * gn, strip = bid / per, rem = bid - strip * per;
-        const int w = min(gn, nblocks - strip * gn);
-        mblk = rem / w;
-        nblk = strip * gn + rem % w;
-    }
+    int mblk, nblk;
+    umv_tile_order(mblocks, nblocks, gn, mblocks, (int)blockIdx.x, mblk, nblk);      // (one super-block)
     const int m0 = mblk * BM;
     const int nt_blk = nblk * (BN / 16);
     const int nt_base = nt_blk + wn * TN;
@@ -164,7 +140,7 @@ __global__ __launch_bounds__(WN * WM * 64) void gemm_tiled8_kernel(umv_gemm8_arg
             src[i] = a.xq + (int64_t)(tvalid[i] ? m : 0) * a.ldq + g * 32 + h * 16;                 // + kt * 128 per step
         }
     }
-    const uint8_t* zero = reinterpret_cast<const uint8_t*>(g_zero_page8);
+    const uint8_t* zero = reinterpret_cast<const uint8_t*>(umv_zero_page);
     f32x4 acc[TN][TM];
 #pragma unroll
     for (int t = 0; t < TN; ++t)
@@ -180,13 +156,13 @@ __global__ __launch_bounds__(WN * WM * 64) void gemm_tiled8_kernel(umv_gemm8_arg
     auto piece = [&](int kt, int buf, int i) {
         const int f = wave * TPW + i;
         const uint8_t* p = (tvalid[i] && kt < KT) ? src[i] + (int64_t)kt * (f < WPL ? 2048 : 128) : zero;
-        __builtin_amdgcn_global_load_lds((const void*)p, (lds8_ptr_t)(smem + buf * BUF + f * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((const void*)p, (umv_lds_ptr_t)(smem + buf * BUF + f * 1024), 16, 0, 0);
     };
 #pragma unroll
     for (int p = 0; p < NBUF - 1; ++p)
 #pragma unroll
         for (int i = 0; i < TPW; ++i) piece(p, p, i);
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(lds8_ptr_t)smem;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(umv_lds_ptr_t)smem;
     const int one = 0x7f7f7f7f;    // E8M0 scale 2^0 in every byte
     constexpr int NMMA = TN * TM, DMA_SPAN = NMMA;
     constexpr bool DMA_IN = NBUF >= 3;
@@ -210,13 +186,13 @@ __global__ __launch_bounds__(WN * WM * 64) void gemm_tiled8_kernel(umv_gemm8_arg
         u32x4 xlo[TM], xhi[TM], wlo[3], whi[3];
         static_for<0, TM>([&](auto J) {
             constexpr int j = decltype(J)::value;
-            lds_read16<j * 2048>(xlo[j], xb);
-            lds_read16<j * 2048 + 1024>(xhi[j], xb);
+            umv_lds_read128<j * 2048>(xlo[j], xb);
+            umv_lds_read128<j * 2048 + 1024>(xhi[j], xb);
         });
         static_for<0, (TN < 2 ? TN : 2)>([&](auto T) {
             constexpr int t = decltype(T)::value;
-            lds_read16<t * 2048>(wlo[t], wb);
-            lds_read16<t * 2048 + 1024>(whi[t], wb);
+            umv_lds_read128<t * 2048>(wlo[t], wb);
+            umv_lds_read128<t * 2048 + 1024>(whi[t], wb);
         });
         i32x8 xf[TM];
         static_for<0, TN>([&](auto T) {
@@ -231,10 +207,10 @@ __global__ __launch_bounds__(WN * WM * 64) void gemm_tiled8_kernel(umv_gemm8_arg
                 constexpr int j = decltype(J)::value;
                 mfma8_asm(acc[t][j], wf, xf[j], one);
                 if constexpr (j == (TM > 1 ? 1 : 0) && t + 2 < TN) {
-                    lds_read16<(t + 2) * 2048>(wlo[(t + 2) % 3], wb);
-                    lds_read16<(t + 2) * 2048 + 1024>(whi[(t + 2) % 3], wb);
+                    umv_lds_read128<(t + 2) * 2048>(wlo[(t + 2) % 3], wb);
+                    umv_lds_read128<(t + 2) * 2048 + 1024>(whi[(t + 2) % 3], wb);
                 }
-                constexpr int pc = DMA_IN ? dma_slot8(t * TM + j, DMA_SPAN, TPW) : -1;       // the DMA piece (if any) behind this MFMA
+                constexpr int pc = DMA_IN ? umv_dma_slot(t * TM + j, DMA_SPAN, TPW) : -1;       // the DMA piece (if any) behind this MFMA
                 if constexpr (pc >= 0) {
                     __builtin_amdgcn_sched_barrier(0);
                     piece(kst, bst, pc);
@@ -251,50 +227,11 @@ __global__ __launch_bounds__(WN * WM * 64) void gemm_tiled8_kernel(umv_gemm8_arg
         for (int j = 0; j < TM; ++j) asm volatile("" : "+v"(acc[t][j]));
     // epilogue: exact power-of-two scales, then the shared bf16 epilogue (bias / activation / SwiGLU / residual)
     EpiCtx e{a.bias, a.residual, a.ldr, a.out, a.ldo, a.N, a.epilogue};
-    if constexpr (BN * BM * 2 <= NBUF * BUF) {   // whole rows through LDS (gemm_epilogue.h): same values, 16-byte stores
-        UMV_BARRIER();             // every wave has read its last fragments: the staging buffers are free
-        epi_wave_tile_lds<TN, TM>(e, acc, smem + wave * (TN * TM * 512), lane, m0 + wm * TM * 16, a.M, a.row_idx, nt_base, NTT, nullptr,
-                                  a.w_scale, a.x_scale);
-        return;
-    }
-    const bool swiglu = (a.epilogue & UMV_EPI_SWIGLU) != 0;
-    static_for<0, TM>([&](auto J) {
-        constexpr int j = decltype(J)::value;
-        const int m = m0 + (wm * TM + j) * 16 + r;
-        if (m < a.M) {
-            const int64_t orow = a.row_idx ? (int64_t)a.row_idx[m] : (int64_t)m;
-            const float sx = a.x_scale[m];
-            if (swiglu) {
-                static_for<0, TN / 2>([&](auto P) {
-                    constexpr int p = decltype(P)::value;
-                    const int ntile = nt_base + 2 * p;
-                    if (ntile < NTT) {
-                        const int c0 = (ntile >> 1) * 16 + g * 4;
-                        const f32x4 sg = *reinterpret_cast<const f32x4*>(a.w_scale + ntile * 16 + g * 4);
-                        const f32x4 su = *reinterpret_cast<const f32x4*>(a.w_scale + (ntile + 1) * 16 + g * 4);
-                        float gg[4] = {acc[2 * p][j].x * sg.x * sx, acc[2 * p][j].y * sg.y * sx, acc[2 * p][j].z * sg.z * sx, acc[2 * p][j].w * sg.w * sx};
-                        float uu[4] = {acc[2 * p + 1][j].x * su.x * sx, acc[2 * p + 1][j].y * su.y * sx, acc[2 * p + 1][j].z * su.z * sx,
-                                       acc[2 * p + 1][j].w * su.w * sx};
-                        epi_swiglu4(e, orow, c0, a.N / 2, gg, uu);
-                    }
-                });
-            } else {
-                static_for<0, TN>([&](auto T) {
-                    constexpr int t = decltype(T)::value;
-                    const int n0 = (nt_base + t) * 16 + g * 4;
-                    if (n0 < a.N) {
-                        const f32x4 sw = *reinterpret_cast<const f32x4*>(a.w_scale + n0);
-                        epi_store4(e, orow, n0, acc[t][j].x * sw.x * sx, acc[t][j].y * sw.y * sx, acc[t][j].z * sw.z * sx, acc[t][j].w * sw.w * sx);
-                    }
-                });
-            }
-        }
-    });
-}
-
-static int raster8_gn() {   // n-blocks per strip of the tile order; UMV_GEMM_RASTER overrides (tuning only)
-    static const int gn = [] { const char* e = getenv("UMV_GEMM_RASTER"); const int v = e ? atoi(e) : 4; return v < 1 ? 1 : v; }();   // (read once, thread-safe)
-    return gn;
+    // whole rows through LDS (gemm_epilogue.h), 16-byte stores: every wave's region fits the staging buffers
+    static_assert(BN * BM * 2 <= NBUF * BUF, "the tile fits the LDS epilogue");
+    UMV_BARRIER();             // every wave has read its last fragments: the staging buffers are free
+    epi_wave_tile_lds<TN, TM>(e, acc, smem + wave * (TN * TM * 512), lane, m0 + wm * TM * 16, a.M, a.row_idx, nt_base, NTT, nullptr,
+                              a.w_scale, a.x_scale);
 }
 
 template <int WN, int WM, int TN, int TM, int NBUF>
@@ -309,7 +246,7 @@ static int launch_tiled8(const umv_gemm8_args& a, int KT, int NTT, hipStream_t s
     }
     const int mblocks = (a.M + BM - 1) / BM, nblocks = (a.N + BN - 1) / BN;
     hipLaunchKernelGGL((gemm_tiled8_kernel<WN, WM, TN, TM, NBUF>), dim3(mblocks * nblocks), dim3(WN * WM * 64), lds, s, a, KT, NTT, mblocks,
-                       nblocks, raster8_gn());
+                       nblocks, UMV_TILE_GN);
     UMV_LAUNCH_CHECK();
     return UMV_OK;
 }
@@ -327,7 +264,7 @@ extern "C" int umv_gemm_fp8a8w(const umv_gemm8_args* ap, umv_stream_t stream) {
     if (a.M == 0) return UMV_OK;
     hipStream_t s = (hipStream_t)stream;
     const int KT = (a.K + 127) / 128, NTT = (a.N + 15) / 16;
-    static const int force = [] { const char* e = getenv("UMV_GEMM8_TILE"); return e ? atoi(e) : 0; }();   // tuning only: UMV_GEMM8_TILE=<256|258|259|128> (read once, thread-safe)
+    static const int force = umv_env_int("UMV_GEMM8_TILE", 0);   // tuning only: UMV_GEMM8_TILE=<256|258|259|128>
     // Measured (tools/gemm_bench.py --fp8): the 256 x 256 tile wins once it gives >= ~144 workgroups (M=2048,N=4608: 69.6 vs
     // 77.4 us); below that the 256 x 128 tile with three stage buffers does (M=1024,N=3584,K=18944: 159 vs 251 us), and its
     // third buffer is worth 5-10% over two on every shape.

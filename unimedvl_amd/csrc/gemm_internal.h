@@ -1,6 +1,8 @@
-// Pieces shared by the tiled GEMM kernels of libunimedvl_hip (gemm.hip, gemm_w4.hip): the workgroup -> tile order, the
-// instruction slots of the interleaved schedules, the launcher of the 4-wave kernels, and the environment knobs of every GEMM
-// launcher.  The weight-streaming decode GEMM is gemm_skinny.h, the weight formats' conversions quant.h.  Internal to csrc/.
+// The frame shared by the MFMA-tiled GEMM kernels of libunimedvl_hip (gemm_tiled.h, gemm_w4.hip, gemm_fp8mfma.hip, gemm_mxfp4t.hip):
+// the workgroup -> tile order with its raster width and super-block size, the instruction slots of the interleaved schedules, the
+// zero page, the ds_read_b128 wrapper, the bias-to-LDS staging, the argument checks of the weight-format entry points, the launcher
+// of the 4-wave kernels, and the environment knobs of every GEMM launcher.  The weight-streaming decode GEMM is gemm_skinny.h, the
+// weight formats' conversions quant.h.  Internal to csrc/.
 #pragma once
 #include "common.h"
 #include "../../include/unimedvl_hip.h"
@@ -11,6 +13,31 @@
 static inline int umv_env_int(const char* name, int dflt) {
     const char* e = getenv(name);
     return e ? atoi(e) : dflt;
+}
+
+// K tails, n-rows past N and surplus staging slots are staged from here (one copy per translation unit)
+static __device__ __attribute__((aligned(16))) const uint32_t umv_zero_page[4] = {0, 0, 0, 0};
+
+typedef __attribute__((address_space(3))) void* umv_lds_ptr_t;
+
+// one ds_read_b128 at a compile-time offset (a free function: clang rejects asm operands that name locals of the enclosing
+// function from inside a generic lambda)
+template <int OFF, class V>
+__device__ __forceinline__ void umv_lds_read128(V& dst, uint32_t addr) {
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
+}
+
+// The tile's BN bias values wait in LDS behind the staging buffers: read after the main loop, a global load there would expose its
+// whole latency once per tile (the first barrier of the main loop orders this write before any read).  Zero past N.
+template <int BN, int NTHREADS>
+__device__ __forceinline__ void umv_bias_to_lds(const umv_gemm_args& a, bf16_t* bias_lds, int nt_blk, int tid) {
+#pragma unroll
+    for (int o = 0; o < BN; o += NTHREADS) {
+        if ((a.epilogue & UMV_EPI_BIAS) && tid + o < BN) {
+            const int n = nt_blk * 16 + tid + o;
+            bias_lds[tid + o] = n < a.N ? a.bias[n] : (bf16_t)0;
+        }
+    }
 }
 
 // read r of NRD goes right after MFMA number (r * SPAN) / NRD, SPAN = 3/4 of the step's MFMAs: evenly spread over the first three
@@ -32,7 +59,9 @@ __host__ __device__ constexpr int umv_dma_slot(int i, int n_mma, int n_pieces) {
 // XCD-aware tile order (blockIdx round-robins over the 8 XCDs): every XCD gets a contiguous run of tiles; inside the run,
 // strips of gn n-blocks, m-block next, n-block within the strip fastest, so that the ~32 tiles an XCD works on at a time share
 // both operands' k-slices in its L2.  M super-blocks of ms m-blocks: all XCDs finish one before the next (x stays in the
-// memory-side cache while the strips of W stream past).  See gemm.hip::gemm_tiled_kernel for the measurements.
+// memory-side cache while the strips of W stream past - with 32 images (M = 32 832, x = 235 MB, act = 1.2 GB) every strip of n-blocks
+// otherwise re-streams all of x from HBM).  gn = 1 is plain m-fastest: every CU of the XCD streams its own x panel and only W is
+// shared; ms = mblocks is one super-block.
 __device__ __forceinline__ void umv_tile_order(int mblocks, int nblocks, int gn, int ms, int block, int& mblk, int& nblk) {
     const int sb_tiles = ms * nblocks;
     const int sb = block / sb_tiles;
@@ -49,18 +78,36 @@ __device__ __forceinline__ void umv_tile_order(int mblocks, int nblocks, int gn,
     nblk = strip * gn + rem % w;
 }
 
+constexpr int UMV_TILE_GN = 4;      // n-blocks per strip of the tile order
+
 // m-blocks per super-block: ~64 MB of x rows above 16k rows, one super-block below (host side)
 static inline int umv_tile_superblock(int mblocks, int BM, int K) {
     int ms = (int)(((int64_t)64 << 20) / ((int64_t)BM * K * 2));
     ms = ms < 8 ? 8 : ms;
-    if ((int64_t)mblocks * BM < 16384) ms = mblocks;
-    if (ms > mblocks || ms * 3 / 2 >= mblocks) ms = mblocks;
-    else ms = (mblocks + (mblocks + ms - 1) / ms - 1) / ((mblocks + ms - 1) / ms);
+    if ((int64_t)mblocks * BM < 16384) ms = mblocks;   // measured (us, on / off): M = 32 832 gate/up 7040 / 7480, down 3880 / 4070, qkv 1013 / 1056;
+                                                       // M = 16 416 down 1975 / 2010, gate/up 3543 / 3528; M = 8208 down 1062 / 1047: off below 16k rows
+    if (ms > mblocks || ms * 3 / 2 >= mblocks) ms = mblocks;        // a short second super-block is not worth a second pass over W
+    else ms = (mblocks + (mblocks + ms - 1) / ms - 1) / ((mblocks + ms - 1) / ms);   // equal super-blocks: no stub at the end
     return ms;
+}
+
+// The argument checks every weight-format entry point makes (umv_gemm_bf16 / _fp8w / _mxfp4w / _mxfp4t); `who` is the entry's name in
+// the messages, kmul the multiple K has to be (8: bf16 / e4m3 images, 32: MXFP4 blocks)
+static inline int umv_gemm_check_args(const umv_gemm_args& a, const char* who, int kmul) {
+    UMV_CHECK(a.M >= 0 && a.N > 0 && a.K > 0, UMV_ERR_ARG, "%s: bad shape M=%d N=%d K=%d", who, a.M, a.N, a.K);
+    if (kmul == 8)
+        UMV_CHECK((a.K % 8) == 0 && (a.ldx % 8) == 0, UMV_ERR_ARG, "%s: K (%d) and ldx (%lld) must be multiples of 8", who, a.K, (long long)a.ldx);
+    else
+        UMV_CHECK((a.K % 32) == 0 && (a.ldx % 8) == 0, UMV_ERR_ARG, "%s: K (%d) must be a multiple of 32 and ldx (%lld) of 8", who, a.K,
+                  (long long)a.ldx);
+    UMV_CHECK(!(a.epilogue & UMV_EPI_BIAS) || a.bias, UMV_ERR_ARG, "%s: BIAS without bias pointer", who);
+    UMV_CHECK(!(a.epilogue & UMV_EPI_RESIDUAL) || a.residual, UMV_ERR_ARG, "%s: RESIDUAL without residual pointer", who);
+    UMV_CHECK(!(a.epilogue & UMV_EPI_SWIGLU) || (a.N % 32) == 0, UMV_ERR_ARG, "%s: SWIGLU needs N %% 32 == 0", who);
+    return UMV_OK;
 }
 
 // gemm_w4.hip: 4-wave tiles with the accumulators in AGPRs (cfg 466 / 468 / 4384); bf16 output, no split-K, operands within
 // 2 GiB of their base pointers (umv_gemm_w4_can_take)
 int umv_gemm_lean_epilogue(const umv_gemm_args& a);      // gemm.hip: >= 0 = the lean epilogue kind of this call, -1 = general
 bool umv_gemm_w4_can_take(const umv_gemm_args& a, int KT, int NTT);
-int umv_gemm_w4_launch(const umv_gemm_args& a, int KT, int NTT, int cfg, int gn, hipStream_t s);
+int umv_gemm_w4_launch(const umv_gemm_args& a, int KT, int NTT, int cfg, hipStream_t s);

@@ -35,14 +35,9 @@ extern "C" int umv_gemm_mxfp4w(const umv_gemm_args* ap, umv_stream_t stream) {
     umv_gemm_args a = *ap;
     UMV_CHECK(a.x && a.wp && a.out, UMV_ERR_ARG, "gemm_mxfp4w: null pointer (x, wp and out are required)");
     UMV_CHECK(!a.w_scale, UMV_ERR_ARG, "gemm_mxfp4w: w_scale must be NULL (the block scales are part of the MXFP4 image)");
-    UMV_CHECK(a.M >= 0 && a.N > 0 && a.K > 0, UMV_ERR_ARG, "gemm_mxfp4w: bad shape M=%d N=%d K=%d", a.M, a.N, a.K);
+    if (const int rc = umv_gemm_check_args(a, "gemm_mxfp4w", 32)) return rc;
     UMV_CHECK(a.M <= 64, UMV_ERR_UNSUPPORTED, "gemm_mxfp4w: the MXFP4 image is the decode (M <= 64) layout; use the bf16 image of the "
               "dequantised weights with umv_gemm_bf16 for M=%d", a.M);
-    UMV_CHECK((a.K % 32) == 0 && (a.ldx % 8) == 0, UMV_ERR_ARG, "gemm_mxfp4w: K (%d) must be a multiple of 32 and ldx (%lld) of 8", a.K,
-              (long long)a.ldx);
-    UMV_CHECK(!(a.epilogue & UMV_EPI_BIAS) || a.bias, UMV_ERR_ARG, "gemm_mxfp4w: BIAS without bias pointer");
-    UMV_CHECK(!(a.epilogue & UMV_EPI_RESIDUAL) || a.residual, UMV_ERR_ARG, "gemm_mxfp4w: RESIDUAL without residual pointer");
-    UMV_CHECK(!(a.epilogue & UMV_EPI_SWIGLU) || (a.N % 32) == 0, UMV_ERR_ARG, "gemm_mxfp4w: SWIGLU needs N %% 32 == 0");
     UMV_CHECK(!a.norm_w && (a.tile_rows == 0 || a.tile_rows == 16), UMV_ERR_UNSUPPORTED, "gemm_mxfp4w: no fused norm / th-row tiles");
     UMV_CHECK(!a.argmax_partial, UMV_ERR_UNSUPPORTED, "gemm_mxfp4w: no argmax_partial (lm_head stays e4m3: umv_gemm_fp8w)");
     UMV_CHECK(a.k_splits <= 1 || (!(a.epilogue & UMV_EPI_SWIGLU) && a.split_stride > 0 && a.k_splits <= 64), UMV_ERR_UNSUPPORTED,

@@ -20,8 +20,6 @@
 #include "gemm_internal.h"
 #include "quant.h"
 
-typedef __attribute__((address_space(3))) void* t4_lds_ptr_t;
-
 // NX / NW = slots of the x / W rings (NX - 1 units of x, NW - 1 units of codes + scales in flight)
 template <int WN, int WM, int NP, int TM, int NX_, int NW>
 struct T4Cfg {
@@ -103,7 +101,7 @@ __global__ __launch_bounds__(WN * WM * 64) void gemm_mxfp4t_kernel(umv_gemm_args
         for (int i = 0; i < XPW; ++i) {
             const int f = wave * XPW + i;
             const int kt = min(2 * uu + (f & 1), KT - 1);
-            __builtin_amdgcn_global_load_lds((const void*)(xsrc[i] + (int64_t)kt * 32), (t4_lds_ptr_t)(dst + ((f & 1) * (WM * TM) + (f >> 1)) * 1024), 16,
+            __builtin_amdgcn_global_load_lds((const void*)(xsrc[i] + (int64_t)kt * 32), (umv_lds_ptr_t)(dst + ((f & 1) * (WM * TM) + (f >> 1)) * 1024), 16,
                                              0, 0);
         }
     };
@@ -113,8 +111,8 @@ __global__ __launch_bounds__(WN * WM * 64) void gemm_mxfp4t_kernel(umv_gemm_args
 #pragma unroll
         for (int i = 0; i < SPW; ++i) {
             const int sp = wave * SPW + i;
-            __builtin_amdgcn_global_load_lds((const void*)(wbase[i] + (int64_t)uu * 1024), (t4_lds_ptr_t)(dst + sp * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const void*)(sbase[i] + (int64_t)uu * 64), (t4_lds_ptr_t)(dst + PPB * 1024 + sp * 256), 4, 0, 0);
+            __builtin_amdgcn_global_load_lds((const void*)(wbase[i] + (int64_t)uu * 1024), (umv_lds_ptr_t)(dst + sp * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((const void*)(sbase[i] + (int64_t)uu * 64), (umv_lds_ptr_t)(dst + PPB * 1024 + sp * 256), 4, 0, 0);
         }
     };
 
@@ -193,50 +191,8 @@ __global__ __launch_bounds__(WN * WM * 64) void gemm_mxfp4t_kernel(umv_gemm_args
         e.flags = UMV_EPI_OUT_F32;
     }
     const int m_wave0 = m0 + wm * TM * 16;
-    if (!(e.flags & UMV_EPI_OUT_F32)) {
-        epi_wave_tile_lds<TN, TM, false>(e, acc, smem + wave * (TN * TM * 512), lane, m_wave0, a.M, a.row_idx, nt_base, NTT);
-        return;
-    }
-    if (a.epilogue & UMV_EPI_SWIGLU) {
-        static_for<0, TM>([&](auto J) {
-            constexpr int j = decltype(J)::value;
-            const int m = m_wave0 + j * 16 + r;
-            if (m < a.M) {
-                const int64_t orow = a.row_idx ? (int64_t)a.row_idx[m] : (int64_t)m;
-                static_for<0, NP>([&](auto P) {
-                    constexpr int p = decltype(P)::value;
-                    const int ntile = nt_base + 2 * p;
-                    if (ntile < NTT) {
-                        const int c0 = (ntile >> 1) * 16 + g * 4;
-                        float gg[4] = {acc[2 * p][j].x, acc[2 * p][j].y, acc[2 * p][j].z, acc[2 * p][j].w};
-                        float uu[4] = {acc[2 * p + 1][j].x, acc[2 * p + 1][j].y, acc[2 * p + 1][j].z, acc[2 * p + 1][j].w};
-                        epi_swiglu4(e, orow, c0, a.N / 2, gg, uu);
-                    }
-                });
-            }
-        });
-        return;
-    }
-    int64_t orow[TM];
-    bool mok[TM];
-#pragma unroll
-    for (int j = 0; j < TM; ++j) {
-        const int m = m_wave0 + j * 16 + r;
-        mok[j] = m < a.M;
-        orow[j] = (mok[j] && a.row_idx) ? (int64_t)a.row_idx[m] : (int64_t)m;
-    }
-    static_for<0, TN>([&](auto T) {
-        constexpr int t = decltype(T)::value;
-        const int n0 = (nt_base + t) * 16 + g * 4;
-        if (n0 < a.N) {
-            float b4[4] = {0.f, 0.f, 0.f, 0.f};
-            if (e.flags & UMV_EPI_BIAS) epi_bias4(e, n0, b4);
-            static_for<0, TM>([&](auto J) {
-                constexpr int j = decltype(J)::value;
-                if (mok[j]) epi_store4(e, orow[j], n0, acc[t][j].x, acc[t][j].y, acc[t][j].z, acc[t][j].w, nullptr, b4);
-            });
-        }
-    });
+    if (e.flags & UMV_EPI_OUT_F32) epi_wave_tile_direct<TN, TM>(e, acc, lane, m_wave0, a.M, a.row_idx, nt_base, NTT);
+    else epi_wave_tile_lds<TN, TM>(e, acc, smem + wave * (TN * TM * 512), lane, m_wave0, a.M, a.row_idx, nt_base, NTT);
 }
 
 template <int WN, int WM, int NP, int TM, int NX_, int NW>
@@ -251,10 +207,8 @@ static int launch_mxfp4t(const umv_gemm_args& a, hipStream_t s) {
     const int mblocks = (a.M + BM - 1) / BM, nblocks = (NPT + Cf::PPB - 1) / Cf::PPB;
     const int splits = a.k_splits > 1 ? a.k_splits : 1;
     const int ksplit = splits > 1 ? (KT + splits - 1) / splits : 0;     // k-tiles per split: umv_gemm_bf16's ranges (its split-K tile steps by one k-tile)
-    static const int gn_env = umv_env_int("UMV_GEMM_RASTER", 4);
-    const int gn = gn_env < 1 ? 1 : gn_env;
     hipLaunchKernelGGL((gemm_mxfp4t_kernel<WN, WM, NP, TM, NX_, NW>), dim3(mblocks * nblocks, splits), dim3(Cf::NWV * 64), Cf::LDS_BYTES, s, a, KT,
-                       KT8, NTT, NPT, mblocks, nblocks, gn, umv_tile_superblock(mblocks, BM, a.K), ksplit);
+                       KT8, NTT, NPT, mblocks, nblocks, UMV_TILE_GN, umv_tile_superblock(mblocks, BM, a.K), ksplit);
     UMV_LAUNCH_CHECK();
     return UMV_OK;
 }
@@ -264,14 +218,9 @@ extern "C" int umv_gemm_mxfp4t(const umv_gemm_args* ap, umv_stream_t stream) {
     umv_gemm_args a = *ap;
     UMV_CHECK(a.x && a.wp && a.out, UMV_ERR_ARG, "gemm_mxfp4t: null pointer (x, wp and out are required)");
     UMV_CHECK(!a.w_scale, UMV_ERR_ARG, "gemm_mxfp4t: w_scale must be NULL (the block scales are part of the MXFP4 image)");
-    UMV_CHECK(a.M >= 0 && a.N > 0 && a.K > 0, UMV_ERR_ARG, "gemm_mxfp4t: bad shape M=%d N=%d K=%d", a.M, a.N, a.K);
-    UMV_CHECK((a.K % 32) == 0 && (a.ldx % 8) == 0, UMV_ERR_ARG, "gemm_mxfp4t: K (%d) must be a multiple of 32 and ldx (%lld) of 8", a.K,
-              (long long)a.ldx);
+    if (const int rc = umv_gemm_check_args(a, "gemm_mxfp4t", 32)) return rc;
     UMV_CHECK(a.M > 64, UMV_ERR_UNSUPPORTED, "gemm_mxfp4t: the tiled MXFP4 kernel takes M > 64; use the weight-streaming kernel "
               "umv_gemm_mxfp4w for M=%d", a.M);
-    UMV_CHECK(!(a.epilogue & UMV_EPI_BIAS) || a.bias, UMV_ERR_ARG, "gemm_mxfp4t: BIAS without bias pointer");
-    UMV_CHECK(!(a.epilogue & UMV_EPI_RESIDUAL) || a.residual, UMV_ERR_ARG, "gemm_mxfp4t: RESIDUAL without residual pointer");
-    UMV_CHECK(!(a.epilogue & UMV_EPI_SWIGLU) || (a.N % 32) == 0, UMV_ERR_ARG, "gemm_mxfp4t: SWIGLU needs N %% 32 == 0");
     UMV_CHECK(!a.norm_w, UMV_ERR_UNSUPPORTED, "gemm_mxfp4t: no fused norm (a decode prologue, M <= 16: umv_gemm_bf16 on a bf16 image)");
     UMV_CHECK(a.tile_rows == 0 || a.tile_rows == 16, UMV_ERR_UNSUPPORTED, "gemm_mxfp4t: no th-row tiles (a bf16 decode layout: umv_gemm_bf16)");
     UMV_CHECK(!a.argmax_partial, UMV_ERR_UNSUPPORTED, "gemm_mxfp4t: no argmax_partial (lm_head stays e4m3: umv_gemm_fp8w)");
@@ -282,11 +231,8 @@ extern "C" int umv_gemm_mxfp4t(const umv_gemm_args* ap, umv_stream_t stream) {
     // Every wave owns 64 x 64 (two pairs x four row tiles) and a SIMD holds two of them: a wave that issues LDS-DMA pieces or converts is
     // off the matrix pipe, and with one wave per SIMD (128 x 64 per wave was tried) nothing fills the gap.  Few rows (the 65..128-row decode
     // step, short prefills): 128 x 128, 2 x 2 waves, 78 KiB of LDS - two workgroups per CU.  More rows: 256(n) x 128, 4 x 2 waves.
-    // UMV_MXFP4T_TILE = 128 | 256 overrides (A/B only)
-    static const int tile_env = umv_env_int("UMV_MXFP4T_TILE", 0);
     const int NPT = ((a.N + 15) / 16 + 1) / 2;
     const long wg256 = (long)((a.M + 127) / 128) * ((NPT + 7) / 8);
-    const int tile = (tile_env == 128 || tile_env == 256) ? tile_env : (a.M <= 128 || wg256 < 256 ? 128 : 256);
-    if (tile == 128) return launch_mxfp4t<2, 2, 2, 4, 3, 6>(a, s);
+    if (a.M <= 128 || wg256 < 256) return launch_mxfp4t<2, 2, 2, 4, 3, 6>(a, s);
     return launch_mxfp4t<4, 2, 2, 4, 3, 4>(a, s);
 }

@@ -3,7 +3,7 @@
 //   out[m,n] = epi(sum_k x[m,k] W[n,k])        M > 64: prefill, ViT, flow passes (qwen2_navit.py:541-543,617-620,
 //                                              modeling_qwen2.py:234-235, siglip_navit.py:216-218,243,256-258)
 //
-// Same operands, LDS image, rings and counted-wait protocol as gemm.hip's SCHED = 3 tile (W: 1 KiB fragment-order pieces of
+// Same operands, LDS image, rings and counted-wait protocol as gemm_tiled.h's full-line loop (SCHED = 3) (W: 1 KiB fragment-order pieces of
 // the packed image; x: 8 rows x 128 bytes = full cache lines, row-major image XOR-swizzled by the row), but a workgroup is
 // WN x WM = 4 waves and a wave owns TN x TM = 8 x 8 (or 8 x 4, 12 x 4) MFMA tiles:
 //   * a 128 x 128 wave tile needs 16 fragment reads per 64 MFMAs where the 8-wave kernel's 128 x 64 tiles need 12 per 32:
@@ -20,14 +20,6 @@
 #include "gemm_epilogue.h"
 #include "gemm_internal.h"
 
-__device__ __attribute__((aligned(16))) const uint32_t g_zero_page_w4[4] = {0, 0, 0, 0};
-
-typedef __attribute__((address_space(3))) void* lds_ptr_w4_t;
-
-template <int OFF>
-__device__ __forceinline__ void w4_lds_read_frag(bf16x8& dst, uint32_t addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
 // acc IDX += a x b with the accumulator named in the instruction text
 template <int IDX>
 __device__ __forceinline__ void w4_mfma(const bf16x8& a, const bf16x8& b) {
@@ -92,16 +84,7 @@ __global__ __launch_bounds__(WN * WM * 64) void gemm_w4_kernel(umv_gemm_args a, 
     const int nt_blk = nblk * (BN / 16);
     const int nt_base = nt_blk + wn * TN;
     bf16_t* bias_lds = reinterpret_cast<bf16_t*>(smem + STAGE_BYTES);
-    if ((a.epilogue & UMV_EPI_BIAS) && tid < BN) {
-        const int n = nt_blk * 16 + tid;
-        bias_lds[tid] = n < a.N ? a.bias[n] : (bf16_t)0;
-    }
-    if constexpr (BN > NW * 64) {
-        if ((a.epilogue & UMV_EPI_BIAS) && tid + NW * 64 < BN) {
-            const int n = nt_blk * 16 + tid + NW * 64;
-            bias_lds[tid + NW * 64] = n < a.N ? a.bias[n] : (bf16_t)0;
-        }
-    }
+    umv_bias_to_lds<BN, NW * 64>(a, bias_lds, nt_blk, tid);
     const int nsteps = KT;
     const int q_last = (a.K - 1) >> 6;               // the last k-step pair that holds data
     // ---- the staging pieces: one 32-bit offset per piece, relative to a.wp / a.x, valid for every k-step
@@ -132,7 +115,7 @@ __global__ __launch_bounds__(WN * WM * 64) void gemm_w4_kernel(umv_gemm_args a, 
         int ktc = min(kt, KT - 1);
         if constexpr (ABL == 1) ktc &= 7;
         const uint32_t off = offW[i];          // (passed directly, the array element makes the host pass drop the kernel stub)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lds_ptr_w4_t)lds_of(slot * WSLOT + (wave * WPW + i) * 1024), 16, off, ktc * 1024, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (umv_lds_ptr_t)lds_of(slot * WSLOT + (wave * WPW + i) * 1024), 16, off, ktc * 1024, 0, 0);
     };
     auto stage_x = [&](int q, auto SLOT, auto HALF, auto I) {
         constexpr int slot = decltype(SLOT)::value, hf = decltype(HALF)::value, i = decltype(I)::value;
@@ -140,7 +123,7 @@ __global__ __launch_bounds__(WN * WM * 64) void gemm_w4_kernel(umv_gemm_args a, 
         uint32_t off = offX[hf * XPB + i];
         if constexpr (RAGK) off = (xtail && qc == q_last) ? 0x80000000u : off;
         if constexpr (ABL == 1) qc &= 3;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr_w4_t)lds_of(XBASE + slot * XSLOT + (wave * XPP + hf * XPB + i) * 1024), 16, off, qc * 128, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (umv_lds_ptr_t)lds_of(XBASE + slot * XSLOT + (wave * XPP + hf * XPB + i) * 1024), 16, off, qc * 128, 0, 0);
     };
     // prologue, in the order the loop would have issued it: x pair 0, W(0), x pair 1, W(1), first half of x pair 2, W(2)
     static_for<0, 3>([&](auto T) {
@@ -155,7 +138,7 @@ __global__ __launch_bounds__(WN * WM * 64) void gemm_w4_kernel(umv_gemm_args a, 
         asm volatile("v_accvgpr_write_b32 a[%0], 0" ::"n"(i));
     });
     bf16x8 wfA[TN], xfA[TM], wfB[TN], xfB[TM];
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_ptr_w4_t)smem;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(umv_lds_ptr_t)smem;
     const uint32_t wbase = lds0 + wn * TN * 1024 + lane * 16;
     // x fragment of k half h: row (wm * TM + j) * 16 + r, chunk (4h + g) ^ (r & 7)
     const uint32_t xbase0 = lds0 + XBASE + (wm * TM * 16 + r) * 128 + ((g ^ (r & 7)) << 4), xbase1 = xbase0 ^ 64;
@@ -165,11 +148,11 @@ __global__ __launch_bounds__(WN * WM * 64) void gemm_w4_kernel(umv_gemm_args a, 
         constexpr int rd = decltype(RD)::value, sw = decltype(SW)::value, sx = decltype(SX)::value, h = decltype(HALF)::value;
         if constexpr (rd < TM) {
             constexpr int off = sx * XSLOT + rd * 2048;          // (the instruction's offset field has 16 bits)
-            if constexpr (off < 65536) w4_lds_read_frag<off>(xf[rd], h ? xbase1 : xbase0);
-            else w4_lds_read_frag<off - 65536>(xf[rd], h ? xbase1_hi : xbase0_hi);
+            if constexpr (off < 65536) umv_lds_read128<off>(xf[rd], h ? xbase1 : xbase0);
+            else umv_lds_read128<off - 65536>(xf[rd], h ? xbase1_hi : xbase0_hi);
         } else {
             static_assert(2 * WSLOT + (TN - 1) * 1024 < 65536, "W fragment offsets fit the instruction");
-            w4_lds_read_frag<sw * WSLOT + (rd - TM) * 1024>(wf[rd - TM], wbase);
+            umv_lds_read128<sw * WSLOT + (rd - TM) * 1024>(wf[rd - TM], wbase);
         }
     };
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * XPB + 2 * WPW) : "memory");      // x pair 0 and W(0) landed; what was issued behind them may fly
@@ -269,7 +252,7 @@ __global__ __launch_bounds__(WN * WM * 64) void gemm_w4_kernel(umv_gemm_args a, 
         });
         // lean >= 0: the branch-free form for this call's flag combination (gemm_epilogue.h::epi_lean_kind), else the general one
         if (!(lean >= 0 && epi_wave_tile_lean_any<TN, JC>(lean, a, acc, wreg, lane, m0 + wm * TM * 16 + h * JC * 16, nt_base, bias_lds + wn * TN * 16)))
-            epi_wave_tile_lds<TN, JC, false>(e, acc, wreg, lane, m0 + wm * TM * 16 + h * JC * 16, a.M, a.row_idx, nt_base, NTT,
+            epi_wave_tile_lds<TN, JC>(e, acc, wreg, lane, m0 + wm * TM * 16 + h * JC * 16, a.M, a.row_idx, nt_base, NTT,
                                             bias_lds + wn * TN * 16);
         if constexpr (ABL == 2 && h == 0) w4_stamp(tw3);
     });
@@ -290,7 +273,7 @@ __global__ __launch_bounds__(WN * WM * 64) void gemm_w4_kernel(umv_gemm_args a, 
 }
 
 template <int WN, int WM, int TN, int TM, int ABL = 0>
-static int launch_w4(const umv_gemm_args& a, int KT, int NTT, int gn, hipStream_t s) {
+static int launch_w4(const umv_gemm_args& a, int KT, int NTT, hipStream_t s) {
     constexpr int BN = WN * TN * 16, BM = WM * TM * 16;
     constexpr size_t lds = (size_t)3 * (BN / 16) * 1024 + (size_t)3 * BM * 128 + (BN * 2 + 15) / 16 * 16;
     static_assert(lds <= 160 * 1024, "LDS budget");
@@ -302,7 +285,7 @@ static int launch_w4(const umv_gemm_args& a, int KT, int NTT, int gn, hipStream_
         static bool attr_set[UMV_MAX_DEVICES] = {};
         if (umv_first_on_device(attr_set))
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_w4_kernel<WN, WM, TN, TM, ABL, ragk>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((gemm_w4_kernel<WN, WM, TN, TM, ABL, ragk>), dim3(mblocks * nblocks), dim3(WN * WM * 64), lds, s, a, KT, NTT, mblocks, nblocks, gn, ms,
+        hipLaunchKernelGGL((gemm_w4_kernel<WN, WM, TN, TM, ABL, ragk>), dim3(mblocks * nblocks), dim3(WN * WM * 64), lds, s, a, KT, NTT, mblocks, nblocks, UMV_TILE_GN, ms,
                            umv_gemm_lean_epilogue(a));
     };
     if (a.K % 32) go(std::true_type{});
@@ -322,17 +305,17 @@ bool umv_gemm_w4_can_take(const umv_gemm_args& a, int KT, int NTT) {
 }
 
 // cfg: 466 = 256(n) x 256(m), 468 = 256(n) x 128(m), 4384 = 384(n) x 128(m); bf16 output, no split-K (umv_gemm_w4_can_take)
-int umv_gemm_w4_launch(const umv_gemm_args& a, int KT, int NTT, int cfg, int gn, hipStream_t s) {
+int umv_gemm_w4_launch(const umv_gemm_args& a, int KT, int NTT, int cfg, hipStream_t s) {
     if (!umv_gemm_w4_can_take(a, KT, NTT)) {
         umv_set_error("gemm_w4: shape / mode not addressable by the 4-wave tiles (fp32 output, K split, or operands beyond 2 GiB)");
         return UMV_ERR_UNSUPPORTED;
     }
-    if (cfg == 466) return launch_w4<2, 2, 8, 8>(a, KT, NTT, gn, s);
-    if (cfg == 468) return launch_w4<2, 2, 8, 4>(a, KT, NTT, gn, s);
-    if (cfg == 4384) return launch_w4<2, 2, 12, 4>(a, KT, NTT, gn, s);
+    if (cfg == 466) return launch_w4<2, 2, 8, 8>(a, KT, NTT, s);
+    if (cfg == 468) return launch_w4<2, 2, 8, 4>(a, KT, NTT, s);
+    if (cfg == 4384) return launch_w4<2, 2, 12, 4>(a, KT, NTT, s);
 #ifdef UMV_GEMM_ABLATIONS
-    if (cfg == 94661) return launch_w4<2, 2, 8, 8, 1>(a, KT, NTT, gn, s);      // timing only: every piece an L2 hit
-    if (cfg == 94662) return launch_w4<2, 2, 8, 8, 2>(a, KT, NTT, gn, s);      // s_memtime trace (a.w_scale = the log)
+    if (cfg == 94661) return launch_w4<2, 2, 8, 8, 1>(a, KT, NTT, s);      // timing only: every piece an L2 hit
+    if (cfg == 94662) return launch_w4<2, 2, 8, 8, 2>(a, KT, NTT, s);      // s_memtime trace (a.w_scale = the log)
 #endif
     umv_set_error("gemm_w4: unknown tile configuration %d", cfg);
     return UMV_ERR_ARG;

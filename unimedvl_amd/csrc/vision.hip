@@ -158,7 +158,7 @@ struct ConvGeom {
 __device__ __attribute__((aligned(16))) const uint32_t g_zero_page_v[4] = {0, 0, 0, 0};
 typedef __attribute__((address_space(3))) void* lds_ptr_v;
 
-// Same pipeline as gemm_tiled_kernel (gemm.hip): WN x WM waves of TN x TM MFMA tiles, k-step KTS*32, NBUF LDS
+// Same pipeline as gemm_tiled_kernel (gemm_tiled.h): WN x WM waves of TN x TM MFMA tiles, k-step KTS*32, NBUF LDS
 // buffers filled by LDS-DMA with counted vmcnt and one raw barrier per step.  W tiles are straight 1 KiB copies
 // of the packed image; an x tile is the im2col fragment gathered per lane (tap / channel decode per k, zero page
 // for padding, upsampled or strided source coordinates by mode).
