@@ -154,6 +154,39 @@ int umv_gemm_mxfp4w(const umv_gemm_args* a, umv_stream_t stream);
  * norm_w, argmax_partial, th-row tiles and M <= 64 are UMV_ERR_UNSUPPORTED */
 int umv_gemm_mxfp4t(const umv_gemm_args* a, umv_stream_t stream);
 
+/* ------------------------------------------------------------------ exact 13-bit image of bf16 weights ("z13"; no reference
+ * counterpart).  The decode GEMMs are HBM-bound and a bf16 weight's 8 exponent bits carry ~2.5 bits of entropy: this image keeps the
+ * sign and the 7 mantissa bits as they are and codes the exponent field in 5 bits below a per-tile-pair base, WITHOUT LOSS:
+ *   umv_gemm_z13w(x, pack_z13(W))  ==  umv_gemm_bf16(x, pack(W))   bit for bit, for every M <= 64, every K split, every epilogue
+ * (finite x, the precondition of the full-line x staging of the weight-streaming kernels; umv_gemm_bf16 under its DEFAULT policy: its
+ * tuning variables UMV_GEMM_SKINNY_MAX and UMV_GEMM_M64_TILED move 33..64-row calls between its weight-streaming kernel and an MFMA tile,
+ * which sum in another order - the contract is not given for the rows they move).
+ * Unit = a PAIR of 16-row n-tiles (2p, 2p + 1; a (gate, up) pair of a SwiGLU image) x 64 k.  NP = ceil(ceil(N/16) / 2), KT8 = K / 64
+ * (K % 64 == 0, K <= 32768).  Image (umv_packed_weight_z13_bytes, 256-byte aligned):
+ *   head   H[NP][16 B] at byte 0, per pair (one scalar load brings both to a workgroup):
+ *            flags u64: bit b is set when rows of the pair hold, in k = [512 b, 512 b + 512), a weight that cannot be coded
+ *                       (512 = the granule the decode kernel cuts K ranges by);
+ *            base  u8:  the pair's largest exponent field BELOW 255 (0 when it has none); then 7 zero bytes;
+ *   records R[p][k/64][3328 B] at byte roundup(16 NP, 256).  Lane = ((k%32)/8)*16 + n%16 holds the weights of the bf16 image's four
+ *          fragments (tile 2p + tt, k half h = (k%64)/32, j = k%8), fragment number f = 2 tt + h:
+ *            [0, 1024) / [1024, 2048): tile 2p / 2p + 1, 16 B per lane: byte 8 h + j = s << 7 | m7 (sign, mantissa);
+ *            [2048, 3072): 16 B per lane, dword f: the low 4 bits of the code of weight j at bit 8 B(j) + 4 (j >> 2),
+ *                          B(j) = 2 (j & 1) + ((j >> 1) & 1);
+ *            [3072, 3328): 4 B per lane: the top bit of the code of (f, j) at bit 8 B(j) + 2 f + (j >> 2).
+ *   code = base - exponent field, in 0..30 (31 is reserved and never written); bf16 bits = s << 15 | (base - code) << 7 | m7.  A field
+ *   of 0 (zeros, subnormals) is a field like any other: codable when base <= 30, otherwise it flags - there is no zero code (it would
+ *   cost the decode an instruction per two weights; trained weights and N(0, s^2) draws hold no zeros).
+ *   Uncodable: field 255 (Inf / NaN) or more than 30 below the base.  Such a weight is written as code 0 and flags its block; rows at
+ *   or beyond N (packed row order) and the missing tile of a ragged last pair never flag and do not count for the base.  The workgroups
+ *   whose pairs and K range meet a set flag run the bf16 kernel on the bf16 image instead, so the bf16 image stays resident.
+ * umv_pack_weight_z13 reads the PACKED bf16 image (umv_pack_weight_bf16 / _swiglu_bf16, the latter with N = 2 I, I % 16 == 0). */
+size_t umv_packed_weight_z13_bytes(int N, int K);
+int umv_pack_weight_z13(const uint16_t* packed16, uint8_t* z13, int N, int K, umv_stream_t stream);
+/* M <= 64 only, 16-row images, K % 64 == 0; a->wp = the bf16 image (the fallback), z13 = its 13-bit image; BIAS, RESIDUAL, SWIGLU,
+ * OUT_F32, row_idx, argmax_partial / sampling keys and split-K partials as umv_gemm_bf16; norm_w and th-row tiles are
+ * UMV_ERR_UNSUPPORTED.  (33..64 rows of a SwiGLU / N >= 16384 GEMM, which umv_gemm_bf16 runs on an MFMA tile, run there.) */
+int umv_gemm_z13w(const umv_gemm_args* a, const void* z13, umv_stream_t stream);
+
 /* W8A8 on the fp8 matrix instruction (v_mfma_scale_f32_16x16x128_f8f6f4) for the MFMA-bound GEMMs of the fp8 mode
  * (M > 64: prefill, flow passes).  Activations are quantised per ROW the way weights are per channel:
  *   sx[m] = smallest 2^e with 448 * 2^e >= max_k |x[m,k]|,  xq = rne_e4m3(x / sx)   (umv_quantize_act_fp8; rows may be

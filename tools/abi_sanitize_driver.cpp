@@ -31,7 +31,8 @@ static void queries() {
     size_t acc = 0;
     for (int n : {1, 16, 17, 1152, 3584, 4608, 37888, 152064})
         for (int k : {8, 32, 608, 1152, 3584, 18944}) {
-            acc += umv_packed_weight_elems(n, k) + umv_packed_weight_fp8_bytes(n, k) + umv_packed_weight_fp8_mfma_bytes(n, k) + umv_packed_weight_mxfp4_bytes(n, k);
+            acc += umv_packed_weight_elems(n, k) + umv_packed_weight_fp8_bytes(n, k) + umv_packed_weight_fp8_mfma_bytes(n, k) + umv_packed_weight_mxfp4_bytes(n, k) +
+                   umv_packed_weight_z13_bytes(n, k);
             for (int th : {1, 9, 14, 16}) acc += umv_repacked_weight_elems(n, k, th);
             for (int m : {1, 8, 64, 65, 272, 1026, 2064, 8208, 16500}) acc += (size_t)umv_gemm_tile_config(m, n, k);
         }
@@ -85,6 +86,19 @@ static void bad_arguments() {
     EXPECT_ERR(umv_gemm_mxfp4t(&g, nullptr));
     g.norm_w = nullptr; g.argmax_partial = (uint64_t*)dummyl;   // lm_head stays e4m3
     EXPECT_ERR(umv_gemm_mxfp4t(&g, nullptr));
+    EXPECT_ERR(umv_gemm_z13w(nullptr, nullptr, nullptr));
+    std::memset(&g, 0, sizeof g);
+    EXPECT_ERR(umv_gemm_z13w(&g, dummy8, nullptr));             // null x / wp / out
+    g.x = dummy16; g.wp = dummy16; g.out = dummy16; g.M = 8; g.N = 16; g.K = 64;
+    EXPECT_ERR(umv_gemm_z13w(&g, nullptr, nullptr));            // no 13-bit image
+    g.K = 96;                                                   // K % 64 != 0
+    EXPECT_ERR(umv_gemm_z13w(&g, dummy8, nullptr));
+    g.K = 64; g.M = 65;                                         // the decode layout only
+    EXPECT_ERR(umv_gemm_z13w(&g, dummy8, nullptr));
+    g.M = 8; g.norm_w = dummy16;                                // no fused norm
+    EXPECT_ERR(umv_gemm_z13w(&g, dummy8, nullptr));
+    g.norm_w = nullptr; g.tile_rows = 14;                       // 16-row images only
+    EXPECT_ERR(umv_gemm_z13w(&g, dummy8, nullptr));
     std::memset(&g, 0, sizeof g);
     EXPECT_ERR(umv_gemm_fp8a8w(nullptr, nullptr));
     umv_gemm8_args g8;
@@ -99,6 +113,8 @@ static void bad_arguments() {
     EXPECT_ERR(umv_quantize_pack_weight_mxfp4(nullptr, nullptr, nullptr, nullptr, nullptr, 16, 512, nullptr));
     EXPECT_ERR(umv_quantize_pack_weight_mxfp4(dummy16, nullptr, dummy8, nullptr, nullptr, 16, 48, nullptr));     // K % 32 != 0
     EXPECT_ERR(umv_quantize_pack_weight_mxfp4(dummy16, dummy16, dummy8, nullptr, nullptr, 17, 64, nullptr));     // SwiGLU I % 16
+    EXPECT_ERR(umv_pack_weight_z13(nullptr, nullptr, 16, 64, nullptr));
+    EXPECT_ERR(umv_pack_weight_z13(dummy16, dummy8, 16, 96, nullptr));                                           // K % 64 != 0
     EXPECT_ERR(umv_quantize_act_fp8(nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, 8, 128, nullptr));
     // attention / qkv_post
     EXPECT_ERR(umv_attn_varlen(nullptr, nullptr));

@@ -88,6 +88,9 @@ _SIGS = {
     "umv_quantize_pack_weight_mxfp4": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                                  C.c_void_p]),
     "umv_gemm_mxfp4w": (C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
+    "umv_packed_weight_z13_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "umv_pack_weight_z13": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "umv_gemm_z13w": (C.c_int, [C.POINTER(GemmArgs), C.c_void_p, C.c_void_p]),
     "umv_gemm_mxfp4t": (C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
     "umv_residual_rmsnorm_bf16": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                             C.c_int, C.c_float, C.c_void_p]),

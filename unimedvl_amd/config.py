@@ -27,6 +27,10 @@ class UniMedVLConfig:
     # and 65..128-row decode steps run the tiled GEMM on the MXFP4 image (umv_gemm_mxfp4t; same bits, 10.6 GB resident for the whole engine,
     # 65..128-sample decode steps 4-7 % faster, prefill GEMMs 1.2-2.0x slower: DESIGN.md section 5.1)
     llm_fp4_keep_bf16: bool = True
+    # llm_weight_dtype == "bf16" only: the `und` expert's gate/up and down projections and lm_head also carry the exact 13-bit image of
+    # their bf16 weights (include/unimedvl_hip.h "z13") and the decode step's GEMMs on them, up to 32 rows, stream it instead (gate/up and
+    # lm_head not at 9..16 rows: a tie there): the same bits from 13/16 of the bytes, for ~10 GB more resident memory.  The environment variable UMV_DECODE_Z13=0 switches it off (A/B).
+    llm_decode_z13: bool = True
     # "fp8" (needs llm_weight_dtype == "fp8"): W8A8 - every LLM forward that is not a one-token decode step rounds the
     # activations of its linear layers per row through e4m3 and runs them on the fp8 matrix instruction
     # (umv_gemm_fp8a8w); decode steps keep bf16 activations on the e4m3 weight stream

@@ -10,6 +10,9 @@
 //   SkBf16<NT>    bf16 image, unit = one 32-k tile (KH = 1 k half); th-row tiles; the fused RMSNorm prologue (NORM)
 //   SkE4m3<NT>    e4m3 image + one power-of-two scale per row, unit = 64 k (KH = 2): 16 B per lane and n-tile -> two fragments
 //   SkMxfp4<NP>   MXFP4 codes + E8M0 block scales, unit = 64 k: 16 B + 4 scale bytes per lane and tile PAIR -> four fragments
+//   SkZ13<NP>     the exact 13-bit image of bf16 weights (sign + mantissa bytes, 5-bit exponent codes below a per-pair base), unit =
+//                 64 k: 52 B per lane and tile pair -> four fragments; HALVES: the K slices are cut in 32-k halves, so they are SkBf16's
+//                 for every K and every split (a half outside the slice decodes to zeros)
 // (the images: pack.hip).  The MFMAs of a chunk issue in the order (u, k half, tile, mb) and every accumulator takes its k in ascending
 // order, so on the same K slices (K % 512 == 0, no split-K) the three images of the same W' give the same bits.
 //
@@ -31,6 +34,7 @@
 template <int NT_>
 struct SkBf16 {       // tile (nt, kt) holds [g][r < TH][8]: TH = a.tile_rows (16 standard); lanes r >= TH of the exact-partition copies carry no row
     static constexpr int NT = NT_, KH = 1;
+    static constexpr bool HALVES = false;
     struct Unit { bf16x8 w[NT]; };
     int TH, tile_elems;
     bool rowlane;
@@ -60,6 +64,7 @@ struct SkBf16 {       // tile (nt, kt) holds [g][r < TH][8]: TH = a.tile_rows (1
 template <int NT_>
 struct SkE4m3 {       // P8[nt][kt8][lane][16 B] (bytes 0..7: k half 0, 8..15: k half 1) + one f32 scale per row in packed order
     static constexpr int NT = NT_, KH = 2, TH = 16;
+    static constexpr bool HALVES = false;
     struct Unit { u32x4 w[NT]; };
     const uint8_t* wbase[NT];
     float wscale[NT];
@@ -87,6 +92,7 @@ struct SkE4m3 {       // P8[nt][kt8][lane][16 B] (bytes 0..7: k half 0, 8..15: k
 template <int NP>
 struct SkMxfp4 {      // codes C[p][kt8][lane][16 B] of tile pairs (4 B per (tile, k half)), then scales S[p][kt8][r][4 B]
     static constexpr int NT = 2 * NP, KH = 2, TH = 16;
+    static constexpr bool HALVES = false;
     struct Unit { u32x4 w[NP]; uint32_t s[NP]; };
     const uint8_t* wbase[NP];
     const uint8_t* sbase[NP];
@@ -116,6 +122,93 @@ struct SkMxfp4 {      // codes C[p][kt8][lane][16 B] of tile pairs (4 B per (til
             wf[1][2 * i] = cvt_fp4x8(b.w[i].y, e8m0_scale((s >> 8) & 0xFFu));
             wf[0][2 * i + 1] = cvt_fp4x8(b.w[i].z, e8m0_scale((s >> 16) & 0xFFu));
             wf[1][2 * i + 1] = cvt_fp4x8(b.w[i].w, e8m0_scale(s >> 24));
+        }
+    }
+};
+
+// The 13-bit image (include/unimedvl_hip.h, pack.hip): per (tile pair, 64 k) one 3328-byte record - two sign/mantissa planes (tile 2p,
+// 2p + 1: 16 B per lane, k half 0 then 1), the low-nibble plane of the exponent codes (16 B per lane, dword f = fragment 2*tile + k half)
+// and their top-bit plane (4 B per lane).  bf16 bits of a weight = s << 15 | (base - code) << 7 | m.  Per fragment the codes are first
+// gathered to one byte each (qa: weights 0..3, qb: 4..7, in the byte order 0, 2, 1, 3 so that a packed 16-bit operation sees the two
+// weights of an output dword), then per output dword: code -> (base - code) << 7 (v_pk_mad_u16 by -128), the s:m7 byte to both bytes of
+// its half (v_perm_b32), one bit-select.  A k half outside the wave's slice takes the constants (0, 0, all ones) and decodes to zeros
+// whatever its bytes are: no extra VALU.
+typedef __attribute__((ext_vector_type(2))) unsigned short umv_u16x2;
+__device__ __forceinline__ uint32_t z13_pk_mad(uint32_t q, uint32_t mul, uint32_t add) {
+    const umv_u16x2 r = __builtin_bit_cast(umv_u16x2, q) * __builtin_bit_cast(umv_u16x2, mul) + __builtin_bit_cast(umv_u16x2, add);
+    return __builtin_bit_cast(uint32_t, r);
+}
+__device__ __forceinline__ uint32_t z13_pk_shr8(uint32_t q) {
+    const umv_u16x2 r = __builtin_bit_cast(umv_u16x2, q) >> (umv_u16x2){8, 8};
+    return __builtin_bit_cast(uint32_t, r);
+}
+// E = fragment number 2*tile + k half (where its top bits sit in t); sm0 / sm1 = the 8 s:m7 bytes, n = the 8 low nibbles
+template <int E>
+__device__ __forceinline__ bf16x8 z13_frag(uint32_t sm0, uint32_t sm1, uint32_t n, uint32_t t, uint32_t mul, uint32_t base7, uint32_t emask) {
+    constexpr int EA = 2 * E, EB = 2 * E + 1;
+    const uint32_t ta = EA < 4 ? t << (4 - EA) : t >> (EA - 4), tb = EB < 4 ? t << (4 - EB) : t >> (EB - 4);
+    const uint32_t qa = (ta & 0x10101010u) | (n & 0x0F0F0F0Fu), qb = (tb & 0x10101010u) | ((n >> 4) & 0x0F0F0F0Fu);
+    const uint32_t e[4] = {z13_pk_mad(qa, mul, base7), z13_pk_mad(z13_pk_shr8(qa), mul, base7), z13_pk_mad(qb, mul, base7),
+                           z13_pk_mad(z13_pk_shr8(qb), mul, base7)};
+    const uint32_t p[4] = {__builtin_amdgcn_perm(sm0, sm0, 0x01010000u), __builtin_amdgcn_perm(sm0, sm0, 0x03030202u),
+                           __builtin_amdgcn_perm(sm1, sm1, 0x01010000u), __builtin_amdgcn_perm(sm1, sm1, 0x03030202u)};
+    u32x4 o;
+    o.x = (e[0] & emask) | (p[0] & ~emask);
+    o.y = (e[1] & emask) | (p[1] & ~emask);
+    o.z = (e[2] & emask) | (p[2] & ~emask);
+    o.w = (e[3] & emask) | (p[3] & ~emask);
+    return __builtin_bit_cast(bf16x8, o);
+}
+
+#define Z13_RECORD 3328
+// bytes before the records: one 16-byte entry per pair (flags u64, base u8, 7 zero bytes), rounded up to 256
+__host__ __device__ __forceinline__ int64_t z13_head_bytes(int NPT) { return ((int64_t)NPT * 16 + 255) / 256 * 256; }
+
+template <int NP>
+struct SkZ13 {        // head H[NPT][16 B] = (flags u64, base u8, 0...), then (256-aligned) records R[p][kt8][3328 B]; a.wp = the image
+    static constexpr int NT = 2 * NP, KH = 2, TH = 16;
+    static constexpr bool HALVES = true;
+    struct Unit { u32x4 sm[NP][2]; u32x4 n[NP]; uint32_t t[NP]; };
+    const uint8_t* rec[NP];      // wave-uniform: the pair's records
+    uint32_t base7[NP];          // (base << 7) in both halves
+    uint32_t lane16, lane4;
+    __device__ __forceinline__ SkZ13(const umv_gemm_args& a, int KT8, int, int NPT, int, int lane) {
+        const uint8_t* img = reinterpret_cast<const uint8_t*>(a.wp);
+        const int p0 = blockIdx.x * NP;
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int p = (p0 + i) < NPT ? p0 + i : 0;          // pairs past the end re-read pair 0; their columns are never stored
+            rec[i] = img + z13_head_bytes(NPT) + (int64_t)p * KT8 * Z13_RECORD;
+            const uint32_t b = reinterpret_cast<const uint32_t*>(img)[4 * p + 2] & 0xFFu;   // next to the flags the kernel has just read
+            base7[i] = (b << 7) * 0x10001u;
+        }
+        lane16 = (uint32_t)lane * 16u;
+        lane4 = 3072u + (uint32_t)lane * 4u;
+    }
+    __device__ __forceinline__ void load(Unit& b, int kt, bool ok) const {
+        const int ktu = __builtin_amdgcn_readfirstlane(kt);      // a wave's unit: scalar base + lane offset addressing
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const uint8_t* r = rec[i] + (int64_t)ktu * Z13_RECORD;
+            const u32x4 z = {0u, 0u, 0u, 0u};
+            b.sm[i][0] = ok ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(r + lane16)) : z;
+            b.sm[i][1] = ok ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(r + 1024 + lane16)) : z;
+            b.n[i] = ok ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(r + 2048 + lane16)) : z;
+            b.t[i] = ok ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(r + lane4)) : 0u;
+        }
+    }
+    // v0 / v1: k half 0 / 1 of the unit lies inside the wave's slice (wave-uniform)
+    __device__ __forceinline__ void frags(const Unit& b, bf16x8 (&wf)[KH][NT], bool in0, bool in1) const {
+        const bool v0 = __builtin_amdgcn_readfirstlane((int)in0) != 0, v1 = __builtin_amdgcn_readfirstlane((int)in1) != 0;   // constants in SGPRs
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const uint32_t mul0 = v0 ? 0xFF80FF80u : 0u, mul1 = v1 ? 0xFF80FF80u : 0u;
+            const uint32_t b0 = v0 ? base7[i] : 0u, b1 = v1 ? base7[i] : 0u;
+            const uint32_t m0 = v0 ? 0x7F807F80u : 0xFFFFFFFFu, m1 = v1 ? 0x7F807F80u : 0xFFFFFFFFu;
+            wf[0][2 * i] = z13_frag<0>(b.sm[i][0].x, b.sm[i][0].y, b.n[i].x, b.t[i], mul0, b0, m0);
+            wf[1][2 * i] = z13_frag<1>(b.sm[i][0].z, b.sm[i][0].w, b.n[i].y, b.t[i], mul1, b1, m1);
+            wf[0][2 * i + 1] = z13_frag<2>(b.sm[i][1].x, b.sm[i][1].y, b.n[i].z, b.t[i], mul0, b0, m0);
+            wf[1][2 * i + 1] = z13_frag<3>(b.sm[i][1].z, b.sm[i][1].w, b.n[i].w, b.t[i], mul1, b1, m1);
         }
     }
 };
@@ -226,12 +319,17 @@ __device__ __forceinline__ void gemm_skinny_body(const umv_gemm_args& a, int KT,
         for (int mb = 0; mb < MB; ++mb) acc[t][mb] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     // split-K (a.k_splits > 1): blockIdx.y owns the units [ks0, ks1) and stores raw fp32 partial sums
+    // HALVES: the same cut in 32-k halves [g_begin, g_end) - SkBf16's slices - and the units that hold them
     const int nsplit = a.k_splits > 1 ? a.k_splits : 1;
-    const int kts = (KT + nsplit - 1) / nsplit;
-    const int ks0 = (int)blockIdx.y * kts, ks1 = min(KT, ks0 + kts);
+    constexpr int SG = F::HALVES ? KH : 1;                          // slice granules per unit
+    const int KTG = KT * SG;
+    const int kts = (KTG + nsplit - 1) / nsplit;
+    const int ks0 = (int)blockIdx.y * kts, ks1 = min(KTG, ks0 + kts);
     const int kt_per = (max(0, ks1 - ks0) + SK_WAVES - 1) / SK_WAVES;
-    const int kt_begin = ks0 + wave * kt_per;
-    const int kt_end = min(ks1, kt_begin + kt_per);
+    const int g_begin = ks0 + wave * kt_per;
+    const int g_end = min(ks1, g_begin + kt_per);
+    const int kt_begin = g_begin / SG;
+    const int kt_end = g_end > g_begin ? (g_end + SG - 1) / SG : kt_begin;
     // XL works on whole lines: a slice that starts inside one (a bf16 slice on an odd k-tile) starts at the line's first unit, with
     // that unit's weights masked to zero - an MFMA that adds exact zeros (the x it multiplies is the neighbour wave's, finite).
     // PRECONDITION of "bit-identical to the plain form": x is finite.  Where x holds Inf / NaN in the neighbour's k-tile the masked
@@ -243,6 +341,7 @@ __device__ __forceinline__ void gemm_skinny_body(const umv_gemm_args& a, int KT,
     const int nchunks = (nk + U - 1) / U;
     const F f(a, KT, NTT, NPT, nt0, lane);
     static_assert(!XL || ((U * KH) % 2 == 0 && NORM == 0), "full-line x staging: whole lines per chunk, no fused norm");
+    static_assert(!F::HALVES || NORM == 0, "half-unit slices: no fused norm");
     static_assert(XL != 1 || MB == 1, "one-piece staging serves one 16-row tile of at most 8 valid rows");
     constexpr int XLN = U * KH / 2, XLP = XL == 1 ? 1 : 2 * MB;     // lines per chunk, pieces per line
     // XL: this lane's row of each 8-row piece and its 16-byte chunk of the line
@@ -388,7 +487,12 @@ __device__ __forceinline__ void gemm_skinny_body(const umv_gemm_args& a, int KT,
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 bf16x8 wf[KH][NT];
-                f.frags(b.w[u], wf);
+                if constexpr (F::HALVES) {
+                    const int g0 = (kt_lo + c * U + u) * SG;
+                    f.frags(b.w[u], wf, g0 >= g_begin && g0 < g_end, g0 + 1 >= g_begin && g0 + 1 < g_end);
+                } else {
+                    f.frags(b.w[u], wf);
+                }
 #pragma unroll
                 for (int h = 0; h < KH; ++h)
 #pragma unroll

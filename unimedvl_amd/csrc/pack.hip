@@ -6,6 +6,8 @@
 //   e4m3   P8[n/16][k/64][lane][16 B] + one power-of-two fp32 scale per output channel (umv_quantize_pack_weight_fp8), and the
 //          K = 128 image of the scaled fp8 MFMA made from it (umv_repack_weight_fp8_mfma)
 //   MXFP4  C[pair of 16-row tiles][k/64][lane][16 B] e2m1 codes, then E8M0 scales per 32 k (umv_quantize_pack_weight_mxfp4)
+//   z13    the bf16 image without loss at 13 bits per weight: flags and bases per tile pair, then R[pair][k/64][3328 B]
+//          (umv_pack_weight_z13)
 //
 // This file and the headers it includes (with PACK_LAYOUT_VERSION) are what unimedvl_amd/packstore.py stamps its on-disk cache of
 // packed images with: an edit here invalidates the cache, an edit of a GEMM / attention / vision kernel does not.
@@ -338,6 +340,116 @@ extern "C" int umv_quantize_pack_weight_mxfp4(const uint16_t* w, const uint16_t*
     const size_t lds = (size_t)32 * 2 * KT8;
     hipLaunchKernelGGL(quantize_pack_mxfp4_kernel, dim3(NP), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)w, (const bf16_t*)w_up,
                        packed4, (bf16_t*)deq, (bf16_t*)deq_up, rows, K, KT8, NTT, NP);
+    UMV_LAUNCH_CHECK();
+    return UMV_OK;
+}
+
+// ----------------------------------------------------------------------------- the exact 13-bit image ("z13")
+// bf16 weights without loss at 13 bits each (decode GEMM: gemm_z13.hip; format: include/unimedvl_hip.h).  Made from the packed bf16
+// image, which stays resident as the fallback of flagged blocks: lane (r, g) of record (pair p, unit u) holds the 32 weights of the
+// bf16 image's fragments (tile 2p + tt, k-tile 2u + h), fragment number f = 2*tt + h.
+//   base[p]  = the largest exponent field below 255 among the pair's rows (rows at or beyond N do not count)
+//   code     = base - field, codable when field != 255 and code <= 30; anything else is written as code 0 and, in a row below N,
+//              flags its (pair, 512-k block)
+#define Z13_RECORD 3328
+static inline size_t z13_head_bytes_host(size_t NPT) { return (NPT * 16 + 255) / 256 * 256; }
+
+__global__ __launch_bounds__(256) void z13_base_kernel(const bf16_t* __restrict__ p16, unsigned long long* __restrict__ head, int N, int KT,
+                                                       int NTT) {
+    __shared__ uint32_t smax[256];
+    const int p = blockIdx.x, tid = threadIdx.x;
+    uint32_t m = 0;
+    for (int tt = 0; tt < 2; ++tt) {
+        const int nt = 2 * p + tt;
+        if (nt >= NTT) continue;
+        for (int64_t idx = tid; idx < (int64_t)KT * 64; idx += 256) {       // one 8-element group per step
+            const int lane = (int)(idx & 63);
+            if (nt * 16 + (lane & 15) >= N) continue;
+            const u32x4 v = *reinterpret_cast<const u32x4*>(p16 + ((int64_t)nt * KT * 64 + idx) * 8);
+            const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t f0 = (wd[j] >> 7) & 0xFFu, f1 = (wd[j] >> 23) & 0xFFu;
+                if (f0 != 255u) m = max(m, f0);
+                if (f1 != 255u) m = max(m, f1);
+            }
+        }
+    }
+    smax[tid] = m;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) smax[tid] = max(smax[tid], smax[tid + s]);
+        __syncthreads();
+    }
+    if (tid == 0) {              // the pair's 16-byte head entry: flags (the encode kernel ORs into them), base, zeros
+        head[2 * p] = 0;
+        head[2 * p + 1] = smax[0];
+    }
+}
+
+// one thread per (pair, unit, lane); z13_base_kernel has zeroed the flags
+__global__ __launch_bounds__(256) void z13_encode_kernel(const bf16_t* __restrict__ p16, uint8_t* __restrict__ img, int N, int KT8, int NTT,
+                                                         int NPT, int64_t total) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= total) return;
+    const int lane = (int)(gid & 63);
+    const int u = (int)((gid >> 6) % KT8);
+    const int p = (int)((gid >> 6) / KT8);
+    const int KT = 2 * KT8;
+    const uint32_t base = img[(int64_t)p * 16 + 8];
+    uint32_t sm[2][4] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}}, nib[4] = {0u, 0u, 0u, 0u}, top = 0u;
+    bool flag = false;
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt) {
+        const int nt = 2 * p + tt;
+        if (nt >= NTT) continue;                                   // the missing tile of a ragged pair: zeros
+        const bool counts = nt * 16 + (lane & 15) < N;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const u32x4 v = *reinterpret_cast<const u32x4*>(p16 + (((int64_t)nt * KT + 2 * u + h) * 64 + lane) * 8);
+            const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
+            const int f = 2 * tt + h;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const uint32_t w = (wd[j >> 1] >> (16 * (j & 1))) & 0xFFFFu;
+                const uint32_t field = (w >> 7) & 0xFFu;
+                const bool codable = field != 255u && base >= field && base - field <= 30u;
+                const uint32_t code = codable ? base - field : 0u;
+                flag = flag || (counts && !codable);
+                const int byte = ((j & 1) << 1) | ((j >> 1) & 1), q = j >> 2;
+                sm[tt][2 * h + (j >> 2)] |= (((w >> 8) & 0x80u) | (w & 0x7Fu)) << (8 * (j & 3));
+                nib[f] |= (code & 15u) << (8 * byte + 4 * q);
+                top |= (code >> 4) << (8 * byte + 2 * f + q);
+            }
+        }
+    }
+    uint8_t* rec = img + ((int64_t)NPT * 16 + 255) / 256 * 256 + ((int64_t)p * KT8 + u) * Z13_RECORD;
+    *reinterpret_cast<u32x4*>(rec + lane * 16) = (u32x4){sm[0][0], sm[0][1], sm[0][2], sm[0][3]};
+    *reinterpret_cast<u32x4*>(rec + 1024 + lane * 16) = (u32x4){sm[1][0], sm[1][1], sm[1][2], sm[1][3]};
+    *reinterpret_cast<u32x4*>(rec + 2048 + lane * 16) = (u32x4){nib[0], nib[1], nib[2], nib[3]};
+    *reinterpret_cast<uint32_t*>(rec + 3072 + lane * 4) = top;
+    if (flag) atomicOr(reinterpret_cast<unsigned long long*>(img) + 2 * p, 1ull << (u >> 3));
+}
+
+extern "C" size_t umv_packed_weight_z13_bytes(int N, int K) {
+    if (N <= 0 || K <= 0) return 0;
+    const size_t np = ((size_t)(N + 15) / 16 + 1) / 2, kt8 = (size_t)(K + 63) / 64;
+    return z13_head_bytes_host(np) + np * kt8 * Z13_RECORD;
+}
+
+extern "C" int umv_pack_weight_z13(const uint16_t* packed16, uint8_t* z13, int N, int K, umv_stream_t stream) {
+    UMV_CHECK(packed16 && z13 && N > 0 && K > 0, UMV_ERR_ARG, "pack_weight_z13: bad args");
+    UMV_CHECK((K % 64) == 0 && K <= 32768, UMV_ERR_ARG, "pack_weight_z13: K (%d) must be a multiple of 64 and <= 32768", K);
+    UMV_CHECK(((uintptr_t)packed16 % 16) == 0 && ((uintptr_t)z13 % 256) == 0, UMV_ERR_ARG,
+              "pack_weight_z13: the bf16 image must be 16-byte and the 13-bit image 256-byte aligned");
+    const int NTT = (N + 15) / 16, NPT = (NTT + 1) / 2, KT8 = K / 64;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(z13_base_kernel, dim3(NPT), dim3(256), 0, s, (const bf16_t*)packed16,
+                       reinterpret_cast<unsigned long long*>(z13), N, 2 * KT8, NTT);
+    UMV_LAUNCH_CHECK();
+    const int64_t total = (int64_t)NPT * KT8 * 64;
+    hipLaunchKernelGGL(z13_encode_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const bf16_t*)packed16, z13, N, KT8, NTT,
+                       NPT, total);
     UMV_LAUNCH_CHECK();
     return UMV_OK;
 }

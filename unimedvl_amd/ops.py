@@ -58,10 +58,13 @@ def _req(t, dtype, name):
     return t
 
 
+Z13_MAX_ROWS = 32      # rows up to which a linear's exact 13-bit image is streamed instead of its bf16 image (measured at 8 and 32)
+
+
 class PackedLinear:
     """nn.Linear weight [N,K] (+bias) re-tiled for the MFMA GEMM kernels."""
 
-    __slots__ = ("wp", "bias", "N", "K", "swiglu", "th", "w8", "scale", "w8m", "w4")
+    __slots__ = ("wp", "bias", "N", "K", "swiglu", "th", "w8", "scale", "w8m", "w4", "wz")
 
     def __init__(self, wp, bias, N, K, swiglu=False, th=16, w8=None, scale=None, w4=None):
         self.wp, self.bias, self.N, self.K, self.swiglu, self.th = wp, bias, N, K, swiglu, th
@@ -75,6 +78,18 @@ class PackedLinear:
         # the tiled MXFP4 GEMM above that; wp is then either the bf16 image of the SAME dequantised weights (M > 64 runs on it when it is
         # there: bit-identical) or None (keep_bf16=False / drop_bf16: the linear stands on its 4-bit image alone)
         self.w4 = w4
+        # optional: the exact 13-bit image of wp (build_z13), streamed instead of wp by the decode forms of the GEMM (SwiGLU, argmax keys,
+        # split-K partials) up to Z13_MAX_ROWS rows: same bits, 13/16 of the bytes; wp stays (its fallback, and every other GEMM)
+        self.wz = None
+
+    def build_z13(self):
+        """Add the exact 13-bit image of the bf16 image (include/unimedvl_hip.h, "z13"): the decode forms of the GEMM then stream it."""
+        if self.wp is None or self.th != 16 or self.w8 is not None or self.w4 is not None or self.K % 64 or self.K > 32768:
+            raise _lib.UmvError("build_z13 needs a plain bf16 linear (16-row image) with K a multiple of 64, K <= 32768")
+        lib = _lib.load()
+        self.wz = torch.empty(lib.umv_packed_weight_z13_bytes(self.N, self.K), dtype=torch.uint8, device=self.wp.device)
+        check(lib.umv_pack_weight_z13(_p(self.wp), _p(self.wz), self.N, self.K, _stream()), "umv_pack_weight_z13")
+        return self
 
     def drop_bf16(self):
         """Release the bf16 image of the dequantised weights of an fp4 linear: M > 64 then runs the tiled GEMM on the MXFP4 image."""
@@ -206,15 +221,31 @@ class PackedLinear:
         return self.wp.numel() * 2 if self.wp is not None else self.w4.numel()
 
 
+def _z13_takes(lin, M, z13, form):
+    """whether a call streams the linear's exact 13-bit image.  form: "splitk" (split-K partials), "epilogue" (SwiGLU or argmax /
+    sampling keys) or None (anything else).  z13 = None: the measured policy (DESIGN.md section 5.2) - split-K up to Z13_MAX_ROWS rows;
+    the epilogue forms up to 8 rows and at 17..Z13_MAX_ROWS, not at 9..16, where gate/up and lm_head only tie with the bf16 kernel;
+    True: whenever umv_gemm_z13w serves the call (M <= 64; tests, A/B); False: never"""
+    if lin.wz is None or z13 is False:
+        return False
+    if z13:
+        return M <= 64
+    if form == "splitk":
+        return M <= Z13_MAX_ROWS
+    return form == "epilogue" and (M <= 8 or 16 < M <= Z13_MAX_ROWS)
+
+
 def gemm(x, lin, out=None, *, M=None, residual=None, act=None, row_idx=None, out_f32=False, use_bias=True,
-         norm_w=None, norm_eps=1e-6, act8=False, argmax_partial=None, sample=None):
+         norm_w=None, norm_eps=1e-6, act8=False, argmax_partial=None, sample=None, z13=None):
     """out = epilogue(x @ W^T).  x [M,K] bf16 (row stride may exceed K).  act in {None,'gelu_tanh','silu'}.
     norm_w: fuse Qwen2RMSNorm(x)*norm_w into the GEMM prologue (M <= 16, K <= 4096).
     act8 (W8A8 mode, needs lin.w8m): the activations are rounded per row through e4m3 - on the fp8 matrix instruction for
     M > 64 rows, as a bf16 copy of the rounded rows for the weight-streaming kernels below that.
     argmax_partial (int64 [M, ceil(N/16)], M <= 64): greedy-argmax keys per 16-column tile, finished by decode_step_end_argmax.
     sample (with argmax_partial): (temperature, seed, step tensor or None) - the keys then order bf16(logit / T) + Gumbel noise, so the
-    row maximum is one draw from softmax(logits / T) (bagel.py:1297-1299) instead of the greedy token."""
+    row maximum is one draw from softmax(logits / T) (bagel.py:1297-1299) instead of the greedy token.
+    z13 (tests and A/B only; leave None): whether a linear's exact 13-bit image is streamed - None = the measured policy of _z13_takes,
+    True = whenever umv_gemm_z13w serves the call, False = never."""
     lib = _lib.load()
     _req(x, BF16, "x")
     assert x.stride(-1) == 1
@@ -313,6 +344,14 @@ def gemm(x, lin, out=None, *, M=None, residual=None, act=None, row_idx=None, out
         M=M, N=lin.N, K=lin.K, epilogue=flags,
         norm_w=norm_w.data_ptr() if norm_w is not None else None, norm_eps=norm_eps, tile_rows=lin.th, argmax_partial=amax,
         x_rows=x.shape[0], **_sample_fields(sample, amax))
+    if _z13_takes(lin, M, z13, "epilogue" if (lin.swiglu or amax is not None) else None) and norm_w is None and \
+            not (flags & (EPI_GELU_TANH | EPI_SILU)):
+        # the exact 13-bit image: the bf16 kernel's bits from 13/16 of the bytes.  Only the forms that were measured against the bf16
+        # kernel and won: the SwiGLU gate/up GEMM and lm_head with the argmax / sampling keys, up to 8 and at
+        # 17..32 rows (split-K down: gemm_splitk).  Every other call on such a linear - a short prefill, MoT text rows, down without a split,
+        # plain lm_head, 33..64 rows - stays on umv_gemm_bf16.
+        check(lib.umv_gemm_z13w(C.byref(a), lin.wz.data_ptr(), _stream()), "umv_gemm_z13w")
+        return out
     check(lib.umv_gemm_bf16(C.byref(a), _stream()), "umv_gemm_bf16")
     return out
 
@@ -488,9 +527,9 @@ def _sample_fields(sample, amax):
     return dict(sample_temperature=float(t), sample_seed=int(seed) & (2 ** 64 - 1), sample_step=None if step is None else step.data_ptr())
 
 
-def gemm_splitk(x, lin, partials, k_splits, *, M=None):
+def gemm_splitk(x, lin, partials, k_splits, *, M=None, z13=None):
     """Split-K decode GEMM (M <= 64): raw fp32 partial sums [k_splits, rows, N] into `partials`; the consumer
-    (qkv_post(partials=...) / residual_rmsnorm) adds the splits and finishes the row."""
+    (qkv_post(partials=...) / residual_rmsnorm) adds the splits and finishes the row.  z13: as in gemm (tests and A/B only)."""
     lib = _lib.load()
     _req(x, BF16, "x")
     _req(partials, torch.float32, "partials")
@@ -508,6 +547,8 @@ def gemm_splitk(x, lin, partials, k_splits, *, M=None):
     elif lin.w4 is not None and lin.wp is None:   # 65..128 rows without a bf16 image of W': the tiled kernel on the MXFP4 image (same partials)
         a.wp = lin.w4.data_ptr()
         check(lib.umv_gemm_mxfp4t(C.byref(a), _stream()), "umv_gemm_mxfp4t")
+    elif _z13_takes(lin, M, z13, "splitk"):      # the exact 13-bit image of wp: the same partials (measured up to 32 rows)
+        check(lib.umv_gemm_z13w(C.byref(a), lin.wz.data_ptr(), _stream()), "umv_gemm_z13w")
     else:
         check(lib.umv_gemm_bf16(C.byref(a), _stream()), "umv_gemm_bf16")
     return partials

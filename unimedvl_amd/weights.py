@@ -7,6 +7,8 @@ callable, moved to the GPU and re-tiled for the MFMA GEMM kernels
 weight and gate/up into one interleaved SwiGLU weight, per expert.
 """
 import math
+import os
+import warnings
 
 import torch
 
@@ -90,6 +92,15 @@ class LLMWeights:
         self.norm = _tensor(get, device, p + "norm.weight")
         self.norm_gen = _tensor(get, device, p + "norm_moe_gen.weight") if load_gen else None
         self.lm_head = _linear(get, device, "language_model.lm_head.weight", fp8=fp8 or fp4)
+        # the exact 13-bit decode images (config.llm_decode_z13): rebuilt from the bf16 images at every load, never stored
+        self.z13 = bool(cfg.llm_decode_z13) and not fp8 and not fp4 and os.environ.get("UMV_DECODE_Z13", "1") != "0"
+        if self.z13:
+            for lin in [self.lm_head] + [l for lw in self.und for l in (lw.gate_up, lw.down)]:
+                if lin.K % 64 == 0 and lin.K <= 32768 and lin.th == 16:
+                    lin.build_z13()
+                else:       # the step would quietly stream bf16: say so
+                    warnings.warn(f"llm_decode_z13: no 13-bit image for a {lin.N} x {lin.K} linear (needs K % 64 == 0, K <= 32768, "
+                                  "16-row tiles); its decode GEMMs stream the bf16 image")
         # rotary tables exactly as Qwen2RotaryEmbedding returns them (modeling_qwen2.py:164-184):
         # fp32 outer product, cos/sin, cast to bf16; built on the CPU so the bits match torch's.
         hd = cfg.head_dim
@@ -131,8 +142,10 @@ class LLMWeights:
 
     def decode_weight_bytes(self):
         """bytes one decode step streams: the e4m3 images when llm_weight_dtype == "fp8", the MXFP4 images (block scales included)
-        and the e4m3 lm_head when "fp4", else the bf16 ones"""
-        nb = (lambda lin: lin.w8.numel()) if self.fp8 else (lambda lin: lin.w4.numel()) if self.fp4 else (lambda lin: lin.nbytes())
+        and the e4m3 lm_head when "fp4", else the bf16 ones - the exact 13-bit image where a linear has one (its few flagged blocks,
+        which stream the bf16 image instead, are counted at 13 bits)"""
+        bf16 = lambda lin: lin.wz.numel() if lin.wz is not None else lin.nbytes()      # noqa: E731
+        nb = (lambda lin: lin.w8.numel()) if self.fp8 else (lambda lin: lin.w4.numel()) if self.fp4 else bf16
         n = self.lm_head.w8.numel() if self.fp4 else nb(self.lm_head)
         for lw in self.und:
             n += nb(lw.qkv) + nb(lw.o) + nb(lw.gate_up) + nb(lw.down)
