@@ -62,13 +62,8 @@ extern "C" int umv_gemm_fp8w(const umv_gemm_args* ap, umv_stream_t stream) {
     umv_gemm_args a = *ap;
     UMV_CHECK(a.x && a.wp && a.out && a.w_scale, UMV_ERR_ARG, "gemm_fp8w: null pointer (x, wp, out and w_scale are required)");
     if (const int rc = umv_gemm_check_args(a, "gemm_fp8w", 8)) return rc;
-    UMV_CHECK(a.M <= 64, UMV_ERR_UNSUPPORTED, "gemm_fp8w: the e4m3 image is the decode (M <= 64) layout; use the bf16 image of the "
-              "dequantised weights with umv_gemm_bf16 for M=%d", a.M);
-    UMV_CHECK(!a.norm_w && (a.tile_rows == 0 || a.tile_rows == 16), UMV_ERR_UNSUPPORTED, "gemm_fp8w: no fused norm / th-row tiles");
-    UMV_CHECK(a.k_splits <= 1 || (!(a.epilogue & UMV_EPI_SWIGLU) && a.split_stride > 0 && a.k_splits <= 64), UMV_ERR_UNSUPPORTED,
-              "gemm_fp8w: split-K (k_splits=%d) needs no SwiGLU, split_stride > 0, k_splits <= 64", a.k_splits);
-    UMV_CHECK(!a.argmax_partial || (a.k_splits <= 1 && !a.row_idx && !(a.epilogue & (UMV_EPI_SWIGLU | UMV_EPI_OUT_F32))), UMV_ERR_UNSUPPORTED,
-              "gemm_fp8w: argmax_partial needs bf16 out, no SwiGLU / split-K / row_idx");
+    if (const int rc = umv_gemm_check_decode(a, "gemm_fp8w", "e4m3", "the bf16 image of the dequantised weights with umv_gemm_bf16", true, false))
+        return rc;
     if (a.M == 0) return UMV_OK;
     hipStream_t s = (hipStream_t)stream;
     const int KT8 = (a.K + 63) / 64, NTT = (a.N + 15) / 16;

@@ -106,6 +106,24 @@ static inline int umv_gemm_check_args(const umv_gemm_args& a, const char* who, i
     return UMV_OK;
 }
 
+// The decode-layout checks of the weight-streaming entry points (umv_gemm_fp8w / _mxfp4w / _z13w), after umv_gemm_check_args.  `image` and
+// `instead` word the M <= 64 message; amax: the entry has the argmax / sampling-key epilogue; temperature: it also checks the sampling
+// temperature (as umv_gemm_bf16 does)
+static inline int umv_gemm_check_decode(const umv_gemm_args& a, const char* who, const char* image, const char* instead, bool amax,
+                                        bool temperature) {
+    UMV_CHECK(a.M <= 64, UMV_ERR_UNSUPPORTED, "%s: the %s image is the decode (M <= 64) layout; use %s for M=%d", who, image, instead, a.M);
+    UMV_CHECK(!a.norm_w && (a.tile_rows == 0 || a.tile_rows == 16), UMV_ERR_UNSUPPORTED, "%s: no fused norm / th-row tiles", who);
+    UMV_CHECK(amax || !a.argmax_partial, UMV_ERR_UNSUPPORTED, "%s: no argmax_partial (lm_head stays e4m3: umv_gemm_fp8w)", who);
+    UMV_CHECK(a.k_splits <= 1 || (!(a.epilogue & UMV_EPI_SWIGLU) && a.split_stride > 0 && a.k_splits <= 64), UMV_ERR_UNSUPPORTED,
+              "%s: split-K (k_splits=%d) needs no SwiGLU, split_stride > 0, k_splits <= 64", who, a.k_splits);
+    UMV_CHECK(!a.argmax_partial || (a.k_splits <= 1 && !a.row_idx && !(a.epilogue & (UMV_EPI_SWIGLU | UMV_EPI_OUT_F32))), UMV_ERR_UNSUPPORTED,
+              "%s: argmax_partial needs bf16 out, no SwiGLU / split-K / row_idx", who);
+    if (temperature)
+        UMV_CHECK(a.sample_temperature >= 0.f && (a.sample_temperature == 0.f || a.argmax_partial), UMV_ERR_ARG,
+                  "%s: sample_temperature (%g) is a mode of the argmax_partial epilogue and must be >= 0", who, (double)a.sample_temperature);
+    return UMV_OK;
+}
+
 // gemm_w4.hip: 4-wave tiles with the accumulators in AGPRs (cfg 466 / 468 / 4384); bf16 output, no split-K, operands within
 // 2 GiB of their base pointers (umv_gemm_w4_can_take)
 int umv_gemm_lean_epilogue(const umv_gemm_args& a);      // gemm.hip: >= 0 = the lean epilogue kind of this call, -1 = general

@@ -36,12 +36,8 @@ extern "C" int umv_gemm_mxfp4w(const umv_gemm_args* ap, umv_stream_t stream) {
     UMV_CHECK(a.x && a.wp && a.out, UMV_ERR_ARG, "gemm_mxfp4w: null pointer (x, wp and out are required)");
     UMV_CHECK(!a.w_scale, UMV_ERR_ARG, "gemm_mxfp4w: w_scale must be NULL (the block scales are part of the MXFP4 image)");
     if (const int rc = umv_gemm_check_args(a, "gemm_mxfp4w", 32)) return rc;
-    UMV_CHECK(a.M <= 64, UMV_ERR_UNSUPPORTED, "gemm_mxfp4w: the MXFP4 image is the decode (M <= 64) layout; use the bf16 image of the "
-              "dequantised weights with umv_gemm_bf16 for M=%d", a.M);
-    UMV_CHECK(!a.norm_w && (a.tile_rows == 0 || a.tile_rows == 16), UMV_ERR_UNSUPPORTED, "gemm_mxfp4w: no fused norm / th-row tiles");
-    UMV_CHECK(!a.argmax_partial, UMV_ERR_UNSUPPORTED, "gemm_mxfp4w: no argmax_partial (lm_head stays e4m3: umv_gemm_fp8w)");
-    UMV_CHECK(a.k_splits <= 1 || (!(a.epilogue & UMV_EPI_SWIGLU) && a.split_stride > 0 && a.k_splits <= 64), UMV_ERR_UNSUPPORTED,
-              "gemm_mxfp4w: split-K (k_splits=%d) needs no SwiGLU, split_stride > 0, k_splits <= 64", a.k_splits);
+    if (const int rc = umv_gemm_check_decode(a, "gemm_mxfp4w", "MXFP4", "the bf16 image of the dequantised weights with umv_gemm_bf16", false, false))
+        return rc;
     if (a.M == 0) return UMV_OK;
     hipStream_t s = (hipStream_t)stream;
     const int KT8 = (a.K + 63) / 64, NTT = (a.N + 15) / 16, NPT = (NTT + 1) / 2;

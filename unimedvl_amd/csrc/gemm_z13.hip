@@ -48,14 +48,7 @@ extern "C" int umv_gemm_z13w(const umv_gemm_args* ap, const void* z13, umv_strea
     UMV_CHECK(!a.w_scale, UMV_ERR_ARG, "gemm_z13w: w_scale must be NULL");
     if (const int rc = umv_gemm_check_args(a, "gemm_z13w", 32)) return rc;
     UMV_CHECK((a.K % 64) == 0 && a.K <= 32768, UMV_ERR_UNSUPPORTED, "gemm_z13w: K (%d) must be a multiple of 64 and <= 32768", a.K);
-    UMV_CHECK(a.M <= 64, UMV_ERR_UNSUPPORTED, "gemm_z13w: the 13-bit image is the decode (M <= 64) layout; use umv_gemm_bf16 for M=%d", a.M);
-    UMV_CHECK(!a.norm_w && (a.tile_rows == 0 || a.tile_rows == 16), UMV_ERR_UNSUPPORTED, "gemm_z13w: no fused norm / th-row tiles");
-    UMV_CHECK(a.k_splits <= 1 || (!(a.epilogue & UMV_EPI_SWIGLU) && a.split_stride > 0 && a.k_splits <= 64), UMV_ERR_UNSUPPORTED,
-              "gemm_z13w: split-K (k_splits=%d) needs no SwiGLU, split_stride > 0, k_splits <= 64", a.k_splits);
-    UMV_CHECK(!a.argmax_partial || (a.k_splits <= 1 && !a.row_idx && !(a.epilogue & (UMV_EPI_SWIGLU | UMV_EPI_OUT_F32))), UMV_ERR_UNSUPPORTED,
-              "gemm_z13w: argmax_partial needs bf16 out, no SwiGLU / split-K / row_idx");
-    UMV_CHECK(a.sample_temperature >= 0.f && (a.sample_temperature == 0.f || a.argmax_partial), UMV_ERR_ARG,
-              "gemm_z13w: sample_temperature (%g) is a mode of the argmax_partial epilogue and must be >= 0", (double)a.sample_temperature);
+    if (const int rc = umv_gemm_check_decode(a, "gemm_z13w", "13-bit", "umv_gemm_bf16", true, true)) return rc;
     UMV_CHECK(((uintptr_t)z13 % 256) == 0, UMV_ERR_ARG, "gemm_z13w: the 13-bit image must be 256-byte aligned");
     if (a.M == 0) return UMV_OK;
     hipStream_t s = (hipStream_t)stream;
@@ -65,7 +58,7 @@ extern "C" int umv_gemm_z13w(const umv_gemm_args* ap, const void* z13, umv_strea
     // dispatch, and it is not everywhere: a workgroup takes whole PAIRS, so where the bf16 kernel runs one n-tile per workgroup
     // (no split, N < 16384, no SwiGLU) this one has half the workgroups, and at 33..64 rows it takes one pair where the bf16 kernel
     // takes four tiles.  Measured are the decode forms at 8, 16 and 32 rows - SwiGLU gate/up <1,1,2> / <2,2,1>, split-K <1,2,1> /
-    // <2,2,1>, lm_head with keys <1,1,2> / <2,2,1> - and the engine routes here the ones that won (ops.py:
+    // <2,2,1>, lm_head with keys <1,1,2> / <2,2,1> - and the engine routes here the ones that won (ops._route:
     // not gate/up and lm_head at 9..16 rows, where <1,1,2> with two-piece x staging holds 151 registers and ties); the other forms
     // are served for the contract's sake.
     if (a.k_splits > 1) {

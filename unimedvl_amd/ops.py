@@ -114,71 +114,77 @@ class PackedLinear:
         return self
 
     @staticmethod
-    def from_weight_fp8(w, bias=None):
-        """Quantise an nn.Linear weight to e4m3 with power-of-two channel scales; see include/unimedvl_hip.h."""
+    def _operands(w, up):
+        """the checked weight of a plain linear (up = None) or the gate / up pair of a SwiGLU one, with rows per operand, N and K"""
+        if up is None:
+            w = _req(w.contiguous(), BF16, "weight")
+        else:
+            w, up = _req(w.contiguous(), BF16, "gate"), _req(up.contiguous(), BF16, "up")
+            assert w.shape[0] % 16 == 0, "intermediate size must be a multiple of 16"
+        rows, K = w.shape
+        return w, up, rows, rows if up is None else 2 * rows, K
+
+    @staticmethod
+    def _bf16(w, up=None, bias=None):
+        """the bf16 image of a plain linear, or of the interleaved SwiGLU pair gate = w / up"""
         lib = _lib.load()
-        w = _req(w.contiguous(), BF16, "weight")
-        N, K = w.shape
-        w8 = torch.empty(lib.umv_packed_weight_fp8_bytes(N, K), dtype=torch.uint8, device=w.device)
-        scale = torch.empty(((N + 15) // 16) * 16, dtype=torch.float32, device=w.device)
-        deq = torch.empty_like(w)
-        check(lib.umv_quantize_pack_weight_fp8(_p(w), None, _p(w8), _p(scale), _p(deq), None, N, K, _stream()),
-              "umv_quantize_pack_weight_fp8")
-        lin = PackedLinear.from_weight(deq, bias)
-        lin.w8, lin.scale = w8, scale
+        w, up, rows, N, K = PackedLinear._operands(w, up)
+        wp = torch.empty(lib.umv_packed_weight_elems(N, K), dtype=BF16, device=w.device)
+        if up is None:
+            check(lib.umv_pack_weight_bf16(_p(w), _p(wp), N, K, _stream()), "umv_pack_weight_bf16")
+        else:
+            check(lib.umv_pack_weight_swiglu_bf16(_p(w), _p(up), _p(wp), rows, K, _stream()), "umv_pack_weight_swiglu_bf16")
+        return PackedLinear(wp, None if bias is None else bias.contiguous(), N, K, swiglu=up is not None)
+
+    @staticmethod
+    def _quantized(fmt, w, up=None, bias=None, keep_bf16=True):
+        """fmt "fp8" (e4m3, power-of-two channel scales) or "mxfp4" (e2m1, one power-of-two scale per 32 k): quantise, pack the
+        dequantised copy with the bf16 constructor (keep_bf16=False: no such copy, not even as scratch), attach the image"""
+        lib = _lib.load()
+        w, up, rows, N, K = PackedLinear._operands(w, up)
+        img = torch.empty(getattr(lib, f"umv_packed_weight_{fmt}_bytes")(N, K), dtype=torch.uint8, device=w.device)
+        scale = torch.empty((N + 15) // 16 * 16, dtype=torch.float32, device=w.device) if fmt == "fp8" else None
+        deq = torch.empty_like(w) if keep_bf16 else None
+        deq_up = torch.empty_like(up) if keep_bf16 and up is not None else None
+        images = (_p(img), _p(scale)) if fmt == "fp8" else (_p(img),)
+        check(getattr(lib, f"umv_quantize_pack_weight_{fmt}")(_p(w), _p(up), *images, _p(deq), _p(deq_up), rows, K, _stream()),
+              f"umv_quantize_pack_weight_{fmt}")
+        if keep_bf16:
+            lin = PackedLinear._bf16(deq, deq_up, bias)
+        else:
+            lin = PackedLinear(None, None if bias is None else bias.contiguous(), N, K, swiglu=up is not None)
+        if fmt == "fp8":
+            lin.w8, lin.scale = img, scale
+        else:
+            lin.w4 = img
         return lin
 
     @staticmethod
+    def from_weight_fp8(w, bias=None):
+        """Quantise an nn.Linear weight to e4m3 with power-of-two channel scales; see include/unimedvl_hip.h."""
+        return PackedLinear._quantized("fp8", w, None, bias)
+
+    @staticmethod
     def from_gate_up_fp8(gate, up):
-        lib = _lib.load()
-        gate = _req(gate.contiguous(), BF16, "gate")
-        up = _req(up.contiguous(), BF16, "up")
-        I, K = gate.shape
-        assert I % 16 == 0, "intermediate size must be a multiple of 16"
-        w8 = torch.empty(lib.umv_packed_weight_fp8_bytes(2 * I, K), dtype=torch.uint8, device=gate.device)
-        scale = torch.empty(2 * I, dtype=torch.float32, device=gate.device)
-        dg, du = torch.empty_like(gate), torch.empty_like(up)
-        check(lib.umv_quantize_pack_weight_fp8(_p(gate), _p(up), _p(w8), _p(scale), _p(dg), _p(du), I, K, _stream()),
-              "umv_quantize_pack_weight_fp8")
-        lin = PackedLinear.from_gate_up(dg, du)
-        lin.w8, lin.scale = w8, scale
-        return lin
+        return PackedLinear._quantized("fp8", gate, up)
 
     @staticmethod
     def from_weight_mxfp4(w, bias=None, keep_bf16=True):
         """Quantise an nn.Linear weight to MXFP4 (e2m1, one power-of-two scale per 32 k); see include/unimedvl_hip.h.
         keep_bf16=False: no bf16 image of the dequantised weights is built (not even as scratch)."""
-        lib = _lib.load()
-        w = _req(w.contiguous(), BF16, "weight")
-        N, K = w.shape
-        w4 = torch.empty(lib.umv_packed_weight_mxfp4_bytes(N, K), dtype=torch.uint8, device=w.device)
-        if not keep_bf16:
-            check(lib.umv_quantize_pack_weight_mxfp4(_p(w), None, _p(w4), None, None, N, K, _stream()), "umv_quantize_pack_weight_mxfp4")
-            return PackedLinear(None, None if bias is None else bias.contiguous(), N, K, w4=w4)
-        deq = torch.empty_like(w)
-        check(lib.umv_quantize_pack_weight_mxfp4(_p(w), None, _p(w4), _p(deq), None, N, K, _stream()), "umv_quantize_pack_weight_mxfp4")
-        lin = PackedLinear.from_weight(deq, bias)
-        lin.w4 = w4
-        return lin
+        return PackedLinear._quantized("mxfp4", w, None, bias, keep_bf16)
 
     @staticmethod
     def from_gate_up_mxfp4(gate, up, keep_bf16=True):
-        lib = _lib.load()
-        gate = _req(gate.contiguous(), BF16, "gate")
-        up = _req(up.contiguous(), BF16, "up")
-        I, K = gate.shape
-        assert I % 16 == 0, "intermediate size must be a multiple of 16"
-        w4 = torch.empty(lib.umv_packed_weight_mxfp4_bytes(2 * I, K), dtype=torch.uint8, device=gate.device)
-        if not keep_bf16:
-            check(lib.umv_quantize_pack_weight_mxfp4(_p(gate), _p(up), _p(w4), None, None, I, K, _stream()),
-                  "umv_quantize_pack_weight_mxfp4")
-            return PackedLinear(None, None, 2 * I, K, swiglu=True, w4=w4)
-        dg, du = torch.empty_like(gate), torch.empty_like(up)
-        check(lib.umv_quantize_pack_weight_mxfp4(_p(gate), _p(up), _p(w4), _p(dg), _p(du), I, K, _stream()),
-              "umv_quantize_pack_weight_mxfp4")
-        lin = PackedLinear.from_gate_up(dg, du)
-        lin.w4 = w4
-        return lin
+        return PackedLinear._quantized("mxfp4", gate, up, None, keep_bf16)
+
+    @staticmethod
+    def from_weight(w, bias=None):
+        return PackedLinear._bf16(w, None, bias)
+
+    @staticmethod
+    def from_gate_up(gate, up):
+        return PackedLinear._bf16(gate, up)
 
     def for_decode(self, n_cus=256):
         """A second, decode-only image with th-row tiles such that the number of tiles is a multiple of the
@@ -197,35 +203,24 @@ class PackedLinear:
         check(lib.umv_repack_weight_rows_bf16(_p(self.wp), _p(out), self.N, self.K, best, _stream()), "umv_repack_weight_rows_bf16")
         return PackedLinear(out, self.bias, self.N, self.K, False, best)
 
-    @staticmethod
-    def from_weight(w, bias=None):
-        lib = _lib.load()
-        w = _req(w.contiguous(), BF16, "weight")
-        N, K = w.shape
-        wp = torch.empty(lib.umv_packed_weight_elems(N, K), dtype=BF16, device=w.device)
-        check(lib.umv_pack_weight_bf16(_p(w), _p(wp), N, K, _stream()), "umv_pack_weight_bf16")
-        return PackedLinear(wp, None if bias is None else bias.contiguous(), N, K)
-
-    @staticmethod
-    def from_gate_up(gate, up):
-        lib = _lib.load()
-        gate = _req(gate.contiguous(), BF16, "gate")
-        up = _req(up.contiguous(), BF16, "up")
-        I, K = gate.shape
-        assert I % 16 == 0, "intermediate size must be a multiple of 16"
-        wp = torch.empty(lib.umv_packed_weight_elems(2 * I, K), dtype=BF16, device=gate.device)
-        check(lib.umv_pack_weight_swiglu_bf16(_p(gate), _p(up), _p(wp), I, K, _stream()), "umv_pack_weight_swiglu_bf16")
-        return PackedLinear(wp, None, 2 * I, K, swiglu=True)
-
     def nbytes(self):
         return self.wp.numel() * 2 if self.wp is not None else self.w4.numel()
 
+    def decode_bytes(self):
+        """bytes of the image a decode step (M <= 64) streams, by the rules of _route: the e4m3 or the MXFP4 image (block scales included)
+        when there is one, else the exact 13-bit image (its few flagged blocks, which stream the bf16 image instead, are counted at 13
+        bits), else the bf16 image"""
+        for image in (self.w8, self.w4, self.wz):
+            if image is not None:
+                return image.numel()
+        return self.wp.numel() * 2
+
 
 def _z13_takes(lin, M, z13, form):
-    """whether a call streams the linear's exact 13-bit image.  form: "splitk" (split-K partials), "epilogue" (SwiGLU or argmax /
-    sampling keys) or None (anything else).  z13 = None: the measured policy (DESIGN.md section 5.2) - split-K up to Z13_MAX_ROWS rows;
-    the epilogue forms up to 8 rows and at 17..Z13_MAX_ROWS, not at 9..16, where gate/up and lm_head only tie with the bf16 kernel;
-    True: whenever umv_gemm_z13w serves the call (M <= 64; tests, A/B); False: never"""
+    """whether a call streams the linear's exact 13-bit image (the z13 step of _route).  form: "splitk" (split-K partials), "epilogue"
+    (SwiGLU or argmax / sampling keys) or None (anything else).  z13 = None: the measured policy - split-K up to
+    Z13_MAX_ROWS rows; the epilogue forms up to 8 rows and at 17..Z13_MAX_ROWS, not at 9..16, where gate/up and lm_head only tie with the
+    bf16 kernel; True: whenever umv_gemm_z13w serves the call (M <= 64; tests, A/B); False: never"""
     if lin.wz is None or z13 is False:
         return False
     if z13:
@@ -233,6 +228,71 @@ def _z13_takes(lin, M, z13, form):
     if form == "splitk":
         return M <= Z13_MAX_ROWS
     return form == "epilogue" and (M <= 8 or 16 < M <= Z13_MAX_ROWS)
+
+
+def _route(lin, M, splitk=False, norm=False, amax=False, act8=False, out_f32=False, act=False, z13=None):
+    """The one rule for which C entry point serves a GEMM call and on which image of the weight: (entry, image that goes into wp,
+    w_scale, 13-bit image), or the error of a call that needs an image the linear does not have.  Reads what the linear holds and the
+    call's form (split-K, norm_w / argmax_partial set, act8, out_f32, a GELU / SiLU epilogue, the z13 override), no tensor data.
+    PackedLinear.decode_bytes counts the image the M <= 64 rules below pick."""
+    if act8 and lin.w8m is None:
+        raise _lib.UmvError("act8 needs a linear with the fp8-MFMA image (enable_fp8_mfma)")
+    skinny = M <= 64 and not norm                   # a weight-streaming kernel can take the call
+    if act8 and not splitk and M > 64 and not norm and not out_f32:
+        return "umv_gemm_fp8a8w", lin.w8m, lin.scale, None     # W8A8: e4m3 activations per row, fp8 matrix instruction
+    if lin.w8 is not None and (skinny or splitk):              # (split-K: whatever M - same split, same consumers)
+        return "umv_gemm_fp8w", lin.w8, lin.scale, None
+    if lin.w4 is not None:
+        if skinny:
+            return "umv_gemm_mxfp4w", lin.w4, None, None
+        if lin.wp is None:                                     # no bf16 image of W': the tiled kernel on the MXFP4 image (split-K: same partials)
+            if not splitk and (norm or amax):
+                raise _lib.UmvError(f"this linear only has its fp4 (MXFP4) image (built with keep_bf16=False / drop_bf16): M={M} rows with "
+                                    f"norm_w={'set' if norm else 'None'}, argmax_partial={'set' if amax else 'None'} need "
+                                    "the bf16 kernel - build the weights with keep_bf16=True (llm_fp4_keep_bf16=True)")
+            return "umv_gemm_mxfp4t", lin.w4, None, None
+    if lin.wp is None and not splitk:
+        raise _lib.UmvError(f"this linear only has fp8 images (the bf16 image was dropped by enable_fp8_mfma): M={M} rows with "
+                            f"act8={act8}, out_f32={out_f32}, norm_w={'set' if norm else 'None'} need the bf16 kernel - "
+                            "build the weights with enable_fp8_mfma(keep_bf16=True)")
+    # the exact 13-bit image: the bf16 kernel's bits from 13/16 of the bytes.  Only the forms that were measured against the bf16 kernel
+    # and won (_z13_takes; DESIGN.md section 5.2): split-K down up to 32 rows, the SwiGLU gate/up GEMM and lm_head with the argmax /
+    # sampling keys up to 8 and at 17..32 rows.  Every other call on such a linear - a short prefill, MoT text rows, down without a
+    # split, plain lm_head, 33..64 rows, a fused norm, a GELU / SiLU epilogue - stays on umv_gemm_bf16.
+    if _z13_takes(lin, M, z13, "splitk" if splitk else "epilogue" if (lin.swiglu or amax) else None) and not norm and not act:
+        return "umv_gemm_z13w", lin.wp, None, lin.wz
+    return "umv_gemm_bf16", lin.wp, None, None
+
+
+def _launch(lib, route, x, lin, out, ldo, M, flags=0, residual=None, row_idx=None, norm_w=None, norm_eps=0.0, amax=None, sample=None,
+            k_splits=0, split_stride=0):
+    """Build the umv_gemm_args of a routed call and launch it.  What only some entries take is set from the route: w_scale; th-row tiles
+    and the bound on x's rows (the bf16 kernel and its 13-bit twin, outside split-K); the sampling mode (not the MXFP4 entries, which
+    have no argmax keys); every other field is the call's"""
+    entry, image, scale, wz = route
+    a = GemmArgs(x=x.data_ptr(), ldx=x.stride(0), wp=None if image is None else image.data_ptr(), out=out.data_ptr(), ldo=ldo,
+                 M=M, N=lin.N, K=lin.K, epilogue=flags, norm_eps=norm_eps, argmax_partial=amax)
+    if flags & EPI_BIAS:
+        a.bias = lin.bias.data_ptr()
+    if residual is not None:
+        a.residual, a.ldr = residual.data_ptr(), residual.stride(0)
+    if row_idx is not None:
+        a.row_idx = row_idx.data_ptr()
+    if norm_w is not None:
+        a.norm_w = norm_w.data_ptr()
+    if scale is not None:
+        a.w_scale = scale.data_ptr()
+    if k_splits:
+        a.k_splits, a.split_stride = k_splits, split_stride
+    elif entry in ("umv_gemm_bf16", "umv_gemm_z13w"):
+        a.tile_rows, a.x_rows = lin.th, x.shape[0]
+    if sample is not None and entry not in ("umv_gemm_mxfp4w", "umv_gemm_mxfp4t"):
+        a.sample_temperature, a.sample_seed, a.sample_step = _sample_fields(sample, amax)
+    if wz is not None:
+        check(lib.umv_gemm_z13w(C.byref(a), wz.data_ptr(), _stream()), entry)
+    else:
+        check(getattr(lib, entry)(C.byref(a), _stream()), entry)
+    return out
 
 
 def gemm(x, lin, out=None, *, M=None, residual=None, act=None, row_idx=None, out_f32=False, use_bias=True,
@@ -244,7 +304,7 @@ def gemm(x, lin, out=None, *, M=None, residual=None, act=None, row_idx=None, out
     argmax_partial (int64 [M, ceil(N/16)], M <= 64): greedy-argmax keys per 16-column tile, finished by decode_step_end_argmax.
     sample (with argmax_partial): (temperature, seed, step tensor or None) - the keys then order bf16(logit / T) + Gumbel noise, so the
     row maximum is one draw from softmax(logits / T) (bagel.py:1297-1299) instead of the greedy token.
-    z13 (tests and A/B only; leave None): whether a linear's exact 13-bit image is streamed - None = the measured policy of _z13_takes,
+    z13 (tests and A/B only; leave None): whether a linear's exact 13-bit image is streamed - None = the measured policy of _route,
     True = whenever umv_gemm_z13w serves the call, False = never."""
     lib = _lib.load()
     _req(x, BF16, "x")
@@ -265,13 +325,10 @@ def gemm(x, lin, out=None, *, M=None, residual=None, act=None, row_idx=None, out
         flags |= EPI_RESIDUAL
     if out_f32:
         flags |= EPI_OUT_F32
-    n_out = lin.N // 2 if lin.swiglu else lin.N
-    rows_out = x.shape[0] if row_idx is None else None
     if out is None:
         assert row_idx is None, "row-indexed GEMM writes into a caller-provided buffer"
-        out = torch.empty((rows_out, n_out), dtype=torch.float32 if out_f32 else BF16, device=x.device)
-    if act8 and lin.w8m is None:
-        raise _lib.UmvError("act8 needs a linear with the fp8-MFMA image (enable_fp8_mfma)")
+        out = torch.empty((x.shape[0], lin.N // 2 if lin.swiglu else lin.N), dtype=torch.float32 if out_f32 else BF16, device=x.device)
+    route = _route(lin, M, False, norm_w is not None, argmax_partial is not None, act8, out_f32, act is not None, z13)
     if act8 and M <= 64:
         x = fake_quantize_act(x, M, row_idx)
     amax = None
@@ -280,80 +337,20 @@ def gemm(x, lin, out=None, *, M=None, residual=None, act=None, row_idx=None, out
         if not (argmax_partial.is_contiguous() and tuple(argmax_partial.shape) == (M, (lin.N + 15) // 16)):
             raise _lib.UmvError(f"argmax_partial must be a contiguous int64 [{M}, {(lin.N + 15) // 16}] tensor")
         amax = argmax_partial.data_ptr()
-    # which kernel family takes the call (mirrors the branches below exactly, so a dropped image raises instead of crashing)
-    use_a8 = act8 and M > 64 and norm_w is None and not out_f32       # fp8 matrix instruction, e4m3 activations
-    use_w8 = lin.w8 is not None and M <= 64 and norm_w is None        # weight-streaming kernel on the e4m3 image
-    use_w4 = lin.w4 is not None and M <= 64 and norm_w is None        # weight-streaming kernel on the MXFP4 image
-    use_w4t = lin.w4 is not None and lin.wp is None and M > 64 and norm_w is None and amax is None    # tiled kernel on the MXFP4 image
-    if lin.wp is None and lin.w4 is not None and not use_w4 and not use_w4t:
-        raise _lib.UmvError(f"this linear only has its fp4 (MXFP4) image (built with keep_bf16=False / drop_bf16): M={M} rows with "
-                            f"norm_w={'set' if norm_w is not None else 'None'}, argmax_partial={'set' if amax is not None else 'None'} need "
-                            "the bf16 kernel - build the weights with keep_bf16=True (llm_fp4_keep_bf16=True)")
-    if lin.wp is None and not use_a8 and not use_w8 and not use_w4 and not use_w4t:
-        raise _lib.UmvError(f"this linear only has fp8 images (the bf16 image was dropped by enable_fp8_mfma): M={M} rows with "
-                            f"act8={act8}, out_f32={out_f32}, norm_w={'set' if norm_w is not None else 'None'} need the bf16 kernel - "
-                            "build the weights with enable_fp8_mfma(keep_bf16=True)")
-    if use_a8:
+    if route[0] == "umv_gemm_fp8a8w":
         # W8A8: per-row e4m3 activations (rows gathered through row_idx), fp8 matrix instruction, exact pow2 scales
-        ldq = (lin.K + 127) // 128 * 128
-        xq = torch.empty((M, ldq), dtype=torch.uint8, device=x.device)
-        xs = torch.empty((M,), dtype=torch.float32, device=x.device)
-        check(lib.umv_quantize_act_fp8(_p(x), x.stride(0), _p(row_idx), _p(xq), ldq, _p(xs), None, 0, M, lin.K, _stream()),
-              "umv_quantize_act_fp8")
-        a8 = _lib.Gemm8Args(
-            xq=xq.data_ptr(), ldq=ldq, x_scale=xs.data_ptr(), wp=lin.w8m.data_ptr(), w_scale=lin.scale.data_ptr(),
-            bias=lin.bias.data_ptr() if (flags & EPI_BIAS) else None,
-            residual=residual.data_ptr() if residual is not None else None,
-            ldr=residual.stride(0) if residual is not None else 0, out=out.data_ptr(), ldo=out.stride(0),
-            row_idx=row_idx.data_ptr() if row_idx is not None else None, M=M, N=lin.N, K=lin.K, epilogue=flags)
+        xq, xs = quantize_act(x, M, row_idx, lin.K)
+        a8 = _lib.Gemm8Args(xq=xq.data_ptr(), ldq=xq.stride(0), x_scale=xs.data_ptr(), wp=lin.w8m.data_ptr(), w_scale=lin.scale.data_ptr(),
+                            out=out.data_ptr(), ldo=out.stride(0), M=M, N=lin.N, K=lin.K, epilogue=flags)
+        if flags & EPI_BIAS:
+            a8.bias = lin.bias.data_ptr()
+        if residual is not None:
+            a8.residual, a8.ldr = residual.data_ptr(), residual.stride(0)
+        if row_idx is not None:
+            a8.row_idx = row_idx.data_ptr()
         check(lib.umv_gemm_fp8a8w(C.byref(a8), _stream()), "umv_gemm_fp8a8w")
         return out
-    if use_w4 or use_w4t:
-        a = GemmArgs(
-            x=x.data_ptr(), ldx=x.stride(0), wp=lin.w4.data_ptr(),
-            bias=lin.bias.data_ptr() if (flags & EPI_BIAS) else None,
-            residual=residual.data_ptr() if residual is not None else None,
-            ldr=residual.stride(0) if residual is not None else 0,
-            out=out.data_ptr(), ldo=out.stride(0),
-            row_idx=row_idx.data_ptr() if row_idx is not None else None,
-            M=M, N=lin.N, K=lin.K, epilogue=flags, norm_w=None, norm_eps=norm_eps, tile_rows=0, argmax_partial=amax)
-        if use_w4t:
-            check(lib.umv_gemm_mxfp4t(C.byref(a), _stream()), "umv_gemm_mxfp4t")
-        else:
-            check(lib.umv_gemm_mxfp4w(C.byref(a), _stream()), "umv_gemm_mxfp4w")
-        return out
-    if use_w8:
-        a = GemmArgs(
-            x=x.data_ptr(), ldx=x.stride(0), wp=lin.w8.data_ptr(),
-            bias=lin.bias.data_ptr() if (flags & EPI_BIAS) else None,
-            residual=residual.data_ptr() if residual is not None else None,
-            ldr=residual.stride(0) if residual is not None else 0,
-            out=out.data_ptr(), ldo=out.stride(0),
-            row_idx=row_idx.data_ptr() if row_idx is not None else None,
-            M=M, N=lin.N, K=lin.K, epilogue=flags, norm_w=None, norm_eps=norm_eps, tile_rows=0,
-            w_scale=lin.scale.data_ptr(), argmax_partial=amax, **_sample_fields(sample, amax))
-        check(lib.umv_gemm_fp8w(C.byref(a), _stream()), "umv_gemm_fp8w")
-        return out
-    a = GemmArgs(
-        x=x.data_ptr(), ldx=x.stride(0), wp=lin.wp.data_ptr(),
-        bias=lin.bias.data_ptr() if (flags & EPI_BIAS) else None,
-        residual=residual.data_ptr() if residual is not None else None,
-        ldr=residual.stride(0) if residual is not None else 0,
-        out=out.data_ptr(), ldo=out.stride(0),
-        row_idx=row_idx.data_ptr() if row_idx is not None else None,
-        M=M, N=lin.N, K=lin.K, epilogue=flags,
-        norm_w=norm_w.data_ptr() if norm_w is not None else None, norm_eps=norm_eps, tile_rows=lin.th, argmax_partial=amax,
-        x_rows=x.shape[0], **_sample_fields(sample, amax))
-    if _z13_takes(lin, M, z13, "epilogue" if (lin.swiglu or amax is not None) else None) and norm_w is None and \
-            not (flags & (EPI_GELU_TANH | EPI_SILU)):
-        # the exact 13-bit image: the bf16 kernel's bits from 13/16 of the bytes.  Only the forms that were measured against the bf16
-        # kernel and won: the SwiGLU gate/up GEMM and lm_head with the argmax / sampling keys, up to 8 and at
-        # 17..32 rows (split-K down: gemm_splitk).  Every other call on such a linear - a short prefill, MoT text rows, down without a split,
-        # plain lm_head, 33..64 rows - stays on umv_gemm_bf16.
-        check(lib.umv_gemm_z13w(C.byref(a), lin.wz.data_ptr(), _stream()), "umv_gemm_z13w")
-        return out
-    check(lib.umv_gemm_bf16(C.byref(a), _stream()), "umv_gemm_bf16")
-    return out
+    return _launch(lib, route, x, lin, out, out.stride(0), M, flags, residual, row_idx, norm_w, norm_eps, amax, sample)
 
 
 def rmsnorm(x, w, eps, out=None, w_gen=None, expert=None):
@@ -489,12 +486,13 @@ def _paging(slab):
     return {} if t is None else dict(page_table=t.data_ptr(), page_table_stride=t.stride(0))
 
 
-def quantize_act(x, M=None, row_idx=None):
-    """Per-row e4m3 quantisation of bf16 activations (umv_quantize_act_fp8): returns (xq uint8 [M, ldq], scale f32 [M])."""
+def quantize_act(x, M=None, row_idx=None, K=None):
+    """Per-row e4m3 quantisation of bf16 activations (umv_quantize_act_fp8): returns (xq uint8 [M, ldq], scale f32 [M]).
+    K: the columns that count (a linear's K) when x is wider"""
     lib = _lib.load()
     _req(x, BF16, "x")
     M = x.shape[0] if M is None else M
-    K = x.shape[1]
+    K = x.shape[1] if K is None else K
     ldq = (K + 127) // 128 * 128
     xq = torch.empty((M, ldq), dtype=torch.uint8, device=x.device)
     xs = torch.empty((M,), dtype=torch.float32, device=x.device)
@@ -517,14 +515,13 @@ def fake_quantize_act(x, M=None, row_idx=None):
 
 
 def _sample_fields(sample, amax):
-    if sample is None:
-        return {}
+    """(sample_temperature, sample_seed, sample_step) of gemm's sample=(temperature, seed, step tensor or None)"""
     if amax is None:
         raise _lib.UmvError("gemm: sample=(temperature, seed, step) is a mode of the argmax_partial epilogue")
     t, seed, step = sample
     if not float(t) > 0.0:
         raise _lib.UmvError(f"gemm: sampling temperature must be > 0 (got {t})")
-    return dict(sample_temperature=float(t), sample_seed=int(seed) & (2 ** 64 - 1), sample_step=None if step is None else step.data_ptr())
+    return float(t), int(seed) & (2 ** 64 - 1), None if step is None else step.data_ptr()
 
 
 def gemm_splitk(x, lin, partials, k_splits, *, M=None, z13=None):
@@ -536,22 +533,8 @@ def gemm_splitk(x, lin, partials, k_splits, *, M=None, z13=None):
     M = x.shape[0] if M is None else M
     assert partials.dim() == 3 and partials.shape[0] == k_splits and partials.shape[2] == lin.N and partials.is_contiguous()
     assert lin.th == 16 and not lin.swiglu
-    a = GemmArgs(x=x.data_ptr(), ldx=x.stride(0), wp=None if lin.wp is None else lin.wp.data_ptr(), out=partials.data_ptr(), ldo=lin.N,
-                 M=M, N=lin.N, K=lin.K, epilogue=0, tile_rows=0, k_splits=k_splits, split_stride=partials.stride(0))
-    if lin.w8 is not None:   # e4m3 image: same split, same consumers
-        a.wp, a.w_scale = lin.w8.data_ptr(), lin.scale.data_ptr()
-        check(lib.umv_gemm_fp8w(C.byref(a), _stream()), "umv_gemm_fp8w")
-    elif lin.w4 is not None and M <= 64:    # MXFP4 image, weight-streaming kernel
-        a.wp = lin.w4.data_ptr()
-        check(lib.umv_gemm_mxfp4w(C.byref(a), _stream()), "umv_gemm_mxfp4w")
-    elif lin.w4 is not None and lin.wp is None:   # 65..128 rows without a bf16 image of W': the tiled kernel on the MXFP4 image (same partials)
-        a.wp = lin.w4.data_ptr()
-        check(lib.umv_gemm_mxfp4t(C.byref(a), _stream()), "umv_gemm_mxfp4t")
-    elif _z13_takes(lin, M, z13, "splitk"):      # the exact 13-bit image of wp: the same partials (measured up to 32 rows)
-        check(lib.umv_gemm_z13w(C.byref(a), lin.wz.data_ptr(), _stream()), "umv_gemm_z13w")
-    else:
-        check(lib.umv_gemm_bf16(C.byref(a), _stream()), "umv_gemm_bf16")
-    return partials
+    route = _route(lin, M, True, z13=z13)
+    return _launch(lib, route, x, lin, partials, lin.N, M, k_splits=k_splits, split_stride=partials.stride(0))
 
 
 def residual_rmsnorm(partials, seq, w, eps, out):

@@ -46,13 +46,26 @@ def _tensor(get, device, name):
     return _store(get).tensor(name, lambda: _dev(get(name), device))
 
 
-def _linear(get, device, wname, bname=None, fp8=False, fp4=False, keep_bf16=True):
+def _pack(w, b=None, fmt="bf16", keep_bf16=True):
+    """ops.PackedLinear of a weight (+ bias) in the weight format fmt: "bf16", "fp8" (e4m3) or "fp4" (MXFP4; keep_bf16 = with the bf16
+    image of the dequantised weights)"""
+    if fmt == "fp4":
+        return ops.PackedLinear.from_weight_mxfp4(w, b, keep_bf16=keep_bf16)
+    return ops.PackedLinear.from_weight_fp8(w, b) if fmt == "fp8" else ops.PackedLinear.from_weight(w, b)
+
+
+def _pack_gate_up(g, u, fmt="bf16", keep_bf16=True):
+    """_pack for the interleaved SwiGLU pair"""
+    if fmt == "fp4":
+        return ops.PackedLinear.from_gate_up_mxfp4(g, u, keep_bf16=keep_bf16)
+    return ops.PackedLinear.from_gate_up_fp8(g, u) if fmt == "fp8" else ops.PackedLinear.from_gate_up(g, u)
+
+
+def _linear(get, device, wname, bname=None, fmt="bf16", keep_bf16=True):
     def build():
         w = _dev(get(wname), device)
         b = _dev(get(bname), device) if bname else None
-        if fp4:
-            return ops.PackedLinear.from_weight_mxfp4(w, b, keep_bf16=keep_bf16)
-        return ops.PackedLinear.from_weight_fp8(w, b) if fp8 else ops.PackedLinear.from_weight(w, b)
+        return _pack(w, b, fmt, keep_bf16)
     return _store(get).linear(wname, build)
 
 
@@ -73,17 +86,18 @@ class LLMWeights:
     def __init__(self, cfg: UniMedVLConfig, get, device, load_gen=True):
         p = "language_model.model."
         check_llm_dtypes(cfg)
-        fp8 = self.fp8 = cfg.llm_weight_dtype == "fp8"
-        # "fp4": MXFP4 for the seven linears of both experts; lm_head stays e4m3 (fused argmax / sampling, 8 bits on the output)
-        fp4 = self.fp4 = cfg.llm_weight_dtype == "fp4"
+        # the one format of the LLM linears.  "fp4": MXFP4 for the seven linears of both experts; lm_head stays e4m3 (fused argmax /
+        # sampling, 8 bits on the output)
+        fmt = cfg.llm_weight_dtype
+        fp8, fp4 = self.fp8, self.fp4 = fmt == "fp8", fmt == "fp4"
         self.act8 = cfg.llm_act_dtype == "fp8"
         # fp4 without the bf16 images of the dequantised weights (llm_fp4_keep_bf16=False): M > 64 runs on the MXFP4 images too
         keep = self.fp4_keep_bf16 = bool(cfg.llm_fp4_keep_bf16) or not fp4
         self.embed = _tensor(get, device, p + "embed_tokens.weight")
         self.und, self.gen = [], []
         for l in range(cfg.layers):
-            self.und.append(self._layer(get, device, p + f"layers.{l}.", "", fp8, fp4, keep))
-            self.gen.append(self._layer(get, device, p + f"layers.{l}.", "_moe_gen", fp8, fp4, keep) if load_gen else None)
+            self.und.append(self._layer(get, device, p + f"layers.{l}.", "", fmt, keep))
+            self.gen.append(self._layer(get, device, p + f"layers.{l}.", "_moe_gen", fmt, keep) if load_gen else None)
             if self.act8:   # W8A8: the fp8-MFMA image replaces the bf16 image of the dequantised weights
                 for lw in (self.und[-1], self.gen[-1]):
                     if lw is not None:
@@ -91,7 +105,7 @@ class LLMWeights:
                             lin.enable_fp8_mfma()
         self.norm = _tensor(get, device, p + "norm.weight")
         self.norm_gen = _tensor(get, device, p + "norm_moe_gen.weight") if load_gen else None
-        self.lm_head = _linear(get, device, "language_model.lm_head.weight", fp8=fp8 or fp4)
+        self.lm_head = _linear(get, device, "language_model.lm_head.weight", fmt="fp8" if fp8 or fp4 else "bf16")
         # the exact 13-bit decode images (config.llm_decode_z13): rebuilt from the bf16 images at every load, never stored
         self.z13 = bool(cfg.llm_decode_z13) and not fp8 and not fp4 and os.environ.get("UMV_DECODE_Z13", "1") != "0"
         if self.z13:
@@ -112,7 +126,7 @@ class LLMWeights:
         self.sin = emb.sin().to(BF16).to(device)
 
     @staticmethod
-    def _layer(get, device, p, suf, fp8=False, fp4=False, keep_bf16=True):
+    def _layer(get, device, p, suf, fmt="bf16", keep_bf16=True):
         lw = LayerWeights()
         a = p + "self_attn."
         st = _store(get)
@@ -120,20 +134,16 @@ class LLMWeights:
         def build_qkv():
             w = torch.cat([_dev(get(a + f"{n}_proj{suf}.weight"), device) for n in "qkv"], 0)
             b = torch.cat([_dev(get(a + f"{n}_proj{suf}.bias"), device) for n in "qkv"], 0)
-            if fp4:
-                return ops.PackedLinear.from_weight_mxfp4(w, b, keep_bf16=keep_bf16)
-            return ops.PackedLinear.from_weight_fp8(w, b) if fp8 else ops.PackedLinear.from_weight(w, b)
+            return _pack(w, b, fmt, keep_bf16)
 
         def build_gate_up():
             g = _dev(get(p + f"mlp{suf}.gate_proj.weight"), device)
             u = _dev(get(p + f"mlp{suf}.up_proj.weight"), device)
-            if fp4:
-                return ops.PackedLinear.from_gate_up_mxfp4(g, u, keep_bf16=keep_bf16)
-            return ops.PackedLinear.from_gate_up_fp8(g, u) if fp8 else ops.PackedLinear.from_gate_up(g, u)
+            return _pack_gate_up(g, u, fmt, keep_bf16)
         lw.qkv = st.linear(a + f"qkv_proj{suf}", build_qkv)
-        lw.o = _linear(get, device, a + f"o_proj{suf}.weight", fp8=fp8, fp4=fp4, keep_bf16=keep_bf16)
+        lw.o = _linear(get, device, a + f"o_proj{suf}.weight", fmt=fmt, keep_bf16=keep_bf16)
         lw.gate_up = st.linear(p + f"mlp{suf}.gate_up_proj", build_gate_up)
-        lw.down = _linear(get, device, p + f"mlp{suf}.down_proj.weight", fp8=fp8, fp4=fp4, keep_bf16=keep_bf16)
+        lw.down = _linear(get, device, p + f"mlp{suf}.down_proj.weight", fmt=fmt, keep_bf16=keep_bf16)
         lw.in_norm = _tensor(get, device, p + f"input_layernorm{suf}.weight")
         lw.post_norm = _tensor(get, device, p + f"post_attention_layernorm{suf}.weight")
         lw.q_norm = _tensor(get, device, a + f"q_norm{suf}.weight")
@@ -141,15 +151,9 @@ class LLMWeights:
         return lw
 
     def decode_weight_bytes(self):
-        """bytes one decode step streams: the e4m3 images when llm_weight_dtype == "fp8", the MXFP4 images (block scales included)
-        and the e4m3 lm_head when "fp4", else the bf16 ones - the exact 13-bit image where a linear has one (its few flagged blocks,
-        which stream the bf16 image instead, are counted at 13 bits)"""
-        bf16 = lambda lin: lin.wz.numel() if lin.wz is not None else lin.nbytes()      # noqa: E731
-        nb = (lambda lin: lin.w8.numel()) if self.fp8 else (lambda lin: lin.w4.numel()) if self.fp4 else bf16
-        n = self.lm_head.w8.numel() if self.fp4 else nb(self.lm_head)
-        for lw in self.und:
-            n += nb(lw.qkv) + nb(lw.o) + nb(lw.gate_up) + nb(lw.down)
-        return n
+        """bytes one decode step streams: for lm_head and every linear of the understanding expert, the image ops._route picks at
+        M <= 64 (ops.PackedLinear.decode_bytes)"""
+        return sum(lin.decode_bytes() for lin in [self.lm_head] + [l for lw in self.und for l in (lw.qkv, lw.o, lw.gate_up, lw.down)])
 
 
 class ViTLayer:
