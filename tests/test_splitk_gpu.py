@@ -71,7 +71,8 @@ def test_splitk_partials_fp8_weights(M, N, K, S):
     assert torch.isfinite(p).all() and (_seq_sum(p) - _seq_sum(p16)).abs().max() <= 1e-3 * scale
 
 
-@pytest.mark.parametrize("T,H,S", [(1, 3584, 4), (8, 3584, 8), (32, 3584, 8), (5, 256, 2), (64, 4096, 3)])
+@pytest.mark.parametrize("T,H,S", [(1, 3584, 4), (8, 3584, 8), (32, 3584, 8), (5, 256, 2), (64, 4096, 3),
+                                   (2, 4104, 2), (2, 1024, 5)])      # residual_rmsnorm_kernel<4, 0>; <2, 0> with the run-time split loop
 def test_residual_rmsnorm(T, H, S):
     ops = _ops()
     g = torch.Generator().manual_seed(T + H + S)
@@ -91,8 +92,14 @@ def test_residual_rmsnorm(T, H, S):
 
 
 def test_qkv_post_from_partials():
+    for S in (4, 6, 9):       # the four-wide, the eight-wide and the run-time form of the split sum
+        for nq, nkv in ((28, 4), (4, 2)):
+            _qkv_post_from_partials_case(S, nq, nkv)
+
+
+def _qkv_post_from_partials_case(S, nq, nkv):
     ops = _ops()
-    nq, nkv, hd, T, S = 28, 4, 128, 8, 4
+    hd, T = 128, 8
     g = torch.Generator().manual_seed(3)
     N = (nq + 2 * nkv) * hd
     p = torch.randn(S, T, N, generator=g).cuda()
@@ -117,7 +124,7 @@ def test_qkv_post_from_partials():
             ops.qkv_post(qkv, q, slab, seg, slot, pos, nq, nkv, hd, 1e-6, qn, kn, cos_tab=cos, sin_tab=sin)
         outs.append((q, slab.k.clone(), slab.vt.clone()))
     for a, b in zip(*outs):
-        assert torch.equal(a, b)
+        assert torch.equal(a, b), (S, nq, nkv)
     assert outs[0][0].abs().sum() > 0 and outs[0][1].abs().sum() > 0 and outs[0][2].abs().sum() > 0
 
 

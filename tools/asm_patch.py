@@ -20,8 +20,12 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from unimedvl_amd import build as product      # noqa: E402  (the flags and the source list are the build's own)
+
 LL = "/opt/rocm/lib/llvm/bin"
-FLAGS = "--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-gpu-rdc -mllvm -amdgpu-mfma-vgpr-form -DUMV_ATTN_PAIR_DEBUG=1".split()
+TARGET = "attention_prefill.hip"
+FLAGS = product.FLAGS + [f for f in product.FILE_FLAGS[TARGET] if not f.startswith("-DUMV_ATTN_PAIR_DEBUG")] + ["-DUMV_ATTN_PAIR_DEBUG=1"]
 PAIR = "_Z19attn_prefill_kernelILi128ELi2ELi2ELb0ELb0EEv13umv_attn_argsfi"
 
 
@@ -70,7 +74,7 @@ def main():
     for f in os.listdir(os.path.join(ROOT, "unimedvl_amd", "csrc")):
         if f.endswith(".h"):
             open(os.path.join(w, f), "w").write(open(os.path.join(ROOT, "unimedvl_amd", "csrc", f)).read())
-    src = open(os.path.join(ROOT, "unimedvl_amd", "csrc", "attention_prefill.hip")).read()
+    src = open(os.path.join(ROOT, "unimedvl_amd", "csrc", TARGET)).read()
     open(os.path.join(w, "ap.hip"), "w").write(src.replace('"../../include/unimedvl_hip.h"', f'"{ROOT}/include/unimedvl_hip.h"'))
     sh("/opt/rocm/bin/hipcc", *FLAGS, "-S", "--cuda-device-only", "-o", "ap.s", "ap.hip", cwd=w)
     s = open(os.path.join(w, "ap.s")).read()
@@ -94,7 +98,7 @@ def main():
        "-input=/dev/null", "-input=dev.out", "-output=dev.hipfb", cwd=w)
     sh("/opt/rocm/bin/hipcc", *FLAGS, "--cuda-host-only", "-Xclang", "-fcuda-include-gpubinary", "-Xclang", "dev.hipfb", "-c", "ap.hip", "-o", "ap_patched.o", cwd=w)
     os.makedirs(os.path.join(ROOT, "tools", "bin"), exist_ok=True)
-    objs = [os.path.join(ROOT, "unimedvl_amd", "lib", f + ".o") for f in ("host_error", "elementwise", "pack", "gemm", "gemm_w4", "gemm_fp8mfma", "attention", "vision")]
+    objs = [os.path.join(product.LIBDIR, f.replace(".hip", ".o")) for f in product.SOURCES if f != TARGET]      # (python -m unimedvl_amd.build made them)
     lib = os.path.join(ROOT, "tools", "bin", f"libunimedvl_hip_{name}.so")
     sh("/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, *objs, os.path.join(w, "ap_patched.o"))
     print("built", lib)

@@ -7,15 +7,17 @@ set -e
 cd "$(dirname "$0")/.."
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 WHAT=${1:-both}
-SRCS="host_error elementwise pack gemm gemm_w4 gemm_fp8mfma gemm_mxfp4 attention attention_prefill vision"
+# one line per source, "name [per-file flags]": the build's own list (unimedvl_amd/build.py), so this script cannot fall behind it
+LIST=$(${PYTHON:-python} -c "from unimedvl_amd.build import SOURCES, FILE_FLAGS
+for s in SOURCES: print(s[:-4], *FILE_FLAGS.get(s, []))")
+SRCS=$(echo "$LIST" | cut -d' ' -f1 | tr '\n' ' ')
 build_and_run() {
   local name=$1 flags=$2 D=unimedvl_amd/lib/san_$1
   mkdir -p $D
-  for f in $SRCS; do
-    extra=""; [ $f = attention_prefill ] && extra="-mllvm -amdgpu-mfma-vgpr-form"
+  while read f extra; do
     $HIPCC --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -ffp-contract=off -fno-gpu-rdc -fno-omit-frame-pointer $flags -fno-gpu-sanitize $extra \
       -Wno-unused-result -Wno-unused-value -c unimedvl_amd/csrc/$f.hip -o $D/$f.o 2> $D/$f.log &
-  done
+  done <<< "$LIST"
   wait
   objs=""; for f in $SRCS; do [ -f $D/$f.o ] || { echo "compile failed: $f"; cat $D/$f.log | tail -20; exit 1; }; objs="$objs $D/$f.o"; done
   $HIPCC --offload-arch=gfx950 -shared -fPIC $flags -o $D/libunimedvl_hip_$name.so $objs

@@ -1,0 +1,56 @@
+// Workgroup reductions of the row kernels (norm.hip, token_pick.hip, vision.hip): wave_sum / wave_max of common.h, then one LDS
+// exchange between the waves.  Every thread of the workgroup must call them.
+#pragma once
+#include "common.h"
+
+// sum / max over the blockDim.x / 64 waves, in wave order; sm: one float per wave.  The leading barrier makes `sm` reusable
+// from one call to the next.
+__device__ __forceinline__ float block_reduce_sum(float v, float* sm) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float r = 0.f;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) r += sm[w];
+    return r;
+}
+__device__ __forceinline__ float block_reduce_max(float v, float* sm) {
+    v = wave_max(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float r = sm[0];
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r = fmaxf(r, sm[w]);
+    return r;
+}
+
+// The sum of a 256-thread workgroup as (p0 + p1) + (p2 + p3): the fixed order of the decode norms, whose results must not
+// depend on which of them a row went through.  part: four floats, written once per kernel.
+__device__ __forceinline__ float four_wave_sum(float v, float* part) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (part[0] + part[1]) + (part[2] + part[3]);
+}
+
+// The largest value of the workgroup and, among equal values, its LOWEST index.  True in the one thread (thread 0) whose
+// (best, bidx) is the result.  smv / smi: one entry per wave, not in use by anything before this call (a caller that reuses
+// them puts a barrier in front).
+__device__ __forceinline__ bool block_best_lowest(float& best_io, int& bidx_io, float* smv, int* smi) {
+    float best = best_io;
+    int bidx = bidx_io;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        float ob = __shfl_xor(best, o, 64);
+        int oi = __shfl_xor(bidx, o, 64);
+        if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
+    }
+    if ((threadIdx.x & 63) == 0) { smv[threadIdx.x >> 6] = best; smi[threadIdx.x >> 6] = bidx; }
+    __syncthreads();
+    if (threadIdx.x != 0) return false;
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w)
+        if (smv[w] > best || (smv[w] == best && smi[w] < bidx)) { best = smv[w]; bidx = smi[w]; }
+    best_io = best;
+    bidx_io = bidx;
+    return true;
+}

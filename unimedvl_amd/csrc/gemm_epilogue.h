@@ -3,6 +3,7 @@
 // GEMM's cross-wave reduction around these pieces is in gemm_skinny.h.
 #pragma once
 #include "common.h"
+#include "token_pick.h"
 #include "../../include/unimedvl_hip.h"
 #include <type_traits>
 
@@ -43,50 +44,23 @@ struct EpiCtx {
 };
 
 // Greedy argmax as an epilogue of the lm_head GEMM (bagel.py:1295-1301: argmax over the bf16 logits): every 16-column tile
-// leaves one 64-bit key per row - (order-preserving image of the bf16 logit) << 32 | (0xFFFFFFFF - column) - so that the
-// maximum key is the largest logit and, among equal logits, the LOWEST column (torch.argmax's tie rule; NaN ranks highest
-// like torch).  umv_decode_step_end_argmax takes the maximum over the tiles.
-__device__ __forceinline__ uint64_t argmax_key(float v, int n) {
-    uint32_t b = __float_as_uint(v == 0.f ? 0.f : v);            // -0 == +0
-    uint32_t k = (v != v) ? 0xFFFFFFFFu : ((b & 0x80000000u) ? ~b : (b | 0x80000000u));
-    return ((uint64_t)k << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)n);
-}
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int mask) {
-    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-    lo = (uint32_t)__shfl_xor((int)lo, mask, 64);
-    hi = (uint32_t)__shfl_xor((int)hi, mask, 64);
-    return ((uint64_t)hi << 32) | lo;
+// leaves one 64-bit key per row (token_pick.h::argmax_key); umv_decode_step_end_argmax takes the maximum over the tiles.
+// Sampling as an argmax (Gumbel-max): with temp > 0 the value whose key is taken is bf16(logit / temp) - ln(-ln(u)), u in (0, 1) - argmax
+// over a row = one draw from softmax(logits / temp) (bagel.py:1297-1299).  The generator and its keying are umv_sample_bf16's
+// (token_pick.h: the same u for the same seed, step, row and column); the noise stays finite (-ln(-ln u) in [-2.8, 16.6]).
+__device__ __forceinline__ float epi_gumbel_value(float logit, float temp, uint64_t row_key, int n) {
+    const float y = rbf(logit / temp);                                    // logits / temperature is a bf16 tensor in the reference
+    const float q = fmaxf(-__logf(sample_uniform(row_key, n)), 5.9604645e-8f);   // Exp(1) draw, held at -ln(1 - 2^-24) whatever the fast log returns next to 1
+    return y - __logf(q);
 }
 // The lane holds columns n0..n0+3 of row m of tile `tile` (lanes l, l^16, l^32, l^48 share the row): reduce the tile's 16
 // columns and let the first lane group write partial[m][tile].  `final` are the values epi_store4 stored (bf16-exact).
 // Must be called by ALL lanes of the wave (shuffles); lanes without a valid element pass valid = false.
-// Sampling as an argmax (Gumbel-max): with temp > 0 the value whose key is taken is bf16(logit / temp) - ln(-ln(u)), u in (0, 1] from
-// splitmix64(row key + column) - argmax over a row = one draw from softmax(logits / temp) (bagel.py:1297-1299).  The generator and its
-// keying are umv_sample_bf16's (elementwise.hip).  u = (r + 0.5) 2^-23 with r the top 23 bits of the hash: strictly inside (0, 1) and exact in
-// fp32 (r + 0.5 needs 24 bits), so the noise stays finite (-ln(-ln u) in [-2.8, 16.6]) and a column can only win through its logit - with
-// u = 1 allowed (round 5) a column won with probability 2^-24 whatever its logit: ~1 % of the draws over a 152 k vocabulary.
-__device__ __forceinline__ uint64_t epi_splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-__device__ __forceinline__ uint64_t epi_sample_row_key(uint64_t seed, const int64_t* step_ptr, int m) {
-    const uint64_t step = step_ptr ? (uint64_t)step_ptr[0] : 0ull;
-    return epi_splitmix64(seed ^ (step * 0xD1B54A32D192ED03ull) ^ ((uint64_t)m << 32));
-}
-__device__ __forceinline__ float epi_gumbel_value(float logit, float temp, uint64_t row_key, int n) {
-    const float y = rbf(logit / temp);                                    // logits / temperature is a bf16 tensor in the reference
-    const uint64_t h = epi_splitmix64(row_key + (uint64_t)n);
-    const float u = ((float)(h >> 41) + 0.5f) * (1.0f / 8388608.0f);      // [2^-24, 1 - 2^-24]
-    const float q = fmaxf(-__logf(u), 5.9604645e-8f);                     // Exp(1) draw, held at -ln(1 - 2^-24) whatever the fast log returns next to 1
-    return y - __logf(q);
-}
 __device__ __forceinline__ void epi_argmax_tile(uint64_t* __restrict__ partial, int64_t ld_partial, int m, int tile, int lane, bool valid,
                                                 int n0, int nend, const float* final, float temp = 0.f, uint64_t seed = 0, const int64_t* step_ptr = nullptr) {
     uint64_t key = 0;
     if (valid) {
-        const uint64_t row_key = temp > 0.f ? epi_sample_row_key(seed, step_ptr, m) : 0ull;
+        const uint64_t row_key = temp > 0.f ? sample_row_key(seed, step_ptr, m) : 0ull;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             if (n0 + j < nend) {

@@ -1,7 +1,7 @@
 // Image-head kernels: CFG combine + renorm + Euler step; VAE (FLUX autoencoder) kernels:
 // NHWC implicit-GEMM convolutions on MFMA, GroupNorm(+swish), latent (un)patchify,
 // sampling and pixel conversion.
-#include "common.h"
+#include "block_reduce.h"
 #include <stdlib.h>
 #include "../../include/unimedvl_hip.h"
 
@@ -11,17 +11,6 @@
 //   v_text_ = v_c + s_t*(v_t - v_c) ; v_ = v_i + s_i*(v_text_ - v_i)
 //   scale = clamp(norm(v_t)/(norm(v_)+1e-8), min, 1) ; v = v_*scale ; x_t -= v*dt
 // One workgroup per sample ("global" norms are per sample; the reference is batch-1 here).
-__device__ __forceinline__ float block_sum(float v, float* sm) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) sm[wave] = v;
-    __syncthreads();
-    float t = 0.f;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sm[w];
-    return t;
-}
-
 __device__ __forceinline__ float cfg_mix(float v, float vc, float s) {
     // vc + s*(v - vc) with bf16 rounding after each op
     return rbf(vc + rbf(s * rbf(v - vc)));
@@ -57,8 +46,8 @@ __global__ __launch_bounds__(1024) void cfg_renorm_euler_kernel(float* __restric
             a0 += v * v;
             a1 += vm * vm;
         }
-        a0 = block_sum(a0, sm);
-        a1 = block_sum(a1, sm);
+        a0 = block_reduce_sum(a0, sm);
+        a1 = block_reduce_sum(a1, sm);
         const float nv = rbf(sqrtf(a0)), nm = rbf(sqrtf(a1));
         float scale = rbf(nv / rbf(nm + 1e-8f));
         scale = fminf(fmaxf(scale, rmin), 1.0f);
