@@ -101,6 +101,14 @@ typedef struct {
                                  over a row is one draw from the softmax.  0: greedy keys. */
     uint64_t sample_seed;
     const int64_t* sample_step; /* device word: the decode step (changes the draw every step under a replayed HIP graph); NULL = 0 */
+    float* lse_partial;       /* optional [M][ceil(N/16)][2] fp32, only together with argmax_partial (UMV_ERR_ARG otherwise): the softmax
+                                 statistics of every 16-column tile of a row for the token log-probability (see "token log-probabilities"
+                                 below).  With y[n] the value the token pick orders WITHOUT noise - the stored bf16 logit when
+                                 sample_temperature == 0, bf16(logit / T) when it is > 0 - entry [m][t] = (m_t, s_t): m_t = max of y over
+                                 the tile's valid columns, s_t = sum of exp(y - m_t) over them (a -inf column adds 0; a tile of -inf only
+                                 is (-inf, 0), never NaN; a NaN column makes s_t NaN).  Fixed order - the lane's four columns, then the
+                                 row's four lane groups as a tree - so the bits do not depend on M or on the workgroup.  Keys and logits
+                                 are the bits of the same call without it.  Finished by umv_decode_step_end_logprob. */
 } umv_gemm_args;
 int umv_gemm_bf16(const umv_gemm_args* a, umv_stream_t stream);
 /* Host-only query: the tiled-kernel configuration umv_gemm_bf16 picks for an M x N x K problem (0 for M <= 64, the
@@ -368,6 +376,28 @@ int umv_decode_step_end(int32_t* tok_slot, int32_t* tok_pos, int32_t* kv_len, co
 int umv_decode_step_end_argmax(int32_t* tok_slot, int32_t* tok_pos, int32_t* kv_len, const uint64_t* argmax_partial, int n_tiles,
                                int64_t* ids, int64_t* in_ids, int64_t* pred_ids, int64_t* step_idx, int B,
                                int max_len, umv_stream_t stream);
+
+/* ------------------------------------------------------------------ token log-probabilities
+ * For row b of a decode step let y[n] be the value the token pick orders, without noise: greedy, y[n] = float(bf16 logit[b][n]), exactly
+ * the value stored to `out`; sampling at temperature T > 0, y[n] = bf16_round(logit[b][n] / T) (bagel.py:1297-1299: logits / temperature
+ * is a bf16 tensor).  Then logprob(b, id) = y[id] - logsumexp_n y[n] in fp32: a -inf column contributes 0, a row with a NaN logit
+ * gives NaN.  Inputs are bf16, so y[id] and the maximum are exact; measured against fp64 the value is within 1e-4 for |logprob| <= 200.
+ *
+ * umv_decode_step_end_logprob = umv_decode_step_end_argmax (same arguments, same bookkeeping, one workgroup and one step counter per
+ * sample) that also merges the tiles' (m_t, s_t) of lse_partial [B][n_tiles][2]: M = max m_t, S = sum s_t * exp(m_t - M), in a fixed
+ * order (thread-strided, the wave tree, waves 0..3), reads y[id] back from the logits the GEMM stored (`logits`, row stride ldo
+ * elements, V columns; temperature as given to the GEMM, 0 = greedy) and writes logprob[s * B + b] (fp32 [max_len][B]).
+ * forced_ids (optional, [max_len][B]): where forced_ids[s][b] >= 0 that token becomes ids[b] and in_ids[s + 1][b] and the
+ * log-probability is its own, while pred_ids[s][b] still records the model's pick; a negative entry leaves the sample free-running
+ * at that step.  A forced token >= V is never fed: the step free-runs and its log-probability is NaN. */
+int umv_decode_step_end_logprob(int32_t* tok_slot, int32_t* tok_pos, int32_t* kv_len, const uint64_t* argmax_partial,
+                                const float* lse_partial, int n_tiles, int64_t* ids, int64_t* in_ids, int64_t* pred_ids,
+                                int64_t* step_idx, const uint16_t* logits, int64_t ldo, int V, float temperature,
+                                const int64_t* forced_ids, float* logprob, int B, int max_len, umv_stream_t stream);
+/* The stand-alone form over bf16 logits [M][V] (row stride ld elements): out[m] = logprob(m, ids[m]) by the definition above, one
+ * workgroup per row.  temperature = 0: greedy (T = 1 without the rounding step).  An id outside [0, V) gives NaN. */
+int umv_token_logprob_bf16(const uint16_t* logits, int64_t ld, const int64_t* ids, float* out, int M, int V, float temperature,
+                           umv_stream_t stream);
 
 
 /* TimestepEmbedder.timestep_embedding (modeling_utils.py:87-109): out[r] = bf16(cat(cos(t[r] * freqs), sin(t[r] * freqs))),

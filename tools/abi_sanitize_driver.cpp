@@ -99,6 +99,10 @@ static void bad_arguments() {
     EXPECT_ERR(umv_gemm_z13w(&g, dummy8, nullptr));
     g.norm_w = nullptr; g.tile_rows = 14;                       // 16-row images only
     EXPECT_ERR(umv_gemm_z13w(&g, dummy8, nullptr));
+    g.tile_rows = 0; g.lse_partial = dummyf;                    // the softmax statistics ride on the argmax keys
+    EXPECT_ERR(umv_gemm_z13w(&g, dummy8, nullptr));
+    EXPECT_ERR(umv_gemm_bf16(&g, nullptr));
+    EXPECT_ERR(umv_gemm_fp8w(&g, nullptr));
     std::memset(&g, 0, sizeof g);
     EXPECT_ERR(umv_gemm_fp8a8w(nullptr, nullptr));
     umv_gemm8_args g8;
@@ -159,6 +163,16 @@ static void bad_arguments() {
     EXPECT_ERR(umv_decode_advance(nullptr, nullptr, nullptr, 8, nullptr));
     EXPECT_ERR(umv_decode_step_end(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 8, 16, nullptr));
     EXPECT_ERR(umv_decode_step_end_argmax(nullptr, nullptr, nullptr, nullptr, 9504, nullptr, nullptr, nullptr, nullptr, 8, 16, nullptr));
+    EXPECT_ERR(umv_decode_step_end_logprob(nullptr, nullptr, nullptr, nullptr, nullptr, 9504, nullptr, nullptr, nullptr, nullptr, nullptr, 152064,
+                                           152064, 0.f, nullptr, nullptr, 8, 16, nullptr));
+    EXPECT_ERR(umv_decode_step_end_logprob(dummyi, dummyi, dummyi, (const uint64_t*)dummyl, dummyf, 4, dummyl, dummyl, dummyl, dummyl, dummy16, 64,
+                                           100, 0.f, nullptr, dummyf, 1, 16, nullptr));           // 100 columns are not 4 tiles
+    EXPECT_ERR(umv_decode_step_end_logprob(dummyi, dummyi, dummyi, (const uint64_t*)dummyl, dummyf, 4, dummyl, dummyl, dummyl, dummyl, dummy16, 64,
+                                           64, -1.f, nullptr, dummyf, 1, 16, nullptr));           // negative temperature
+    EXPECT_ERR(umv_token_logprob_bf16(nullptr, 0, nullptr, nullptr, 8, 152064, 0.f, nullptr));
+    EXPECT_ERR(umv_token_logprob_bf16(dummy16, 32, dummyl, dummyf, 1, 64, 0.f, nullptr));         // row stride below V
+    EXPECT_ERR(umv_token_logprob_bf16(dummy16, 64, dummyl, dummyf, 1, 64, -1.f, nullptr));        // negative temperature
+    EXPECT_OK(umv_token_logprob_bf16(dummy16, 64, dummyl, dummyf, 0, 64, 0.f, nullptr));          // no rows
     EXPECT_ERR(umv_timestep_embed(nullptr, nullptr, nullptr, 4, 128, nullptr));
     EXPECT_ERR(umv_cfg_renorm_euler(nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 1, 4.0f, 1.5f, 0.f, 0, 0.1f, 64, nullptr));
     // VAE

@@ -20,6 +20,7 @@ class GemmArgs(C.Structure):
         ("norm_w", C.c_void_p), ("norm_eps", C.c_float), ("tile_rows", C.c_int), ("w_scale", C.c_void_p),
         ("k_splits", C.c_int), ("split_stride", C.c_int64), ("argmax_partial", C.c_void_p), ("x_rows", C.c_int64),
         ("sample_temperature", C.c_float), ("sample_seed", C.c_uint64), ("sample_step", C.c_void_p),
+        ("lse_partial", C.c_void_p),
     ]
 
 
@@ -115,6 +116,10 @@ _SIGS = {
                                       C.c_int, C.c_void_p]),
     "umv_decode_step_end_argmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "umv_decode_step_end_logprob": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                              C.c_int, C.c_int, C.c_void_p]),
+    "umv_token_logprob_bf16": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "umv_timestep_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "umv_cfg_renorm_euler": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.c_void_p]),

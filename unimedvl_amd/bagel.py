@@ -310,11 +310,15 @@ class Bagel(BagelPrep):
     def generate_text(self, past_key_values: NaiveCache, packed_key_value_indexes=None, key_values_lens=None,
                       packed_start_tokens=None, packed_query_position_ids=None, max_length: int = 0,
                       do_sample: bool = False, temperature: float = 1.0, end_token_id: int = None,
-                      return_logits: bool = False, per_sample_eos: bool = False):
+                      return_logits: bool = False, per_sample_eos: bool = False, return_logprobs: bool = False):
         """Greedy decode (bagel.py:1236-1317).  Returns [steps, B] int64 whose row 0 holds the
         start tokens.  Like the reference, the batch stops when SAMPLE 0 emits end_token_id
         (bagel.py:1313); per_sample_eos=True is the batched extension (stops when every sample
-        has emitted it; rows after a sample's EOS keep decoding and should be ignored)."""
+        has emitted it; rows after a sample's EOS keep decoding and should be ignored).
+        return_logprobs=True: returns (ids, logprobs) - or (ids, logits, logprobs) with return_logits - where logprobs is fp32
+        [rows, B]: logprobs[s] is the log-probability of the token step s picked, ids[s + 1] where that row exists (of
+        softmax(logits) in greedy decoding, of softmax(bf16(logits / temperature)) with do_sample).  Needs B <= 64; the step stays
+        in the captured graph."""
         # do_sample: softmax(logits / temperature) + multinomial on the device (bagel.py:1297-1299).  The
         # draw is keyed by a seed derived from torch.initial_seed(), so torch.manual_seed(s) makes runs
         # reproducible; the stream itself is not torch's (no device can reproduce another's RNG).
@@ -323,10 +327,15 @@ class Bagel(BagelPrep):
             raise ValueError("key_values_lens disagree with the cache")
         if max_length <= 0:   # nothing to decode (the reference would fail on torch.stack([]) here, bagel.py:1316)
             out = torch.zeros((0, len(past_key_values.lens)), dtype=torch.int64, device=self.device)
-            return (out, torch.zeros((0, len(past_key_values.lens), self.cfg.vocab), dtype=BF16, device=self.device)) if return_logits else out
+            res = (out,)
+            if return_logits:
+                res += (torch.zeros((0, len(past_key_values.lens), self.cfg.vocab), dtype=BF16, device=self.device),)
+            if return_logprobs:
+                res += (torch.zeros((0, len(past_key_values.lens)), dtype=torch.float32, device=self.device),)
+            return res if len(res) > 1 else out
         sess = DecodeSession(self.language_model, past_key_values, packed_start_tokens, packed_query_position_ids,
                              max_length, use_graph=self.decode_use_graph and not return_logits,
-                             do_sample=do_sample, temperature=temperature, seed=seed)
+                             do_sample=do_sample, temperature=temperature, seed=seed, logprobs=return_logprobs)
         logits = []
         steps = 0
         stop = None
@@ -349,16 +358,20 @@ class Bagel(BagelPrep):
         rows = stop if stop is not None else steps
         sess.commit(rows)
         out = sess.in_ids[:rows].clone()
+        res = (out,)
         if return_logits:
-            return out, torch.stack(logits[:rows], 0)
-        return out
+            res += (torch.stack(logits[:rows], 0),)
+        if return_logprobs:
+            res += (sess.pred_logprobs[:rows].clone(),)
+        return res if len(res) > 1 else out
 
     # ------------------------------------------------------------------ convenience (evaluation path)
     @torch.no_grad()
     @ops.on_device
     def chat(self, tokenizer, new_token_ids, image_transform, images, prompt, max_length: int,
-             do_sample: bool = False, temperature: float = 1.0):
-        """ViT-only VQA convenience path (bagel.py:1321-1392)."""
+             do_sample: bool = False, temperature: float = 1.0, return_logprobs: bool = False):
+        """ViT-only VQA convenience path (bagel.py:1321-1392).  return_logprobs=True: returns (answer, token_ids, token_logprobs) -
+        the generated tokens behind the answer (the end token excluded) and the log-probability of each (generate_text)."""
         if self.chat_cache_tokens > 0:       # serving: one reserved cache reused by every request (stable slabs -> graph prefill)
             if self._chat_cache is None or self._chat_cache.cap < self.chat_cache_tokens:
                 self._chat_cache = NaiveCache(self.cfg.layers)
@@ -375,9 +388,62 @@ class Bagel(BagelPrep):
         cache = self.forward_cache_update_text(cache, **gi)
         gi = self.prepare_start_tokens(newlens, new_rope, new_token_ids)
         ids = self.generate_text(past_key_values=cache, max_length=max_length, do_sample=do_sample,
-                                 temperature=temperature, end_token_id=new_token_ids["eos_token_id"], **gi)
+                                 temperature=temperature, end_token_id=new_token_ids["eos_token_id"],
+                                 return_logprobs=return_logprobs, **gi)
+        if return_logprobs:
+            ids, lp = ids
         output = tokenizer.decode(ids[:, 0].cpu())
-        return output.split("<|im_end|>")[0].split("<|im_start|>")[1]
+        answer = output.split("<|im_end|>")[0].split("<|im_start|>")[1]
+        if return_logprobs:          # lp[s] belongs to ids[s + 1]
+            n = max(ids.shape[0] - 1, 0)
+            return answer, ids[1:, 0].tolist(), lp[:n, 0].tolist()
+        return answer
+
+    @torch.no_grad()
+    @ops.on_device
+    def score(self, tokenizer, new_token_ids, image_transform, images, prompt, candidates, append_eos: bool = True):
+        """Closed-set answering: how probable is each candidate answer after the context of `chat` (images, then the prompt)?
+        candidates: strings (tokenizer.encode) or lists of token ids, at most 64.  The context is prefilled ONCE, laid out once
+        per candidate (NaiveCache.merged) and one forced decode session feeds every candidate its own tokens - append_eos adds the
+        end token, so that "yes" is not favoured over "yes, but" for being a prefix - with -1 (free-running, ignored) past a
+        candidate's end.  Greedy definition: log-softmax of the bf16 logits.  Returns one dict per candidate: token_ids (the scored
+        tokens, EOS included), token_logprobs (one fp32 value per token) and logprob (their sum, added in fp64 on the host).
+        Samples are independent rows of every kernel, so a candidate's values do not depend on the others.
+        Forced decoding costs one decode step per token - the right trade for answers of a few tokens; long continuations want a
+        prefill-time scorer, which this is not."""
+        cands = list(candidates)
+        if not 1 <= len(cands) <= 64:
+            raise ValueError(f"score takes 1..64 candidates, got {len(cands)}")
+        toks = []
+        for c in cands:
+            t = [int(v) for v in (tokenizer.encode(c) if isinstance(c, str) else c)]
+            if append_eos:
+                t.append(int(new_token_ids["eos_token_id"]))
+            if not t:
+                raise ValueError("score: an empty candidate (and append_eos=False) has nothing to score")
+            toks.append(t)
+        cfg, n, steps = self.cfg, len(toks), max(len(t) for t in toks)
+        cache = NaiveCache(cfg.layers)
+        newlens, new_rope = [0], [0]
+        for image in images:
+            gi, newlens, new_rope = self.prepare_vit_images(newlens, new_rope, [image], image_transform, new_token_ids)
+            cache = self.forward_cache_update_vit(cache, **gi)
+        gi, newlens, new_rope = self.prepare_prompts(newlens, new_rope, [prompt], tokenizer, new_token_ids)
+        cache = self.forward_cache_update_text(cache, **gi)
+        gi = self.prepare_start_tokens(newlens, new_rope, new_token_ids)
+        many = NaiveCache.merged([cache] * n, [1] * n, steps + 1, cfg.kv_heads, cfg.head_dim, self.device) if n > 1 else cache
+        forced = torch.full((steps, n), -1, dtype=torch.int64)
+        for b, t in enumerate(toks):
+            forced[:len(t), b] = torch.tensor(t, dtype=torch.int64)
+        sess = DecodeSession(self.language_model, many, gi["packed_start_tokens"].repeat(n), gi["packed_query_position_ids"].repeat(n),
+                             steps, use_graph=self.decode_use_graph, forced_ids=forced)
+        sess.step(steps)
+        lp = sess.pred_logprobs.cpu()
+        out = []
+        for b, t in enumerate(toks):
+            vals = lp[:len(t), b]
+            out.append({"token_ids": t, "token_logprobs": vals.tolist(), "logprob": float(vals.double().sum())})
+        return out
 
 
 class FlowSession:

@@ -49,7 +49,7 @@ struct EpiCtx {
 // over a row = one draw from softmax(logits / temp) (bagel.py:1297-1299).  The generator and its keying are umv_sample_bf16's
 // (token_pick.h: the same u for the same seed, step, row and column); the noise stays finite (-ln(-ln u) in [-2.8, 16.6]).
 __device__ __forceinline__ float epi_gumbel_value(float logit, float temp, uint64_t row_key, int n) {
-    const float y = rbf(logit / temp);                                    // logits / temperature is a bf16 tensor in the reference
+    const float y = pick_value(logit, temp);                              // logits / temperature is a bf16 tensor in the reference
     const float q = fmaxf(-__logf(sample_uniform(row_key, n)), 5.9604645e-8f);   // Exp(1) draw, held at -ln(1 - 2^-24) whatever the fast log returns next to 1
     return y - __logf(q);
 }
@@ -74,6 +74,29 @@ __device__ __forceinline__ void epi_argmax_tile(uint64_t* __restrict__ partial, 
     o = shfl_xor_u64(key, 32);
     key = o > key ? o : key;
     if (valid && (lane >> 4) == 0) partial[(int64_t)m * ld_partial + tile] = key;
+}
+// The softmax statistics of the same tile for the token log-probability (include/unimedvl_hip.h, lse_partial), called where
+// epi_argmax_tile is and with its arguments: y = the value the keys order without the noise (token_pick.h::pick_value), m_t its
+// maximum over the tile's valid columns, s_t = sum exp(y - m_t).  The maximum is exact; the sum runs over the lane's four columns
+// in order, then lanes (l, l ^ 16), then (.., l ^ 32): the same tree in all four lanes, whatever M and the workgroup.  A tile of
+// -inf only leaves (-inf, 0) - the reference point moves to 0 as in attn_kernel - and a NaN column leaves s_t = NaN.
+__device__ __forceinline__ void epi_lse_tile(float* __restrict__ lse, int64_t ld_partial, int m, int tile, int lane, bool valid, int n0,
+                                             int nend, const float* final, float temp) {
+    float y[4], mx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        y[j] = (valid && n0 + j < nend) ? pick_value(final[j], temp) : -INFINITY;
+        mx = fmaxf(mx, y[j]);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float ref = (mx == -INFINITY) ? 0.f : mx;
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s += __expf(y[j] - ref);
+    s += __shfl_xor(s, 16, 64);
+    s += __shfl_xor(s, 32, 64);
+    if (valid && (lane >> 4) == 0) *reinterpret_cast<umv_f32x2*>(lse + ((int64_t)m * ld_partial + tile) * 2) = (umv_f32x2){mx, s};
 }
 
 // The bias of columns n0..n0+3 (zero beyond N): one 8-byte load when the four columns exist and the address is 8-byte aligned.

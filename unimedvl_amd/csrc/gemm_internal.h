@@ -103,6 +103,7 @@ static inline int umv_gemm_check_args(const umv_gemm_args& a, const char* who, i
     UMV_CHECK(!(a.epilogue & UMV_EPI_BIAS) || a.bias, UMV_ERR_ARG, "%s: BIAS without bias pointer", who);
     UMV_CHECK(!(a.epilogue & UMV_EPI_RESIDUAL) || a.residual, UMV_ERR_ARG, "%s: RESIDUAL without residual pointer", who);
     UMV_CHECK(!(a.epilogue & UMV_EPI_SWIGLU) || (a.N % 32) == 0, UMV_ERR_ARG, "%s: SWIGLU needs N %% 32 == 0", who);
+    UMV_CHECK(!a.lse_partial || a.argmax_partial, UMV_ERR_ARG, "%s: lse_partial rides on the argmax_partial epilogue and needs it set", who);
     return UMV_OK;
 }
 

@@ -272,8 +272,10 @@ __device__ __forceinline__ void skinny16_reduce_epilogue(const umv_gemm_args& a,
                 et.N = nend;
                 epi_store4(et, orow, n0, s.x, s.y, s.z, s.w, fin);
             }
-            if (a.argmax_partial && nt0 + t < NTT)   // wave-uniform: greedy argmax rides on the lm_head epilogue
+            if (a.argmax_partial && nt0 + t < NTT) { // wave-uniform: greedy argmax rides on the lm_head epilogue
                 epi_argmax_tile(a.argmax_partial, NTT, m, nt0 + t, l, valid, n0, nend, fin, a.sample_temperature, a.sample_seed, a.sample_step);
+                if (a.lse_partial) epi_lse_tile(a.lse_partial, NTT, m, nt0 + t, l, valid, n0, nend, fin, a.sample_temperature);   // and the softmax statistics
+            }
         }
     }
 }

@@ -22,6 +22,15 @@ __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int mask) {
     return ((uint64_t)hi << 32) | lo;
 }
 
+// The value the token pick orders, without noise, and the y of the token log-probability (include/unimedvl_hip.h): the bf16 logit
+// itself in greedy decoding (temp == 0), bf16(logit / T) when sampling - logits / temperature is a bf16 tensor in the reference
+// (bagel.py:1297-1299).
+__device__ __forceinline__ float pick_value(float logit, float temp) { return temp > 0.f ? rbf(logit / temp) : logit; }
+
+// logprob = y[id] - logsumexp y from the merged statistics: M = max y (exact), S = sum exp(y - M).  (y - M) first: both are bf16
+// values, so the difference is exact or nearly so and the one rounding that matters is log's.
+__device__ __forceinline__ float logprob_finish(float y_id, float M, float S) { return (y_id - M) - logf(S); }
+
 // The sampler's stream: splitmix64 of (seed, step, row) gives the row key, splitmix64 of (row key + column) the draw - reproducible
 // for a given seed, NOT torch's CPU / CUDA stream.
 __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {

@@ -31,15 +31,22 @@ BF16 = torch.bfloat16
 
 class DecodeSession:
     def __init__(self, llm, cache: NaiveCache, start_tokens, positions, max_length, use_graph=True, nsplit=None,
-                 do_sample=False, temperature=1.0, seed=0):
+                 do_sample=False, temperature=1.0, seed=0, logprobs=False, forced_ids=None):
+        """logprobs: also record pred_logprobs (fp32 [max_length, B]) - row s is the log-probability of in_ids[s + 1], the token step s
+        picked (include/unimedvl_hip.h, token log-probabilities: of softmax(logits) in greedy decoding, of softmax(bf16(logits / T))
+        when sampling).  forced_ids (int64 [max_length, B]): where an entry is >= 0 that token is fed to the next step instead of the
+        pick - pred_ids still records the pick, pred_logprobs the forced token's value; negative = free-running.  Implies logprobs.
+        Both ride on the fused step end: B <= 64 and UMV_DECODE_FUSED_ARGMAX not 0, ValueError otherwise."""
         with ops.device_scope(llm.device):
-            self._init(llm, cache, start_tokens, positions, max_length, use_graph, nsplit, do_sample, temperature, seed)
+            self._init(llm, cache, start_tokens, positions, max_length, use_graph, nsplit, do_sample, temperature, seed, logprobs,
+                       forced_ids)
 
     @property
     def device(self):
         return self.dev
 
-    def _init(self, llm, cache, start_tokens, positions, max_length, use_graph, nsplit, do_sample, temperature, seed):
+    def _init(self, llm, cache, start_tokens, positions, max_length, use_graph, nsplit, do_sample, temperature, seed, logprobs=False,
+              forced_ids=None):
         cfg, dev = llm.cfg, llm.device
         self.llm, self.cache, self.cfg, self.dev = llm, cache, cfg, dev
         B = len(cache.lens)
@@ -102,6 +109,23 @@ class DecodeSession:
         self.fused_argmax = B <= 64 and os.environ.get("UMV_DECODE_FUSED_ARGMAX", "1") not in ("0", "")
         if self.fused_argmax:
             self.amax_part = torch.zeros((B, (cfg.vocab + 15) // 16), dtype=torch.int64, device=dev)
+        # token log-probabilities / forced tokens: the lm_head epilogue also leaves the softmax statistics of every tile, and the step
+        # ends with umv_decode_step_end_logprob instead - same launch count, still one graph
+        self.logprobs = bool(logprobs) or forced_ids is not None
+        self.forced_ids = self.pred_logprobs = self.lse_part = None
+        if self.logprobs:
+            if not self.fused_argmax:
+                raise ValueError("logprobs / forced_ids ride on the fused step end: at most 64 samples and UMV_DECODE_FUSED_ARGMAX not 0 "
+                                 f"(got B={B}, UMV_DECODE_FUSED_ARGMAX={os.environ.get('UMV_DECODE_FUSED_ARGMAX', '1')!r})")
+            if forced_ids is not None:
+                f = torch.as_tensor(forced_ids, dtype=torch.int64)
+                if tuple(f.shape) != (max_length, B):
+                    raise ValueError(f"forced_ids must be [max_length, B] = [{max_length}, {B}], got {tuple(f.shape)}")
+                if f.numel() and int(f.max()) >= cfg.vocab:
+                    raise ValueError(f"forced_ids holds token {int(f.max())} >= vocab {cfg.vocab}")
+                self.forced_ids = f.to(dev).contiguous()
+            self.lse_part = torch.zeros((B, (cfg.vocab + 15) // 16, 2), dtype=torch.float32, device=dev)
+            self.pred_logprobs = torch.zeros((max_length, B), dtype=torch.float32, device=dev)
         w = llm.w
         # K splits of the QKV / o / down GEMMs: "q,o,d" (1 = that GEMM is not split), "0" = none, "auto" by batch / weights.
         # Measured on MI355X (bench.py --batch B, ms per step), no split -> 3,4,4:
@@ -188,6 +212,14 @@ class DecodeSession:
             else:
                 ops.gemm(self.act, down_w, out=self.seq, residual=self.seq)
                 ops.rmsnorm(self.seq, nxt, cfg.rms_eps, out=dst)
+        if self.logprobs:
+            ops.gemm(self.hn, w.lm_head, out=self.logits, argmax_partial=self.amax_part, lse_partial=self.lse_part,
+                     sample=(self.temperature, self.seed, self.step_idx) if self.do_sample else None)
+            # the fused step end below, plus pred_logprobs[step] = log-probability of the token fed next (the pick or the forced one)
+            ops.decode_step_end_logprob(self.tok_slot, self.tok_pos, self.kv_len, self.amax_part, self.lse_part, self.ids, self.in_ids,
+                                        self.pred_ids, self.step_idx, self.logits, self.pred_logprobs,
+                                        self.temperature if self.do_sample else 0.0, self.forced_ids)
+            return
         if self.fused_argmax:
             ops.gemm(self.hn, w.lm_head, out=self.logits, argmax_partial=self.amax_part,
                      sample=(self.temperature, self.seed, self.step_idx) if self.do_sample else None)
@@ -244,7 +276,7 @@ class DecodeSession:
 
     @ops.on_device
     def rewind_outputs(self):
-        """Start writing in_ids / pred_ids at row 0 again (the caller has harvested the previous rows)."""
+        """Start writing in_ids / pred_ids (and pred_logprobs) at row 0 again (the caller has harvested the previous rows)."""
         self.step_idx.zero_()
         self.in_ids[0].copy_(self.ids)      # the tokens the next step is fed (set_slot may have changed them)
         self.steps_done = 0

@@ -157,8 +157,27 @@ class VQAInferencer:
             input_image = Image.open(image_path).convert("RGB")
         start = time.time()
         images, conversation = process_conversation([input_image], prompt)
+        # "return_logprobs" (not a reference key; default off): the result also carries "token_ids" and "token_logprobs", the generated
+        # tokens behind the answer and the log-probability of each (Bagel.generate_text).  Without it the result is the reference's.
+        want_lp = bool(self.config.get("return_logprobs", False))
+        extra = {"return_logprobs": True} if want_lp else {}
         answer = self.model.chat(self.tokenizer, self.new_token_ids, self.image_transform, images=images,
                                  prompt=conversation, max_length=max_new_tokens, do_sample=do_sample,
-                                 temperature=temperature)
-        return {"answer": answer, "input_image": input_image, "time": time.time() - start, "image_path": image_path,
-                "prompt": prompt, "timestamp": datetime.now().strftime("%Y-%m-%d %H:%M:%S")}
+                                 temperature=temperature, **extra)
+        if want_lp:
+            answer, token_ids, token_logprobs = answer
+        result = {"answer": answer, "input_image": input_image, "time": time.time() - start, "image_path": image_path,
+                  "prompt": prompt, "timestamp": datetime.now().strftime("%Y-%m-%d %H:%M:%S")}
+        if want_lp:
+            result.update(token_ids=token_ids, token_logprobs=token_logprobs)
+        return result
+
+    def score(self, image, question, candidates, append_eos=True):
+        """Closed-set answering (Bagel.score): one dict per candidate - token_ids, token_logprobs, logprob - for the answers
+        `candidates` (strings or token-id lists, at most 64) to `question` about `image` (a PIL image or a path)."""
+        if not self.loaded:
+            raise RuntimeError("Model not loaded, please call load_model() first")
+        input_image = image.convert("RGB") if isinstance(image, Image.Image) else Image.open(image).convert("RGB")
+        images, conversation = process_conversation([input_image], question)
+        return self.model.score(self.tokenizer, self.new_token_ids, self.image_transform, images, conversation, candidates,
+                                append_eos=append_eos)

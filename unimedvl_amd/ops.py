@@ -265,7 +265,7 @@ def _route(lin, M, splitk=False, norm=False, amax=False, act8=False, out_f32=Fal
 
 
 def _launch(lib, route, x, lin, out, ldo, M, flags=0, residual=None, row_idx=None, norm_w=None, norm_eps=0.0, amax=None, sample=None,
-            k_splits=0, split_stride=0):
+            k_splits=0, split_stride=0, lse=None):
     """Build the umv_gemm_args of a routed call and launch it.  What only some entries take is set from the route: w_scale; th-row tiles
     and the bound on x's rows (the bf16 kernel and its 13-bit twin, outside split-K); the sampling mode (not the MXFP4 entries, which
     have no argmax keys); every other field is the call's"""
@@ -288,6 +288,8 @@ def _launch(lib, route, x, lin, out, ldo, M, flags=0, residual=None, row_idx=Non
         a.tile_rows, a.x_rows = lin.th, x.shape[0]
     if sample is not None and entry not in ("umv_gemm_mxfp4w", "umv_gemm_mxfp4t"):
         a.sample_temperature, a.sample_seed, a.sample_step = _sample_fields(sample, amax)
+    if lse is not None:
+        a.lse_partial = lse
     if wz is not None:
         check(lib.umv_gemm_z13w(C.byref(a), wz.data_ptr(), _stream()), entry)
     else:
@@ -296,7 +298,7 @@ def _launch(lib, route, x, lin, out, ldo, M, flags=0, residual=None, row_idx=Non
 
 
 def gemm(x, lin, out=None, *, M=None, residual=None, act=None, row_idx=None, out_f32=False, use_bias=True,
-         norm_w=None, norm_eps=1e-6, act8=False, argmax_partial=None, sample=None, z13=None):
+         norm_w=None, norm_eps=1e-6, act8=False, argmax_partial=None, sample=None, z13=None, lse_partial=None):
     """out = epilogue(x @ W^T).  x [M,K] bf16 (row stride may exceed K).  act in {None,'gelu_tanh','silu'}.
     norm_w: fuse Qwen2RMSNorm(x)*norm_w into the GEMM prologue (M <= 16, K <= 4096).
     act8 (W8A8 mode, needs lin.w8m): the activations are rounded per row through e4m3 - on the fp8 matrix instruction for
@@ -304,6 +306,9 @@ def gemm(x, lin, out=None, *, M=None, residual=None, act=None, row_idx=None, out
     argmax_partial (int64 [M, ceil(N/16)], M <= 64): greedy-argmax keys per 16-column tile, finished by decode_step_end_argmax.
     sample (with argmax_partial): (temperature, seed, step tensor or None) - the keys then order bf16(logit / T) + Gumbel noise, so the
     row maximum is one draw from softmax(logits / T) (bagel.py:1297-1299) instead of the greedy token.
+    lse_partial (with argmax_partial; fp32 [M, ceil(N/16), 2]): per tile and row the maximum of the value the keys order without noise
+    and the sum of exp(value - maximum) - the softmax statistics decode_step_end_logprob turns into the token's log-probability.  It
+    rides on the argmax_partial epilogue: without argmax_partial the library refuses it (UMV_ERR_ARG).
     z13 (tests and A/B only; leave None): whether a linear's exact 13-bit image is streamed - None = the measured policy of _route,
     True = whenever umv_gemm_z13w serves the call, False = never."""
     lib = _lib.load()
@@ -337,7 +342,15 @@ def gemm(x, lin, out=None, *, M=None, residual=None, act=None, row_idx=None, out
         if not (argmax_partial.is_contiguous() and tuple(argmax_partial.shape) == (M, (lin.N + 15) // 16)):
             raise _lib.UmvError(f"argmax_partial must be a contiguous int64 [{M}, {(lin.N + 15) // 16}] tensor")
         amax = argmax_partial.data_ptr()
+    lse = None
+    if lse_partial is not None:
+        _req(lse_partial, torch.float32, "lse_partial")
+        if not (lse_partial.is_contiguous() and tuple(lse_partial.shape) == (M, (lin.N + 15) // 16, 2)):
+            raise _lib.UmvError(f"lse_partial must be a contiguous fp32 [{M}, {(lin.N + 15) // 16}, 2] tensor")
+        lse = lse_partial.data_ptr()
     if route[0] == "umv_gemm_fp8a8w":
+        if lse is not None:
+            raise _lib.UmvError("gemm: lse_partial rides on the argmax_partial epilogue of the M <= 64 kernels")
         # W8A8: per-row e4m3 activations (rows gathered through row_idx), fp8 matrix instruction, exact pow2 scales
         xq, xs = quantize_act(x, M, row_idx, lin.K)
         a8 = _lib.Gemm8Args(xq=xq.data_ptr(), ldq=xq.stride(0), x_scale=xs.data_ptr(), wp=lin.w8m.data_ptr(), w_scale=lin.scale.data_ptr(),
@@ -350,7 +363,7 @@ def gemm(x, lin, out=None, *, M=None, residual=None, act=None, row_idx=None, out
             a8.row_idx = row_idx.data_ptr()
         check(lib.umv_gemm_fp8a8w(C.byref(a8), _stream()), "umv_gemm_fp8a8w")
         return out
-    return _launch(lib, route, x, lin, out, out.stride(0), M, flags, residual, row_idx, norm_w, norm_eps, amax, sample)
+    return _launch(lib, route, x, lin, out, out.stride(0), M, flags, residual, row_idx, norm_w, norm_eps, amax, sample, lse=lse)
 
 
 def rmsnorm(x, w, eps, out=None, w_gen=None, expert=None):
@@ -652,6 +665,59 @@ def decode_step_end_argmax(tok_slot, tok_pos, kv_len, argmax_partial, ids, in_id
     check(lib.umv_decode_step_end_argmax(_p(tok_slot), _p(tok_pos), _p(kv_len), _p(argmax_partial), argmax_partial.shape[1], _p(ids),
                                          _p(in_ids), _p(pred_ids), _p(step_idx), B, in_ids.shape[0], _stream()),
           "umv_decode_step_end_argmax")
+
+
+def decode_step_end_logprob(tok_slot, tok_pos, kv_len, argmax_partial, lse_partial, ids, in_ids, pred_ids, step_idx, logits, logprobs,
+                            temperature=0.0, forced_ids=None):
+    """decode_step_end_argmax that also writes logprobs[s] (fp32 [max_len, B]): the log-probability of the token the next step is fed,
+    from the per-tile softmax statistics the lm_head GEMM left in lse_partial ([B, n_tiles, 2]) and the logits it stored.  temperature:
+    the one the GEMM sampled at, 0 = greedy.  forced_ids (int64 [max_len, B] or None): an entry >= 0 replaces the pick as ids /
+    in_ids[s + 1] - and the log-probability is that token's - while pred_ids[s] keeps the model's own pick; negative = free-running."""
+    lib = _lib.load()
+    for t, name in ((argmax_partial, "argmax_partial"), (ids, "ids"), (in_ids, "in_ids"), (pred_ids, "pred_ids"), (step_idx, "step_idx")):
+        _req(t, torch.int64, name)
+    _req(lse_partial, torch.float32, "lse_partial")
+    _req(logprobs, torch.float32, "logprobs")
+    _req(logits, BF16, "logits")
+    B = ids.numel()
+    if step_idx.numel() < B:
+        raise _lib.UmvError(f"decode_step_end_logprob: step_idx holds {step_idx.numel()} counters for {B} samples")
+    if not (in_ids.is_contiguous() and pred_ids.is_contiguous() and in_ids.shape == pred_ids.shape and in_ids.shape[1] == B
+            and argmax_partial.is_contiguous() and argmax_partial.shape[0] == B and lse_partial.is_contiguous()
+            and tuple(lse_partial.shape) == tuple(argmax_partial.shape) + (2,) and logprobs.is_contiguous()
+            and logprobs.shape == in_ids.shape):
+        raise _lib.UmvError("decode_step_end_logprob: in_ids / pred_ids / logprobs [max_len, B], argmax_partial [B, n_tiles], "
+                            "lse_partial [B, n_tiles, 2], all contiguous")
+    if logits.dim() != 2 or logits.shape[0] < B or logits.stride(1) != 1:
+        raise _lib.UmvError("decode_step_end_logprob: logits must be [B, V] with unit column stride")
+    if forced_ids is not None:
+        _req(forced_ids, torch.int64, "forced_ids")
+        if not (forced_ids.is_contiguous() and forced_ids.shape == in_ids.shape):
+            raise _lib.UmvError("decode_step_end_logprob: forced_ids must be a contiguous int64 [max_len, B] tensor")
+    check(lib.umv_decode_step_end_logprob(_p(tok_slot), _p(tok_pos), _p(kv_len), _p(argmax_partial), _p(lse_partial), argmax_partial.shape[1],
+                                          _p(ids), _p(in_ids), _p(pred_ids), _p(step_idx), _p(logits), logits.stride(0), logits.shape[1],
+                                          float(temperature), _p(forced_ids), _p(logprobs), B, in_ids.shape[0], _stream()),
+          "umv_decode_step_end_logprob")
+
+
+def token_logprob(logits, ids, temperature=0.0, out=None):
+    """out[m] = log_softmax(y[m])[ids[m]] in fp32 for bf16 logits [M, V] (any row stride): y = the logits (temperature 0: greedy) or
+    bf16(logits / temperature), the value sampling orders.  For callers who hold logits - return_logits=True, a prefill's last rows."""
+    lib = _lib.load()
+    _req(logits, BF16, "logits")
+    _req(ids, torch.int64, "ids")
+    if logits.dim() != 2 or logits.stride(1) != 1 or ids.numel() != logits.shape[0] or not ids.is_contiguous():
+        raise _lib.UmvError("token_logprob: logits [M, V] with unit column stride, ids a contiguous int64 [M]")
+    M, V = logits.shape
+    if out is None:
+        out = torch.empty((M,), dtype=torch.float32, device=logits.device)
+    else:
+        _req(out, torch.float32, "out")
+        if not (out.is_contiguous() and out.numel() == M):
+            raise _lib.UmvError("token_logprob: out must be a contiguous fp32 [M] tensor")
+    check(lib.umv_token_logprob_bf16(_p(logits), logits.stride(0), _p(ids), _p(out), M, V, float(temperature), _stream()),
+          "umv_token_logprob_bf16")
+    return out
 
 
 def timestep_embed(t, freqs):

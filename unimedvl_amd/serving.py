@@ -37,19 +37,22 @@ class _Request:
     prompt: str
     max_new_tokens: int
     tokens: List[int] = field(default_factory=list)
+    logprobs: List[float] = field(default_factory=list)
 
 
 class ContinuousBatcher:
     def __init__(self, model, tokenizer, new_token_ids, image_transform, slots: int = 8, max_context: int = 2048,
                  max_new_tokens: int = 256, check_every: int = 16, do_sample: bool = False, temperature: float = 1.0,
                  use_graph: bool = True, growable: bool = True, context_limit: Optional[int] = None, paged: bool = False,
-                 pool_pages: Optional[int] = None):
+                 pool_pages: Optional[int] = None, logprobs: bool = False):
         """max_context: the context (prompt + images) the slots are RESERVED for; with growable=True longer requests enlarge
         the cache (up to context_limit tokens of context when given), with growable=False they are refused.
         paged=True: block-table KV (kvcache.PagedCache) instead of slabs - the slots draw 256-token pages from ONE pool of `pool_pages`
         pages per layer (default: what max_context + max_new_tokens needs for every slot, plus as much again), a request of any length
         up to context_limit (default 32 768) is admitted without re-allocating or re-capturing anything, and a finished request returns
-        its pages.  Same answers as the slab cache (tests/test_paged_kv_gpu.py)."""
+        its pages.  Same answers as the slab cache (tests/test_paged_kv_gpu.py).
+        logprobs=True: self.logprobs[rid] holds one float per emitted token of the request - the token's log-probability as
+        DecodeSession(logprobs=True) records it - cut at EOS or the budget exactly as the tokens are.  Needs slots <= 64."""
         self.model, self.tokenizer, self.new_token_ids, self.image_transform = model, tokenizer, new_token_ids, image_transform
         self.device = model.device
         self.slots, self.check_every = int(slots), int(check_every)
@@ -68,6 +71,8 @@ class ContinuousBatcher:
         self.cache.reserve(self.slots, per_slot, cfg.kv_heads, cfg.head_dim, model.device)
         self.queue: Deque[_Request] = deque()
         self.results: Dict[int, str] = {}
+        self.want_logprobs = bool(logprobs)
+        self.logprobs: Dict[int, List[float]] = {}
         self._next_id = 0
         self.stats = {"decode_steps": 0, "prefills": 0, "tokens": 0, "cache_grows": 0}
 
@@ -107,7 +112,7 @@ class ContinuousBatcher:
             pos = torch.tensor([s[2] for s in state], dtype=torch.int64)
             lens_now = list(cache.lens)
             sn = DecodeSession(m.language_model, cache, start, pos, self.check_every, use_graph=self.use_graph,
-                               do_sample=self.do_sample, temperature=self.temperature, seed=seed)
+                               do_sample=self.do_sample, temperature=self.temperature, seed=seed, logprobs=self.want_logprobs)
             cache.lens = lens_now                       # the session only reads them; this loop owns the bookkeeping
             self._grew = False
             return sn
@@ -125,6 +130,7 @@ class ContinuousBatcher:
             self._between_rounds()                      # (queued behind the decode steps; the host reads the ids after both)
             self.stats["decode_steps"] += k
             ids = sess.pred_ids[:k].cpu()               # [k, B]; the only host sync of the round
+            lps = sess.pred_logprobs[:k].cpu() if self.want_logprobs else None
             freed = []
             for b in range(B):
                 req = active[b]
@@ -133,12 +139,15 @@ class ContinuousBatcher:
                     state[b] = (bos, 0, 0)
                     continue
                 col = ids[:, b].tolist()
+                n_before = len(req.tokens)
                 done = False
                 for t in col:
                     if t == eos or len(req.tokens) >= req.max_new_tokens:
                         done = True
                         break
                     req.tokens.append(int(t))
+                if lps is not None:                     # one value per token emitted this round
+                    req.logprobs.extend(lps[:len(req.tokens) - n_before, b].tolist())
                 if len(req.tokens) >= req.max_new_tokens:
                     done = True
                 if not done:
@@ -282,6 +291,8 @@ class ContinuousBatcher:
         bos = self.new_token_ids["bos_token_id"]
         text = self.tokenizer.decode(torch.tensor([bos] + req.tokens, dtype=torch.int64))
         self.results[req.rid] = text.split("<|im_end|>")[0].split("<|im_start|>")[1]   # inferencer.py:277-278
+        if self.want_logprobs:
+            self.logprobs[req.rid] = list(req.logprobs)
         self.stats["tokens"] += len(req.tokens)
 
 
