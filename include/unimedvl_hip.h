@@ -399,6 +399,43 @@ int umv_decode_step_end_logprob(int32_t* tok_slot, int32_t* tok_pos, int32_t* kv
 int umv_token_logprob_bf16(const uint16_t* logits, int64_t ld, const int64_t* ids, float* out, int M, int V, float temperature,
                            umv_stream_t stream);
 
+/* ------------------------------------------------------------------ truncated sampling: top-k, top-p (nucleus), min-p
+ * For one row, y[n] = bf16_round(logit[n] / T), T > 0 - the value the sampling keys and the log-probabilities above use.  A CLASS is the
+ * set of columns that share one value of y (-0 == +0; at most 65 536 classes).  Every filter keeps or drops whole classes, so a tie is
+ * never split, and the kept set is always "every column whose y is at or above a cutoff value":
+ *   top_k (int, 0 = off): every class at or above the k-th largest value of the row - ties with the k-th value are kept (the rule of
+ *     HF's TopKLogitsWarper), so n_kept >= min(k, V);
+ *   top_p (float in (0, 1], 1 = off): applies to what top_k kept, whose mass is Z_k: the smallest set of highest classes whose mass
+ *     reaches top_p * Z_k.  The mass of a class is count * expf(y - M), M the row maximum (the top class weighs count * 1 whatever
+ *     its value), accumulated over the classes in descending order in fp64;
+ *   min_p (float in [0, 1), 0 = off): the classes with y - M >= logf(min_p).
+ * The cutoff is the highest of the three, so the top class is always kept.  The token is the argmax over the kept columns of
+ * bf16_round(logit / T) + Gumbel noise, lowest column on equal keys - the noise of the lm_head sampling epilogue (argmax_partial with
+ * sample_temperature > 0), keyed by (seed, step, row, column), so where the untruncated pick is itself kept it IS the truncated pick.
+ * Consequences: a NaN logit ranks highest and wins, as in the untruncated sampler (the NaN columns are the kept set, cut_y is NaN);
+ * a row of -inf only is one class and behaves as the untruncated sampler does; top_k = 1 picks from the top class - greedy unless the
+ * maximum is tied; token log-probabilities keep their definition, that of the UNTRUNCATED softmax(y).  With all three filters off
+ * there is nothing to truncate: both entries return UMV_ERR_ARG (the untruncated sampler is umv_sample_bf16 / the sampling epilogue
+ * with umv_decode_step_end_argmax or _logprob), as they do for top_k < 0, top_p outside (0, 1], min_p outside [0, 1), T <= 0.
+ * The cutoff is found from integer class counts and fixed-order fp64 sums: a row's result does not depend on the batch it sits in.
+ *
+ * umv_sample_truncated_bf16: the stand-alone form over bf16 logits [M][V] (row stride ld elements), one workgroup per row.  step: device
+ * pointer to the step counter (NULL = 0), as umv_sample_bf16's.  cut_y (fp32 [M], may be NULL) receives the cutoff value, n_kept
+ * (int32 [M], may be NULL) the number of kept columns. */
+int umv_sample_truncated_bf16(const uint16_t* logits, int64_t ld, int64_t* out_ids, int M, int V, float temperature, uint64_t seed,
+                              const int64_t* step, int top_k, float top_p, float min_p, float* cut_y, int32_t* n_kept,
+                              umv_stream_t stream);
+/* The step end of a truncated sampling step: umv_decode_step_end_logprob's arguments, bookkeeping and per-sample step counters, after
+ * an lm_head GEMM that sampled with (temperature, seed, step_idx) into argmax_partial.  Per sample it finds the cutoff from the stored
+ * logits, keeps the untruncated pick of argmax_partial if y[pick] >= cutoff, and takes the Gumbel maximum over the kept columns with
+ * regenerated noise otherwise.  logprob and lse_partial may be NULL together (no log-probabilities).  cut_y (fp32 [max_len][B]) and
+ * n_kept (int32 [max_len][B]) receive row s like logprob; either may be NULL. */
+int umv_decode_step_end_truncated(int32_t* tok_slot, int32_t* tok_pos, int32_t* kv_len, const uint64_t* argmax_partial,
+                                  const float* lse_partial, int n_tiles, int64_t* ids, int64_t* in_ids, int64_t* pred_ids,
+                                  int64_t* step_idx, const uint16_t* logits, int64_t ldo, int V, float temperature,
+                                  const int64_t* forced_ids, float* logprob, int B, int max_len, uint64_t seed, int top_k, float top_p,
+                                  float min_p, float* cut_y, int32_t* n_kept, umv_stream_t stream);
+
 
 /* TimestepEmbedder.timestep_embedding (modeling_utils.py:87-109): out[r] = bf16(cat(cos(t[r] * freqs), sin(t[r] * freqs))),
  * out [n, 2*half]; freqs [half] fp32 = exp(-ln(10000) * i / half) from the caller.  The two linears + SiLU of the embedder

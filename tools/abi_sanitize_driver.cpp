@@ -173,6 +173,24 @@ static void bad_arguments() {
     EXPECT_ERR(umv_token_logprob_bf16(dummy16, 32, dummyl, dummyf, 1, 64, 0.f, nullptr));         // row stride below V
     EXPECT_ERR(umv_token_logprob_bf16(dummy16, 64, dummyl, dummyf, 1, 64, -1.f, nullptr));        // negative temperature
     EXPECT_OK(umv_token_logprob_bf16(dummy16, 64, dummyl, dummyf, 0, 64, 0.f, nullptr));          // no rows
+    EXPECT_ERR(umv_sample_truncated_bf16(nullptr, 0, nullptr, 8, 152064, 1.0f, 1, nullptr, 50, 0.9f, 0.05f, nullptr, nullptr, nullptr));
+    EXPECT_ERR(umv_sample_truncated_bf16(dummy16, 64, dummyl, 1, 64, 0.0f, 1, nullptr, 50, 0.9f, 0.f, nullptr, nullptr, nullptr));   // temperature 0
+    EXPECT_ERR(umv_sample_truncated_bf16(dummy16, 64, dummyl, 1, 64, 1.0f, 1, nullptr, -1, 0.9f, 0.f, nullptr, nullptr, nullptr));   // top_k < 0
+    EXPECT_ERR(umv_sample_truncated_bf16(dummy16, 64, dummyl, 1, 64, 1.0f, 1, nullptr, 0, 0.0f, 0.f, dummyf, dummyi, nullptr));      // top_p = 0
+    EXPECT_ERR(umv_sample_truncated_bf16(dummy16, 64, dummyl, 1, 64, 1.0f, 1, nullptr, 0, 1.5f, 0.f, dummyf, dummyi, nullptr));      // top_p > 1
+    EXPECT_ERR(umv_sample_truncated_bf16(dummy16, 64, dummyl, 1, 64, 1.0f, 1, nullptr, 5, 1.0f, 1.0f, dummyf, dummyi, nullptr));     // min_p = 1
+    EXPECT_ERR(umv_sample_truncated_bf16(dummy16, 64, dummyl, 1, 64, 1.0f, 1, nullptr, 0, 1.0f, 0.f, dummyf, dummyi, nullptr));      // no filter on
+    EXPECT_OK(umv_sample_truncated_bf16(dummy16, 64, dummyl, 0, 64, 1.0f, 1, nullptr, 5, 0.9f, 0.1f, dummyf, dummyi, nullptr));      // no rows
+    EXPECT_ERR(umv_decode_step_end_truncated(nullptr, nullptr, nullptr, nullptr, nullptr, 9504, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                             152064, 152064, 1.f, nullptr, nullptr, 8, 16, 1, 50, 0.9f, 0.f, nullptr, nullptr, nullptr));
+    EXPECT_ERR(umv_decode_step_end_truncated(dummyi, dummyi, dummyi, (const uint64_t*)dummyl, nullptr, 4, dummyl, dummyl, dummyl, dummyl, dummy16,
+                                             64, 64, 1.f, nullptr, nullptr, 1, 16, 1, 0, 2.0f, 0.f, dummyf, dummyi, nullptr));   // top_p > 1
+    EXPECT_ERR(umv_decode_step_end_truncated(dummyi, dummyi, dummyi, (const uint64_t*)dummyl, nullptr, 4, dummyl, dummyl, dummyl, dummyl, dummy16,
+                                             64, 64, 1.f, nullptr, dummyf, 1, 16, 1, 5, 0.9f, 0.f, dummyf, dummyi, nullptr));    // logprob without lse_partial
+    EXPECT_ERR(umv_decode_step_end_truncated(dummyi, dummyi, dummyi, (const uint64_t*)dummyl, nullptr, 4, dummyl, dummyl, dummyl, dummyl, dummy16,
+                                             64, 64, 0.f, nullptr, nullptr, 1, 16, 1, 5, 0.9f, 0.f, dummyf, dummyi, nullptr));   // temperature 0
+    EXPECT_OK(umv_decode_step_end_truncated(dummyi, dummyi, dummyi, (const uint64_t*)dummyl, nullptr, 4, dummyl, dummyl, dummyl, dummyl, dummy16,
+                                            64, 64, 1.f, nullptr, nullptr, 0, 16, 1, 5, 0.9f, 0.f, dummyf, dummyi, nullptr));    // no samples
     EXPECT_ERR(umv_timestep_embed(nullptr, nullptr, nullptr, 4, 128, nullptr));
     EXPECT_ERR(umv_cfg_renorm_euler(nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 1, 4.0f, 1.5f, 0.f, 0, 0.1f, 64, nullptr));
     // VAE

@@ -310,7 +310,8 @@ class Bagel(BagelPrep):
     def generate_text(self, past_key_values: NaiveCache, packed_key_value_indexes=None, key_values_lens=None,
                       packed_start_tokens=None, packed_query_position_ids=None, max_length: int = 0,
                       do_sample: bool = False, temperature: float = 1.0, end_token_id: int = None,
-                      return_logits: bool = False, per_sample_eos: bool = False, return_logprobs: bool = False):
+                      return_logits: bool = False, per_sample_eos: bool = False, return_logprobs: bool = False,
+                      top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """Greedy decode (bagel.py:1236-1317).  Returns [steps, B] int64 whose row 0 holds the
         start tokens.  Like the reference, the batch stops when SAMPLE 0 emits end_token_id
         (bagel.py:1313); per_sample_eos=True is the batched extension (stops when every sample
@@ -318,7 +319,10 @@ class Bagel(BagelPrep):
         return_logprobs=True: returns (ids, logprobs) - or (ids, logits, logprobs) with return_logits - where logprobs is fp32
         [rows, B]: logprobs[s] is the log-probability of the token step s picked, ids[s + 1] where that row exists (of
         softmax(logits) in greedy decoding, of softmax(bf16(logits / temperature)) with do_sample).  Needs B <= 64; the step stays
-        in the captured graph."""
+        in the captured graph.
+        top_k / top_p / min_p (0 / 1.0 / 0.0 = off; with do_sample): truncated sampling as include/unimedvl_hip.h defines it, in the
+        captured step (DecodeSession); B <= 64.  The log-probabilities stay those of the untruncated softmax."""
+        top_k, top_p, min_p = ops.check_truncation(top_k, top_p, min_p)
         # do_sample: softmax(logits / temperature) + multinomial on the device (bagel.py:1297-1299).  The
         # draw is keyed by a seed derived from torch.initial_seed(), so torch.manual_seed(s) makes runs
         # reproducible; the stream itself is not torch's (no device can reproduce another's RNG).
@@ -335,7 +339,8 @@ class Bagel(BagelPrep):
             return res if len(res) > 1 else out
         sess = DecodeSession(self.language_model, past_key_values, packed_start_tokens, packed_query_position_ids,
                              max_length, use_graph=self.decode_use_graph and not return_logits,
-                             do_sample=do_sample, temperature=temperature, seed=seed, logprobs=return_logprobs)
+                             do_sample=do_sample, temperature=temperature, seed=seed, logprobs=return_logprobs,
+                             top_k=top_k, top_p=top_p, min_p=min_p)
         logits = []
         steps = 0
         stop = None
@@ -369,7 +374,8 @@ class Bagel(BagelPrep):
     @torch.no_grad()
     @ops.on_device
     def chat(self, tokenizer, new_token_ids, image_transform, images, prompt, max_length: int,
-             do_sample: bool = False, temperature: float = 1.0, return_logprobs: bool = False):
+             do_sample: bool = False, temperature: float = 1.0, return_logprobs: bool = False,
+             top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """ViT-only VQA convenience path (bagel.py:1321-1392).  return_logprobs=True: returns (answer, token_ids, token_logprobs) -
         the generated tokens behind the answer (the end token excluded) and the log-probability of each (generate_text)."""
         if self.chat_cache_tokens > 0:       # serving: one reserved cache reused by every request (stable slabs -> graph prefill)
@@ -389,7 +395,7 @@ class Bagel(BagelPrep):
         gi = self.prepare_start_tokens(newlens, new_rope, new_token_ids)
         ids = self.generate_text(past_key_values=cache, max_length=max_length, do_sample=do_sample,
                                  temperature=temperature, end_token_id=new_token_ids["eos_token_id"],
-                                 return_logprobs=return_logprobs, **gi)
+                                 return_logprobs=return_logprobs, top_k=top_k, top_p=top_p, min_p=min_p, **gi)
         if return_logprobs:
             ids, lp = ids
         output = tokenizer.decode(ids[:, 0].cpu())

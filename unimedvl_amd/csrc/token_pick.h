@@ -50,3 +50,15 @@ __device__ __forceinline__ float sample_uniform(uint64_t row_key, int n) {
     const uint64_t h = splitmix64(row_key + (uint64_t)n);
     return ((float)(h >> 41) + 0.5f) * (1.0f / 8388608.0f);
 }
+
+// Truncated sampling (include/unimedvl_hip.h, "truncated sampling"): a class is the set of columns that share one y = pick_value, a
+// bf16 value, so at most 65 536 of them.  class_key is the 16-bit order-preserving image of a bf16 value (a logit, or y) -
+// argmax_key's, on the upper half of the fp32 word: -0 == +0, every NaN is 0xFFFF, the highest - and class_value its inverse.
+__device__ __forceinline__ uint32_t class_key(float y) {
+    if (y != y) return 0xFFFFu;
+    const uint32_t b = __float_as_uint(y == 0.f ? 0.f : y) >> 16;
+    return (b & 0x8000u) ? (~b & 0xFFFFu) : (b | 0x8000u);
+}
+__device__ __forceinline__ float class_value(uint32_t key) {
+    return __uint_as_float(((key & 0x8000u) ? (key ^ 0x8000u) : (~key & 0xFFFFu)) << 16);
+}

@@ -31,22 +31,26 @@ BF16 = torch.bfloat16
 
 class DecodeSession:
     def __init__(self, llm, cache: NaiveCache, start_tokens, positions, max_length, use_graph=True, nsplit=None,
-                 do_sample=False, temperature=1.0, seed=0, logprobs=False, forced_ids=None):
+                 do_sample=False, temperature=1.0, seed=0, logprobs=False, forced_ids=None, top_k=0, top_p=1.0, min_p=0.0):
         """logprobs: also record pred_logprobs (fp32 [max_length, B]) - row s is the log-probability of in_ids[s + 1], the token step s
         picked (include/unimedvl_hip.h, token log-probabilities: of softmax(logits) in greedy decoding, of softmax(bf16(logits / T))
         when sampling).  forced_ids (int64 [max_length, B]): where an entry is >= 0 that token is fed to the next step instead of the
         pick - pred_ids still records the pick, pred_logprobs the forced token's value; negative = free-running.  Implies logprobs.
-        Both ride on the fused step end: B <= 64 and UMV_DECODE_FUSED_ARGMAX not 0, ValueError otherwise."""
+        Both ride on the fused step end: B <= 64 and UMV_DECODE_FUSED_ARGMAX not 0, ValueError otherwise.
+        top_k / top_p / min_p (0 / 1.0 / 0.0 = off): truncated sampling (include/unimedvl_hip.h) - they need do_sample and, like
+        logprobs, the fused step end.  With one on, the step ends with umv_decode_step_end_truncated - still two launches after the last
+        norm, still one graph - and pred_cut_y (fp32) / pred_n_kept (int32), both [max_length, B], record each step's cutoff value and
+        kept-column count.  pred_logprobs stay those of the untruncated softmax.  All off: today's step, launch for launch."""
         with ops.device_scope(llm.device):
             self._init(llm, cache, start_tokens, positions, max_length, use_graph, nsplit, do_sample, temperature, seed, logprobs,
-                       forced_ids)
+                       forced_ids, top_k, top_p, min_p)
 
     @property
     def device(self):
         return self.dev
 
     def _init(self, llm, cache, start_tokens, positions, max_length, use_graph, nsplit, do_sample, temperature, seed, logprobs=False,
-              forced_ids=None):
+              forced_ids=None, top_k=0, top_p=1.0, min_p=0.0):
         cfg, dev = llm.cfg, llm.device
         self.llm, self.cache, self.cfg, self.dev = llm, cache, cfg, dev
         B = len(cache.lens)
@@ -126,6 +130,20 @@ class DecodeSession:
                 self.forced_ids = f.to(dev).contiguous()
             self.lse_part = torch.zeros((B, (cfg.vocab + 15) // 16, 2), dtype=torch.float32, device=dev)
             self.pred_logprobs = torch.zeros((max_length, B), dtype=torch.float32, device=dev)
+        # truncated sampling: the lm_head call stays the sampling call; the step end finds the cutoff from the logits it stored
+        self.top_k, self.top_p, self.min_p = ops.check_truncation(top_k, top_p, min_p)
+        self.truncated = self.top_k > 0 or self.top_p < 1.0 or self.min_p > 0.0
+        self.pred_cut_y = self.pred_n_kept = None
+        if self.truncated:
+            if not do_sample:
+                raise ValueError("top_k / top_p / min_p truncate the sampler: they need do_sample=True")
+            if float(temperature) <= 0.0:
+                raise ValueError(f"truncated sampling needs temperature > 0 (got {temperature})")
+            if not self.fused_argmax:
+                raise ValueError("top_k / top_p / min_p ride on the fused step end: at most 64 samples and UMV_DECODE_FUSED_ARGMAX not 0 "
+                                 f"(got B={B}, UMV_DECODE_FUSED_ARGMAX={os.environ.get('UMV_DECODE_FUSED_ARGMAX', '1')!r})")
+            self.pred_cut_y = torch.zeros((max_length, B), dtype=torch.float32, device=dev)
+            self.pred_n_kept = torch.zeros((max_length, B), dtype=torch.int32, device=dev)
         w = llm.w
         # K splits of the QKV / o / down GEMMs: "q,o,d" (1 = that GEMM is not split), "0" = none, "auto" by batch / weights.
         # Measured on MI355X (bench.py --batch B, ms per step), no split -> 3,4,4:
@@ -212,6 +230,16 @@ class DecodeSession:
             else:
                 ops.gemm(self.act, down_w, out=self.seq, residual=self.seq)
                 ops.rmsnorm(self.seq, nxt, cfg.rms_eps, out=dst)
+        if self.truncated:
+            ops.gemm(self.hn, w.lm_head, out=self.logits, argmax_partial=self.amax_part, lse_partial=self.lse_part,
+                     sample=(self.temperature, self.seed, self.step_idx))
+            # the fused step end whose pick is the epilogue's only if that column survived the filters (the kept set's Gumbel maximum
+            # otherwise), plus pred_cut_y[step] / pred_n_kept[step] - and pred_logprobs[step] when log-probabilities are on
+            ops.decode_step_end_truncated(self.tok_slot, self.tok_pos, self.kv_len, self.amax_part, self.ids, self.in_ids, self.pred_ids,
+                                          self.step_idx, self.logits, self.temperature, self.seed, self.top_k, self.top_p, self.min_p,
+                                          lse_partial=self.lse_part, logprobs=self.pred_logprobs, forced_ids=self.forced_ids,
+                                          cut_y=self.pred_cut_y, n_kept=self.pred_n_kept)
+            return
         if self.logprobs:
             ops.gemm(self.hn, w.lm_head, out=self.logits, argmax_partial=self.amax_part, lse_partial=self.lse_part,
                      sample=(self.temperature, self.seed, self.step_idx) if self.do_sample else None)

@@ -35,6 +35,10 @@ DEFAULT_CONFIG = {
     "enable_auto_bf16_conversion": True,
     "use_model_checkpoint": False,  # False = ema.safetensors, True = model.safetensors
     "offload_folder": "/tmp/bagel_offload",
+    # truncated sampling (not reference keys; off = the reference's full-softmax draw): Bagel.generate_text
+    "top_k": 0,
+    "top_p": 1.0,
+    "min_p": 0.0,
 }
 
 # codes/data/default.yaml vlm_sft.image_transform_args (read by eval/vlm/utils.py:486-502)
@@ -143,12 +147,16 @@ class VQAInferencer:
         gc.collect()
         self.show_gpu_memory()
 
-    def infer_single(self, image_path, prompt, temperature=None, max_new_tokens=None, do_sample=None, show_image=False):
+    def infer_single(self, image_path, prompt, temperature=None, max_new_tokens=None, do_sample=None, show_image=False,
+                     top_k=None, top_p=None, min_p=None):
         if not self.loaded:
             raise RuntimeError("Model not loaded, please call load_model() first")
         temperature = temperature if temperature is not None else self.config["temperature"]
         max_new_tokens = max_new_tokens if max_new_tokens is not None else self.config["max_new_tokens"]
         do_sample = do_sample if do_sample is not None else self.config["do_sample"]
+        top_k = top_k if top_k is not None else self.config.get("top_k", 0)
+        top_p = top_p if top_p is not None else self.config.get("top_p", 1.0)
+        min_p = min_p if min_p is not None else self.config.get("min_p", 0.0)
         if isinstance(image_path, Image.Image):
             input_image, image_path = image_path.convert("RGB"), None
         else:
@@ -163,7 +171,7 @@ class VQAInferencer:
         extra = {"return_logprobs": True} if want_lp else {}
         answer = self.model.chat(self.tokenizer, self.new_token_ids, self.image_transform, images=images,
                                  prompt=conversation, max_length=max_new_tokens, do_sample=do_sample,
-                                 temperature=temperature, **extra)
+                                 temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, **extra)
         if want_lp:
             answer, token_ids, token_logprobs = answer
         result = {"answer": answer, "input_image": input_image, "time": time.time() - start, "image_path": image_path,

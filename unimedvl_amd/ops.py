@@ -424,6 +424,41 @@ def sample(logits, temperature, seed, step=None, out=None):
     return out
 
 
+def check_truncation(top_k, top_p, min_p):
+    """The filters of truncated sampling as (int, float, float), ValueError outside their ranges (0 / 1.0 / 0.0 = off)."""
+    if isinstance(top_k, bool) or int(top_k) != top_k or top_k < 0:
+        raise ValueError(f"top_k must be an integer >= 0 (0 = off), got {top_k!r}")
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_p must be in (0, 1] (1.0 = off), got {top_p!r}")
+    if not 0.0 <= min_p < 1.0:
+        raise ValueError(f"min_p must be in [0, 1) (0.0 = off), got {min_p!r}")
+    return int(top_k), float(top_p), float(min_p)
+
+
+def sample_truncated(logits, temperature, seed, step=None, top_k=0, top_p=1.0, min_p=0.0, out=None, cut_y=None, n_kept=None):
+    """One draw per row from softmax(bf16(logits / temperature)) truncated by top-k / top-p / min-p (include/unimedvl_hip.h, truncated
+    sampling; at least one filter on) -> int64 [M].  Same noise as the lm_head sampling epilogue for the same (seed, step, row, column).
+    cut_y (fp32 [M]) / n_kept (int32 [M]), if given, receive the cutoff value and the number of kept columns."""
+    lib = _lib.load()
+    _req(logits, BF16, "logits")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise _lib.UmvError("sample_truncated: logits [M, V] with unit column stride")
+    M, V = logits.shape
+    out = torch.empty((M,), dtype=torch.int64, device=logits.device) if out is None else out
+    _req(out, torch.int64, "out")
+    for t, dt, name in ((cut_y, torch.float32, "cut_y"), (n_kept, torch.int32, "n_kept")):
+        if t is not None:
+            _req(t, dt, name)
+            if not (t.is_contiguous() and t.numel() == M):
+                raise _lib.UmvError(f"sample_truncated: {name} must be a contiguous [M] tensor")
+    if not (out.is_contiguous() and out.numel() == M):
+        raise _lib.UmvError("sample_truncated: out must be a contiguous int64 [M] tensor")
+    check(lib.umv_sample_truncated_bf16(_p(logits), logits.stride(0), _p(out), M, V, float(temperature), int(seed) & (2 ** 64 - 1), _p(step),
+                                        int(top_k), float(top_p), float(min_p), _p(cut_y), _p(n_kept), _stream()),
+          "umv_sample_truncated_bf16")
+    return out
+
+
 def cast_pad(x, Kp):
     lib = _lib.load()
     _req(x, torch.float32, "x")
@@ -698,6 +733,44 @@ def decode_step_end_logprob(tok_slot, tok_pos, kv_len, argmax_partial, lse_parti
                                           _p(ids), _p(in_ids), _p(pred_ids), _p(step_idx), _p(logits), logits.stride(0), logits.shape[1],
                                           float(temperature), _p(forced_ids), _p(logprobs), B, in_ids.shape[0], _stream()),
           "umv_decode_step_end_logprob")
+
+
+def decode_step_end_truncated(tok_slot, tok_pos, kv_len, argmax_partial, ids, in_ids, pred_ids, step_idx, logits, temperature, seed,
+                              top_k=0, top_p=1.0, min_p=0.0, lse_partial=None, logprobs=None, forced_ids=None, cut_y=None, n_kept=None):
+    """The step end of a truncated sampling step (include/unimedvl_hip.h): the pick is the lm_head sampling epilogue's (argmax_partial,
+    sampled at the same temperature, seed and step_idx) where that column survives top-k / top-p / min-p, the Gumbel maximum over the kept
+    columns under the same noise otherwise; then decode_step_end_logprob's bookkeeping.  lse_partial with logprobs, and forced_ids, as
+    there; cut_y (fp32) / n_kept (int32), both [max_len, B], receive row s."""
+    lib = _lib.load()
+    for t, name in ((argmax_partial, "argmax_partial"), (ids, "ids"), (in_ids, "in_ids"), (pred_ids, "pred_ids"), (step_idx, "step_idx")):
+        _req(t, torch.int64, name)
+    _req(logits, BF16, "logits")
+    B = ids.numel()
+    if step_idx.numel() < B:
+        raise _lib.UmvError(f"decode_step_end_truncated: step_idx holds {step_idx.numel()} counters for {B} samples")
+    if not (in_ids.is_contiguous() and pred_ids.is_contiguous() and in_ids.shape == pred_ids.shape and in_ids.shape[1] == B
+            and argmax_partial.is_contiguous() and argmax_partial.shape[0] == B):
+        raise _lib.UmvError("decode_step_end_truncated: in_ids / pred_ids [max_len, B], argmax_partial [B, n_tiles], all contiguous")
+    if (lse_partial is None) != (logprobs is None):
+        raise _lib.UmvError("decode_step_end_truncated: lse_partial and logprobs go together")
+    if lse_partial is not None:
+        _req(lse_partial, torch.float32, "lse_partial")
+        if not (lse_partial.is_contiguous() and tuple(lse_partial.shape) == tuple(argmax_partial.shape) + (2,)):
+            raise _lib.UmvError("decode_step_end_truncated: lse_partial must be a contiguous [B, n_tiles, 2] tensor")
+    for t, dt, name in ((logprobs, torch.float32, "logprobs"), (forced_ids, torch.int64, "forced_ids"), (cut_y, torch.float32, "cut_y"),
+                        (n_kept, torch.int32, "n_kept")):
+        if t is not None:
+            _req(t, dt, name)
+            if not (t.is_contiguous() and t.shape == in_ids.shape):
+                raise _lib.UmvError(f"decode_step_end_truncated: {name} must be a contiguous [max_len, B] tensor")
+    if logits.dim() != 2 or logits.shape[0] < B or logits.stride(1) != 1:
+        raise _lib.UmvError("decode_step_end_truncated: logits must be [B, V] with unit column stride")
+    check(lib.umv_decode_step_end_truncated(_p(tok_slot), _p(tok_pos), _p(kv_len), _p(argmax_partial), _p(lse_partial), argmax_partial.shape[1],
+                                            _p(ids), _p(in_ids), _p(pred_ids), _p(step_idx), _p(logits), logits.stride(0), logits.shape[1],
+                                            float(temperature), _p(forced_ids), _p(logprobs), B, in_ids.shape[0],
+                                            int(seed) & (2 ** 64 - 1), int(top_k), float(top_p), float(min_p), _p(cut_y), _p(n_kept),
+                                            _stream()),
+          "umv_decode_step_end_truncated")
 
 
 def token_logprob(logits, ids, temperature=0.0, out=None):

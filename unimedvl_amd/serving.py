@@ -44,7 +44,7 @@ class ContinuousBatcher:
     def __init__(self, model, tokenizer, new_token_ids, image_transform, slots: int = 8, max_context: int = 2048,
                  max_new_tokens: int = 256, check_every: int = 16, do_sample: bool = False, temperature: float = 1.0,
                  use_graph: bool = True, growable: bool = True, context_limit: Optional[int] = None, paged: bool = False,
-                 pool_pages: Optional[int] = None, logprobs: bool = False):
+                 pool_pages: Optional[int] = None, logprobs: bool = False, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """max_context: the context (prompt + images) the slots are RESERVED for; with growable=True longer requests enlarge
         the cache (up to context_limit tokens of context when given), with growable=False they are refused.
         paged=True: block-table KV (kvcache.PagedCache) instead of slabs - the slots draw 256-token pages from ONE pool of `pool_pages`
@@ -52,7 +52,11 @@ class ContinuousBatcher:
         up to context_limit (default 32 768) is admitted without re-allocating or re-capturing anything, and a finished request returns
         its pages.  Same answers as the slab cache (tests/test_paged_kv_gpu.py).
         logprobs=True: self.logprobs[rid] holds one float per emitted token of the request - the token's log-probability as
-        DecodeSession(logprobs=True) records it - cut at EOS or the budget exactly as the tokens are.  Needs slots <= 64."""
+        DecodeSession(logprobs=True) records it - cut at EOS or the budget exactly as the tokens are.  Needs slots <= 64.
+        top_k / top_p / min_p: truncated sampling (DecodeSession), batcher-wide like temperature; they need do_sample and slots <= 64."""
+        self.top_k, self.top_p, self.min_p = ops.check_truncation(top_k, top_p, min_p)
+        if (self.top_k > 0 or self.top_p < 1.0 or self.min_p > 0.0) and not do_sample:
+            raise ValueError("top_k / top_p / min_p truncate the sampler: they need do_sample=True")
         self.model, self.tokenizer, self.new_token_ids, self.image_transform = model, tokenizer, new_token_ids, image_transform
         self.device = model.device
         self.slots, self.check_every = int(slots), int(check_every)
@@ -112,7 +116,8 @@ class ContinuousBatcher:
             pos = torch.tensor([s[2] for s in state], dtype=torch.int64)
             lens_now = list(cache.lens)
             sn = DecodeSession(m.language_model, cache, start, pos, self.check_every, use_graph=self.use_graph,
-                               do_sample=self.do_sample, temperature=self.temperature, seed=seed, logprobs=self.want_logprobs)
+                               do_sample=self.do_sample, temperature=self.temperature, seed=seed, logprobs=self.want_logprobs,
+                               top_k=self.top_k, top_p=self.top_p, min_p=self.min_p)
             cache.lens = lens_now                       # the session only reads them; this loop owns the bookkeeping
             self._grew = False
             return sn
