@@ -12,6 +12,7 @@ stand-alone, session, forced session and generate_text alike; |logprob| up to ~1
 import functools
 import math
 
+import numpy as np
 import pytest
 import torch
 
@@ -247,6 +248,56 @@ def test_forced_tokens_kernel(temp):
     for k in ("in_ids", "pred", "lp"):
         assert torch.equal(before[k], b[k])
     assert torch.equal(b["ids"], pick) and torch.equal(b["slot"], before["slot"] + 1) and torch.equal(b["step"], before["step"] + 1)
+
+
+# ----------------------------------------------------------------------------- 5b. more tiles than one pass of the tile loops
+V_MANY, PEAKS = 65560, (5, 16 * 2048 + 3, 65555)
+
+
+@functools.lru_cache(maxsize=None)
+def _many_tiles(temp):
+    """4098 tiles: three passes of a 256-thread step end's walk over the keys (8 loads in flight: 2048 tiles a pass) and seventeen of
+    its walks over the statistics, the last of each partial.  x = e_r, so row r's logits are column r of the weight: N(0, 2^2) and one
+    logit 30 above the row maximum at PEAKS[r] - in tile 0, in the first tile of the second pass, in the last tile (8 columns)."""
+    ops = _ops()
+    Km, B, nt = 32, len(PEAKS), (V_MANY + 15) // 16
+    w = torch.zeros((V_MANY, Km))
+    w[:, :B] = torch.randn(V_MANY, B, generator=torch.Generator().manual_seed(V_MANY)) * 2
+    for r, c in enumerate(PEAKS):
+        w[c, r] = w[:, r].max() + 30
+    x = torch.zeros((B, Km), dtype=BF16, device="cuda")
+    x[torch.arange(B), torch.arange(B)] = 1.0
+    keys = torch.zeros((B, nt), dtype=torch.int64, device="cuda")
+    st = torch.full((B, nt, 2), 7.0, dtype=torch.float32, device="cuda")
+    out = torch.full((B, V_MANY), 3.0, dtype=BF16, device="cuda")
+    ops.gemm(x, ops.PackedLinear.from_weight(w.to(BF16).cuda()), out=out, argmax_partial=keys, lse_partial=st,
+             sample=(temp, SEED, None) if temp else None)
+    return out, keys, st
+
+
+def _key_ids(keys):
+    k = keys.cpu().numpy().view(np.uint64).max(axis=1)
+    return torch.from_numpy((np.uint64(0xFFFFFFFF) - (k & np.uint64(0xFFFFFFFF))).astype(np.int64))
+
+
+@pytest.mark.parametrize("temp", [0.0, T_SAMPLE])
+def test_more_tiles_than_one_pass(temp):
+    ops = _ops()
+    logits, keys, st = _many_tiles(temp)
+    B = len(PEAKS)
+    want_ids = _key_ids(keys)                             # the host-side maximum over the keys
+    if not temp:
+        assert want_ids.tolist() == list(PEAKS)
+    b = _finish(logits, keys, st, temp)
+    a = _step_bufs(B, 2)
+    ops.decode_step_end_argmax(a["slot"], a["pos"], a["kvl"], keys, a["ids"], a["in_ids"], a["pred"], a["step"])
+    assert torch.equal(a["ids"].cpu(), want_ids) and torch.equal(b["ids"].cpu(), want_ids)
+    for k in ("slot", "pos", "kvl", "in_ids", "pred", "step"):
+        assert torch.equal(a[k], b[k]), k
+    err = (b["lp"][0].double().cpu() - R.logprob(logits, b["ids"], temp)).abs().max().item()
+    print(f"{(V_MANY + 15) // 16} tiles T={temp}: largest |error| {err:.3g}")
+    assert err <= BOUND
+    assert (b["lp"][1] == 99.0).all()                     # only row s is written
 
 
 # ----------------------------------------------------------------------------- the engine, at the tiny configuration

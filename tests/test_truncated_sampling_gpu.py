@@ -24,6 +24,7 @@ BF16 = torch.bfloat16
 EPS = 2e-6
 T = 0.7
 SEED = 4321
+BOUND = 1e-4          # of a log-probability: the bound test_logprob_gpu.py derives
 COMBINED = dict(top_k=50, top_p=0.9, min_p=0.05)
 
 
@@ -298,6 +299,57 @@ def test_step_end_with_forced_tokens_and_logprobs():
         print(f"step {s}: largest |logprob error| {err:.3g}")
         assert err <= 1e-4
     assert (b["step"] == L).all()
+
+
+# ----------------------------------------------------------------------------- 8b. more tiles than one pass of the tile loops
+V_MANY, PEAKS = 65560, (5, 16 * 2048 + 3, 65555)
+
+
+@functools.lru_cache(maxsize=None)
+def _many_tiles():
+    """4098 tiles: two passes of the 512-thread step end's walk over the keys (8 loads in flight: 4096 tiles a pass) and nine of its
+    walks over the statistics, the last of each partial.  x = e_r, so row r's logits are column r of the weight: N(0, 2^2) and one
+    logit 30 above the row maximum at PEAKS[r] - in tile 0, in tile 2048, in the last tile (8 columns).  Sampled at step 0."""
+    ops = _ops()
+    K, B, nt = 32, len(PEAKS), (V_MANY + 15) // 16
+    w = torch.zeros((V_MANY, K))
+    w[:, :B] = torch.randn(V_MANY, B, generator=torch.Generator().manual_seed(V_MANY)) * 2
+    for r, c in enumerate(PEAKS):
+        w[c, r] = w[:, r].max() + 30
+    x = torch.zeros((B, K), dtype=BF16, device="cuda")
+    x[torch.arange(B), torch.arange(B)] = 1.0
+    keys = torch.zeros((B, nt), dtype=torch.int64, device="cuda")
+    st = torch.full((B, nt, 2), 7.0, dtype=torch.float32, device="cuda")
+    out = torch.full((B, V_MANY), 3.0, dtype=BF16, device="cuda")
+    ops.gemm(x, ops.PackedLinear.from_weight(w.to(BF16).cuda()), out=out, argmax_partial=keys, lse_partial=st,
+             sample=(T, SEED, torch.zeros(B, dtype=torch.int64, device="cuda")))
+    return out, keys, st
+
+
+@pytest.mark.parametrize("with_logprobs", [False, True])
+def test_more_tiles_than_one_pass(with_logprobs):
+    ops = _ops()
+    out, keys, st = _many_tiles()
+    B = len(PEAKS)
+    y = R.pick_value(out.cpu(), T)
+    for flt in (dict(top_k=V_MANY), dict(top_k=1)):
+        b = _step_bufs(B, 2)
+        lp = dict(lse_partial=st, logprobs=b["lp"]) if with_logprobs else {}
+        ops.decode_step_end_truncated(b["slot"], b["pos"], b["kvl"], keys, b["ids"], b["in_ids"], b["pred"], b["step"], out, T, SEED,
+                                      cut_y=b["cut"], n_kept=b["kept"], **lp, **flt)
+        ids = b["ids"].cpu()
+        if flt["top_k"] == 1:
+            assert ids.tolist() == list(PEAKS) and (b["kept"][0] == 1).all()
+            assert torch.equal(b["cut"][0].cpu(), y[torch.arange(B), torch.tensor(PEAKS)].float())
+        else:
+            assert torch.equal(ids, _key_ids(keys)), "nothing dropped: the maximum over the keys"
+        assert torch.equal(b["pred"][0].cpu(), ids) and torch.equal(b["in_ids"][1].cpu(), ids) and (b["step"] == 1).all()
+        if with_logprobs:
+            err = (b["lp"][0].double().cpu() - LR.logprob(out, b["ids"], T)).abs().max().item()
+            print(f"{flt}: largest |logprob error| {err:.3g}")
+            assert err <= BOUND and (b["lp"][1] == 99.0).all()
+        else:
+            assert (b["lp"] == 99.0).all()
 
 
 # ----------------------------------------------------------------------------- the engine, at the tiny configuration

@@ -2,6 +2,7 @@
 // exchange between the waves.  Every thread of the workgroup must call them.
 #pragma once
 #include "common.h"
+#include "token_pick.h"         // shfl_xor_u64
 
 // sum / max over the blockDim.x / 64 waves, in wave order; sm: one float per wave.  The leading barrier makes `sm` reusable
 // from one call to the next.
@@ -22,6 +23,26 @@ __device__ __forceinline__ float block_reduce_max(float v, float* sm) {
     float r = sm[0];
     for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r = fmaxf(r, sm[w]);
     return r;
+}
+
+// The point a sum of exponentials is taken about, given its maximum M: M itself, and 0 for a row of -inf only - every term is then
+// exp(-inf - 0) = 0, not exp(-inf + inf) = NaN.
+__device__ __forceinline__ float softmax_ref(float M) { return (M == -INFINITY) ? 0.f : M; }
+
+// The maximum of a 64-bit value (an argmax key, token_pick.h) over a workgroup of T threads: complete in every thread (ALL) or in
+// thread 0 only.  sm: one word per wave, not in use by anything before this call; an ALL caller that reuses it puts a barrier behind.
+template <int T, bool ALL>
+__device__ __forceinline__ uint64_t block_max_u64(uint64_t best, uint64_t* sm) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint64_t ob = shfl_xor_u64(best, o);
+        best = ob > best ? ob : best;
+    }
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (ALL || threadIdx.x == 0)
+        for (int w = ALL ? 0 : 1; w < T / 64; ++w) best = sm[w] > best ? sm[w] : best;
+    return best;
 }
 
 // The sum of a 256-thread workgroup as (p0 + p1) + (p2 + p3): the fixed order of the decode norms, whose results must not

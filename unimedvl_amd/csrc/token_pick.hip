@@ -1,9 +1,9 @@
 // Next-token picking and the bookkeeping that ends a decode step: argmax and temperature sampling over bf16 logits, the
-// step-end kernels (two of them finish the lm_head GEMM's argmax epilogue, one with the token's log-probability) and the stand-alone
-// token log-probability.
+// step-end kernels (three of them finish the lm_head GEMM's argmax epilogue: plain, with the token's log-probability, and with
+// top-k / top-p / min-p), the stand-alone token log-probability and the stand-alone truncated sampler.
 #include "block_reduce.h"
-#include "gemm_epilogue.h"      // epi_gumbel_value: the noise of the lm_head epilogue, regenerated by the truncated sampler
 #include "token_pick.h"
+#include "truncation.h"
 #include "../../include/unimedvl_hip.h"
 
 // ----------------------------------------------------------------------------- argmax (bf16 logits, lowest index wins)
@@ -133,120 +133,150 @@ extern "C" int umv_decode_step_end(int32_t* tok_slot, int32_t* tok_pos, int32_t*
     return UMV_OK;
 }
 
-// The maximum of a sample's n_tiles keys, complete in thread 0 of a 256-thread workgroup; sm: one word per wave.
-__device__ __forceinline__ uint64_t block_max_key(const uint64_t* __restrict__ row, int n_tiles, uint64_t* sm) {
+// ----------------------------------------------------------------------------- the fused step ends
+// One workgroup per sample finishes what the lm_head GEMM epilogue left per 16-column tile - the argmax keys (token_pick.h::argmax_key)
+// and, for log-probabilities, the softmax statistics (gemm_epilogue.h::epi_lse_tile) - then does decode_step_end_kernel's bookkeeping
+// for its sample.  The step counter is PER SAMPLE - step_idx[b], all equal, read at the top of each kernel - so that no workgroup
+// reads a word another workgroup of the same launch writes (rounds 2-3 shared step_idx[0] behind a relaxed ticket; correct on this
+// hardware, not by the memory model).  The pieces take the workgroup's thread count T as a template parameter.
+struct StepEnd {                 // what every fused step end reads and writes
+    int32_t *slot, *pos, *kv_len;
+    int64_t *ids, *in_ids, *pred_ids, *step_idx;
+    int B, max_len;
+};
+
+// A thread's share of the maximum of a sample's n_tiles keys.
+template <int T>
+__device__ __forceinline__ uint64_t strided_max_key(const uint64_t* __restrict__ row, int n_tiles) {
     uint64_t best = 0;
-    constexpr int UA = 8;      // all loads of a thread in flight together: one round trip for up to 2048 tiles per pass
-    for (int c0 = threadIdx.x; c0 < n_tiles; c0 += 256 * UA) {
+    constexpr int UA = 8;      // all loads of a thread in flight together: one round trip for up to 8 T tiles per pass
+    for (int c0 = threadIdx.x; c0 < n_tiles; c0 += T * UA) {
         uint64_t v[UA];
 #pragma unroll
         for (int u = 0; u < UA; ++u) {
-            const int c = c0 + u * 256;
+            const int c = c0 + u * T;
             v[u] = c < n_tiles ? row[c] : 0ull;
         }
 #pragma unroll
         for (int u = 0; u < UA; ++u) best = v[u] > best ? v[u] : best;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint64_t ob = shfl_xor_u64(best, o);
-        best = ob > best ? ob : best;
-    }
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = best;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < 4; ++w) best = sm[w] > best ? sm[w] : best;
     return best;
 }
 
-// Greedy pick + end of step in one launch: one workgroup per sample takes the maximum of the per-tile keys the lm_head GEMM
-// epilogue left (token_pick.h::argmax_key), then does decode_step_end_kernel's bookkeeping for its sample.  The step counter
-// is PER SAMPLE - step_idx[b], all equal - so that no workgroup reads a word another workgroup of the same launch writes
-// (rounds 2-3 shared step_idx[0] behind a relaxed ticket; correct on this hardware, not by the memory model).
-__global__ __launch_bounds__(256) void decode_step_end_argmax_kernel(int32_t* slot, int32_t* pos, int32_t* kv_len,
-                                                                     const uint64_t* __restrict__ part, int n_tiles, int64_t* ids,
-                                                                     int64_t* in_ids, int64_t* pred_ids, int64_t* step_idx,
-                                                                     int B, int max_len) {
+// The merge of a sample's per-tile softmax statistics (m_t, s_t) into (ref, S), in every thread: M = max m_t, ref = softmax_ref(M),
+// S = sum s_t exp(m_t - ref).  Two passes over the 8 n_tiles bytes (L2 resident: the GEMM has just written them), each thread-strided
+// by T, then the wave tree, then the waves in order (block_reduce.h) - a fixed order for a given T, so a sample's bits do not depend
+// on the batch it sits in.  A tile of -inf only is (-inf, 0) and adds 0 * exp(-inf) = 0; a NaN s_t makes S NaN.  smf: one float per wave.
+template <int T>
+__device__ __forceinline__ void merge_tile_stats(const umv_f32x2* __restrict__ st, int n_tiles, float* smf, float& ref, float& S) {
+    float M = -INFINITY;
+    for (int c = threadIdx.x; c < n_tiles; c += T) M = fmaxf(M, st[c].x);
+    M = block_reduce_max(M, smf);
+    ref = softmax_ref(M);
+    S = 0.f;
+    for (int c = threadIdx.x; c < n_tiles; c += T) {
+        const umv_f32x2 v = st[c];
+        S += v.y * expf(v.x - ref);
+    }
+    S = block_reduce_sum(S, smf);
+}
+
+// Thread 0's tail for sample b at step s, id the pick.  The token the next step is fed is the forced one where there is one inside
+// the vocabulary (a forced token outside it is never fed: the pick is, with a NaN log-probability).  Row s of lp.out / co.cut_y /
+// co.n_kept - each optional - takes that token's log-probability from the merged (ref, S) and the row's cutoff; then the bookkeeping
+// and the sample's own step counter.  (e by value: taken by reference, the truncated kernel came out with 36 bytes of scratch reserved.)
+struct StepLogprob {             // the sample's logits row of V columns, the temperature, the merged statistics; out: [max_len, B]
+    const bf16_t* row = nullptr;
+    int V = 0;
+    float temp = 0.f, ref = 0.f, S = 0.f;
+    float* out = nullptr;
+};
+struct StepCutoff {              // the row's cutoff value and kept-column count; cut_y / n_kept: [max_len, B]
+    float cut = 0.f;
+    uint32_t kept = 0u;
+    float* cut_y = nullptr;
+    int32_t* n_kept = nullptr;
+};
+__device__ __forceinline__ void step_end_finish(const StepEnd e, int b, int64_t s, int64_t id, const int64_t* __restrict__ forced = nullptr,
+                                                const StepLogprob lp = {}, const StepCutoff co = {}) {
+    const int64_t f = (forced && s < e.max_len) ? forced[s * e.B + b] : -1;
+    const int64_t next = (f >= 0 && f < lp.V) ? f : id;
+    e.ids[b] = next;
+    if (s < e.max_len) {
+        if (lp.out) lp.out[s * e.B + b] = f < lp.V ? logprob_finish(pick_value(bf2f(lp.row[next]), lp.temp), lp.ref, lp.S) : NAN;
+        if (co.cut_y) co.cut_y[s * e.B + b] = co.cut;
+        if (co.n_kept) co.n_kept[s * e.B + b] = (int32_t)co.kept;
+    }
+    step_end_sample(e.slot, e.pos, e.kv_len, e.in_ids, e.pred_ids, b, id, next, s, e.B, e.max_len);
+    e.step_idx[b] = s + 1;
+}
+
+// Greedy (or untruncated sampled) pick + end of step in one launch.
+__global__ __launch_bounds__(256) void decode_step_end_argmax_kernel(StepEnd e, const uint64_t* __restrict__ part, int n_tiles) {
     __shared__ uint64_t sm[4];
     const int b = blockIdx.x;
-    const int64_t s = step_idx[b];
-    const uint64_t best = block_max_key(part + (int64_t)b * n_tiles, n_tiles, sm);
-    if (threadIdx.x == 0) {
-        const int64_t id = argmax_key_column(best);
-        ids[b] = id;
-        step_end_sample(slot, pos, kv_len, in_ids, pred_ids, b, id, id, s, B, max_len);
-        step_idx[b] = s + 1;
-    }
+    const int64_t s = e.step_idx[b];
+    const uint64_t best = block_max_u64<256, false>(strided_max_key<256>(part + (int64_t)b * n_tiles, n_tiles), sm);
+    if (threadIdx.x == 0) step_end_finish(e, b, s, argmax_key_column(best));
 }
+
+// The same, plus the log-probability of the token the next step is fed - the pick, or the forced token
+// (include/unimedvl_hip.h, token log-probabilities).
+__global__ __launch_bounds__(256) void decode_step_end_logprob_kernel(StepEnd e, const uint64_t* __restrict__ part,
+                                                                      const float* __restrict__ lse, int n_tiles,
+                                                                      const bf16_t* __restrict__ logits, int64_t ldo, int V, float temp,
+                                                                      const int64_t* __restrict__ forced, float* logprob) {
+    __shared__ uint64_t sm[4];
+    __shared__ float smf[4];
+    const int b = blockIdx.x;
+    const int64_t s = e.step_idx[b];
+    const uint64_t best = block_max_u64<256, false>(strided_max_key<256>(part + (int64_t)b * n_tiles, n_tiles), sm);
+    float ref, S;
+    merge_tile_stats<256>(reinterpret_cast<const umv_f32x2*>(lse) + (int64_t)b * n_tiles, n_tiles, smf, ref, S);
+    if (threadIdx.x == 0) step_end_finish(e, b, s, argmax_key_column(best), forced, {logits + (int64_t)b * ldo, V, temp, ref, S, logprob});
+}
+
+// The host side the fused entries share.  rest: the entry's own required arguments.
+static int step_end_args_ok(const char* who, const StepEnd& e, const uint64_t* argmax_partial, int n_tiles, bool rest) {
+    UMV_CHECK(e.slot && e.pos && e.kv_len && argmax_partial && e.ids && e.in_ids && e.pred_ids && e.step_idx && rest && e.max_len > 0 &&
+                  n_tiles > 0,
+              UMV_ERR_ARG, "%s: bad args", who);
+    return UMV_OK;
+}
+static int tile_columns_ok(const char* who, int V, int n_tiles, int64_t ldo) {
+    UMV_CHECK(V > 0 && V <= n_tiles * 16 && V > (n_tiles - 1) * 16 && ldo >= V, UMV_ERR_ARG,
+              "%s: V (%d) must be the column count behind the %d tiles and ldo (%lld) >= V", who, V, n_tiles, (long long)ldo);
+    return UMV_OK;
+}
+
 extern "C" int umv_decode_step_end_argmax(int32_t* tok_slot, int32_t* tok_pos, int32_t* kv_len, const uint64_t* argmax_partial, int n_tiles,
                                           int64_t* ids, int64_t* in_ids, int64_t* pred_ids, int64_t* step_idx, int B,
                                           int max_len, umv_stream_t stream) {
-    UMV_CHECK(tok_slot && tok_pos && kv_len && argmax_partial && ids && in_ids && pred_ids && step_idx && max_len > 0 && n_tiles > 0,
-              UMV_ERR_ARG, "decode_step_end_argmax: bad args");
+    const StepEnd e{tok_slot, tok_pos, kv_len, ids, in_ids, pred_ids, step_idx, B, max_len};
+    if (int rc = step_end_args_ok("decode_step_end_argmax", e, argmax_partial, n_tiles, true)) return rc;
     if (B == 0) return UMV_OK;
-    hipLaunchKernelGGL(decode_step_end_argmax_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, tok_slot, tok_pos, kv_len, argmax_partial,
-                       n_tiles, ids, in_ids, pred_ids, step_idx, B, max_len);
+    hipLaunchKernelGGL(decode_step_end_argmax_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, e, argmax_partial, n_tiles);
+    UMV_LAUNCH_CHECK();
+    return UMV_OK;
+}
+
+extern "C" int umv_decode_step_end_logprob(int32_t* tok_slot, int32_t* tok_pos, int32_t* kv_len, const uint64_t* argmax_partial,
+                                           const float* lse_partial, int n_tiles, int64_t* ids, int64_t* in_ids, int64_t* pred_ids,
+                                           int64_t* step_idx, const uint16_t* logits, int64_t ldo, int V, float temperature,
+                                           const int64_t* forced_ids, float* logprob, int B, int max_len, umv_stream_t stream) {
+    const StepEnd e{tok_slot, tok_pos, kv_len, ids, in_ids, pred_ids, step_idx, B, max_len};
+    if (int rc = step_end_args_ok("decode_step_end_logprob", e, argmax_partial, n_tiles, lse_partial && logits && logprob)) return rc;
+    if (int rc = tile_columns_ok("decode_step_end_logprob", V, n_tiles, ldo)) return rc;
+    UMV_CHECK(temperature >= 0.f, UMV_ERR_ARG, "decode_step_end_logprob: temperature (%g) must be >= 0 (0 = greedy)", (double)temperature);
+    if (B == 0) return UMV_OK;
+    hipLaunchKernelGGL(decode_step_end_logprob_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, e, argmax_partial, lse_partial, n_tiles,
+                       logits, ldo, V, temperature, forced_ids, logprob);
     UMV_LAUNCH_CHECK();
     return UMV_OK;
 }
 
 // ----------------------------------------------------------------------------- token log-probabilities (include/unimedvl_hip.h)
-// decode_step_end_argmax_kernel that also merges the sample's per-tile softmax statistics (gemm_epilogue.h::epi_lse_tile) and
-// writes the log-probability of the token the next step is fed - the pick, or the forced token.  Two passes over the 8 n_tiles
-// bytes (L2 resident: the GEMM has just written them): M = max m_t, then S = sum s_t exp(m_t - M) about that maximum, each
-// thread-strided, then the wave tree, then waves 0..3 in order (block_reduce.h) - a fixed order, so a sample's bits do not depend
-// on the batch it sits in.  A tile of -inf only is (-inf, 0) and adds 0 * exp(-inf) = 0; a NaN s_t makes S NaN.
-__global__ __launch_bounds__(256) void decode_step_end_logprob_kernel(int32_t* slot, int32_t* pos, int32_t* kv_len,
-                                                                      const uint64_t* __restrict__ part, const float* __restrict__ lse,
-                                                                      int n_tiles, int64_t* ids, int64_t* in_ids, int64_t* pred_ids,
-                                                                      int64_t* step_idx, const bf16_t* __restrict__ logits, int64_t ldo, int V,
-                                                                      float temp, const int64_t* __restrict__ forced, float* logprob, int B,
-                                                                      int max_len) {
-    __shared__ uint64_t sm[4];
-    __shared__ float smf[4];
-    const int b = blockIdx.x;
-    const int64_t s = step_idx[b];
-    const uint64_t best = block_max_key(part + (int64_t)b * n_tiles, n_tiles, sm);
-    const umv_f32x2* st = reinterpret_cast<const umv_f32x2*>(lse) + (int64_t)b * n_tiles;
-    float M = -INFINITY;
-    for (int c = threadIdx.x; c < n_tiles; c += 256) M = fmaxf(M, st[c].x);
-    M = block_reduce_max(M, smf);
-    const float ref = (M == -INFINITY) ? 0.f : M;
-    float S = 0.f;
-    for (int c = threadIdx.x; c < n_tiles; c += 256) {
-        const umv_f32x2 v = st[c];
-        S += v.y * expf(v.x - ref);
-    }
-    S = block_reduce_sum(S, smf);
-    if (threadIdx.x == 0) {
-        const int64_t id = argmax_key_column(best);
-        const int64_t f = (forced && s < max_len) ? forced[s * B + b] : -1;
-        const int64_t next = (f >= 0 && f < V) ? f : id;      // a forced token outside the vocabulary is never fed: the pick is, with a NaN
-        ids[b] = next;
-        if (s < max_len)
-            logprob[s * B + b] = f < V ? logprob_finish(pick_value(bf2f(logits[(int64_t)b * ldo + next]), temp), ref, S) : NAN;
-        step_end_sample(slot, pos, kv_len, in_ids, pred_ids, b, id, next, s, B, max_len);
-        step_idx[b] = s + 1;
-    }
-}
-extern "C" int umv_decode_step_end_logprob(int32_t* tok_slot, int32_t* tok_pos, int32_t* kv_len, const uint64_t* argmax_partial,
-                                           const float* lse_partial, int n_tiles, int64_t* ids, int64_t* in_ids, int64_t* pred_ids,
-                                           int64_t* step_idx, const uint16_t* logits, int64_t ldo, int V, float temperature,
-                                           const int64_t* forced_ids, float* logprob, int B, int max_len, umv_stream_t stream) {
-    UMV_CHECK(tok_slot && tok_pos && kv_len && argmax_partial && lse_partial && ids && in_ids && pred_ids && step_idx && logits && logprob &&
-                  max_len > 0 && n_tiles > 0,
-              UMV_ERR_ARG, "decode_step_end_logprob: bad args");
-    UMV_CHECK(V > 0 && V <= n_tiles * 16 && V > (n_tiles - 1) * 16 && ldo >= V, UMV_ERR_ARG,
-              "decode_step_end_logprob: V (%d) must be the column count behind the %d tiles and ldo (%lld) >= V", V, n_tiles, (long long)ldo);
-    UMV_CHECK(temperature >= 0.f, UMV_ERR_ARG, "decode_step_end_logprob: temperature (%g) must be >= 0 (0 = greedy)", (double)temperature);
-    if (B == 0) return UMV_OK;
-    hipLaunchKernelGGL(decode_step_end_logprob_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, tok_slot, tok_pos, kv_len, argmax_partial,
-                       lse_partial, n_tiles, ids, in_ids, pred_ids, step_idx, logits, ldo, V, temperature, forced_ids, logprob, B, max_len);
-    UMV_LAUNCH_CHECK();
-    return UMV_OK;
-}
-
-// The stand-alone form: one workgroup per row of bf16 logits, the same definition from the logits themselves - the maximum of y
+// The stand-alone form: one workgroup per row of bf16 logits, the definition of merge_tile_stats from the logits themselves - the maximum of y
 // (exact), then the sum of exp(y - M) thread-strided in column order, the wave tree, the waves in order.
 __global__ __launch_bounds__(1024) void token_logprob_kernel(const bf16_t* __restrict__ logits, int64_t ld, const int64_t* __restrict__ ids,
                                                              float* __restrict__ out, int V, float temp) {
@@ -256,7 +286,7 @@ __global__ __launch_bounds__(1024) void token_logprob_kernel(const bf16_t* __res
     float M = -INFINITY;
     for (int i = threadIdx.x; i < V; i += blockDim.x) M = fmaxf(M, pick_value(bf2f(row[i]), temp));
     M = block_reduce_max(M, smf);
-    const float ref = (M == -INFINITY) ? 0.f : M;
+    const float ref = softmax_ref(M);
     float S = 0.f;
     for (int i = threadIdx.x; i < V; i += blockDim.x) S += expf(pick_value(bf2f(row[i]), temp) - ref);
     S = block_reduce_sum(S, smf);
@@ -276,326 +306,7 @@ extern "C" int umv_token_logprob_bf16(const uint16_t* logits, int64_t ld, const 
 }
 
 // ----------------------------------------------------------------------------- truncated sampling (include/unimedvl_hip.h)
-// top-k / top-p / min-p keep whole classes - the columns that share one y = bf16(logit / T) - at or above a cutoff class, so the
-// cutoff comes from a histogram of the row: integer counts from LDS atomics (the order of the threads cannot show), then a scan in
-// descending order - counts for top-k, count x expf(y - M) in fp64 for top-p.  The histogram is over the bf16 LOGITS, one bin per
-// value (token_pick.h::class_key of the logit): y is a non-decreasing function of the logit, so a class is a run of adjacent bins,
-// the sweeps over the row do no division, and logit / T is formed once per non-empty bin instead of once per column and sweep.
-// One workgroup of 512 threads per row holds 32 768 bins (128 KiB of LDS): the window of keys that ends at the row maximum, and
-// only where the answer needs it the window below (the two cover all 65 536 keys).  A thread owns 64 consecutive bins; it keeps the
-// upper window's counts in registers while the lower window takes the LDS (512 threads, not 1024: two waves per SIMD leave 256
-// registers each, and the 64 counts with the fp64 sums spilled at 128).  Every sum has a fixed order (the thread's bins in order,
-// the wave's Hillis-Steele scan, the waves in order), so a row's cutoff does not depend on the batch it sits in.
-constexpr int TR_THREADS = 512, TR_BINS = 32768, TR_PER = TR_BINS / TR_THREADS;
-
-struct TruncShared {
-    uint32_t whi[TR_THREADS / 64], wc[TR_THREADS / 64];      // per wave: highest key, scan totals
-    double wm[TR_THREADS / 64];
-    uint64_t wbest[TR_THREADS / 64];
-    double zk;                                    // mass of what top-k kept
-    uint32_t kk, kp, km;                          // the three cutoff classes, as class_key(y); 0 = the filter is off
-    uint32_t owner, floor_k, floor_cut, n_kept;   // first thread whose bins reach top_p; lowest bin of the top-k class / of the cutoff class
-    float smf[TR_THREADS / 64];
-};
-
-// f(column, logit) for every column of the row, 16-byte loads where the row's address allows; every thread of the workgroup calls it.
-// UA loads of a thread are in flight together.
-template <int UA = 8, class F>
-__device__ __forceinline__ void for_each_column(const bf16_t* __restrict__ row, int V, F f) {
-    const int nv = (reinterpret_cast<uintptr_t>(row) & 15) == 0 ? V / 8 : 0;
-    for (int c0 = threadIdx.x; c0 < nv; c0 += TR_THREADS * UA) {
-        bf16x8 v[UA];
-#pragma unroll
-        for (int u = 0; u < UA; ++u) {
-            const int c = c0 + u * TR_THREADS;
-            v[u] = c < nv ? ldg_frag(row + c * 8) : zero_frag();
-        }
-#pragma unroll
-        for (int u = 0; u < UA; ++u) {
-            const int c = c0 + u * TR_THREADS;
-            if (c < nv) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) f(c * 8 + j, bf2f((bf16_t)v[u][j]));
-            }
-        }
-    }
-    for (int i = nv * 8 + threadIdx.x; i < V; i += TR_THREADS) f(i, bf2f(row[i]));
-}
-
-// Histogram of the logit keys in (khi - TR_BINS, khi], bin = khi - key: thread t owns bins 64 t + j, the keys khi - 64 t - j in
-// descending order.  A bin below key 0 stays empty and is never weighed.
-template <int UA>
-__device__ __forceinline__ void window_histogram(uint32_t* hist, const bf16_t* __restrict__ row, int V, int khi) {
-    u32x4* h4 = reinterpret_cast<u32x4*>(hist);
-    for (int i = threadIdx.x; i < TR_BINS / 4; i += TR_THREADS) h4[i] = (u32x4){0u, 0u, 0u, 0u};
-    __syncthreads();
-    for_each_column<UA>(row, V, [&](int, float x) {
-        const uint32_t bin = (uint32_t)(khi - (int)class_key(x));
-        if (bin < (uint32_t)TR_BINS) atomicAdd(&hist[bin], 1u);
-    });
-    __syncthreads();
-}
-
-// What the bins of one row share: y of a bin and its softmax weight about the row maximum mx (mref: mx, 0 for a row of -inf only).
-// Every bin of the top class weighs 1 whatever mx is (inf - inf); expf, not the fast form: at most 65 536 evaluations per row.
-struct RowScale {
-    float temp, mx, mref;
-    __device__ __forceinline__ float y(uint32_t key) const { return pick_value(class_value(key), temp); }
-    __device__ __forceinline__ float weight(uint32_t key) const {
-        const float v = y(key);
-        return v == mx ? 1.f : expf(v - mref);
-    }
-};
-
-// body(j) for the thread's bins in order: unrolled where the counts sit in registers (REGS), a loop where they sit in LDS
-template <bool REGS, class F>
-__device__ __forceinline__ void for_each_bin(F body) {
-    if constexpr (REGS) {
-#pragma unroll
-        for (int j = 0; j < TR_PER; ++j) body(j);
-    } else {
-#pragma unroll 1
-        for (int j = 0; j < TR_PER; ++j) body(j);
-    }
-}
-// count(j): the columns of the thread's j-th bin (key k0 - j).  Their number and their mass, summed in the order of j.
-template <bool REGS, class C>
-__device__ __forceinline__ void thread_bins(C count, int k0, const RowScale& rs, uint32_t& lc, double& lm) {
-    lc = 0;
-    lm = 0.0;
-    for_each_bin<REGS>([&](int j) {
-        const uint32_t cj = count(j);
-        if (cj) {
-            lc += cj;
-            lm += (double)cj * (double)rs.weight((uint32_t)(k0 - j));
-        }
-    });
-}
-
-// Exclusive prefix (pc, pm) of (lc, lm) over the threads in order, and the totals (tc, tm), the same in every thread.
-__device__ __forceinline__ void block_scan(uint32_t lc, double lm, TruncShared& sh, uint32_t& pc, double& pm, uint32_t& tc, double& tm) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t ic = lc;
-    double im = lm;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t uc = __shfl_up(ic, o, 64);
-        const double um = __shfl_up(im, o, 64);
-        if (lane >= o) { ic += uc; im += um; }
-    }
-    double em = __shfl_up(im, 1, 64);
-    if (lane == 0) em = 0.0;
-    __syncthreads();                 // wc / wm of the previous scan have been read
-    if (lane == 63) { sh.wc[w] = ic; sh.wm[w] = im; }
-    __syncthreads();
-    uint32_t bc = 0;
-    double bm = 0.0;
-    tc = 0;
-    tm = 0.0;
-    for (int i = 0; i < TR_THREADS / 64; ++i) {
-        if (i == w) { bc = tc; bm = tm; }
-        tc += sh.wc[i];
-        tm += sh.wm[i];
-    }
-    pc = bc + (ic - lc);
-    pm = bm + em;
-}
-
-// The thread's first non-empty bin, in descending order, at which pred(key, columns so far, mass so far) holds - "so far" counts
-// the bin itself and everything above it in the row.  The mass at bin j is pm + (sum of the thread's bins 0..j in order), the sum
-// thread_bins formed, so the last bin of a thread stands at exactly pm + lm.
-template <bool REGS, class C, class P>
-__device__ __forceinline__ bool first_bin(C count, int k0, uint32_t pc, double pm, const RowScale& rs, P pred, uint32_t& key, uint32_t& cnt,
-                                          double& mass) {
-    bool found = false;
-    uint32_t n = pc;
-    double s = 0.0;
-    for_each_bin<REGS>([&](int j) {
-        const uint32_t cj = count(j);
-        if (cj && !found) {
-            n += cj;
-            s += (double)cj * (double)rs.weight((uint32_t)(k0 - j));
-            if (pred((uint32_t)(k0 - j), n, pm + s)) { found = true; key = (uint32_t)(k0 - j); cnt = n; mass = pm + s; }
-        }
-    });
-    return found;
-}
-
-// The cutoff of a row, in every thread: cut_y its value, floor_key the lowest logit key of the kept set (a column is kept iff
-// class_key(logit) >= floor_key), n_kept the number of kept columns.  hist: TR_BINS words of LDS.
-__device__ __forceinline__ void truncation_cutoff(const bf16_t* __restrict__ row, int V, float temp, int top_k, float top_p, float min_p,
-                                                  uint32_t* hist, TruncShared& sh, float& cut_y, uint32_t& floor_key, uint32_t& n_kept) {
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    // the highest logit of the row
-    uint32_t khi = 0u;
-    for_each_column(row, V, [&](int, float x) {
-        const uint32_t k = class_key(x);
-        khi = k > khi ? k : khi;
-    });
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t b = __shfl_xor(khi, o, 64);
-        khi = b > khi ? b : khi;
-    }
-    if (lane == 0) sh.whi[w] = khi;
-    if (t == 0) {
-        sh.kk = 0u; sh.kp = 0u; sh.km = 0xFFFFu; sh.owner = 0xFFFFFFFFu; sh.floor_k = 0xFFFFu; sh.floor_cut = 0xFFFFu; sh.n_kept = 0u; sh.zk = 0.0;
-    }
-    __syncthreads();
-    for (int i = 0; i < TR_THREADS / 64; ++i) khi = sh.whi[i] > khi ? sh.whi[i] : khi;
-    const uint32_t kmax = khi;
-    RowScale rs;
-    rs.temp = temp;
-    rs.mx = rs.y(kmax);
-    rs.mref = (rs.mx == -INFINITY) ? 0.f : rs.mx;
-
-    // the upper window, kept in registers
-    uint32_t c1[TR_PER], lc1, pc1, C1;
-    double lm1, pm1, Z1;
-    const int k01 = (int)kmax - t * TR_PER;
-    window_histogram<8>(hist, row, V, (int)kmax);
-#pragma unroll
-    for (int q = 0; q < TR_PER / 4; ++q) {
-        const u32x4 v = reinterpret_cast<const u32x4*>(hist)[t * (TR_PER / 4) + q];
-        c1[4 * q] = v.x; c1[4 * q + 1] = v.y; c1[4 * q + 2] = v.z; c1[4 * q + 3] = v.w;
-    }
-    thread_bins<true>([&](int j) { return c1[j]; }, k01, rs, lc1, lm1);
-    block_scan(lc1, lm1, sh, pc1, pm1, C1, Z1);
-    uint32_t key = 0, cnt = 0;
-    double mass = 0.0;
-    // top-k that ends in the upper window: the class of the bin that holds the k-th largest value
-    const bool k_upper = top_k > 0 && C1 >= (uint32_t)top_k;
-    if (k_upper) {
-        const uint32_t k = (uint32_t)top_k;
-        if (lc1 && pc1 < k && k <= pc1 + lc1 &&
-            first_bin<true>([&](int j) { return c1[j]; }, k01, pc1, pm1, rs, [&](uint32_t, uint32_t n, double) { return n >= k; }, key, cnt, mass))
-            sh.kk = class_key(rs.y(key));
-        __syncthreads();
-    }
-    // the lower window: only if the row reaches into it, and not if the top-k class ends above it (then every cutoff does): y of the
-    // upper window's lowest key is already below that class
-    const int khi0 = (int)kmax - TR_BINS, k00 = khi0 - t * TR_PER;
-    const bool lower = C1 < (uint32_t)V && !(k_upper && class_key(rs.y((uint32_t)(khi0 + 1))) < sh.kk);
-    uint32_t lc0 = 0, pc0 = 0, C0 = 0;
-    double lm0 = 0.0, pm0 = 0.0, Z0 = 0.0;
-    if (lower) {
-        window_histogram<4>(hist, row, V, khi0);          // these bins stay in LDS; fewer loads in flight: c1 holds 64 registers
-        thread_bins<false>([&](int j) { return hist[t * TR_PER + j]; }, k00, rs, lc0, lm0);
-        block_scan(lc0, lm0, sh, pc0, pm0, C0, Z0);
-        pc0 += C1;
-        pm0 = Z1 + pm0;
-    }
-    const uint32_t C = C1 + C0;
-    const double Z = Z1 + Z0;
-    // first_bin over this thread's bins of the upper (win = 1) or the lower window
-    auto walk = [&](int win, auto pred, uint32_t& key, uint32_t& cnt, double& mass) {
-        if (win) return first_bin<true>([&](int j) { return c1[j]; }, k01, pc1, pm1, rs, pred, key, cnt, mass);
-        return first_bin<false>([&](int j) { return hist[t * TR_PER + j]; }, k00, pc0, pm0, rs, pred, key, cnt, mass);
-    };
-    // the lowest non-empty bin whose class is at or above the class ykey, into *slot (atomicMin): bins and classes descend together
-    auto class_floor = [&](uint32_t ykey, uint32_t* slot) {
-        uint32_t best = 0xFFFFFFFFu;
-#pragma unroll
-        for (int j = 0; j < TR_PER; ++j)
-            if (c1[j] && class_key(rs.y((uint32_t)(k01 - j))) >= ykey) best = (uint32_t)(k01 - j);
-        if (lower)
-            for (int j = 0; j < TR_PER; ++j)
-                if (hist[t * TR_PER + j] && class_key(rs.y((uint32_t)(k00 - j))) >= ykey) best = (uint32_t)(k00 - j);
-        if (best != 0xFFFFFFFFu) atomicMin(slot, best);
-    };
-    // the columns and the mass down to bin `key`, in the thread that owns it
-    auto at_bin = [&](uint32_t key, uint32_t& cnt, double& mass) {
-        const int b1 = (int)kmax - (int)key, b0 = khi0 - (int)key;
-        const int win = (b1 < TR_BINS && b1 / TR_PER == t) ? 1 : (lower && b0 >= 0 && b0 / TR_PER == t) ? 0 : -1;
-        uint32_t k2;
-        return win >= 0 && walk(win, [&](uint32_t k, uint32_t, double) { return k == key; }, k2, cnt, mass);
-    };
-    const bool nan_row = kmax == 0xFFFFu;
-
-    // top-k that ends in the lower window; Z_k = the mass down to the end of the top-k class.  Off, or k > V: everything, Z_k = Z.
-    const bool k_on = top_k > 0 && (uint32_t)top_k <= C;
-    if (k_on && !k_upper) {
-        const uint32_t k = (uint32_t)top_k;
-        if (lower && lc0 && pc0 < k && k <= pc0 + lc0 && walk(0, [&](uint32_t, uint32_t n, double) { return n >= k; }, key, cnt, mass))
-            sh.kk = class_key(rs.y(key));
-    } else if (!k_on && t == 0) {
-        sh.zk = Z;
-    }
-    // min-p: the lowest class with y - M >= ln(min_p)
-    if (min_p > 0.f) {
-        const float lnp = logf(min_p);
-        uint32_t best = 0xFFFFFFFFu;
-        auto keeps = [&](uint32_t kb) {
-            const float v = rs.y(kb);
-            return v == rs.mx || v - rs.mref >= lnp;
-        };
-#pragma unroll
-        for (int j = 0; j < TR_PER; ++j)
-            if (c1[j] && keeps((uint32_t)(k01 - j))) best = (uint32_t)(k01 - j);
-        if (lower)
-            for (int j = 0; j < TR_PER; ++j)
-                if (hist[t * TR_PER + j] && keeps((uint32_t)(k00 - j))) best = (uint32_t)(k00 - j);
-        if (best != 0xFFFFFFFFu) atomicMin(&sh.km, class_key(rs.y(best)));
-    } else if (t == 0) {
-        sh.km = 0u;
-    }
-    __syncthreads();
-    if (k_on) {
-        class_floor(sh.kk, &sh.floor_k);
-        __syncthreads();
-        if (at_bin(sh.floor_k, cnt, mass)) sh.zk = mass;
-        __syncthreads();
-    }
-    // top-p: the class of the first bin, descending, at which the mass reaches top_p Z_k (the class whose end first reaches it).  The
-    // first THREAD whose last bin reaches it holds that bin.
-    if (top_p < 1.f) {
-        const double thr = (double)top_p * sh.zk;
-        if (lc1 && pm1 + lm1 >= thr) atomicMin(&sh.owner, (uint32_t)t);
-        else if (lower && lc0 && pm0 + lm0 >= thr) atomicMin(&sh.owner, (uint32_t)(TR_THREADS + t));
-        __syncthreads();
-        const uint32_t o = sh.owner;
-        if ((o == (uint32_t)t || o == (uint32_t)(TR_THREADS + t)) &&
-            walk(o < (uint32_t)TR_THREADS, [&](uint32_t, uint32_t, double m) { return m >= thr; }, key, cnt, mass))
-            sh.kp = class_key(rs.y(key));
-        __syncthreads();
-    }
-    // the cutoff is the highest of the three (0 = nothing is dropped; a NaN class takes all); the kept set ends with its class
-    uint32_t yc = sh.kk > sh.kp ? sh.kk : sh.kp;
-    yc = sh.km > yc ? sh.km : yc;
-    yc = nan_row ? 0xFFFFu : yc;
-    class_floor(yc, &sh.floor_cut);
-    __syncthreads();
-    const uint32_t fl = sh.floor_cut;
-    if (at_bin(fl, cnt, mass)) sh.n_kept = cnt;
-    __syncthreads();
-    cut_y = rs.y(fl);
-    floor_key = fl;
-    n_kept = sh.n_kept;
-}
-
-// The Gumbel maximum over the kept columns, with the noise of the lm_head epilogue (gemm_epilogue.h::epi_gumbel_value): complete in
-// thread 0.
-__device__ __forceinline__ uint64_t kept_gumbel_max(const bf16_t* __restrict__ row, int V, float temp, uint64_t row_key, uint32_t floor_key,
-                                                    TruncShared& sh) {
-    uint64_t best = 0;
-    for_each_column(row, V, [&](int n, float x) {
-        if (class_key(x) >= floor_key) {
-            const uint64_t k = argmax_key(epi_gumbel_value(x, temp, row_key, n), n);
-            best = k > best ? k : best;
-        }
-    });
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint64_t ob = shfl_xor_u64(best, o);
-        best = ob > best ? ob : best;
-    }
-    if ((threadIdx.x & 63) == 0) sh.wbest[threadIdx.x >> 6] = best;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < TR_THREADS / 64; ++w) best = sh.wbest[w] > best ? sh.wbest[w] : best;
-    return best;
-}
-
+// The cutoff of a row and the Gumbel maximum over what it keeps: truncation.h.
 __global__ __launch_bounds__(TR_THREADS) void sample_truncated_kernel(const bf16_t* __restrict__ logits, int64_t ld, int64_t* __restrict__ out,
                                                                       int V, float temp, uint64_t seed, const int64_t* __restrict__ step_ptr,
                                                                       int top_k, float top_p, float min_p, float* __restrict__ cut_y,
@@ -638,70 +349,28 @@ extern "C" int umv_sample_truncated_bf16(const uint16_t* logits, int64_t ld, int
 
 // The step end of a truncated sampling step: decode_step_end_logprob_kernel whose pick is the lm_head epilogue's only if that
 // column survived the filters - then the argmax over the kept set under the same noise IS that column - and the Gumbel maximum over
-// the kept columns otherwise.  The step counter is per sample, as there: sample b reads and writes step_idx[b] alone.
+// the kept columns otherwise.  A kernel of its own for the 128 KiB of LDS the cutoff takes.
 __global__ __launch_bounds__(TR_THREADS) void decode_step_end_truncated_kernel(
-    int32_t* slot, int32_t* pos, int32_t* kv_len, const uint64_t* __restrict__ part, const float* __restrict__ lse, int n_tiles, int64_t* ids,
-    int64_t* in_ids, int64_t* pred_ids, int64_t* step_idx, const bf16_t* __restrict__ logits, int64_t ldo, int V, float temp, uint64_t seed,
-    int top_k, float top_p, float min_p, const int64_t* __restrict__ forced, float* logprob, float* cut_y, int32_t* n_kept, int B, int max_len) {
+    StepEnd e, const uint64_t* __restrict__ part, const float* __restrict__ lse, int n_tiles, const bf16_t* __restrict__ logits, int64_t ldo,
+    int V, float temp, uint64_t seed, int top_k, float top_p, float min_p, const int64_t* __restrict__ forced, float* logprob, float* cut_y,
+    int32_t* n_kept) {
     __shared__ uint32_t hist[TR_BINS];
     __shared__ TruncShared sh;
     const int b = blockIdx.x;
-    const int64_t s = step_idx[b];
+    const int64_t s = e.step_idx[b];
     const bf16_t* row = logits + (int64_t)b * ldo;
     float cut;
     uint32_t floor_key, kept;
     truncation_cutoff(row, V, temp, top_k, top_p, min_p, hist, sh, cut, floor_key, kept);
-    // the untruncated pick: the maximum of the sample's per-tile keys
-    uint64_t best = 0;
-    constexpr int UK = 8;            // all loads of a thread in flight together, as in block_max_key
-    for (int c0 = threadIdx.x; c0 < n_tiles; c0 += TR_THREADS * UK) {
-        uint64_t v[UK];
-#pragma unroll
-        for (int u = 0; u < UK; ++u) {
-            const int c = c0 + u * TR_THREADS;
-            v[u] = c < n_tiles ? part[(int64_t)b * n_tiles + c] : 0ull;
-        }
-#pragma unroll
-        for (int u = 0; u < UK; ++u) best = v[u] > best ? v[u] : best;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint64_t ob = shfl_xor_u64(best, o);
-        best = ob > best ? ob : best;
-    }
-    if ((threadIdx.x & 63) == 0) sh.wbest[threadIdx.x >> 6] = best;
-    __syncthreads();
-    for (int w = 0; w < TR_THREADS / 64; ++w) best = sh.wbest[w] > best ? sh.wbest[w] : best;
+    // the untruncated pick: the maximum of the sample's per-tile keys, in every thread
+    uint64_t best = block_max_u64<TR_THREADS, true>(strided_max_key<TR_THREADS>(part + (int64_t)b * n_tiles, n_tiles), sh.wbest);
     const int64_t fused = argmax_key_column(best);
     const bool fused_kept = fused >= 0 && fused < V && class_key(bf2f(row[fused])) >= floor_key;     // the same in every thread
     __syncthreads();                 // wbest has been read
-    if (!fused_kept) best = kept_gumbel_max(row, V, temp, sample_row_key(seed, step_idx + b, b), floor_key, sh);
-    float mref = 0.f, S = 0.f;
-    if (logprob) {
-        const umv_f32x2* st = reinterpret_cast<const umv_f32x2*>(lse) + (int64_t)b * n_tiles;
-        float mx = -INFINITY;
-        for (int c = threadIdx.x; c < n_tiles; c += TR_THREADS) mx = fmaxf(mx, st[c].x);
-        mx = block_reduce_max(mx, sh.smf);
-        mref = (mx == -INFINITY) ? 0.f : mx;
-        for (int c = threadIdx.x; c < n_tiles; c += TR_THREADS) {
-            const umv_f32x2 v = st[c];
-            S += v.y * expf(v.x - mref);
-        }
-        S = block_reduce_sum(S, sh.smf);
-    }
-    if (threadIdx.x == 0) {
-        const int64_t id = argmax_key_column(best);
-        const int64_t f = (forced && s < max_len) ? forced[s * B + b] : -1;
-        const int64_t next = (f >= 0 && f < V) ? f : id;
-        ids[b] = next;
-        if (s < max_len) {
-            if (logprob) logprob[s * B + b] = f < V ? logprob_finish(pick_value(bf2f(row[next]), temp), mref, S) : NAN;
-            if (cut_y) cut_y[s * B + b] = cut;
-            if (n_kept) n_kept[s * B + b] = (int32_t)kept;
-        }
-        step_end_sample(slot, pos, kv_len, in_ids, pred_ids, b, id, next, s, B, max_len);
-        step_idx[b] = s + 1;
-    }
+    if (!fused_kept) best = kept_gumbel_max(row, V, temp, sample_row_key(seed, e.step_idx + b, b), floor_key, sh);
+    float ref = 0.f, S = 0.f;
+    if (logprob) merge_tile_stats<TR_THREADS>(reinterpret_cast<const umv_f32x2*>(lse) + (int64_t)b * n_tiles, n_tiles, sh.smf, ref, S);
+    if (threadIdx.x == 0) step_end_finish(e, b, s, argmax_key_column(best), forced, {row, V, temp, ref, S, logprob}, {cut, kept, cut_y, n_kept});
 }
 
 extern "C" int umv_decode_step_end_truncated(int32_t* tok_slot, int32_t* tok_pos, int32_t* kv_len, const uint64_t* argmax_partial,
@@ -709,18 +378,15 @@ extern "C" int umv_decode_step_end_truncated(int32_t* tok_slot, int32_t* tok_pos
                                              int64_t* step_idx, const uint16_t* logits, int64_t ldo, int V, float temperature,
                                              const int64_t* forced_ids, float* logprob, int B, int max_len, uint64_t seed, int top_k,
                                              float top_p, float min_p, float* cut_y, int32_t* n_kept, umv_stream_t stream) {
-    UMV_CHECK(tok_slot && tok_pos && kv_len && argmax_partial && ids && in_ids && pred_ids && step_idx && logits && max_len > 0 && n_tiles > 0 &&
-                  B >= 0,
-              UMV_ERR_ARG, "decode_step_end_truncated: bad args");
+    const StepEnd e{tok_slot, tok_pos, kv_len, ids, in_ids, pred_ids, step_idx, B, max_len};
+    if (int rc = step_end_args_ok("decode_step_end_truncated", e, argmax_partial, n_tiles, logits && B >= 0)) return rc;
     UMV_CHECK((logprob != nullptr) == (lse_partial != nullptr), UMV_ERR_ARG,
               "decode_step_end_truncated: logprob and lse_partial go together (both or neither)");
-    UMV_CHECK(V > 0 && V <= n_tiles * 16 && V > (n_tiles - 1) * 16 && ldo >= V, UMV_ERR_ARG,
-              "decode_step_end_truncated: V (%d) must be the column count behind the %d tiles and ldo (%lld) >= V", V, n_tiles, (long long)ldo);
+    if (int rc = tile_columns_ok("decode_step_end_truncated", V, n_tiles, ldo)) return rc;
     if (int rc = truncation_args_ok("decode_step_end_truncated", temperature, top_k, top_p, min_p)) return rc;
     if (B == 0) return UMV_OK;
-    hipLaunchKernelGGL(decode_step_end_truncated_kernel, dim3(B), dim3(TR_THREADS), 0, (hipStream_t)stream, tok_slot, tok_pos, kv_len,
-                       argmax_partial, lse_partial, n_tiles, ids, in_ids, pred_ids, step_idx, logits, ldo, V, temperature, seed, top_k, top_p,
-                       min_p, forced_ids, logprob, cut_y, n_kept, B, max_len);
+    hipLaunchKernelGGL(decode_step_end_truncated_kernel, dim3(B), dim3(TR_THREADS), 0, (hipStream_t)stream, e, argmax_partial, lse_partial,
+                       n_tiles, logits, ldo, V, temperature, seed, top_k, top_p, min_p, forced_ids, logprob, cut_y, n_kept);
     UMV_LAUNCH_CHECK();
     return UMV_OK;
 }

@@ -113,14 +113,17 @@ class DecodeSession:
         self.fused_argmax = B <= 64 and os.environ.get("UMV_DECODE_FUSED_ARGMAX", "1") not in ("0", "")
         if self.fused_argmax:
             self.amax_part = torch.zeros((B, (cfg.vocab + 15) // 16), dtype=torch.int64, device=dev)
+
+        def need_fused(what):
+            if not self.fused_argmax:
+                raise ValueError(f"{what} ride on the fused step end: at most 64 samples and UMV_DECODE_FUSED_ARGMAX not 0 "
+                                 f"(got B={B}, UMV_DECODE_FUSED_ARGMAX={os.environ.get('UMV_DECODE_FUSED_ARGMAX', '1')!r})")
         # token log-probabilities / forced tokens: the lm_head epilogue also leaves the softmax statistics of every tile, and the step
         # ends with umv_decode_step_end_logprob instead - same launch count, still one graph
         self.logprobs = bool(logprobs) or forced_ids is not None
         self.forced_ids = self.pred_logprobs = self.lse_part = None
         if self.logprobs:
-            if not self.fused_argmax:
-                raise ValueError("logprobs / forced_ids ride on the fused step end: at most 64 samples and UMV_DECODE_FUSED_ARGMAX not 0 "
-                                 f"(got B={B}, UMV_DECODE_FUSED_ARGMAX={os.environ.get('UMV_DECODE_FUSED_ARGMAX', '1')!r})")
+            need_fused("logprobs / forced_ids")
             if forced_ids is not None:
                 f = torch.as_tensor(forced_ids, dtype=torch.int64)
                 if tuple(f.shape) != (max_length, B):
@@ -139,9 +142,7 @@ class DecodeSession:
                 raise ValueError("top_k / top_p / min_p truncate the sampler: they need do_sample=True")
             if float(temperature) <= 0.0:
                 raise ValueError(f"truncated sampling needs temperature > 0 (got {temperature})")
-            if not self.fused_argmax:
-                raise ValueError("top_k / top_p / min_p ride on the fused step end: at most 64 samples and UMV_DECODE_FUSED_ARGMAX not 0 "
-                                 f"(got B={B}, UMV_DECODE_FUSED_ARGMAX={os.environ.get('UMV_DECODE_FUSED_ARGMAX', '1')!r})")
+            need_fused("top_k / top_p / min_p")
             self.pred_cut_y = torch.zeros((max_length, B), dtype=torch.float32, device=dev)
             self.pred_n_kept = torch.zeros((max_length, B), dtype=torch.int32, device=dev)
         w = llm.w
@@ -187,6 +188,16 @@ class DecodeSession:
         # QKV GEMM is not split: B = 8: 3.32 vs 3.39 ms without a split, 3.28 vs 3.24 with the default 3-way split, B = 32: 4.80 vs
         # 4.52; the default path splits, so the step always runs umv_qkv_post + umv_attn_varlen)
         self.do_sample, self.temperature, self.seed = bool(do_sample), float(temperature), int(seed)
+        # how the step ends, decided once: what the lm_head call leaves besides the logits, and the call that closes the step
+        self.lm_head_kw = {}
+        if self.fused_argmax:
+            self.lm_head_kw["argmax_partial"] = self.amax_part
+            if self.logprobs or self.truncated:
+                self.lm_head_kw["lse_partial"] = self.lse_part
+            self.lm_head_kw["sample"] = (self.temperature, self.seed, self.step_idx) if self.do_sample else None
+        # (a name, not a bound method: a session that refers to itself is freed by the cycle collector only - at any allocation, another
+        # session's graph capture included, where releasing device memory aborts)
+        self.step_end = "truncated" if self.truncated else "logprob" if self.logprobs else "argmax" if self.fused_argmax else "unfused"
         self.steps_done = 0
         self.graph = None
         if use_graph:
@@ -230,38 +241,30 @@ class DecodeSession:
             else:
                 ops.gemm(self.act, down_w, out=self.seq, residual=self.seq)
                 ops.rmsnorm(self.seq, nxt, cfg.rms_eps, out=dst)
-        if self.truncated:
-            ops.gemm(self.hn, w.lm_head, out=self.logits, argmax_partial=self.amax_part, lse_partial=self.lse_part,
-                     sample=(self.temperature, self.seed, self.step_idx))
+        ops.gemm(self.hn, w.lm_head, out=self.logits, **self.lm_head_kw)
+        if self.step_end == "truncated":
             # the fused step end whose pick is the epilogue's only if that column survived the filters (the kept set's Gumbel maximum
             # otherwise), plus pred_cut_y[step] / pred_n_kept[step] - and pred_logprobs[step] when log-probabilities are on
             ops.decode_step_end_truncated(self.tok_slot, self.tok_pos, self.kv_len, self.amax_part, self.ids, self.in_ids, self.pred_ids,
                                           self.step_idx, self.logits, self.temperature, self.seed, self.top_k, self.top_p, self.min_p,
                                           lse_partial=self.lse_part, logprobs=self.pred_logprobs, forced_ids=self.forced_ids,
                                           cut_y=self.pred_cut_y, n_kept=self.pred_n_kept)
-            return
-        if self.logprobs:
-            ops.gemm(self.hn, w.lm_head, out=self.logits, argmax_partial=self.amax_part, lse_partial=self.lse_part,
-                     sample=(self.temperature, self.seed, self.step_idx) if self.do_sample else None)
+        elif self.step_end == "logprob":
             # the fused step end below, plus pred_logprobs[step] = log-probability of the token fed next (the pick or the forced one)
             ops.decode_step_end_logprob(self.tok_slot, self.tok_pos, self.kv_len, self.amax_part, self.lse_part, self.ids, self.in_ids,
                                         self.pred_ids, self.step_idx, self.logits, self.pred_logprobs,
                                         self.temperature if self.do_sample else 0.0, self.forced_ids)
-            return
-        if self.fused_argmax:
-            ops.gemm(self.hn, w.lm_head, out=self.logits, argmax_partial=self.amax_part,
-                     sample=(self.temperature, self.seed, self.step_idx) if self.do_sample else None)
+        elif self.step_end == "argmax":
             # ids = argmax; pred_ids[step] = in_ids[step + 1] = ids; slot / position / kv_len / step += 1: one launch
             ops.decode_step_end_argmax(self.tok_slot, self.tok_pos, self.kv_len, self.amax_part, self.ids, self.in_ids, self.pred_ids,
                                        self.step_idx)
-            return
-        ops.gemm(self.hn, w.lm_head, out=self.logits)
-        if self.do_sample:
-            ops.sample(self.logits, self.temperature, self.seed, step=self.step_idx, out=self.ids)
         else:
-            ops.argmax(self.logits, out=self.ids)
-        # pred_ids[step] = in_ids[step + 1] = ids; slot / position / kv_len / step += 1: one launch
-        ops.decode_step_end(self.tok_slot, self.tok_pos, self.kv_len, self.ids, self.in_ids, self.pred_ids, self.step_idx)
+            if self.do_sample:
+                ops.sample(self.logits, self.temperature, self.seed, step=self.step_idx, out=self.ids)
+            else:
+                ops.argmax(self.logits, out=self.ids)
+            # pred_ids[step] = in_ids[step + 1] = ids; slot / position / kv_len / step += 1: one launch
+            ops.decode_step_end(self.tok_slot, self.tok_pos, self.kv_len, self.ids, self.in_ids, self.pred_ids, self.step_idx)
 
     def _capture(self):
         # the captured step appends at slot = lens0 and bumps the counters; warm up on a side

@@ -685,18 +685,39 @@ def decode_step_end(tok_slot, tok_pos, kv_len, ids, in_ids, pred_ids, step_idx):
                                   ids.numel(), in_ids.shape[0], _stream()), "umv_decode_step_end")
 
 
-def decode_step_end_argmax(tok_slot, tok_pos, kv_len, argmax_partial, ids, in_ids, pred_ids, step_idx):
-    """ids = argmax over the per-tile keys the lm_head GEMM left in argmax_partial, then decode_step_end's bookkeeping.
-    step_idx: one counter per sample ([B] int64, all equal)."""
-    lib = _lib.load()
+def _check_fused_step_end(who, argmax_partial, ids, in_ids, pred_ids, step_idx, lse_partial=None, logits=None, **rows):
+    """What the decode_step_end_* wrappers below check alike, under the wrapper's name: int64 keys / ids / counters, one counter per sample,
+    contiguous in_ids / pred_ids [max_len, B] and argmax_partial [B, n_tiles], lse_partial [B, n_tiles, 2] where there is one, the
+    optional [max_len, B] tensors in `rows` (name -> (tensor or None, dtype)) and bf16 logits [B, V].  Returns B."""
     for t, name in ((argmax_partial, "argmax_partial"), (ids, "ids"), (in_ids, "in_ids"), (pred_ids, "pred_ids"), (step_idx, "step_idx")):
         _req(t, torch.int64, name)
     B = ids.numel()
     if step_idx.numel() < B:
-        raise _lib.UmvError(f"decode_step_end_argmax: step_idx holds {step_idx.numel()} counters for {B} samples")
+        raise _lib.UmvError(f"{who}: step_idx holds {step_idx.numel()} counters for {B} samples")
     if not (in_ids.is_contiguous() and pred_ids.is_contiguous() and in_ids.shape == pred_ids.shape and in_ids.shape[1] == B
             and argmax_partial.is_contiguous() and argmax_partial.shape[0] == B):
-        raise _lib.UmvError("decode_step_end_argmax: in_ids / pred_ids [max_len, B], argmax_partial [B, n_tiles], all contiguous")
+        raise _lib.UmvError(f"{who}: in_ids / pred_ids [max_len, B], argmax_partial [B, n_tiles], all contiguous")
+    if lse_partial is not None:
+        _req(lse_partial, torch.float32, "lse_partial")
+        if not (lse_partial.is_contiguous() and tuple(lse_partial.shape) == tuple(argmax_partial.shape) + (2,)):
+            raise _lib.UmvError(f"{who}: lse_partial must be a contiguous [B, n_tiles, 2] tensor")
+    for name, (t, dt) in rows.items():
+        if t is not None:
+            _req(t, dt, name)
+            if not (t.is_contiguous() and t.shape == in_ids.shape):
+                raise _lib.UmvError(f"{who}: {name} must be a contiguous [max_len, B] tensor")
+    if logits is not None:
+        _req(logits, BF16, "logits")
+        if logits.dim() != 2 or logits.shape[0] < B or logits.stride(1) != 1:
+            raise _lib.UmvError(f"{who}: logits must be [B, V] with unit column stride")
+    return B
+
+
+def decode_step_end_argmax(tok_slot, tok_pos, kv_len, argmax_partial, ids, in_ids, pred_ids, step_idx):
+    """ids = argmax over the per-tile keys the lm_head GEMM left in argmax_partial, then decode_step_end's bookkeeping.
+    step_idx: one counter per sample ([B] int64, all equal)."""
+    lib = _lib.load()
+    B = _check_fused_step_end("decode_step_end_argmax", argmax_partial, ids, in_ids, pred_ids, step_idx)
     check(lib.umv_decode_step_end_argmax(_p(tok_slot), _p(tok_pos), _p(kv_len), _p(argmax_partial), argmax_partial.shape[1], _p(ids),
                                          _p(in_ids), _p(pred_ids), _p(step_idx), B, in_ids.shape[0], _stream()),
           "umv_decode_step_end_argmax")
@@ -709,26 +730,8 @@ def decode_step_end_logprob(tok_slot, tok_pos, kv_len, argmax_partial, lse_parti
     the one the GEMM sampled at, 0 = greedy.  forced_ids (int64 [max_len, B] or None): an entry >= 0 replaces the pick as ids /
     in_ids[s + 1] - and the log-probability is that token's - while pred_ids[s] keeps the model's own pick; negative = free-running."""
     lib = _lib.load()
-    for t, name in ((argmax_partial, "argmax_partial"), (ids, "ids"), (in_ids, "in_ids"), (pred_ids, "pred_ids"), (step_idx, "step_idx")):
-        _req(t, torch.int64, name)
-    _req(lse_partial, torch.float32, "lse_partial")
-    _req(logprobs, torch.float32, "logprobs")
-    _req(logits, BF16, "logits")
-    B = ids.numel()
-    if step_idx.numel() < B:
-        raise _lib.UmvError(f"decode_step_end_logprob: step_idx holds {step_idx.numel()} counters for {B} samples")
-    if not (in_ids.is_contiguous() and pred_ids.is_contiguous() and in_ids.shape == pred_ids.shape and in_ids.shape[1] == B
-            and argmax_partial.is_contiguous() and argmax_partial.shape[0] == B and lse_partial.is_contiguous()
-            and tuple(lse_partial.shape) == tuple(argmax_partial.shape) + (2,) and logprobs.is_contiguous()
-            and logprobs.shape == in_ids.shape):
-        raise _lib.UmvError("decode_step_end_logprob: in_ids / pred_ids / logprobs [max_len, B], argmax_partial [B, n_tiles], "
-                            "lse_partial [B, n_tiles, 2], all contiguous")
-    if logits.dim() != 2 or logits.shape[0] < B or logits.stride(1) != 1:
-        raise _lib.UmvError("decode_step_end_logprob: logits must be [B, V] with unit column stride")
-    if forced_ids is not None:
-        _req(forced_ids, torch.int64, "forced_ids")
-        if not (forced_ids.is_contiguous() and forced_ids.shape == in_ids.shape):
-            raise _lib.UmvError("decode_step_end_logprob: forced_ids must be a contiguous int64 [max_len, B] tensor")
+    B = _check_fused_step_end("decode_step_end_logprob", argmax_partial, ids, in_ids, pred_ids, step_idx, lse_partial, logits,
+                              logprobs=(logprobs, torch.float32), forced_ids=(forced_ids, torch.int64))
     check(lib.umv_decode_step_end_logprob(_p(tok_slot), _p(tok_pos), _p(kv_len), _p(argmax_partial), _p(lse_partial), argmax_partial.shape[1],
                                           _p(ids), _p(in_ids), _p(pred_ids), _p(step_idx), _p(logits), logits.stride(0), logits.shape[1],
                                           float(temperature), _p(forced_ids), _p(logprobs), B, in_ids.shape[0], _stream()),
@@ -742,29 +745,11 @@ def decode_step_end_truncated(tok_slot, tok_pos, kv_len, argmax_partial, ids, in
     columns under the same noise otherwise; then decode_step_end_logprob's bookkeeping.  lse_partial with logprobs, and forced_ids, as
     there; cut_y (fp32) / n_kept (int32), both [max_len, B], receive row s."""
     lib = _lib.load()
-    for t, name in ((argmax_partial, "argmax_partial"), (ids, "ids"), (in_ids, "in_ids"), (pred_ids, "pred_ids"), (step_idx, "step_idx")):
-        _req(t, torch.int64, name)
-    _req(logits, BF16, "logits")
-    B = ids.numel()
-    if step_idx.numel() < B:
-        raise _lib.UmvError(f"decode_step_end_truncated: step_idx holds {step_idx.numel()} counters for {B} samples")
-    if not (in_ids.is_contiguous() and pred_ids.is_contiguous() and in_ids.shape == pred_ids.shape and in_ids.shape[1] == B
-            and argmax_partial.is_contiguous() and argmax_partial.shape[0] == B):
-        raise _lib.UmvError("decode_step_end_truncated: in_ids / pred_ids [max_len, B], argmax_partial [B, n_tiles], all contiguous")
     if (lse_partial is None) != (logprobs is None):
         raise _lib.UmvError("decode_step_end_truncated: lse_partial and logprobs go together")
-    if lse_partial is not None:
-        _req(lse_partial, torch.float32, "lse_partial")
-        if not (lse_partial.is_contiguous() and tuple(lse_partial.shape) == tuple(argmax_partial.shape) + (2,)):
-            raise _lib.UmvError("decode_step_end_truncated: lse_partial must be a contiguous [B, n_tiles, 2] tensor")
-    for t, dt, name in ((logprobs, torch.float32, "logprobs"), (forced_ids, torch.int64, "forced_ids"), (cut_y, torch.float32, "cut_y"),
-                        (n_kept, torch.int32, "n_kept")):
-        if t is not None:
-            _req(t, dt, name)
-            if not (t.is_contiguous() and t.shape == in_ids.shape):
-                raise _lib.UmvError(f"decode_step_end_truncated: {name} must be a contiguous [max_len, B] tensor")
-    if logits.dim() != 2 or logits.shape[0] < B or logits.stride(1) != 1:
-        raise _lib.UmvError("decode_step_end_truncated: logits must be [B, V] with unit column stride")
+    B = _check_fused_step_end("decode_step_end_truncated", argmax_partial, ids, in_ids, pred_ids, step_idx, lse_partial, logits,
+                              logprobs=(logprobs, torch.float32), forced_ids=(forced_ids, torch.int64), cut_y=(cut_y, torch.float32),
+                              n_kept=(n_kept, torch.int32))
     check(lib.umv_decode_step_end_truncated(_p(tok_slot), _p(tok_pos), _p(kv_len), _p(argmax_partial), _p(lse_partial), argmax_partial.shape[1],
                                             _p(ids), _p(in_ids), _p(pred_ids), _p(step_idx), _p(logits), logits.stride(0), logits.shape[1],
                                             float(temperature), _p(forced_ids), _p(logprobs), B, in_ids.shape[0],
