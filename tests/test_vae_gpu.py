@@ -32,7 +32,12 @@ def rnd(shape, seed, scale=1.0):
                                                # the input-stationary kernel (conv3x3_patch_kernel: Cin % 64 == 0, stride 1), forced
                                                # by UMV_CONV_PATCH=2 below: ragged tiles, several 64-channel slices, Cout < / > 128
                                                (0, 64, 128, 16, 16), (0, 128, 64, 13, 9), (0, 192, 160, 37, 21), (0, 256, 256, 32, 48),
-                                               (1, 64, 64, 8, 8), (1, 128, 128, 9, 13), (1, 256, 128, 24, 24)])
+                                               (1, 64, 64, 8, 8), (1, 128, 128, 9, 13), (1, 256, 128, 24, 24),
+                                               # the gather kernel's other tiles and epilogue paths: the Cout <= 16 tile with the scalar
+                                               # epilogue (M = 800: a ragged last 256-row block); a channel group partly inside Cout; the
+                                               # packed epilogue with Cout % 16 != 0 (lanes with n0 >= Cout write nothing); 400 workgroups
+                                               # of the 128 x 128 x 64 tile (wg128 >= 384)
+                                               (0, 128, 3, 20, 20), (0, 64, 6, 9, 9), (0, 64, 36, 8, 8), (0, 8, 128, 160, 160)])
 def test_conv3x3(mode, cin, cout, h, w):
     from unimedvl_amd import _lib
     from unimedvl_amd.vae import _Conv, _stream
@@ -55,7 +60,8 @@ def test_conv3x3(mode, cin, cout, h, w):
     Ho, Wo = ref.shape[2], ref.shape[3]
     resn = None if res is None else res.permute(0, 2, 3, 1).contiguous().cuda()
     # mode | 32 = the gather kernel (conv_tiled_kernel), | 16 = the input-stationary kernel (conv3x3_patch_kernel), plain = the policy
-    variants = [mode, mode | 32] + ([mode | 16] if (mode in (0, 1) and cin % 64 == 0) else [])
+    # (| 16 is an error where the input-stationary kernel cannot run: it needs Cin % 64 == 0 and Cout % 4 == 0)
+    variants = [mode, mode | 32] + ([mode | 16] if (mode in (0, 1) and cin % 64 == 0 and cout % 4 == 0) else [])
     for mv in variants:
         out = torch.full((2, Ho, Wo, cout), float("nan"), dtype=BF16, device="cuda")
         _lib.check(lib.umv_conv2d_nhwc_bf16(xn.data_ptr(), c.lin.wp.data_ptr(), c.bias.data_ptr(),
@@ -64,6 +70,32 @@ def test_conv3x3(mode, cin, cout, h, w):
         got = out.cpu().permute(0, 3, 1, 2).float()
         err = (got - ref.float()).abs().max().item()
         assert err <= 2 ** -6 * max(1.0, ref.float().abs().max().item()), f"conv mode {mv}: max err {err}"
+
+
+@pytest.mark.parametrize("cin,cout,h,w,with_res", [(128, 256, 13, 9, False), (64, 64, 16, 16, True)])
+def test_conv1x1(cin, cout, h, w, with_res):
+    """the 1x1 convolutions (nin_shortcut; proj_out with its residual): the gather kernel by policy and under | 32"""
+    from unimedvl_amd import _lib
+    from unimedvl_amd.vae import _Conv, _stream
+    lib = _lib.load()
+    x = rnd((2, cin, h, w), 1)
+    wt, b = rnd((cout, cin, 1, 1), 2, 1 / cin ** 0.5), rnd((cout,), 3, 0.1)
+    ref = F.conv2d(x.float(), wt.float(), b.float()).to(BF16)
+    res = None
+    if with_res:
+        res = rnd(tuple(ref.shape), 4)
+        ref = ref + res
+    c = _Conv(wt, b, "cuda")
+    xn = x.permute(0, 2, 3, 1).contiguous().cuda()
+    resn = None if res is None else res.permute(0, 2, 3, 1).contiguous().cuda()
+    for mv in (0, 32):
+        out = torch.full((2, h, w, cout), float("nan"), dtype=BF16, device="cuda")
+        _lib.check(lib.umv_conv2d_nhwc_bf16(xn.data_ptr(), c.lin.wp.data_ptr(), c.bias.data_ptr(),
+                                            None if resn is None else resn.data_ptr(), out.data_ptr(), 2, cin, h, w, cout, 1,
+                                            mv, _stream()), "conv")
+        got = out.cpu().permute(0, 3, 1, 2).float()
+        err = (got - ref.float()).abs().max().item()
+        assert err <= 2 ** -6 * max(1.0, ref.float().abs().max().item()), f"conv 1x1 mode {mv}: max err {err}"
 
 
 @pytest.mark.parametrize("C,hw,swish", [(32, 64, True), (128, 300, True), (512, 1024, False), (64, 257, True)])

@@ -1,4 +1,4 @@
-// Workgroup reductions of the row kernels (norm.hip, token_pick.hip, vision.hip): wave_sum / wave_max of common.h, then one LDS
+// Workgroup reductions of the row kernels (norm.hip, token_pick.hip, image_head.hip): wave_sum / wave_max of common.h, then one LDS
 // exchange between the waves.  Every thread of the workgroup must call them.
 #pragma once
 #include "common.h"
