@@ -189,8 +189,11 @@ extern "C" int umv_nchw_f32_to_nhwc_bf16(const float* x, uint16_t* out, int B, i
     return UMV_OK;
 }
 
-// latent tokens [h*w, p*p*c] (fp32 x_t or bf16) -> NHWC bf16 [1, h*p, w*p, c] with z/scale + shift
-// (inferencer.py:239-241 "nhwpqc->nchpwq" and autoencoder.py:306), bf16 rounding per op.
+// latent tokens [h*w, p*p*c] fp32 (the flow's x_t) -> NHWC bf16 [1, h*p, w*p, c] with z/scale + shift
+// (inferencer.py:239-241 "nhwpqc->nchpwq" and autoencoder.py:306), bf16 rounding per op: bf16(bf16(bf16(tok) / scale) + shift).
+// scale and shift are fp32 constants, as torch hands a Python scalar to a device kernel.  torch on the CPU rounds the scalar of
+// `bf16_tensor + scalar` to bf16 first (0.1159 -> 0.11572265625), so the CPU oracle and its goldens differ from this kernel by at
+// most one bf16 ulp at the addition (DESIGN.md "The VAE's shift constant"; tests/test_vae_ref_cpu.py, tests/test_vae_boundary_gpu.py).
 __global__ void unpatchify_latent_kernel(const float* __restrict__ tok, bf16_t* __restrict__ out, int h, int w, int p, int c,
                                          float scale, float shift) {
     int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -239,6 +242,9 @@ extern "C" int umv_pixels_to_u8(const uint16_t* x, uint8_t* out, int64_t npix, i
 // encoder tail: moments NHWC bf16 [B,Hm,Wm,2z] -> z = mean + exp(0.5*logvar)*noise ; scale*(z - shift)
 // (autoencoder.py:266-272,300-303) then 2x2 patchify "chpwq->hwpqc" of the top-left h*p x w*p window
 // (bagel.py:771-775) -> tokens bf16 [h*w, p*p*z].  noise is NCHW bf16 [B,z,Hm,Wm] as torch.randn_like draws it.
+// bf16(scale * bf16(bf16(mean + bf16(bf16(exp(bf16(0.5 * logvar))) * noise)) - shift)) with fp32 scale and shift, as torch computes
+// them on a device; the CPU oracle subtracts the shift rounded to bf16 and differs by at most one bf16 ulp of that step (see
+// unpatchify_latent_kernel).
 __global__ void latent_sample_patchify_kernel(const bf16_t* __restrict__ mom, const bf16_t* __restrict__ noise, bf16_t* __restrict__ tok,
                                               int b, int Hm, int Wm, int z, int h, int w, int p, float scale, float shift) {
     int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
