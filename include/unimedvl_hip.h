@@ -51,7 +51,12 @@ int umv_pack_weight_swiglu_bf16(const uint16_t* gate, const uint16_t* up, uint16
  * modeling_utils.py:108,120-122.  Epilogue order (each step rounds to bf16 exactly
  * where the reference's bf16 tensors are materialised):
  *   v = acc (+bias) -> bf16 ; GELU_TANH / SILU -> bf16 ; SWIGLU: bf16(bf16(silu(g))*u) ;
- *   RESIDUAL: bf16(v + residual[m,n]) */
+ *   RESIDUAL: bf16(v + residual[m,n])
+ * Values: every add is one fp32 addition (denormals kept) rounded to nearest even; bf16 subnormal weights and
+ * activations take part in the product.  GELU_TANH (torch's approximate="tanh") and SILU are x / (1 + 2^t) on the
+ * hardware exp2 / rcp: at most one bf16 value from the exact function; where 1 / (1 + 2^t) is below 2^-126 (SiLU:
+ * x <= -87.5, GELU: x <= -10.0625, and |x| < 2^-126) the result may be flushed to zero - the left tails give -0.
+ * +inf -> +inf, -inf -> NaN (x * 0, as torch on the device), NaN -> NaN. */
 enum {
     UMV_EPI_BIAS = 1,
     UMV_EPI_GELU_TANH = 2,

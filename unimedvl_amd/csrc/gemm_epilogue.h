@@ -20,17 +20,23 @@ __device__ __forceinline__ void static_for(F&& f) {
 __device__ __forceinline__ float gelu_tanh_f(float x) {
     // torch gelu(approximate="tanh"): 0.5*x*(1+tanh(u)), u = sqrt(2/pi)*(x+0.044715*x^3).  With tanh(u) = 1 - 2/(e^(2u)+1) this is
     // x / (1 + e^(-2u)) = x * rcp(1 + 2^(x*(c0 + c1*x^2))): 7 VALU ops, two of them v_exp_f32 / v_rcp_f32 (libm's tanhf is ~40;
-    // the textbook form 15).  Abs error ~1e-7, far below the bf16 rounding that follows.  The exponent is clamped so that
-    // 2^(..) stays finite: x -> -inf gives -0 like the reference, never inf * 0.
+    // the textbook form 15).  Abs error ~1e-7, far below the bf16 rounding that follows.
+    // The left tail: the exponent is NOT clamped.  Once 2^(..) passes 2^126 (x <= -10.0625 among bf16 values) the factor 1 / (1 + e) is
+    // below the smallest normal fp32: v_rcp_f32 flushes it, or v_exp_f32 has overflowed to inf and rcp(inf) = 0, so every finite x
+    // there gives -0 (the exact value is below 2^-126 |x|).  A clamp at 126 returned x * 2^-126 instead: -3.97 at x = -3.39e38.
+    // x = -inf: -inf * rcp(inf) = NaN, as torch's 0.5 * x * (1 + tanh(u)) gives; +inf -> +inf; NaN -> NaN.
+    // (tests/test_gemm_epilogue_values_gpu.py walks all 65 536 bf16 values through every epilogue copy.)
     const float c0 = -2.0f * 1.4426950408889634f * 0.7978845608028654f;   // -2 log2(e) sqrt(2/pi)
     const float c1 = c0 * 0.044715f;
     const float p = __builtin_fmaf(c1, x * x, c0);
-    const float e = __builtin_amdgcn_exp2f(fminf(x * p, 126.0f));
+    const float e = __builtin_amdgcn_exp2f(x * p);
     return x * __builtin_amdgcn_rcpf(1.0f + e);
 }
-// x * sigmoid(x) on v_exp_f32 / v_rcp_f32 (relative error ~2e-7 before the bf16 rounding)
+// x * sigmoid(x) on v_exp_f32 / v_rcp_f32 (relative error ~2e-7 before the bf16 rounding).  The left tail as in gelu_tanh_f: no
+// clamp, so for x <= -87.5 the sigmoid flushes or underflows to 0 and the result is -0 (exact value below 2^-126 |x|; torch's fp32
+// sigmoid does the same from x <= -89); x = -inf: -inf * 0 = NaN, as torch's x * sigmoid(x); +inf -> +inf; NaN -> NaN.
 __device__ __forceinline__ float silu_f(float x) {
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(fminf(-x * 1.4426950408889634f, 126.0f)));
+    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-x * 1.4426950408889634f));
 }
 
 struct EpiCtx {
