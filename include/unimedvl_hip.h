@@ -441,6 +441,63 @@ int umv_decode_step_end_truncated(int32_t* tok_slot, int32_t* tok_pos, int32_t* 
                                   const int64_t* forced_ids, float* logprob, int B, int max_len, uint64_t seed, int top_k, float top_p,
                                   float min_p, float* cut_y, int32_t* n_kept, umv_stream_t stream);
 
+/* ------------------------------------------------------------------ logit penalties and bias
+ * Repetition, presence and frequency penalties and a static logit bias, applied to the stored bf16 logits of a decode step BEFORE
+ * anything picks from them.  For row b let l[n] = float(stored bf16 logit), c[n] the number of times column n was generated so far in
+ * this request (the tokens fed at steps 1..s - the model's picks, or the forced tokens where they were fed; the start token is not
+ * counted), P an optional set of context (prompt) columns, bias[n] an optional fp32 bias (0 where absent, -inf bans a column) and
+ * seen(n) = c[n] > 0 or n in P.  The adjusted logit is formed in fp32, one rounding per operation, nothing contracted to an FMA:
+ *     a = l[n]
+ *     if seen(n) and r != 1:  a = (a < 0) ? a * r : a / r             repetition_penalty r > 0 (the HF / CTRL rule; includes P)
+ *     if c[n] > 0:            a = a - (presence + frequency * float(c[n]))   product, sum, difference (the OpenAI rule; generated only)
+ *     if bias[n] != 0:        a = a + bias[n]
+ *     l'[n] = bf16_round_nearest_even(a)
+ * NaN stays NaN and -inf stays -inf (bias = +inf on a -inf logit is the NaN the arithmetic gives); a column that is neither seen nor
+ * biased, and every column while r = 1, presence = frequency = 0 and bias = 0, keeps its bits.  l' REPLACES l in memory, and everything
+ * downstream is defined on l' in the words used above: the greedy pick, y = bf16(l' / T) and its Gumbel key, the token
+ * log-probabilities - those of the ADJUSTED, untruncated softmax - and the truncation classes.  So penalties come before temperature and
+ * before truncation (the order of HF's logits processors).  A row's result depends only on its own logits, history, context and bias.
+ *
+ * umv_logit_penalty_bf16: one workgroup per row, between the lm_head GEMM and whatever picks.  Per row, in this order:
+ *   record   list_len[b] < 0 marks a FRESH slot: the word becomes n_static and nothing is counted (ids[b] is the start token).
+ *            Otherwise c[ids[b]] += 1 and, if that column is not listed yet and list_len[b] < cap, it is appended to the row's visit
+ *            list.  Nothing is ever written at or beyond cap (a column that found no room is counted but not penalised).  An id
+ *            outside [0, V) is ignored.
+ *   patch    every list entry is one column, handled by one thread: l[n] -> l'[n].  The list is distinct by construction, so no column
+ *            is patched twice.
+ *   tiles    with argmax_partial: for every list entry the whole 16-column tile is recomputed from the patched row and
+ *            argmax_partial[b][tile] - and lse_partial[b][tile] when given - stored, with the bits the lm_head epilogue of
+ *            umv_gemm_bf16 leaves for those logits: greedy keys when temperature = 0, the sampling keys of (temperature, seed, *step)
+ *            otherwise.  argmax_partial = NULL: record and patch only (the unfused step, where umv_argmax_bf16 / umv_sample_bf16 read
+ *            the logits afterwards).
+ * Memory.  count [M][V] int32: bits 0..29 c[n] (saturating), bit 30 (UMV_PENALTY_CONTEXT) n is in P, bit 31 (UMV_PENALTY_LISTED) n is
+ * in the row's list; the caller zeroes a row and sets the two flags of its static columns.  list [M][cap] int32: entries 0..n_static-1
+ * are the STATIC ones the caller seeds - the context and bias columns, distinct, -1 = unused - and bias [M][n_static] fp32 (may be NULL)
+ * runs parallel to them; the generated columns follow from n_static on.  list_len [M] int32: the caller writes -1 to start a request.
+ * UMV_ERR_ARG: repetition_penalty <= 0 or not finite, presence / frequency not finite, temperature < 0, lse_partial without
+ * argmax_partial, cap < n_static, n_tiles that is not ceil(V / 16) with argmax_partial. */
+#define UMV_PENALTY_COUNT_MASK 0x3FFFFFFFu
+#define UMV_PENALTY_CONTEXT 0x40000000u
+#define UMV_PENALTY_LISTED 0x80000000u
+typedef struct {
+    uint16_t* logits;          /* [M][V] bf16, row stride ld elements; patched in place */
+    int64_t ld;
+    const int64_t* ids;        /* [M]: the token each row is fed at this step */
+    int32_t* count;            /* [M][V] */
+    int32_t* list;             /* [M][cap] */
+    int32_t* list_len;         /* [M] */
+    const float* bias;         /* [M][n_static] or NULL */
+    int M, V, cap, n_static;
+    float repetition_penalty, presence_penalty, frequency_penalty;
+    float temperature;         /* as given to the lm_head GEMM: 0 = greedy keys and y = l' */
+    uint64_t* argmax_partial;  /* optional [M][n_tiles] */
+    float* lse_partial;        /* optional [M][n_tiles][2], only with argmax_partial */
+    int n_tiles;
+    uint64_t seed;             /* sample_seed / sample_step of the lm_head call (temperature > 0) */
+    const int64_t* step;
+} umv_logit_penalty_args;
+int umv_logit_penalty_bf16(const umv_logit_penalty_args* a, umv_stream_t stream);
+
 
 /* TimestepEmbedder.timestep_embedding (modeling_utils.py:87-109): out[r] = bf16(cat(cos(t[r] * freqs), sin(t[r] * freqs))),
  * out [n, 2*half]; freqs [half] fp32 = exp(-ln(10000) * i / half) from the caller.  The two linears + SiLU of the embedder

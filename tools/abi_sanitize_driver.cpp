@@ -8,6 +8,7 @@
 // thread-safe first use).  Exit code 0 = no entry point crashed, returned success for invalid input, or left the error text empty.
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
 #include <thread>
 #include <vector>
@@ -191,6 +192,27 @@ static void bad_arguments() {
                                              64, 64, 0.f, nullptr, nullptr, 1, 16, 1, 5, 0.9f, 0.f, dummyf, dummyi, nullptr));   // temperature 0
     EXPECT_OK(umv_decode_step_end_truncated(dummyi, dummyi, dummyi, (const uint64_t*)dummyl, nullptr, 4, dummyl, dummyl, dummyl, dummyl, dummy16,
                                             64, 64, 1.f, nullptr, nullptr, 0, 16, 1, 5, 0.9f, 0.f, dummyf, dummyi, nullptr));    // no samples
+    // logit penalties
+    EXPECT_ERR(umv_logit_penalty_bf16(nullptr, nullptr));
+    umv_logit_penalty_args lp;
+    std::memset(&lp, 0, sizeof lp);
+    EXPECT_ERR(umv_logit_penalty_bf16(&lp, nullptr));
+    lp.logits = dummy16; lp.ld = 64; lp.ids = dummyl; lp.count = dummyi; lp.list = dummyi; lp.list_len = dummyi;
+    lp.M = 1; lp.V = 64; lp.cap = 8; lp.n_static = 2; lp.repetition_penalty = 1.1f;
+    lp.repetition_penalty = 0.f;                                 // r <= 0
+    EXPECT_ERR(umv_logit_penalty_bf16(&lp, nullptr));
+    lp.repetition_penalty = 1.1f; lp.presence_penalty = INFINITY;   // not finite
+    EXPECT_ERR(umv_logit_penalty_bf16(&lp, nullptr));
+    lp.presence_penalty = 0.f; lp.temperature = -1.f;            // negative temperature
+    EXPECT_ERR(umv_logit_penalty_bf16(&lp, nullptr));
+    lp.temperature = 0.f; lp.lse_partial = dummyf;               // lse_partial without argmax_partial
+    EXPECT_ERR(umv_logit_penalty_bf16(&lp, nullptr));
+    lp.lse_partial = nullptr; lp.n_static = 9;                   // cap below the static length
+    EXPECT_ERR(umv_logit_penalty_bf16(&lp, nullptr));
+    lp.n_static = 2; lp.argmax_partial = (uint64_t*)dummyl; lp.n_tiles = 3;     // 64 columns are not 3 tiles
+    EXPECT_ERR(umv_logit_penalty_bf16(&lp, nullptr));
+    lp.n_tiles = 4; lp.M = 0;
+    EXPECT_OK(umv_logit_penalty_bf16(&lp, nullptr));             // no rows
     EXPECT_ERR(umv_timestep_embed(nullptr, nullptr, nullptr, 4, 128, nullptr));
     EXPECT_ERR(umv_cfg_renorm_euler(nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 1, 4.0f, 1.5f, 0.f, 0, 0.1f, 64, nullptr));
     // VAE

@@ -65,6 +65,20 @@ class Gemm8Args(C.Structure):
     ]
 
 
+class LogitPenaltyArgs(C.Structure):
+    _fields_ = [
+        ("logits", C.c_void_p), ("ld", C.c_int64), ("ids", C.c_void_p), ("count", C.c_void_p), ("list", C.c_void_p),
+        ("list_len", C.c_void_p), ("bias", C.c_void_p), ("M", C.c_int), ("V", C.c_int), ("cap", C.c_int), ("n_static", C.c_int),
+        ("repetition_penalty", C.c_float), ("presence_penalty", C.c_float), ("frequency_penalty", C.c_float),
+        ("temperature", C.c_float), ("argmax_partial", C.c_void_p), ("lse_partial", C.c_void_p), ("n_tiles", C.c_int),
+        ("seed", C.c_uint64), ("step", C.c_void_p),
+    ]
+
+
+# umv_logit_penalty_args.count words: bits 0..29 the count, then "in the context set" and "in the row's visit list"
+PENALTY_COUNT_MASK, PENALTY_CONTEXT, PENALTY_LISTED = 0x3FFFFFFF, 0x40000000, 0x80000000
+
+
 _SIGS = {
     "umv_packed_weight_fp8_mfma_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "umv_repack_weight_fp8_mfma": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -126,6 +140,7 @@ _SIGS = {
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                                                 C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                                 C.c_void_p]),
+    "umv_logit_penalty_bf16": (C.c_int, [C.POINTER(LogitPenaltyArgs), C.c_void_p]),
     "umv_timestep_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "umv_cfg_renorm_euler": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.c_void_p]),

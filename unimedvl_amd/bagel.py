@@ -310,8 +310,9 @@ class Bagel(BagelPrep):
     def generate_text(self, past_key_values: NaiveCache, packed_key_value_indexes=None, key_values_lens=None,
                       packed_start_tokens=None, packed_query_position_ids=None, max_length: int = 0,
                       do_sample: bool = False, temperature: float = 1.0, end_token_id: int = None,
-                      return_logits: bool = False, per_sample_eos: bool = False, return_logprobs: bool = False,
-                      top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+                      return_logits: bool = False, per_sample_eos: bool = False, return_logprobs: bool = False, *,
+                      repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+                      logit_bias=None, penalty_context_ids=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """Greedy decode (bagel.py:1236-1317).  Returns [steps, B] int64 whose row 0 holds the
         start tokens.  Like the reference, the batch stops when SAMPLE 0 emits end_token_id
         (bagel.py:1313); per_sample_eos=True is the batched extension (stops when every sample
@@ -321,8 +322,13 @@ class Bagel(BagelPrep):
         softmax(logits) in greedy decoding, of softmax(bf16(logits / temperature)) with do_sample).  Needs B <= 64; the step stays
         in the captured graph.
         top_k / top_p / min_p (0 / 1.0 / 0.0 = off; with do_sample): truncated sampling as include/unimedvl_hip.h defines it, in the
-        captured step (DecodeSession); B <= 64.  The log-probabilities stay those of the untruncated softmax."""
+        captured step (DecodeSession); B <= 64.  The log-probabilities stay those of the untruncated softmax.
+        repetition_penalty / presence_penalty / frequency_penalty (1.0 / 0.0 / 0.0 = off) and logit_bias ({token: float}, -inf bans
+        a token): the logit penalties of include/unimedvl_hip.h, applied in the captured step before temperature and truncation; ids,
+        logits and logprobs are those of the adjusted logits.  penalty_context_ids: per sample a list of tokens (the prompt) that
+        count as seen for the repetition penalty - this call has no token ids of its own, so without it that set is empty."""
         top_k, top_p, min_p = ops.check_truncation(top_k, top_p, min_p)
+        ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, vocab=self.cfg.vocab)
         # do_sample: softmax(logits / temperature) + multinomial on the device (bagel.py:1297-1299).  The
         # draw is keyed by a seed derived from torch.initial_seed(), so torch.manual_seed(s) makes runs
         # reproducible; the stream itself is not torch's (no device can reproduce another's RNG).
@@ -340,7 +346,9 @@ class Bagel(BagelPrep):
         sess = DecodeSession(self.language_model, past_key_values, packed_start_tokens, packed_query_position_ids,
                              max_length, use_graph=self.decode_use_graph and not return_logits,
                              do_sample=do_sample, temperature=temperature, seed=seed, logprobs=return_logprobs,
-                             top_k=top_k, top_p=top_p, min_p=min_p)
+                             top_k=top_k, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
+                             presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, logit_bias=logit_bias,
+                             penalty_context_ids=penalty_context_ids)
         logits = []
         steps = 0
         stop = None
@@ -374,10 +382,14 @@ class Bagel(BagelPrep):
     @torch.no_grad()
     @ops.on_device
     def chat(self, tokenizer, new_token_ids, image_transform, images, prompt, max_length: int,
-             do_sample: bool = False, temperature: float = 1.0, return_logprobs: bool = False,
-             top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+             do_sample: bool = False, temperature: float = 1.0, return_logprobs: bool = False, *,
+             repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None,
+             penalize_prompt: bool = False, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """ViT-only VQA convenience path (bagel.py:1321-1392).  return_logprobs=True: returns (answer, token_ids, token_logprobs) -
-        the generated tokens behind the answer (the end token excluded) and the log-probability of each (generate_text)."""
+        the generated tokens behind the answer (the end token excluded) and the log-probability of each (generate_text).
+        repetition_penalty / presence_penalty / frequency_penalty / logit_bias: the logit penalties of generate_text;
+        penalize_prompt=True makes the prompt's token ids the repetition penalty's context set (off: generated tokens only) - the
+        text's own tokens, not the bos / eos wrapper around them: a penalised end token would only make answers longer."""
         if self.chat_cache_tokens > 0:       # serving: one reserved cache reused by every request (stable slabs -> graph prefill)
             if self._chat_cache is None or self._chat_cache.cap < self.chat_cache_tokens:
                 self._chat_cache = NaiveCache(self.cfg.layers)
@@ -391,11 +403,14 @@ class Bagel(BagelPrep):
             gi, newlens, new_rope = self.prepare_vit_images(newlens, new_rope, [image], image_transform, new_token_ids)
             cache = self.forward_cache_update_vit(cache, **gi)
         gi, newlens, new_rope = self.prepare_prompts(newlens, new_rope, [prompt], tokenizer, new_token_ids)
+        prompt_ids = [gi["packed_text_ids"].tolist()[1:-1]] if penalize_prompt else None        # without the bos / eos wrapper
         cache = self.forward_cache_update_text(cache, **gi)
         gi = self.prepare_start_tokens(newlens, new_rope, new_token_ids)
         ids = self.generate_text(past_key_values=cache, max_length=max_length, do_sample=do_sample,
                                  temperature=temperature, end_token_id=new_token_ids["eos_token_id"],
-                                 return_logprobs=return_logprobs, top_k=top_k, top_p=top_p, min_p=min_p, **gi)
+                                 return_logprobs=return_logprobs, top_k=top_k, top_p=top_p, min_p=min_p,
+                                 repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                                 frequency_penalty=frequency_penalty, logit_bias=logit_bias, penalty_context_ids=prompt_ids, **gi)
         if return_logprobs:
             ids, lp = ids
         output = tokenizer.decode(ids[:, 0].cpu())

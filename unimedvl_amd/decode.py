@@ -23,15 +23,22 @@ import os
 
 import torch
 
-from . import ops
+from . import _lib, ops
 from .kvcache import NaiveCache
 
 BF16 = torch.bfloat16
 
 
+def _lib_flag(word):
+    """a count-table flag word (unsigned 32 bit) as the int32 torch stores"""
+    return word - (1 << 32) if word & 0x80000000 else word
+
+
 class DecodeSession:
     def __init__(self, llm, cache: NaiveCache, start_tokens, positions, max_length, use_graph=True, nsplit=None,
-                 do_sample=False, temperature=1.0, seed=0, logprobs=False, forced_ids=None, top_k=0, top_p=1.0, min_p=0.0):
+                 do_sample=False, temperature=1.0, seed=0, logprobs=False, forced_ids=None, *,
+                 repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, penalty_context_ids=None,
+                 penalty_context_room=None, penalty_history=None, top_k=0, top_p=1.0, min_p=0.0):
         """logprobs: also record pred_logprobs (fp32 [max_length, B]) - row s is the log-probability of in_ids[s + 1], the token step s
         picked (include/unimedvl_hip.h, token log-probabilities: of softmax(logits) in greedy decoding, of softmax(bf16(logits / T))
         when sampling).  forced_ids (int64 [max_length, B]): where an entry is >= 0 that token is fed to the next step instead of the
@@ -40,17 +47,29 @@ class DecodeSession:
         top_k / top_p / min_p (0 / 1.0 / 0.0 = off): truncated sampling (include/unimedvl_hip.h) - they need do_sample and, like
         logprobs, the fused step end.  With one on, the step ends with umv_decode_step_end_truncated - still two launches after the last
         norm, still one graph - and pred_cut_y (fp32) / pred_n_kept (int32), both [max_length, B], record each step's cutoff value and
-        kept-column count.  pred_logprobs stay those of the untruncated softmax.  All off: today's step, launch for launch."""
+        kept-column count.  pred_logprobs stay those of the untruncated softmax.  All off: today's step, launch for launch.
+        repetition_penalty / presence_penalty / frequency_penalty (1.0 / 0.0 / 0.0 = off) and logit_bias ({token: float}, -inf bans a
+        token): the logit penalties of include/unimedvl_hip.h - one umv_logit_penalty_bf16 launch between the lm_head call and the step
+        end rewrites the stored logits of the columns a sample has generated (the tokens fed at steps 1.., forced ones included), of its
+        context set and of the biased columns, and the tiles' keys and statistics with them; greedy and sampled picks, pred_logprobs,
+        truncation and `logits` are all those of the ADJUSTED logits.  penalty_context_ids: per sample a list of tokens (the prompt)
+        that count as seen for the repetition penalty.  The session owns the history: set_slot resets a slot's, rewind_outputs keeps
+        it.  penalty_context_room: context tokens per slot to reserve for later set_slot calls (default: the longest list given) -
+        keep it at what the prompts need: the kernel walks the whole reservation of every row at every step;
+        penalty_history: distinct generated tokens per slot to reserve (default max_length - more when requests outlive a round of
+        max_length steps).  All neutral: today's step, launch for launch, no buffer allocated.  Works on the unfused step too."""
         with ops.device_scope(llm.device):
             self._init(llm, cache, start_tokens, positions, max_length, use_graph, nsplit, do_sample, temperature, seed, logprobs,
-                       forced_ids, top_k, top_p, min_p)
+                       forced_ids, top_k, top_p, min_p,
+                       dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+                            logit_bias=logit_bias, context=penalty_context_ids, room=penalty_context_room, history=penalty_history))
 
     @property
     def device(self):
         return self.dev
 
     def _init(self, llm, cache, start_tokens, positions, max_length, use_graph, nsplit, do_sample, temperature, seed, logprobs=False,
-              forced_ids=None, top_k=0, top_p=1.0, min_p=0.0):
+              forced_ids=None, top_k=0, top_p=1.0, min_p=0.0, penalties=None):
         cfg, dev = llm.cfg, llm.device
         self.llm, self.cache, self.cfg, self.dev = llm, cache, cfg, dev
         B = len(cache.lens)
@@ -198,10 +217,96 @@ class DecodeSession:
         # (a name, not a bound method: a session that refers to itself is freed by the cycle collector only - at any allocation, another
         # session's graph capture included, where releasing device memory aborts)
         self.step_end = "truncated" if self.truncated else "logprob" if self.logprobs else "argmax" if self.fused_argmax else "unfused"
+        self._init_penalties(penalties or {})
         self.steps_done = 0
         self.graph = None
         if use_graph:
             self._capture()
+
+    # ---- logit penalties (include/unimedvl_hip.h): per slot a count word per column, the list of columns to visit (static entries
+    # first: the context and the biased columns, seeded here; then the generated ones, appended by the kernel) and its length
+    def _init_penalties(self, kw):
+        cfg, dev, B = self.cfg, self.dev, self.B
+        r, p, f, bias = ops.check_penalties(kw.get("repetition_penalty", 1.0), kw.get("presence_penalty", 0.0),
+                                            kw.get("frequency_penalty", 0.0), kw.get("logit_bias"), vocab=cfg.vocab)
+        bias = {t: v for t, v in bias.items() if v != 0.0}
+        self.pen = None
+        self.pen_count = self.pen_list = self.pen_len = self.pen_bias = None
+        context = kw.get("context")
+        if r == 1.0 and p == 0.0 and f == 0.0 and not bias:
+            return                                  # neutral (a context set alone changes nothing): today's step
+        if context is None:
+            context = [[] for _ in range(B)]
+        if len(context) != B:
+            raise ValueError(f"penalty_context_ids must hold one token list per sample ({B}), got {len(context)}")
+        context = [self._penalty_context(c) for c in context]
+        room = max([len(c) for c in context] + [0]) if kw.get("room") is None else int(kw["room"])
+        history = self.max_length if kw.get("history") is None else int(kw["history"])
+        self.pen_bias_cols = bias
+        self.pen_room = room
+        self.pen_static = min(room, cfg.vocab) + len(bias)
+        cap = self.pen_static + max(1, min(history, cfg.vocab))
+        self.pen = (r, p, f)
+        self.pen_count = torch.zeros((B, cfg.vocab), dtype=torch.int32, device=dev)
+        self.pen_list = torch.full((B, cap), -1, dtype=torch.int32, device=dev)
+        self.pen_len = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        self.pen_bias = torch.zeros((B, self.pen_static), dtype=torch.float32, device=dev) if self.pen_static else None
+        for b in range(B):
+            self._reset_penalty_slot(b, context[b])
+
+    def _penalty_context(self, tokens):
+        """distinct tokens of a context list, in order of first appearance"""
+        out = list(dict.fromkeys(int(t) for t in (tokens.tolist() if hasattr(tokens, "tolist") else tokens or ())))
+        if any(t < 0 or t >= self.cfg.vocab for t in out):
+            raise ValueError(f"penalty_context_ids holds a token outside [0, {self.cfg.vocab})")
+        return out
+
+    def _reset_penalty_slot(self, b, context):
+        """Slot b starts a request: no generated tokens, `context` (distinct tokens) as its context set, the length word "fresh"."""
+        if len(context) > self.pen_room:
+            raise ValueError(f"slot {b}: {len(context)} distinct context tokens, the session reserved room for {self.pen_room} "
+                             "(penalty_context_room)")
+        listed, ctx = _lib_flag(_lib.PENALTY_LISTED), _lib_flag(_lib.PENALTY_LISTED | _lib.PENALTY_CONTEXT)
+        inside = set(context)
+        cols = context + [t for t in self.pen_bias_cols if t not in inside]
+        words = [ctx] * len(context) + [listed] * (len(cols) - len(context))
+        self.pen_count[b].zero_()
+        self.pen_list[b, :self.pen_static].fill_(-1)
+        if cols:
+            at = torch.tensor(cols, dtype=torch.int64, device=self.dev)
+            self.pen_count[b, at] = torch.tensor(words, dtype=torch.int32, device=self.dev)
+            self.pen_list[b, :len(cols)] = at.to(torch.int32)
+            self.pen_bias[b].zero_()
+            self.pen_bias[b, :len(cols)] = torch.tensor([self.pen_bias_cols.get(t, 0.0) for t in cols], dtype=torch.float32, device=self.dev)
+        self.pen_len[b:b + 1].fill_(-1)
+
+    @ops.on_device
+    def copy_penalty_history(self, other, slots=None):
+        """Take over another session's penalty state for `slots` (default: all) - a re-captured step goes on with those requests.  The
+        sessions hold the same slots and biased columns; this one's static section and list may be larger (more room for context)."""
+        if self.pen is None:
+            return
+        grow = 0 if other.pen is None else self.pen_static - other.pen_static
+        if other.pen is None or other.pen_count.shape != self.pen_count.shape or other.pen_bias_cols != self.pen_bias_cols or grow < 0 or \
+                other.pen_list.shape[1] + grow > self.pen_list.shape[1]:
+            raise ValueError("copy_penalty_history: the sessions do not share a penalty layout")
+        rows = list(range(self.B)) if slots is None else [int(b) for b in slots]
+        if not rows:
+            return
+        at = torch.tensor(rows, dtype=torch.int64, device=self.dev)
+        old, n_gen = other.pen_static, other.pen_list.shape[1] - other.pen_static
+        self.pen_count[at] = other.pen_count[at]
+        lst = torch.full((len(rows), self.pen_list.shape[1]), -1, dtype=torch.int32, device=self.dev)
+        lst[:, :old] = other.pen_list[at, :old]                                          # static entries, then this session's extra room
+        lst[:, self.pen_static:self.pen_static + n_gen] = other.pen_list[at, old:]       # the generated columns follow the static section
+        self.pen_list[at] = lst
+        ln = other.pen_len[at]
+        self.pen_len[at] = torch.where(ln < 0, ln, ln + grow)
+        if self.pen_bias is not None:
+            bias = torch.zeros((len(rows), self.pen_static), dtype=torch.float32, device=self.dev)
+            if old:
+                bias[:, :old] = other.pen_bias[at]
+            self.pen_bias[at] = bias
 
     def _step(self):
         cfg, w, c = self.cfg, self.llm.w, self.cache
@@ -242,6 +347,14 @@ class DecodeSession:
                 ops.gemm(self.act, down_w, out=self.seq, residual=self.seq)
                 ops.rmsnorm(self.seq, nxt, cfg.rms_eps, out=dst)
         ops.gemm(self.hn, w.lm_head, out=self.logits, **self.lm_head_kw)
+        if self.pen is not None:
+            # record the token this step was fed, patch the logits of the seen / biased columns, recompute the tiles they sit in - with
+            # the (temperature, seed, step) the lm_head call got, so whichever step end follows reads the adjusted distribution
+            r, p, f = self.pen
+            ops.logit_penalty(self.logits, self.ids, self.pen_count, self.pen_list, self.pen_len, self.pen_static, bias=self.pen_bias,
+                              repetition_penalty=r, presence_penalty=p, frequency_penalty=f,
+                              temperature=self.temperature if self.do_sample else 0.0, seed=self.seed, step=self.step_idx,
+                              argmax_partial=self.lm_head_kw.get("argmax_partial"), lse_partial=self.lm_head_kw.get("lse_partial"))
         if self.step_end == "truncated":
             # the fused step end whose pick is the epilogue's only if that column survived the filters (the kept set's Gumbel maximum
             # otherwise), plus pred_cut_y[step] / pred_n_kept[step] - and pred_logprobs[step] when log-probabilities are on
@@ -269,14 +382,17 @@ class DecodeSession:
     def _capture(self):
         # the captured step appends at slot = lens0 and bumps the counters; warm up on a side
         # stream first (lazy module loading), then restore the counters so capture sees a clean state
-        saved = [t.clone() for t in (self.ids, self.tok_slot, self.tok_pos, self.kv_len, self.step_idx)]
+        state = (self.ids, self.tok_slot, self.tok_pos, self.kv_len, self.step_idx)
+        if self.pen is not None:                    # the warm-up step records into the penalty history as well
+            state += (self.pen_count, self.pen_list, self.pen_len)
+        saved = [t.clone() for t in state]
         s = torch.cuda.Stream(device=self.dev)
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             self._step()
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
-        for t, v in zip((self.ids, self.tok_slot, self.tok_pos, self.kv_len, self.step_idx), saved):
+        for t, v in zip(state, saved):
             t.copy_(v)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
@@ -298,8 +414,11 @@ class DecodeSession:
     # ---- continuous batching support (serving.py): the captured step reads these from device memory, so a slot can be
     # re-pointed at a new request between replays without re-capturing
     @ops.on_device
-    def set_slot(self, b, token, kv_len, pos):
-        """Sample b continues from `token` with `kv_len` tokens already in its cache segment and rope position `pos`."""
+    def set_slot(self, b, token, kv_len, pos, penalty_context_ids=None):
+        """Sample b continues from `token` with `kv_len` tokens already in its cache segment and rope position `pos`.  With penalties
+        on, the slot's history starts over: no generated tokens, penalty_context_ids as its context set, `token` as its start token."""
+        if self.pen is not None:
+            self._reset_penalty_slot(b, self._penalty_context(penalty_context_ids))
         self.ids[b:b + 1].fill_(int(token))
         self.tok_slot[b:b + 1].fill_(int(kv_len))
         self.kv_len[b:b + 1].fill_(int(kv_len) + 1)
@@ -307,7 +426,8 @@ class DecodeSession:
 
     @ops.on_device
     def rewind_outputs(self):
-        """Start writing in_ids / pred_ids (and pred_logprobs) at row 0 again (the caller has harvested the previous rows)."""
+        """Start writing in_ids / pred_ids (and pred_logprobs) at row 0 again (the caller has harvested the previous rows).  The
+        penalty history is NOT touched: a request lives across rounds."""
         self.step_idx.zero_()
         self.in_ids[0].copy_(self.ids)      # the tokens the next step is fed (set_slot may have changed them)
         self.steps_done = 0

@@ -29,6 +29,12 @@ The planning process is enclosed within <think> </think> tags; that is, <think> 
 '''
 
 
+def _penalties(repetition_penalty, presence_penalty, frequency_penalty, logit_bias):
+    """the text_* penalty keywords of a pipeline as gen_text's keywords"""
+    return dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+                logit_bias=logit_bias)
+
+
 class InterleaveInferencer:
     def __init__(self, model, vae_model, tokenizer, vae_transform, vit_transform, new_token_ids):
         self.model = model
@@ -133,9 +139,12 @@ class InterleaveInferencer:
         return Image.fromarray(pixels.cpu().numpy())
 
     @torch.no_grad()
-    def gen_text(self, gen_context, max_length: int = 500, do_sample: bool = True, temperature: float = 1.0,
+    def gen_text(self, gen_context, max_length: int = 500, do_sample: bool = True, temperature: float = 1.0, *,
+                 repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None,
                  top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         # top_k / top_p / min_p: truncated sampling (Bagel.generate_text), off by default as in the reference
+        # repetition_penalty / presence_penalty / frequency_penalty / logit_bias: the logit penalties of Bagel.generate_text, off by
+        # default (the reference has none); a context holds no token ids, so the penalties see the generated tokens only
         # the reference decodes on a deepcopy so that the context keeps its length (inferencer.py:261); here the decode
         # appends in place beyond the committed length and the length is simply put back afterwards
         cache = gen_context["past_key_values"]
@@ -144,7 +153,9 @@ class InterleaveInferencer:
         try:
             ids = self.model.generate_text(past_key_values=cache, max_length=max_length, do_sample=do_sample,
                                            temperature=temperature, end_token_id=self.new_token_ids["eos_token_id"],
-                                           top_k=top_k, top_p=top_p, min_p=min_p, **gi)
+                                           top_k=top_k, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
+                                           presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+                                           logit_bias=logit_bias, **gi)
         finally:
             if cache.slabs is not None:
                 cache.lens = lens0
@@ -156,10 +167,13 @@ class InterleaveInferencer:
     def interleave_inference(self, input_lists: List[Union[str, Image.Image]], think=False, understanding_output=False,
                              max_think_token_n=1000, do_sample=False, text_temperature=0.3, cfg_text_scale=3.0,
                              cfg_img_scale=1.5, cfg_interval=(0.4, 1.0), timestep_shift=3.0, num_timesteps=50,
-                             cfg_renorm_min=0.0, cfg_renorm_type="global", image_shapes=(1024, 1024),
+                             cfg_renorm_min=0.0, cfg_renorm_type="global", image_shapes=(1024, 1024), *,
+                             text_repetition_penalty=1.0, text_presence_penalty=0.0, text_frequency_penalty=0.0, text_logit_bias=None,
                              text_top_k=0, text_top_p=1.0, text_min_p=0.0) -> List[Union[str, Image.Image]]:
-        """inferencer.py:552-638.  text_top_k / text_top_p / text_min_p: truncated sampling of the text passes (gen_text)."""
-        filters = dict(top_k=text_top_k, top_p=text_top_p, min_p=text_min_p)
+        """inferencer.py:552-638.  text_top_k / text_top_p / text_min_p: truncated sampling of the text passes (gen_text);
+        text_repetition_penalty / text_presence_penalty / text_frequency_penalty / text_logit_bias: their logit penalties."""
+        filters = dict(top_k=text_top_k, top_p=text_top_p, min_p=text_min_p,
+                       **_penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias))
         output_list = []
         need_cfg = not understanding_output
         gen_context = self.init_gen_context()
@@ -214,7 +228,8 @@ class InterleaveInferencer:
             text_temperature: float = 0.3, cfg_text_scale: float = 3.0, cfg_img_scale: float = 1.5,
             cfg_interval: list = (0.4, 1.0), timestep_shift: float = 3.0, num_timesteps: int = 50,
             cfg_renorm_min: float = 0.0, cfg_renorm_type: str = "global", image_shapes: tuple = (1024, 1024),
-            text_top_k: int = 0, text_top_p: float = 1.0, text_min_p: float = 0.0
+            *, text_repetition_penalty: float = 1.0, text_presence_penalty: float = 0.0, text_frequency_penalty: float = 0.0,
+            text_logit_bias=None, text_top_k: int = 0, text_top_p: float = 1.0, text_min_p: float = 0.0
     ) -> List[Union[str, Image.Image]]:
         """VQA, then optionally reconstruct every input image from the answer (inferencer.py:282-362)."""
         output_list = []
@@ -230,7 +245,9 @@ class InterleaveInferencer:
             else:
                 raise ValueError(f"Unsupported input type: {type(input_term)}")
         vqa_answer = self.gen_text(vqa_context, do_sample=do_sample, temperature=text_temperature,
-                                   max_length=max_think_token_n, top_k=text_top_k, top_p=text_top_p, min_p=text_min_p)
+                                   max_length=max_think_token_n, top_k=text_top_k, top_p=text_top_p, min_p=text_min_p,
+                                   repetition_penalty=text_repetition_penalty, presence_penalty=text_presence_penalty,
+                                   frequency_penalty=text_frequency_penalty, logit_bias=text_logit_bias)
         output_list.append(vqa_answer)
         if not reconstruct_image or not vqa_answer or not vqa_answer.strip():
             return output_list
@@ -256,7 +273,7 @@ class InterleaveInferencer:
 
     def _vqa_then_rebuild(self, input_lists, reconstruct_image, first_only, do_sample, text_temperature, max_think_token_n,
                           cfg_interval, timestep_shift, num_timesteps, cfg_renorm_min, cfg_renorm_type, text_top_k=0, text_top_p=1.0,
-                          text_min_p=0.0):
+                          text_min_p=0.0, penalties=None):
         """Shared body of the two older VQA+reconstruction variants (inferencer.py:366-549): answer the question with
         the image(s) in both ViT and VAE form, then regenerate the image(s) from a FRESH context = [image, answer], with
         cfg_text context = [image] and cfg_img context = [answer], both guidance scales fixed at 7.0 by the reference."""
@@ -269,7 +286,7 @@ class InterleaveInferencer:
             else:
                 raise ValueError(f"Unsupported input type: {type(item)}")
         answer = self.gen_text(ctx, do_sample=do_sample, temperature=text_temperature, max_length=max_think_token_n,
-                               top_k=text_top_k, top_p=text_top_p, min_p=text_min_p)
+                               top_k=text_top_k, top_p=text_top_p, min_p=text_min_p, **(penalties or {}))
         outputs = [answer]
         pictures = [it for it in input_lists if isinstance(it, Image.Image)]
         if not reconstruct_image or not answer or not answer.strip() or not pictures:
@@ -295,13 +312,15 @@ class InterleaveInferencer:
             text_temperature: float = 0.3, cfg_text_scale: float = 3.0, cfg_img_scale: float = 1.5,
             cfg_interval: list = (0.4, 1.0), timestep_shift: float = 3.0, num_timesteps: int = 50,
             cfg_renorm_min: float = 0.0, cfg_renorm_type: str = "global", image_shapes: tuple = (1024, 1024),
-            text_top_k: int = 0, text_top_p: float = 1.0, text_min_p: float = 0.0
+            *, text_repetition_penalty: float = 1.0, text_presence_penalty: float = 0.0, text_frequency_penalty: float = 0.0,
+            text_logit_bias=None, text_top_k: int = 0, text_top_p: float = 1.0, text_min_p: float = 0.0
     ) -> List[Union[str, Image.Image]]:
         """inferencer.py:366-463: VQA, then one reconstruction per input image.  (cfg_*_scale / think / image_shapes are
         accepted and ignored, as in the reference.)"""
         return self._vqa_then_rebuild(input_lists, reconstruct_image, False, do_sample, text_temperature, max_think_token_n,
                                       cfg_interval, timestep_shift, num_timesteps, cfg_renorm_min, cfg_renorm_type,
-                                      text_top_k, text_top_p, text_min_p)
+                                      text_top_k, text_top_p, text_min_p,
+                                      _penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias))
 
     @torch.no_grad()
     def interleave_inference_for_vqa_reconstruction_ver0(
@@ -310,12 +329,14 @@ class InterleaveInferencer:
             text_temperature: float = 0.3, cfg_text_scale: float = 3.0, cfg_img_scale: float = 1.5,
             cfg_interval: list = (0.4, 1.0), timestep_shift: float = 3.0, num_timesteps: int = 50,
             cfg_renorm_min: float = 0.0, cfg_renorm_type: str = "global", image_shapes: tuple = (1024, 1024),
-            text_top_k: int = 0, text_top_p: float = 1.0, text_min_p: float = 0.0
+            *, text_repetition_penalty: float = 1.0, text_presence_penalty: float = 0.0, text_frequency_penalty: float = 0.0,
+            text_logit_bias=None, text_top_k: int = 0, text_top_p: float = 1.0, text_min_p: float = 0.0
     ) -> List[Union[str, Image.Image]]:
         """inferencer.py:466-549: VQA, then a reconstruction of the FIRST input image only."""
         return self._vqa_then_rebuild(input_lists, reconstruct_image, True, do_sample, text_temperature, max_think_token_n,
                                       cfg_interval, timestep_shift, num_timesteps, cfg_renorm_min, cfg_renorm_type,
-                                      text_top_k, text_top_p, text_min_p)
+                                      text_top_k, text_top_p, text_min_p,
+                                      _penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias))
 
     # ------------------------------------------------------------------ batch extension (additive; SURVEY.md section 8b B1)
     # The reference runs one sample per call (contexts are lists of length 1).  Samples are independent segments of
@@ -346,7 +367,8 @@ class InterleaveInferencer:
         return ctx
 
     @torch.no_grad()
-    def gen_text_batch(self, ctx, max_length: int = 500, do_sample: bool = True, temperature: float = 1.0,
+    def gen_text_batch(self, ctx, max_length: int = 500, do_sample: bool = True, temperature: float = 1.0, *,
+                       repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None,
                        top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0) -> List[str]:
         """gen_text for every sample of a batched context; each answer ends at that sample's own EOS."""
         cache = ctx["past_key_values"]
@@ -356,7 +378,9 @@ class InterleaveInferencer:
         try:        # decode in place beyond the committed lengths, then put the lengths back (see gen_text)
             ids = self.model.generate_text(past_key_values=cache, max_length=max_length, do_sample=do_sample,
                                            temperature=temperature, end_token_id=eos, per_sample_eos=True,
-                                           top_k=top_k, top_p=top_p, min_p=min_p, **gi).cpu()
+                                           top_k=top_k, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
+                                           presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+                                           logit_bias=logit_bias, **gi).cpu()
         finally:
             if cache.slabs is not None:
                 cache.lens = lens0
@@ -402,7 +426,9 @@ class InterleaveInferencer:
                                    understanding_output=False, max_think_token_n=1000, do_sample=False, text_temperature=0.3,
                                    cfg_text_scale=3.0, cfg_img_scale=1.5, cfg_interval=(0.4, 1.0), timestep_shift=3.0,
                                    num_timesteps=50, cfg_renorm_min=0.0, cfg_renorm_type="global", image_shapes=(1024, 1024),
-                                   text_top_k=0, text_top_p=1.0, text_min_p=0.0) -> List[List[Union[str, Image.Image]]]:
+                                   *, text_repetition_penalty=1.0, text_presence_penalty=0.0, text_frequency_penalty=0.0,
+                                   text_logit_bias=None, text_top_k=0, text_top_p=1.0,
+                                   text_min_p=0.0) -> List[List[Union[str, Image.Image]]]:
         """interleave_inference (inferencer.py:552-638) over B samples at once.  Every sample must have the same
         sequence of item types; lengths (prompt tokens, image sizes) may differ.  Returns one output list per sample."""
         n = len(input_lists)
@@ -437,15 +463,16 @@ class InterleaveInferencer:
                 if need_cfg:
                     cfg_text_ctx = self._snap(ctx)
         outputs = [[] for _ in range(n)]
+        penalties = _penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias)
         if understanding_output:
             for o, t in zip(outputs, self.gen_text_batch(ctx, do_sample=do_sample, temperature=text_temperature,
                                                          max_length=max_think_token_n, top_k=text_top_k, top_p=text_top_p,
-                                                         min_p=text_min_p)):
+                                                         min_p=text_min_p, **penalties)):
                 o.append(t)
             return outputs
         if think:
             thoughts = self.gen_text_batch(ctx, do_sample=do_sample, temperature=text_temperature, max_length=max_think_token_n,
-                                           top_k=text_top_k, top_p=text_top_p, min_p=text_min_p)
+                                           top_k=text_top_k, top_p=text_top_p, min_p=text_min_p, **penalties)
             ctx = self._update_batch_text(thoughts, ctx)
             for o, t in zip(outputs, thoughts):
                 o.append(t)

@@ -39,6 +39,12 @@ DEFAULT_CONFIG = {
     "top_k": 0,
     "top_p": 1.0,
     "min_p": 0.0,
+    # logit penalties (not reference keys; off = the reference's logits): Bagel.generate_text
+    "repetition_penalty": 1.0,
+    "presence_penalty": 0.0,
+    "frequency_penalty": 0.0,
+    "logit_bias": None,
+    "penalize_prompt": False,       # True: the prompt's own tokens (not the bos / eos wrapper) count as seen for repetition_penalty
 }
 
 # codes/data/default.yaml vlm_sft.image_transform_args (read by eval/vlm/utils.py:486-502)
@@ -147,7 +153,8 @@ class VQAInferencer:
         gc.collect()
         self.show_gpu_memory()
 
-    def infer_single(self, image_path, prompt, temperature=None, max_new_tokens=None, do_sample=None, show_image=False,
+    def infer_single(self, image_path, prompt, temperature=None, max_new_tokens=None, do_sample=None, show_image=False, *,
+                     repetition_penalty=None, presence_penalty=None, frequency_penalty=None, logit_bias=None, penalize_prompt=None,
                      top_k=None, top_p=None, min_p=None):
         if not self.loaded:
             raise RuntimeError("Model not loaded, please call load_model() first")
@@ -157,6 +164,9 @@ class VQAInferencer:
         top_k = top_k if top_k is not None else self.config.get("top_k", 0)
         top_p = top_p if top_p is not None else self.config.get("top_p", 1.0)
         min_p = min_p if min_p is not None else self.config.get("min_p", 0.0)
+        given = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+                     logit_bias=logit_bias, penalize_prompt=penalize_prompt)
+        penalties = {k: v if v is not None else self.config.get(k, DEFAULT_CONFIG[k]) for k, v in given.items()}
         if isinstance(image_path, Image.Image):
             input_image, image_path = image_path.convert("RGB"), None
         else:
@@ -171,7 +181,7 @@ class VQAInferencer:
         extra = {"return_logprobs": True} if want_lp else {}
         answer = self.model.chat(self.tokenizer, self.new_token_ids, self.image_transform, images=images,
                                  prompt=conversation, max_length=max_new_tokens, do_sample=do_sample,
-                                 temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, **extra)
+                                 temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, **penalties, **extra)
         if want_lp:
             answer, token_ids, token_logprobs = answer
         result = {"answer": answer, "input_image": input_image, "time": time.time() - start, "image_path": image_path,

@@ -8,7 +8,7 @@ import torch
 
 from . import _lib
 from ._lib import (EPI_BIAS, EPI_GELU_TANH, EPI_OUT_F32, EPI_RESIDUAL, EPI_SILU, EPI_SWIGLU, AttnArgs, GemmArgs,
-                   QkvPostArgs, check)
+                   LogitPenaltyArgs, QkvPostArgs, check)
 
 BF16 = torch.bfloat16
 
@@ -457,6 +457,79 @@ def sample_truncated(logits, temperature, seed, step=None, top_k=0, top_p=1.0, m
                                         int(top_k), float(top_p), float(min_p), _p(cut_y), _p(n_kept), _stream()),
           "umv_sample_truncated_bf16")
     return out
+
+
+def check_penalties(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, vocab=None):
+    """The logit penalties (include/unimedvl_hip.h, logit penalties and bias) as (float, float, float, {int: float}), ValueError
+    outside their ranges: repetition_penalty finite and > 0 (1.0 = off), presence / frequency finite (0.0 = off), logit_bias a
+    {token: bias} mapping of integer tokens >= 0 (below `vocab` when given) to floats that are not NaN (-inf bans the token)."""
+    import math
+
+    def number(v, name):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"{name} must be a number, got {v!r}")
+        return float(v)
+    r, p, f = (number(v, n) for v, n in ((repetition_penalty, "repetition_penalty"), (presence_penalty, "presence_penalty"),
+                                         (frequency_penalty, "frequency_penalty")))
+    if not (math.isfinite(r) and r > 0.0):
+        raise ValueError(f"repetition_penalty must be finite and > 0 (1.0 = off), got {repetition_penalty!r}")
+    if not (math.isfinite(p) and math.isfinite(f)):
+        raise ValueError(f"presence_penalty / frequency_penalty must be finite (0.0 = off), got {presence_penalty!r} / {frequency_penalty!r}")
+    bias = {}
+    if logit_bias is not None:
+        if not hasattr(logit_bias, "items"):
+            raise ValueError(f"logit_bias must be a {{token: bias}} mapping, got {type(logit_bias).__name__}")
+        for tok, v in logit_bias.items():
+            if isinstance(tok, bool) or not isinstance(tok, int) or tok < 0 or (vocab is not None and tok >= vocab):
+                raise ValueError(f"logit_bias: token {tok!r} is not an integer in [0, {'vocab' if vocab is None else vocab})")
+            v = number(v, f"logit_bias[{tok}]")
+            if math.isnan(v):
+                raise ValueError(f"logit_bias[{tok}] is NaN")
+            bias[int(tok)] = v
+    return r, p, f, bias
+
+
+def logit_penalty(logits, ids, count, vlist, list_len, n_static, bias=None, repetition_penalty=1.0, presence_penalty=0.0,
+                  frequency_penalty=0.0, temperature=0.0, seed=0, step=None, argmax_partial=None, lse_partial=None):
+    """umv_logit_penalty_bf16 on bf16 logits [M, V], in place: record ids (int64 [M], the tokens this step is fed) in count (int32 [M, V])
+    and the visit list vlist (int32 [M, cap], the first n_static entries seeded by the caller, bias fp32 [M, n_static] parallel to them)
+    / list_len (int32 [M], -1 = fresh slot), patch the listed columns, and - with argmax_partial ([M, n_tiles] int64, lse_partial
+    [M, n_tiles, 2] fp32) - recompute the tiles they sit in as the lm_head call with sample=(temperature, seed, step) leaves them
+    (temperature 0: greedy)."""
+    lib = _lib.load()
+    _req(logits, BF16, "logits")
+    _req(ids, torch.int64, "ids")
+    for t, name in ((count, "count"), (vlist, "list"), (list_len, "list_len")):
+        _req(t, torch.int32, name)
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise _lib.UmvError("logit_penalty: logits [M, V] with unit column stride")
+    M, V = logits.shape
+    if not (ids.is_contiguous() and ids.numel() == M and list_len.is_contiguous() and list_len.numel() == M and count.is_contiguous()
+            and tuple(count.shape) == (M, V) and vlist.is_contiguous() and vlist.dim() == 2 and vlist.shape[0] == M):
+        raise _lib.UmvError("logit_penalty: ids [M], count [M, V], list [M, cap], list_len [M], all contiguous")
+    if bias is not None:
+        _req(bias, torch.float32, "bias")
+        if not (bias.is_contiguous() and tuple(bias.shape) == (M, int(n_static))):
+            raise _lib.UmvError("logit_penalty: bias must be a contiguous fp32 [M, n_static] tensor")
+    a = LogitPenaltyArgs()
+    a.logits, a.ld, a.ids, a.count, a.list, a.list_len = logits.data_ptr(), logits.stride(0), ids.data_ptr(), count.data_ptr(), \
+        vlist.data_ptr(), list_len.data_ptr()
+    a.bias = None if bias is None else bias.data_ptr()
+    a.M, a.V, a.cap, a.n_static = M, V, vlist.shape[1], int(n_static)
+    a.repetition_penalty, a.presence_penalty, a.frequency_penalty = float(repetition_penalty), float(presence_penalty), float(frequency_penalty)
+    a.temperature, a.seed, a.step = float(temperature), int(seed) & (2 ** 64 - 1), None if step is None else step.data_ptr()
+    if argmax_partial is not None:
+        _req(argmax_partial, torch.int64, "argmax_partial")
+        if not (argmax_partial.is_contiguous() and argmax_partial.dim() == 2 and argmax_partial.shape[0] == M):
+            raise _lib.UmvError("logit_penalty: argmax_partial must be a contiguous [M, n_tiles] tensor")
+        a.argmax_partial, a.n_tiles = argmax_partial.data_ptr(), argmax_partial.shape[1]
+    if lse_partial is not None:
+        _req(lse_partial, torch.float32, "lse_partial")
+        if argmax_partial is not None and not (lse_partial.is_contiguous() and tuple(lse_partial.shape) == tuple(argmax_partial.shape) + (2,)):
+            raise _lib.UmvError("logit_penalty: lse_partial must be a contiguous [M, n_tiles, 2] tensor")
+        a.lse_partial = lse_partial.data_ptr()
+    check(lib.umv_logit_penalty_bf16(C.byref(a), _stream()), "umv_logit_penalty_bf16")
+    return logits
 
 
 def cast_pad(x, Kp):

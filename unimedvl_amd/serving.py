@@ -38,13 +38,16 @@ class _Request:
     max_new_tokens: int
     tokens: List[int] = field(default_factory=list)
     logprobs: List[float] = field(default_factory=list)
+    prompt_ids: Optional[List[int]] = None      # penalize_prompt: the prompt's tokens, the repetition penalty's context set
 
 
 class ContinuousBatcher:
     def __init__(self, model, tokenizer, new_token_ids, image_transform, slots: int = 8, max_context: int = 2048,
                  max_new_tokens: int = 256, check_every: int = 16, do_sample: bool = False, temperature: float = 1.0,
                  use_graph: bool = True, growable: bool = True, context_limit: Optional[int] = None, paged: bool = False,
-                 pool_pages: Optional[int] = None, logprobs: bool = False, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+                 pool_pages: Optional[int] = None, logprobs: bool = False, *, repetition_penalty: float = 1.0,
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, penalize_prompt: bool = False,
+                 top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """max_context: the context (prompt + images) the slots are RESERVED for; with growable=True longer requests enlarge
         the cache (up to context_limit tokens of context when given), with growable=False they are refused.
         paged=True: block-table KV (kvcache.PagedCache) instead of slabs - the slots draw 256-token pages from ONE pool of `pool_pages`
@@ -53,12 +56,23 @@ class ContinuousBatcher:
         its pages.  Same answers as the slab cache (tests/test_paged_kv_gpu.py).
         logprobs=True: self.logprobs[rid] holds one float per emitted token of the request - the token's log-probability as
         DecodeSession(logprobs=True) records it - cut at EOS or the budget exactly as the tokens are.  Needs slots <= 64.
-        top_k / top_p / min_p: truncated sampling (DecodeSession), batcher-wide like temperature; they need do_sample and slots <= 64."""
+        top_k / top_p / min_p: truncated sampling (DecodeSession), batcher-wide like temperature; they need do_sample and slots <= 64.
+        repetition_penalty / presence_penalty / frequency_penalty / logit_bias: the logit penalties (DecodeSession), batcher-wide like
+        temperature; a slot's history starts over when a request is admitted to it and lives across the rounds of that request.
+        penalize_prompt=True: a request's prompt token ids (the text between the bos / eos wrapper, which is NOT part of the set: a
+        penalised end token would only make answers longer) are its context set for the repetition penalty.  The session reserves
+        room for the longest prompt admitted so far (a power of two, at least 32 distinct tokens) - the penalty kernel walks that
+        reservation every step - and the step is re-captured, histories carried over, when a longer prompt arrives."""
         self.top_k, self.top_p, self.min_p = ops.check_truncation(top_k, top_p, min_p)
         if (self.top_k > 0 or self.top_p < 1.0 or self.min_p > 0.0) and not do_sample:
             raise ValueError("top_k / top_p / min_p truncate the sampler: they need do_sample=True")
         self.model, self.tokenizer, self.new_token_ids, self.image_transform = model, tokenizer, new_token_ids, image_transform
         self.device = model.device
+        self.penalties = dict(zip(("repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias"),
+                                  ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty, logit_bias,
+                                                      vocab=model.cfg.vocab)))
+        self.penalize_prompt = bool(penalize_prompt)
+        self._pen_room = 0                              # distinct context tokens per slot the decode session reserves
         self.slots, self.check_every = int(slots), int(check_every)
         self.max_context, self.default_new = int(max_context), int(max_new_tokens)
         self.do_sample, self.temperature, self.use_graph = do_sample, temperature, use_graph
@@ -111,16 +125,33 @@ class ContinuousBatcher:
             state[b] = st
         seed = m._sampling_seed() if self.do_sample else 0
 
-        def new_session():        # (re-)capture the decode step on the cache's current slabs; every slot continues from `state`
+        def context_of(b):
+            return active[b].prompt_ids if active[b] is not None else None
+
+        def room_short(slots):    # does a prompt of these slots hold more distinct tokens than the session reserves?  Then reserve more.
+            need = max([len(set(context_of(b) or ())) for b in slots] + [0])
+            if not self.penalize_prompt or need <= self._pen_room:
+                return False
+            self._pen_room = max(32, 1 << (need - 1).bit_length())
+            return True
+
+        def new_session(prev=None, keep=()):
+            # (re-)capture the decode step on the cache's current slabs; every slot continues from `state`, the slots in `keep` with the
+            # penalty history they had in `prev` (the others start a request: the constructor seeds their context sets)
             start = torch.tensor([s[0] for s in state], dtype=torch.int64)
             pos = torch.tensor([s[2] for s in state], dtype=torch.int64)
             lens_now = list(cache.lens)
             sn = DecodeSession(m.language_model, cache, start, pos, self.check_every, use_graph=self.use_graph,
                                do_sample=self.do_sample, temperature=self.temperature, seed=seed, logprobs=self.want_logprobs,
-                               top_k=self.top_k, top_p=self.top_p, min_p=self.min_p)
+                               top_k=self.top_k, top_p=self.top_p, min_p=self.min_p, **self.penalties,
+                               penalty_context_ids=[context_of(b) for b in range(B)],
+                               penalty_context_room=self._pen_room, penalty_history=m.cfg.vocab)
+            if prev is not None:                        # the requests go on: so do their penalty histories
+                sn.copy_penalty_history(prev, keep)
             cache.lens = lens_now                       # the session only reads them; this loop owns the bookkeeping
             self._grew = False
             return sn
+        room_short(range(B))
         sess = new_session()
         while any(r is not None for r in active) or self._other_work():
             if not any(r is not None for r in active):  # only the other kind of work is left (MixedBatcher: flow passes)
@@ -170,11 +201,13 @@ class ContinuousBatcher:
                     state[b] = (bos, 0, 0)
             # every slot that was freed this round is refilled by ONE batched prefill (images of the new requests share the
             # ViT and LLM forward; the other slots take part with zero query tokens)
-            for b, (tok, kvl, rope) in zip(freed, self._prefill_many(freed, [active[b] for b in freed])):
-                sess.set_slot(b, tok, kvl, rope)
-                state[b] = (tok, kvl, rope)
-            if self._grew:                              # an admitted request enlarged the cache: new slabs, new captured step
-                sess = new_session()
+            for b, st in zip(freed, self._prefill_many(freed, [active[b] for b in freed])):
+                state[b] = st
+            if room_short(freed) or self._grew:         # an admitted request enlarged the cache (new slabs) or brought a prompt longer
+                sess = new_session(sess, [b for b in range(B) if b not in freed])       # than the penalty reservation: new captured step
+            else:
+                for b in freed:
+                    sess.set_slot(b, *state[b], penalty_context_ids=context_of(b))
         return dict(self.results)
 
     # ------------------------------------------------------------------ hooks (MixedBatcher)
@@ -215,6 +248,8 @@ class ContinuousBatcher:
             room(kvl[0])
             view = m.forward_cache_update_vit(view, **gi)
         gi, kvl, rope = m.prepare_prompts(kvl, rope, [req.prompt], self.tokenizer, self.new_token_ids)
+        if self.penalize_prompt:
+            req.prompt_ids = gi["packed_text_ids"].tolist()[1:-1]        # without the bos / eos wrapper
         room(kvl[0])
         view = m.forward_cache_update_text(view, **gi)
         if view.cap != cap:
@@ -255,6 +290,9 @@ class ContinuousBatcher:
         gi, kvl, rope = m.prepare_prompts(kvl, rope, [r.prompt for r in reqs], self.tokenizer, self.new_token_ids)
         for n, r in zip(kvl, reqs):
             cap = self._check_room(n, r, cap)
+        if self.penalize_prompt:
+            for r, ids in zip(reqs, gi["packed_text_ids"].split(gi["text_token_lens"].tolist())):
+                r.prompt_ids = ids.tolist()[1:-1]                        # without the bos / eos wrapper
         gi["text_token_lens"] = spread(gi["text_token_lens"])
         gi["key_values_lens"] = gi["packed_key_value_indexes"] = gi["packed_text_indexes"] = None
         m.forward_cache_update_text(cache, **gi)
