@@ -65,6 +65,23 @@ enum {
     UMV_EPI_SWIGLU = 16, /* packed weight from umv_pack_weight_swiglu_bf16; out is [M, N/2] */
     UMV_EPI_OUT_F32 = 32 /* store raw fp32 accumulators (+bias), no rounding */
 };
+/* Per-row sampling parameters of a decode step: one element per row, in DEVICE memory, 16-byte aligned, 48 bytes:
+ *   offset 0 seed, 8 draw, 16 stream, 20 temperature, 24 top_k, 28 top_p, 32 min_p, 36 repetition_penalty, 40 presence_penalty,
+ *   44 frequency_penalty.
+ * Read by the lm_head epilogue (umv_gemm_bf16_rows / _z13w_rows / _fp8w_rows), umv_logit_penalty_bf16 (rows) and umv_decode_step_end_rows; the semantics
+ * are spelled out under "per-row sampling parameters" below.  The entries cannot look into device memory: the CALLER guarantees
+ * temperature finite (any value <= 0 marks a greedy row), and on a sampled row top_k >= 0, top_p in (0, 1], min_p in [0, 1); on every
+ * row repetition_penalty finite and > 0, presence_penalty and frequency_penalty finite; draw >= 0. */
+typedef struct {
+    uint64_t seed;        /* the request's seed */
+    int64_t  draw;        /* the request's own draw counter: takes the place of *sample_step in the key; the step end adds 1 */
+    uint32_t stream;      /* takes the place of the row index m in the key */
+    float    temperature; /* > 0: sample; anything else (0, negative, NaN): a greedy row, and the row's filters are ignored */
+    int32_t  top_k;       /* 0 = off */
+    float    top_p;       /* 1 = off */
+    float    min_p;       /* 0 = off */
+    float    repetition_penalty, presence_penalty, frequency_penalty;   /* 1 / 0 / 0 = off */
+} umv_row_sampling;
 typedef struct {
     const uint16_t* x;        /* [M,K] bf16, row stride ldx (elements), K%8==0 */
     int64_t ldx;
@@ -116,6 +133,12 @@ typedef struct {
                                  are the bits of the same call without it.  Finished by umv_decode_step_end_logprob. */
 } umv_gemm_args;
 int umv_gemm_bf16(const umv_gemm_args* a, umv_stream_t stream);
+/* The lm_head call with a per-row sampling table (see "per-row sampling parameters"; umv_gemm_fp8w_rows and umv_gemm_z13w_rows are the
+ * same for the other two images that carry argmax_partial): rows [M], device memory, 16-byte aligned, read only.  Row m takes its
+ * temperature and the (seed, draw, stream) of its sampling key from rows[m] instead of sample_temperature / sample_seed / *sample_step /
+ * m - greedy and sampled rows in one call.  UMV_ERR_ARG without rows, without argmax_partial, above 64 rows or with
+ * sample_temperature != 0; everything else as the entry without the table, whose struct - and so every kernel argument - is unchanged. */
+int umv_gemm_bf16_rows(const umv_gemm_args* a, const umv_row_sampling* rows, umv_stream_t stream);
 /* Host-only query: the tiled-kernel configuration umv_gemm_bf16 picks for an M x N x K problem (0 for M <= 64, the
  * weight-streaming kernels; 266 = 256x256x32 interleaved, 268 = 256(n)x128(m), 384 = 384(n)x128(m), 270 = 128x128,
  * 64 = 128(n)x64(m)x64).
@@ -136,6 +159,7 @@ int umv_quantize_pack_weight_fp8(const uint16_t* w, const uint16_t* w_up, uint8_
                                  uint16_t* deq_up, int rows, int K, umv_stream_t stream);
 /* M <= 64 only; a->wp = the e4m3 image, a->w_scale = its scales; norm_w / tile_rows unsupported */
 int umv_gemm_fp8w(const umv_gemm_args* a, umv_stream_t stream);
+int umv_gemm_fp8w_rows(const umv_gemm_args* a, const umv_row_sampling* rows, umv_stream_t stream);   /* see umv_gemm_bf16_rows */
 
 /* ------------------------------------------------------------------ MXFP4 weights (llm_weight_dtype = "fp4"; no reference
  * counterpart).  Weight-only e2m1 with one E8M0 power-of-two scale per BLOCK of 32 consecutive k of a row (K % 32 == 0):
@@ -199,6 +223,7 @@ int umv_pack_weight_z13(const uint16_t* packed16, uint8_t* z13, int N, int K, um
  * OUT_F32, row_idx, argmax_partial / sampling keys and split-K partials as umv_gemm_bf16; norm_w and th-row tiles are
  * UMV_ERR_UNSUPPORTED.  (33..64 rows of a SwiGLU / N >= 16384 GEMM, which umv_gemm_bf16 runs on an MFMA tile, run there.) */
 int umv_gemm_z13w(const umv_gemm_args* a, const void* z13, umv_stream_t stream);
+int umv_gemm_z13w_rows(const umv_gemm_args* a, const void* z13, const umv_row_sampling* rows, umv_stream_t stream);   /* see umv_gemm_bf16_rows */
 
 /* W8A8 on the fp8 matrix instruction (v_mfma_scale_f32_16x16x128_f8f6f4) for the MFMA-bound GEMMs of the fp8 mode
  * (M > 64: prefill, flow passes).  Activations are quantised per ROW the way weights are per channel:
@@ -495,8 +520,37 @@ typedef struct {
     int n_tiles;
     uint64_t seed;             /* sample_seed / sample_step of the lm_head call (temperature > 0) */
     const int64_t* step;
+    const umv_row_sampling* rows; /* optional [M] ("per-row sampling parameters"): r / presence / frequency of row b are rows[b]'s, and the
+                                  tiles are recomputed with rows[b]'s temperature and (seed, draw, stream).  The scalar fields must then
+                                  be neutral - repetition_penalty 1, presence / frequency 0, temperature 0 - UMV_ERR_ARG otherwise.
+                                  Read only. */
 } umv_logit_penalty_args;
 int umv_logit_penalty_bf16(const umv_logit_penalty_args* a, umv_stream_t stream);
+
+/* ------------------------------------------------------------------ per-row sampling parameters
+ * One captured decode step can serve rows with different samplers: a table of umv_row_sampling (above), one entry per row, replaces
+ * the scalar temperature / seed / step / filters / penalties of the entries above.  EVERY per-row definition is the scalar definition
+ * with the row's own values: the sampling key of row m, column n is that of umv_gemm_args.sample_temperature with
+ *   (sample_seed, *sample_step, m)  :=  (rows[m].seed, rows[m].draw, rows[m].stream),
+ * i.e. row key = splitmix64(seed ^ draw * 0xD1B54A32D192ED03 ^ (uint64_t)stream << 32); y, the log-probabilities, the truncation
+ * classes and the penalties are those of the sections above with rows[m].temperature, top_k / top_p / min_p and the three penalty
+ * values.  So a table whose rows all hold the values of a scalar call, with stream = m and draw = *sample_step, leaves the bits of that
+ * scalar call; and a request's draws depend only on its own (seed, stream, draw), not on the row it sits in.
+ * A row with temperature > 0 samples; any other temperature (0, negative, NaN) marks a GREEDY row: greedy keys, y = the logit, and
+ * the row's filters are ignored.  Greedy and sampled rows may share a call, a workgroup and a 16-row fragment.
+ * The GEMMs and the penalty kernel only read the table.
+ *
+ * umv_decode_step_end_rows: the step end of such a step - umv_decode_step_end_truncated's arguments without the scalar temperature /
+ * seed / top_k / top_p / min_p, plus the table, one workgroup per sample.  Per row:
+ *   temperature > 0 and a filter on (top_k > 0, top_p < 1 or min_p > 0): umv_decode_step_end_truncated's pick with the row's values;
+ *   otherwise: the maximum of the row's keys (umv_decode_step_end_argmax / _logprob); cut_y = -inf, n_kept = V.
+ * logprob and lse_partial may be NULL together; forced_ids, cut_y and n_kept as in umv_decode_step_end_truncated.  Last, thread 0 of
+ * the row's workgroup stores rows[b].draw + 1 to rows[b].draw - the only word of the table anything writes.  UMV_ERR_ARG: a NULL or
+ * misaligned table, logprob without lse_partial (or the reverse), V that is not the column count behind n_tiles. */
+int umv_decode_step_end_rows(int32_t* tok_slot, int32_t* tok_pos, int32_t* kv_len, const uint64_t* argmax_partial,
+                             const float* lse_partial, int n_tiles, int64_t* ids, int64_t* in_ids, int64_t* pred_ids,
+                             int64_t* step_idx, const uint16_t* logits, int64_t ldo, int V, const int64_t* forced_ids, float* logprob,
+                             int B, int max_len, umv_row_sampling* rows, float* cut_y, int32_t* n_kept, umv_stream_t stream);
 
 
 /* TimestepEmbedder.timestep_embedding (modeling_utils.py:87-109): out[r] = bf16(cat(cos(t[r] * freqs), sin(t[r] * freqs))),

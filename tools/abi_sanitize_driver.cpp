@@ -192,6 +192,38 @@ static void bad_arguments() {
                                              64, 64, 0.f, nullptr, nullptr, 1, 16, 1, 5, 0.9f, 0.f, dummyf, dummyi, nullptr));   // temperature 0
     EXPECT_OK(umv_decode_step_end_truncated(dummyi, dummyi, dummyi, (const uint64_t*)dummyl, nullptr, 4, dummyl, dummyl, dummyl, dummyl, dummy16,
                                             64, 64, 1.f, nullptr, nullptr, 0, 16, 1, 5, 0.9f, 0.f, dummyf, dummyi, nullptr));    // no samples
+    // per-row sampling parameters
+    alignas(16) umv_row_sampling rows[2];
+    std::memset(rows, 0, sizeof rows);
+    EXPECT_ERR(umv_decode_step_end_rows(nullptr, nullptr, nullptr, nullptr, nullptr, 9504, nullptr, nullptr, nullptr, nullptr, nullptr, 152064,
+                                        152064, nullptr, nullptr, 8, 16, nullptr, nullptr, nullptr, nullptr));
+    EXPECT_ERR(umv_decode_step_end_rows(dummyi, dummyi, dummyi, (const uint64_t*)dummyl, nullptr, 4, dummyl, dummyl, dummyl, dummyl, dummy16, 64,
+                                        64, nullptr, nullptr, 1, 16, nullptr, dummyf, dummyi, nullptr));                 // no table
+    EXPECT_ERR(umv_decode_step_end_rows(dummyi, dummyi, dummyi, (const uint64_t*)dummyl, nullptr, 4, dummyl, dummyl, dummyl, dummyl, dummy16, 64,
+                                        64, nullptr, dummyf, 1, 16, rows, dummyf, dummyi, nullptr));                     // logprob without lse_partial
+    EXPECT_ERR(umv_decode_step_end_rows(dummyi, dummyi, dummyi, (const uint64_t*)dummyl, nullptr, 3, dummyl, dummyl, dummyl, dummyl, dummy16, 64,
+                                        64, nullptr, nullptr, 1, 16, rows, dummyf, dummyi, nullptr));                    // 64 columns are not 3 tiles
+    EXPECT_OK(umv_decode_step_end_rows(dummyi, dummyi, dummyi, (const uint64_t*)dummyl, nullptr, 4, dummyl, dummyl, dummyl, dummyl, dummy16, 64,
+                                       64, nullptr, nullptr, 0, 16, rows, dummyf, dummyi, nullptr));                     // no samples
+    {
+        umv_gemm_args gr;
+        std::memset(&gr, 0, sizeof gr);
+        gr.x = dummy16; gr.wp = dummy16; gr.out = dummy16; gr.ldx = 64; gr.ldo = 64; gr.M = 1; gr.N = 64; gr.K = 64;
+        EXPECT_ERR(umv_gemm_bf16_rows(nullptr, rows, nullptr));
+        EXPECT_ERR(umv_gemm_fp8w_rows(nullptr, rows, nullptr));
+        EXPECT_ERR(umv_gemm_z13w_rows(nullptr, dummy8, rows, nullptr));
+        EXPECT_ERR(umv_gemm_bf16_rows(&gr, rows, nullptr));      // the table without argmax_partial
+        EXPECT_ERR(umv_gemm_fp8w_rows(&gr, rows, nullptr));
+        EXPECT_ERR(umv_gemm_z13w_rows(&gr, dummy8, rows, nullptr));
+        gr.argmax_partial = (uint64_t*)dummyl;
+        EXPECT_ERR(umv_gemm_bf16_rows(&gr, nullptr, nullptr));   // no table
+        gr.sample_temperature = 0.7f;                            // next to a scalar temperature
+        EXPECT_ERR(umv_gemm_bf16_rows(&gr, rows, nullptr));
+        EXPECT_ERR(umv_gemm_fp8w_rows(&gr, rows, nullptr));
+        gr.sample_temperature = 0.f; gr.M = 65;                  // above 64 rows
+        EXPECT_ERR(umv_gemm_bf16_rows(&gr, rows, nullptr));
+        EXPECT_ERR(umv_gemm_z13w_rows(&gr, dummy8, rows, nullptr));
+    }
     // logit penalties
     EXPECT_ERR(umv_logit_penalty_bf16(nullptr, nullptr));
     umv_logit_penalty_args lp;
@@ -211,7 +243,9 @@ static void bad_arguments() {
     EXPECT_ERR(umv_logit_penalty_bf16(&lp, nullptr));
     lp.n_static = 2; lp.argmax_partial = (uint64_t*)dummyl; lp.n_tiles = 3;     // 64 columns are not 3 tiles
     EXPECT_ERR(umv_logit_penalty_bf16(&lp, nullptr));
-    lp.n_tiles = 4; lp.M = 0;
+    lp.n_tiles = 4; lp.rows = rows;                              // non-neutral scalars (r = 1.1) next to the per-row table
+    EXPECT_ERR(umv_logit_penalty_bf16(&lp, nullptr));
+    lp.rows = nullptr; lp.M = 0;
     EXPECT_OK(umv_logit_penalty_bf16(&lp, nullptr));             // no rows
     EXPECT_ERR(umv_timestep_embed(nullptr, nullptr, nullptr, 4, 128, nullptr));
     EXPECT_ERR(umv_cfg_renorm_euler(nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 1, 4.0f, 1.5f, 0.f, 0, 0.1f, 64, nullptr));

@@ -71,7 +71,16 @@ class LogitPenaltyArgs(C.Structure):
         ("list_len", C.c_void_p), ("bias", C.c_void_p), ("M", C.c_int), ("V", C.c_int), ("cap", C.c_int), ("n_static", C.c_int),
         ("repetition_penalty", C.c_float), ("presence_penalty", C.c_float), ("frequency_penalty", C.c_float),
         ("temperature", C.c_float), ("argmax_partial", C.c_void_p), ("lse_partial", C.c_void_p), ("n_tiles", C.c_int),
-        ("seed", C.c_uint64), ("step", C.c_void_p),
+        ("seed", C.c_uint64), ("step", C.c_void_p), ("rows", C.c_void_p),
+    ]
+
+
+class RowSampling(C.Structure):
+    """umv_row_sampling: one row of the per-row sampling table (device memory; sampling.ROW_DTYPE is the same layout for numpy)"""
+    _fields_ = [
+        ("seed", C.c_uint64), ("draw", C.c_int64), ("stream", C.c_uint32), ("temperature", C.c_float), ("top_k", C.c_int32),
+        ("top_p", C.c_float), ("min_p", C.c_float), ("repetition_penalty", C.c_float), ("presence_penalty", C.c_float),
+        ("frequency_penalty", C.c_float),
     ]
 
 
@@ -99,6 +108,9 @@ _SIGS = {
     "umv_quantize_pack_weight_fp8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_int, C.c_int, C.c_void_p]),
     "umv_gemm_fp8w": (C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
+    "umv_gemm_bf16_rows": (C.c_int, [C.POINTER(GemmArgs), C.c_void_p, C.c_void_p]),
+    "umv_gemm_fp8w_rows": (C.c_int, [C.POINTER(GemmArgs), C.c_void_p, C.c_void_p]),
+    "umv_gemm_z13w_rows": (C.c_int, [C.POINTER(GemmArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
     "umv_packed_weight_mxfp4_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "umv_quantize_pack_weight_mxfp4": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                                  C.c_void_p]),
@@ -140,6 +152,9 @@ _SIGS = {
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                                                 C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                                 C.c_void_p]),
+    "umv_decode_step_end_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "umv_logit_penalty_bf16": (C.c_int, [C.POINTER(LogitPenaltyArgs), C.c_void_p]),
     "umv_timestep_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "umv_cfg_renorm_euler": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,

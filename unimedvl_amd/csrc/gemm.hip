@@ -26,11 +26,21 @@ template <int MB, int NT, int U, bool DB, int NORM, int XL = 0>   // NORM: 0 = o
 __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(umv_gemm_args a, int KT, int NTT) {
     gemm_skinny_body<SkBf16<NT>, MB, U, DB, NORM, XL>(a, KT, NTT, 0);
 }
+// the lm_head call with a per-row sampling table (umv_gemm_bf16_rows): the same body, the epilogue's keys and statistics per row
+template <int MB, int NT, int U, bool DB, int XL = 0>
+__global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_rows_kernel(umv_gemm_args a, int KT, int NTT, const umv_row_sampling* rows) {
+    gemm_skinny_body<SkBf16<NT>, MB, U, DB, 0, XL, true>(a, KT, NTT, 0, rows);
+}
 
 template <int MB, int NT, int U, bool DB, int NORM>
 static int launch_skinny(const umv_gemm_args& a, int KT, int NTT, hipStream_t s) {
     return launch_skinny_body<MB, NT, U, 1, NORM>([](auto XL) { return &gemm_skinny_kernel<MB, NT, U, DB, NORM, decltype(XL)::value>; }, a, KT,
                                                   NTT, s, KT, NTT);
+}
+template <int MB, int NT, int U, bool DB>
+static int launch_skinny_rows(const umv_gemm_args& a, int KT, int NTT, hipStream_t s, const umv_row_sampling* rows) {
+    return launch_skinny_body<MB, NT, U, 1, 0>([](auto XL) { return &gemm_skinny_rows_kernel<MB, NT, U, DB, decltype(XL)::value>; }, a, KT, NTT,
+                                               s, KT, NTT, rows);
 }
 
 // ----------------------------------------------------------------------------- fp8 weights (decode, BASELINE.json configs[4])
@@ -50,14 +60,24 @@ template <int MB, int NT, int U, int XL = 0>
 __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny8_kernel(umv_gemm_args a, int KT8, int NTT) {
     gemm_skinny_body<SkE4m3<NT>, MB, U, true, 0, XL>(a, KT8, NTT, 0);
 }
+template <int MB, int NT, int U, int XL = 0>      // the lm_head call with a per-row sampling table (umv_gemm_fp8w_rows)
+__global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny8_rows_kernel(umv_gemm_args a, int KT8, int NTT, const umv_row_sampling* rows) {
+    gemm_skinny_body<SkE4m3<NT>, MB, U, true, 0, XL, true>(a, KT8, NTT, 0, rows);
+}
 
 template <int MB, int NT, int U>
 static int launch_skinny8(const umv_gemm_args& a, int KT8, int NTT, hipStream_t s) {
     return launch_skinny_body<MB, NT, U, 2, 0>([](auto XL) { return &gemm_skinny8_kernel<MB, NT, U, decltype(XL)::value>; }, a, KT8, NTT, s,
                                                KT8, NTT);
 }
+template <int MB, int NT, int U>
+static int launch_skinny8_rows(const umv_gemm_args& a, int KT8, int NTT, hipStream_t s, const umv_row_sampling* rows) {
+    return launch_skinny_body<MB, NT, U, 2, 0>([](auto XL) { return &gemm_skinny8_rows_kernel<MB, NT, U, decltype(XL)::value>; }, a, KT8, NTT, s,
+                                               KT8, NTT, rows);
+}
 
-extern "C" int umv_gemm_fp8w(const umv_gemm_args* ap, umv_stream_t stream) {
+// rows: the per-row sampling table of umv_gemm_fp8w_rows (checked there), NULL for umv_gemm_fp8w
+static int gemm_fp8w(const umv_gemm_args* ap, const umv_row_sampling* rows, umv_stream_t stream) {
     UMV_CHECK(ap != nullptr, UMV_ERR_ARG, "gemm_fp8w: null args");
     umv_gemm_args a = *ap;
     UMV_CHECK(a.x && a.wp && a.out && a.w_scale, UMV_ERR_ARG, "gemm_fp8w: null pointer (x, wp, out and w_scale are required)");
@@ -73,6 +93,11 @@ extern "C" int umv_gemm_fp8w(const umv_gemm_args* ap, umv_stream_t stream) {
         return launch_skinny8<4, 4, 1>(a, KT8, NTT, s);
     }
     const bool two = (a.epilogue & UMV_EPI_SWIGLU) || NTT >= 1024;
+    if (rows) {    // the lm_head call with a per-row table: the shapes below, instantiated with the per-row epilogue
+        if (a.M <= 16) return two ? launch_skinny8_rows<1, 2, 2>(a, KT8, NTT, s, rows) : launch_skinny8_rows<1, 1, 8>(a, KT8, NTT, s, rows);
+        if (a.M <= 32) return two ? launch_skinny8_rows<2, 4, 1>(a, KT8, NTT, s, rows) : launch_skinny8_rows<2, 1, 4>(a, KT8, NTT, s, rows);
+        return two ? launch_skinny8_rows<4, 4, 1>(a, KT8, NTT, s, rows) : launch_skinny8_rows<4, 1, 2>(a, KT8, NTT, s, rows);
+    }
     // (NT, U) from a sweep on MI355X at M = 8 (tools/skinny_bench.py, FP8=1): gate/up 25.5 us with <2,2> (110 VGPRs, two
     // workgroups per CU) vs 33.9 <2,4>, 27.9 <4,1>; down_proj 18.2 us with <1,8> vs 23.7 for NT = 2 (only 112 workgroups)
     if (a.M <= 16) return two ? launch_skinny8<1, 2, 2>(a, KT8, NTT, s) : launch_skinny8<1, 1, 8>(a, KT8, NTT, s);
@@ -80,6 +105,13 @@ extern "C" int umv_gemm_fp8w(const umv_gemm_args* ap, umv_stream_t stream) {
     if (two && nt4) return a.M <= 32 ? launch_skinny8<2, 4, 1>(a, KT8, NTT, s) : launch_skinny8<4, 4, 1>(a, KT8, NTT, s);
     if (a.M <= 32) return two ? launch_skinny8<2, 2, 2>(a, KT8, NTT, s) : launch_skinny8<2, 1, 4>(a, KT8, NTT, s);
     return two ? launch_skinny8<4, 2, 1>(a, KT8, NTT, s) : launch_skinny8<4, 1, 2>(a, KT8, NTT, s);
+}
+
+extern "C" int umv_gemm_fp8w(const umv_gemm_args* ap, umv_stream_t stream) { return gemm_fp8w(ap, nullptr, stream); }
+extern "C" int umv_gemm_fp8w_rows(const umv_gemm_args* ap, const umv_row_sampling* rows, umv_stream_t stream) {
+    UMV_CHECK(ap != nullptr, UMV_ERR_ARG, "gemm_fp8w_rows: null args");
+    if (const int rc = umv_gemm_check_rows(*ap, rows, "gemm_fp8w_rows")) return rc;
+    return gemm_fp8w(ap, rows, stream);
 }
 
 // ----------------------------------------------------------------------------- tiled (M > 64): gemm_tiled.h
@@ -164,7 +196,8 @@ extern "C" int umv_gemm_tile_config(int M, int N, int K) {
     return 64;
 }
 
-extern "C" int umv_gemm_bf16(const umv_gemm_args* ap, umv_stream_t stream) {
+// rows: the per-row sampling table of umv_gemm_bf16_rows (checked there), NULL for umv_gemm_bf16
+static int gemm_bf16(const umv_gemm_args* ap, const umv_row_sampling* rows, umv_stream_t stream) {
     UMV_CHECK(ap != nullptr, UMV_ERR_ARG, "gemm: null args");
     umv_gemm_args a = *ap;
     UMV_CHECK(a.x && a.wp && a.out, UMV_ERR_ARG, "gemm: null pointer");
@@ -211,6 +244,13 @@ extern "C" int umv_gemm_bf16(const umv_gemm_args* ap, umv_stream_t stream) {
         // (33..64 rows on a tiled kernel over the K ranges - 128 x 64 full-line or UMV_SPLITK_TILED_MIN=33 - measured 6.25 / 6.45 ms per
         // 64-sample step against 5.41: the weight-streaming kernel stays)
         return launch_skinny<4, 4, 1, true, 0>(a, KT, NTT, s);
+    }
+    if (rows) {    // the lm_head call with a per-row sampling table (M <= 64, 16-row image, no split - checked above): the default
+        // policy's shapes below, instantiated with the per-row epilogue.  The bits of a GEMM do not depend on the grouping.
+        const bool two = NTT >= 1024;
+        if (a.M <= 16) return two ? launch_skinny_rows<1, 2, 4, true>(a, KT, NTT, s, rows) : launch_skinny_rows<1, 1, 8, true>(a, KT, NTT, s, rows);
+        if (a.M <= 32) return two ? launch_skinny_rows<2, 4, 2, true>(a, KT, NTT, s, rows) : launch_skinny_rows<2, 1, 4, false>(a, KT, NTT, s, rows);
+        return two ? launch_skinny_rows<4, 4, 1, true>(a, KT, NTT, s, rows) : launch_skinny_rows<4, 1, 4, false>(a, KT, NTT, s, rows);
     }
     if (a.M <= 64 && (a.M <= skinny_max || TH != 16)) {
         const bool two = (a.epilogue & UMV_EPI_SWIGLU) || NTT >= 1024;
@@ -294,4 +334,11 @@ extern "C" int umv_gemm_bf16(const umv_gemm_args* ap, umv_stream_t stream) {
     case 370: return launch_tiled<2, 2, 4, 4, 1, 4, 3>(a, KT, NTT, s);
     default: return launch_tiled<2, 2, 4, 2, 2, 3>(a, KT, NTT, s);       // 64: 128(n) x 64(m) x 64, 3 buffers (72 KiB)
     }
+}
+
+extern "C" int umv_gemm_bf16(const umv_gemm_args* ap, umv_stream_t stream) { return gemm_bf16(ap, nullptr, stream); }
+extern "C" int umv_gemm_bf16_rows(const umv_gemm_args* ap, const umv_row_sampling* rows, umv_stream_t stream) {
+    UMV_CHECK(ap != nullptr, UMV_ERR_ARG, "gemm_bf16_rows: null args");
+    if (const int rc = umv_gemm_check_rows(*ap, rows, "gemm_bf16_rows")) return rc;
+    return gemm_bf16(ap, rows, stream);
 }

@@ -62,11 +62,14 @@ __device__ __forceinline__ float epi_gumbel_value(float logit, float temp, uint6
 // The lane holds columns n0..n0+3 of row m of tile `tile` (lanes l, l^16, l^32, l^48 share the row): reduce the tile's 16
 // columns and let the first lane group write partial[m][tile].  `final` are the values epi_store4 stored (bf16-exact).
 // Must be called by ALL lanes of the wave (shuffles); lanes without a valid element pass valid = false.
-__device__ __forceinline__ void epi_argmax_tile(uint64_t* __restrict__ partial, int64_t ld_partial, int m, int tile, int lane, bool valid,
-                                                int n0, int nend, const float* final, float temp = 0.f, uint64_t seed = 0, const int64_t* step_ptr = nullptr) {
+// The row's key comes from `rk`, a callable evaluated only by a valid lane of a sampled row (temp may differ from lane to lane: the
+// per-row table gives every row its own; the branch is per lane, the shuffles are not).
+template <class RowKey>
+__device__ __forceinline__ void epi_argmax_tile_keyed(uint64_t* __restrict__ partial, int64_t ld_partial, int m, int tile, int lane, bool valid,
+                                                      int n0, int nend, const float* final, float temp, RowKey rk) {
     uint64_t key = 0;
     if (valid) {
-        const uint64_t row_key = temp > 0.f ? sample_row_key(seed, step_ptr, m) : 0ull;
+        const uint64_t row_key = temp > 0.f ? rk() : 0ull;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             if (n0 + j < nend) {
@@ -80,6 +83,18 @@ __device__ __forceinline__ void epi_argmax_tile(uint64_t* __restrict__ partial, 
     o = shfl_xor_u64(key, 32);
     key = o > key ? o : key;
     if (valid && (lane >> 4) == 0) partial[(int64_t)m * ld_partial + tile] = key;
+}
+__device__ __forceinline__ void epi_argmax_tile(uint64_t* __restrict__ partial, int64_t ld_partial, int m, int tile, int lane, bool valid,
+                                                int n0, int nend, const float* final, float temp = 0.f, uint64_t seed = 0, const int64_t* step_ptr = nullptr) {
+    epi_argmax_tile_keyed(partial, ld_partial, m, tile, lane, valid, n0, nend, final, temp, [&] { return sample_row_key(seed, step_ptr, m); });
+}
+// Row m's temperature (0 for a greedy row) and row key from the per-row table (include/unimedvl_hip.h, umv_row_sampling)
+__device__ __forceinline__ float row_sampling_temp(const umv_row_sampling* __restrict__ rows, int m) {
+    const float t = rows[m].temperature;
+    return t > 0.f ? t : 0.f;
+}
+__device__ __forceinline__ uint64_t row_sampling_key(const umv_row_sampling* __restrict__ rows, int m) {
+    return sample_row_key_of(rows[m].seed, (uint64_t)rows[m].draw, (uint64_t)rows[m].stream);
 }
 // The softmax statistics of the same tile for the token log-probability (include/unimedvl_hip.h, lse_partial), called where
 // epi_argmax_tile is and with its arguments: y = the value the keys order without the noise (token_pick.h::pick_value), m_t its

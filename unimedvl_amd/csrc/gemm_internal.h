@@ -106,6 +106,13 @@ static inline int umv_gemm_check_args(const umv_gemm_args& a, const char* who, i
     UMV_CHECK(!a.lse_partial || a.argmax_partial, UMV_ERR_ARG, "%s: lse_partial rides on the argmax_partial epilogue and needs it set", who);
     return UMV_OK;
 }
+// The *_rows entries (the lm_head call with a per-row sampling table), after the null checks of the entry without the table
+static inline int umv_gemm_check_rows(const umv_gemm_args& a, const umv_row_sampling* rows, const char* who) {
+    UMV_CHECK(rows && ((uintptr_t)rows % 16) == 0 && a.argmax_partial && a.M >= 0 && a.M <= 64 && a.sample_temperature == 0.f, UMV_ERR_ARG,
+              "%s: the per-row sampling table (16-byte aligned) needs argmax_partial, M <= 64 (got %d) and sample_temperature == 0 (got %g)",
+              who, a.M, (double)a.sample_temperature);
+    return UMV_OK;
+}
 
 // The decode-layout checks of the weight-streaming entry points (umv_gemm_fp8w / _mxfp4w / _z13w), after umv_gemm_check_args.  `image` and
 // `instead` word the M <= 64 message; amax: the entry has the argmax / sampling-key epilogue; temperature: it also checks the sampling

@@ -217,10 +217,13 @@ struct SkZ13 {        // head H[NPT][16 B] = (flags u64, base u8, 0...), then (2
 // Every wave parks its NT x MB accumulator fragments in `red` ([NW waves][NT*MB][64] f32x4), the sums run in wave order 0..NW-1, then
 // bias / activation / residual / SwiGLU (with the argmax / sampling keys of the lm_head) or, for split-K (nsplit > 1), the raw fp32
 // partial sums of split blockIdx.y.  Tiles of TH rows (TH < 16: the exact-partition bf16 images).  The caller has made `red` free (no
-// wave still reads its x staging there).
-template <int NW, int NT, int MB>
+// wave still reads its x staging there).  ROWS: the lm_head keys and statistics take every row's temperature and sampling key from the
+// per-row table `rows` (include/unimedvl_hip.h, umv_row_sampling; a kernel argument of its own behind umv_gemm_args) - instantiations of
+// their own (gemm.hip, gemm_z13.hip: the shapes an lm_head call reaches), so that no other kernel's code, arguments or registers move.
+template <int NW, int NT, int MB, bool ROWS = false>
 __device__ __forceinline__ void skinny16_reduce_epilogue(const umv_gemm_args& a, float* red, const f32x4 (&acc)[NT][MB], int tid,
-                                                         int lane, int wave, int nt0, int NTT, int nsplit, int TH) {
+                                                         int lane, int wave, int nt0, int NTT, int nsplit, int TH,
+                                                         const umv_row_sampling* __restrict__ rows = nullptr) {
     constexpr int E4 = NT * MB;
 #pragma unroll
     for (int t = 0; t < NT; ++t)
@@ -272,7 +275,15 @@ __device__ __forceinline__ void skinny16_reduce_epilogue(const umv_gemm_args& a,
                 et.N = nend;
                 epi_store4(et, orow, n0, s.x, s.y, s.z, s.w, fin);
             }
-            if (a.argmax_partial && nt0 + t < NTT) { // wave-uniform: greedy argmax rides on the lm_head epilogue
+            if constexpr (ROWS) {
+                if (a.argmax_partial && nt0 + t < NTT) {   // wave-uniform; row m's own temperature and (seed, draw, stream): a greedy and
+                    // a sampled row may sit in one fragment - the branch on temp is per lane, the shuffles are everyone's
+                    const float temp = valid ? row_sampling_temp(rows, m) : 0.f;
+                    epi_argmax_tile_keyed(a.argmax_partial, NTT, m, nt0 + t, l, valid, n0, nend, fin, temp,
+                                          [&] { return row_sampling_key(rows, m); });
+                    if (a.lse_partial) epi_lse_tile(a.lse_partial, NTT, m, nt0 + t, l, valid, n0, nend, fin, temp);
+                }
+            } else if (a.argmax_partial && nt0 + t < NTT) { // wave-uniform: greedy argmax rides on the lm_head epilogue
                 epi_argmax_tile(a.argmax_partial, NTT, m, nt0 + t, l, valid, n0, nend, fin, a.sample_temperature, a.sample_seed, a.sample_step);
                 if (a.lse_partial) epi_lse_tile(a.lse_partial, NTT, m, nt0 + t, l, valid, n0, nend, fin, a.sample_temperature);   // and the softmax statistics
             }
@@ -296,8 +307,8 @@ struct SkBuf {
     u32x4 xp[XL ? U * F::KH / 2 : 1][XL == 1 ? 1 : (XL ? 2 * MB : 1)];     // XL: the x pieces of the chunk's lines on their way to LDS
 };
 
-template <class F, int MB, int U, bool DB, int NORM, int XL>   // NORM: 0 = off, 8 / 16 = fused RMSNorm keeping that many x rows
-__device__ __forceinline__ void gemm_skinny_body(const umv_gemm_args& a, int KT, int NTT, int NPT) {
+template <class F, int MB, int U, bool DB, int NORM, int XL, bool ROWS = false>   // NORM: 0 = off, 8 / 16 = fused RMSNorm keeping that many x rows
+__device__ __forceinline__ void gemm_skinny_body(const umv_gemm_args& a, int KT, int NTT, int NPT, const umv_row_sampling* rows = nullptr) {
     constexpr int NT = F::NT, KH = F::KH;
     extern __shared__ __attribute__((aligned(16))) float red[];  // [SK_WAVES][NT*MB*4][64] (+ norm partials and x) / XL staging
     const int tid = threadIdx.x;
@@ -515,7 +526,7 @@ __device__ __forceinline__ void gemm_skinny_body(const umv_gemm_args& a, int KT,
         }
     }
     if constexpr (XL != 0) __syncthreads();      // the reduction buffer overlays the waves' x staging KiBs: everyone has left the main loop
-    skinny16_reduce_epilogue<SK_WAVES, NT, MB>(a, red, acc, tid, lane, wave, nt0, NTT, nsplit, f.TH);
+    skinny16_reduce_epilogue<SK_WAVES, NT, MB, ROWS>(a, red, acc, tid, lane, wave, nt0, NTT, nsplit, f.TH, rows);
 }
 
 // ----------------------------------------------------------------------------- launcher

@@ -39,9 +39,13 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
     x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
     return x ^ (x >> 31);
 }
+// The three words of a row key: the scalar entries pass (seed, *step, row index), the per-row table (include/unimedvl_hip.h,
+// umv_row_sampling) a row's own (seed, draw, stream) - the same function, so equal words name the same draws on either path.
+__device__ __forceinline__ uint64_t sample_row_key_of(uint64_t seed, uint64_t step, uint64_t stream) {
+    return splitmix64(seed ^ (step * 0xD1B54A32D192ED03ull) ^ (stream << 32));
+}
 __device__ __forceinline__ uint64_t sample_row_key(uint64_t seed, const int64_t* step_ptr, int m) {
-    const uint64_t step = step_ptr ? (uint64_t)step_ptr[0] : 0ull;
-    return splitmix64(seed ^ (step * 0xD1B54A32D192ED03ull) ^ ((uint64_t)m << 32));
+    return sample_row_key_of(seed, step_ptr ? (uint64_t)step_ptr[0] : 0ull, (uint64_t)m);
 }
 // u = (r + 0.5) 2^-23 with r the top 23 bits of the hash: in [2^-24, 1 - 2^-24], strictly inside (0, 1), and exact in fp32
 // (r + 0.5 needs 24 bits), so -ln(u) is a finite, positive Exp(1) draw and a column can only win through its logit - with u = 1

@@ -167,14 +167,17 @@ __device__ __forceinline__ uint64_t strided_max_key(const uint64_t* __restrict__
 // S = sum s_t exp(m_t - ref).  Two passes over the 8 n_tiles bytes (L2 resident: the GEMM has just written them), each thread-strided
 // by T, then the wave tree, then the waves in order (block_reduce.h) - a fixed order for a given T, so a sample's bits do not depend
 // on the batch it sits in.  A tile of -inf only is (-inf, 0) and adds 0 * exp(-inf) = 0; a NaN s_t makes S NaN.  smf: one float per wave.
-template <int T>
+// TA < T: only the first TA threads take tiles, in TA's order - the other waves add +0 behind them, so a workgroup of T threads gets
+// the bits a workgroup of TA threads gets (the per-row step end runs the 256-thread kernels' merge in its 512 threads).
+template <int T, int TA = T>
 __device__ __forceinline__ void merge_tile_stats(const umv_f32x2* __restrict__ st, int n_tiles, float* smf, float& ref, float& S) {
+    const int c_first = (TA == T || (int)threadIdx.x < TA) ? (int)threadIdx.x : n_tiles;
     float M = -INFINITY;
-    for (int c = threadIdx.x; c < n_tiles; c += T) M = fmaxf(M, st[c].x);
+    for (int c = c_first; c < n_tiles; c += TA) M = fmaxf(M, st[c].x);
     M = block_reduce_max(M, smf);
     ref = softmax_ref(M);
     S = 0.f;
-    for (int c = threadIdx.x; c < n_tiles; c += T) {
+    for (int c = c_first; c < n_tiles; c += TA) {
         const umv_f32x2 v = st[c];
         S += v.y * expf(v.x - ref);
     }
@@ -387,6 +390,68 @@ extern "C" int umv_decode_step_end_truncated(int32_t* tok_slot, int32_t* tok_pos
     if (B == 0) return UMV_OK;
     hipLaunchKernelGGL(decode_step_end_truncated_kernel, dim3(B), dim3(TR_THREADS), 0, (hipStream_t)stream, e, argmax_partial, lse_partial,
                        n_tiles, logits, ldo, V, temperature, seed, top_k, top_p, min_p, forced_ids, logprob, cut_y, n_kept);
+    UMV_LAUNCH_CHECK();
+    return UMV_OK;
+}
+
+// ----------------------------------------------------------------------------- per-row sampling parameters (include/unimedvl_hip.h)
+// The step end of a step whose rows carry their own sampler (umv_row_sampling): per workgroup - uniformly - either
+// decode_step_end_truncated_kernel's path with the row's temperature, filters and (seed, draw, stream), or the key maximum of
+// decode_step_end_logprob_kernel (a greedy row, or a sampled one with no filter on), its statistics merged in that kernel's 256-thread
+// order.  Thread 0 then advances the row's own draw counter: the one word of the table this launch writes, read by nobody else in it.
+__global__ __launch_bounds__(TR_THREADS) void decode_step_end_rows_kernel(StepEnd e, const uint64_t* __restrict__ part,
+                                                                          const float* __restrict__ lse, int n_tiles,
+                                                                          const bf16_t* __restrict__ logits, int64_t ldo, int V,
+                                                                          umv_row_sampling* rows, const int64_t* __restrict__ forced,
+                                                                          float* logprob, float* cut_y, int32_t* n_kept) {
+    __shared__ uint32_t hist[TR_BINS];
+    __shared__ TruncShared sh;
+    const int b = blockIdx.x;
+    const int64_t s = e.step_idx[b];
+    const bf16_t* row = logits + (int64_t)b * ldo;
+    const float temp = row_sampling_temp(rows, b);
+    const int top_k = rows[b].top_k;
+    const float top_p = rows[b].top_p, min_p = rows[b].min_p;
+    const int64_t draw = rows[b].draw;
+    const bool truncated = temp > 0.f && (top_k > 0 || top_p < 1.f || min_p > 0.f);       // the same in every thread
+    float cut = -INFINITY;
+    uint32_t floor_key = 0u, kept = (uint32_t)V;
+    if (truncated) truncation_cutoff(row, V, temp, top_k, top_p, min_p, hist, sh, cut, floor_key, kept);
+    uint64_t best = block_max_u64<TR_THREADS, true>(strided_max_key<TR_THREADS>(part + (int64_t)b * n_tiles, n_tiles), sh.wbest);
+    if (truncated) {
+        const int64_t fused = argmax_key_column(best);
+        const bool fused_kept = fused >= 0 && fused < V && class_key(bf2f(row[fused])) >= floor_key;
+        __syncthreads();                 // wbest has been read
+        if (!fused_kept)
+            best = kept_gumbel_max(row, V, temp, sample_row_key_of(rows[b].seed, (uint64_t)draw, (uint64_t)rows[b].stream), floor_key, sh);
+    }
+    float ref = 0.f, S = 0.f;
+    if (logprob) {
+        const umv_f32x2* st = reinterpret_cast<const umv_f32x2*>(lse) + (int64_t)b * n_tiles;
+        if (truncated) merge_tile_stats<TR_THREADS>(st, n_tiles, sh.smf, ref, S);
+        else merge_tile_stats<TR_THREADS, 256>(st, n_tiles, sh.smf, ref, S);
+    }
+    if (threadIdx.x == 0) {
+        step_end_finish(e, b, s, argmax_key_column(best), forced, {row, V, temp, ref, S, logprob}, {cut, kept, cut_y, n_kept});
+        rows[b].draw = draw + 1;
+    }
+}
+
+extern "C" int umv_decode_step_end_rows(int32_t* tok_slot, int32_t* tok_pos, int32_t* kv_len, const uint64_t* argmax_partial,
+                                        const float* lse_partial, int n_tiles, int64_t* ids, int64_t* in_ids, int64_t* pred_ids,
+                                        int64_t* step_idx, const uint16_t* logits, int64_t ldo, int V, const int64_t* forced_ids,
+                                        float* logprob, int B, int max_len, umv_row_sampling* rows, float* cut_y, int32_t* n_kept,
+                                        umv_stream_t stream) {
+    const StepEnd e{tok_slot, tok_pos, kv_len, ids, in_ids, pred_ids, step_idx, B, max_len};
+    if (int rc = step_end_args_ok("decode_step_end_rows", e, argmax_partial, n_tiles, logits && B >= 0)) return rc;
+    UMV_CHECK(rows && ((uintptr_t)rows % 16) == 0, UMV_ERR_ARG, "decode_step_end_rows: rows (the per-row sampling table) must be set and "
+              "16-byte aligned");
+    UMV_CHECK((logprob != nullptr) == (lse_partial != nullptr), UMV_ERR_ARG,
+              "decode_step_end_rows: logprob and lse_partial go together (both or neither)");
+    if (int rc = tile_columns_ok("decode_step_end_rows", V, n_tiles, ldo)) return rc;
+    if (B == 0) return UMV_OK;
+    hipLaunchKernelGGL(decode_step_end_rows_kernel, dim3(B), dim3(TR_THREADS), 0, (hipStream_t)stream, e, argmax_partial, lse_partial,
+                       n_tiles, logits, ldo, V, rows, forced_ids, logprob, cut_y, n_kept);
     UMV_LAUNCH_CHECK();
     return UMV_OK;
 }

@@ -24,6 +24,7 @@ import os
 import torch
 
 from . import _lib, ops
+from . import sampling as sampling_mod
 from .kvcache import NaiveCache
 
 BF16 = torch.bfloat16
@@ -38,7 +39,8 @@ class DecodeSession:
     def __init__(self, llm, cache: NaiveCache, start_tokens, positions, max_length, use_graph=True, nsplit=None,
                  do_sample=False, temperature=1.0, seed=0, logprobs=False, forced_ids=None, *,
                  repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, penalty_context_ids=None,
-                 penalty_context_room=None, penalty_history=None, top_k=0, top_p=1.0, min_p=0.0):
+                 penalty_context_room=None, penalty_history=None, row_sampling=None, row_streams=None, row_penalties=False,
+                 top_k=0, top_p=1.0, min_p=0.0):
         """logprobs: also record pred_logprobs (fp32 [max_length, B]) - row s is the log-probability of in_ids[s + 1], the token step s
         picked (include/unimedvl_hip.h, token log-probabilities: of softmax(logits) in greedy decoding, of softmax(bf16(logits / T))
         when sampling).  forced_ids (int64 [max_length, B]): where an entry is >= 0 that token is fed to the next step instead of the
@@ -57,19 +59,38 @@ class DecodeSession:
         it.  penalty_context_room: context tokens per slot to reserve for later set_slot calls (default: the longest list given) -
         keep it at what the prompts need: the kernel walks the whole reservation of every row at every step;
         penalty_history: distinct generated tokens per slot to reserve (default max_length - more when requests outlive a round of
-        max_length steps).  All neutral: today's step, launch for launch, no buffer allocated.  Works on the unfused step too."""
+        max_length steps).  All neutral: today's step, launch for launch, no buffer allocated.  Works on the unfused step too.
+        row_sampling (a list of B sampling.SamplingParams): per-row sampling parameters (include/unimedvl_hip.h) - every sample decodes
+        with its OWN sampler, penalties and sampling key inside the one captured step: the session owns a table of B 48-byte rows in
+        device memory, the lm_head epilogue, the penalty kernel and umv_decode_step_end_rows read it.  Excludes the scalar keywords
+        above (do_sample, temperature, top_k / top_p / min_p, the three penalties); `seed` is the seed of the rows whose params carry
+        none, logit_bias stays session-wide.  row_streams: the `stream` word of every row's key (default: the row index - the scalar
+        session's keying); a row's draw counter starts at 0, advances by one per step and is NOT rewound by rewind_outputs.
+        set_slot(b, ..., sampling=, stream=, draw=) gives a slot new parameters between replays without a re-capture.  pred_cut_y /
+        pred_n_kept are always recorded (a row without a filter: -inf / vocab).  The penalty buffers are allocated only if a row is
+        not neutral, a bias is given, or row_penalties=True reserves them for later set_slot calls.  Rides on the fused step end
+        (B <= 64).  Without row_sampling nothing is allocated and the step is today's, launch for launch."""
+        if row_sampling is not None:
+            given = dict(do_sample=do_sample is not False, temperature=temperature != 1.0, top_k=top_k != 0, top_p=top_p != 1.0,
+                         min_p=min_p != 0.0, repetition_penalty=repetition_penalty != 1.0, presence_penalty=presence_penalty != 0.0,
+                         frequency_penalty=frequency_penalty != 0.0)
+            if any(given.values()):
+                raise ValueError(f"row_sampling excludes the scalar sampler keywords (got {[k for k, v in given.items() if v]})")
+        elif row_streams is not None or row_penalties:
+            raise ValueError("row_streams / row_penalties go with row_sampling")
         with ops.device_scope(llm.device):
             self._init(llm, cache, start_tokens, positions, max_length, use_graph, nsplit, do_sample, temperature, seed, logprobs,
                        forced_ids, top_k, top_p, min_p,
                        dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
-                            logit_bias=logit_bias, context=penalty_context_ids, room=penalty_context_room, history=penalty_history))
+                            logit_bias=logit_bias, context=penalty_context_ids, room=penalty_context_room, history=penalty_history),
+                       dict(params=row_sampling, streams=row_streams, reserve=bool(row_penalties)))
 
     @property
     def device(self):
         return self.dev
 
     def _init(self, llm, cache, start_tokens, positions, max_length, use_graph, nsplit, do_sample, temperature, seed, logprobs=False,
-              forced_ids=None, top_k=0, top_p=1.0, min_p=0.0, penalties=None):
+              forced_ids=None, top_k=0, top_p=1.0, min_p=0.0, penalties=None, rows=None):
         cfg, dev = llm.cfg, llm.device
         self.llm, self.cache, self.cfg, self.dev = llm, cache, cfg, dev
         B = len(cache.lens)
@@ -164,6 +185,19 @@ class DecodeSession:
             need_fused("top_k / top_p / min_p")
             self.pred_cut_y = torch.zeros((max_length, B), dtype=torch.float32, device=dev)
             self.pred_n_kept = torch.zeros((max_length, B), dtype=torch.int32, device=dev)
+        # per-row sampling parameters: the table the lm_head epilogue, the penalty kernel and the step end read
+        self.row_table = self.row_params = self.row_streams = None
+        rows = rows or {}
+        if rows.get("params") is not None:
+            need_fused("row_sampling")
+            params = list(rows["params"])
+            streams = list(range(B)) if rows.get("streams") is None else [int(v) for v in rows["streams"]]
+            if len(params) != B or len(streams) != B:
+                raise ValueError(f"row_sampling / row_streams must hold one entry per sample ({B}), got {len(params)} / {len(streams)}")
+            self.row_params, self.row_streams = params, streams
+            self.row_table = sampling_mod.to_tensor(sampling_mod.pack(params, seed=int(seed), streams=streams), dev)
+            self.pred_cut_y = torch.zeros((max_length, B), dtype=torch.float32, device=dev)
+            self.pred_n_kept = torch.zeros((max_length, B), dtype=torch.int32, device=dev)
         w = llm.w
         # K splits of the QKV / o / down GEMMs: "q,o,d" (1 = that GEMM is not split), "0" = none, "auto" by batch / weights.
         # Measured on MI355X (bench.py --batch B, ms per step), no split -> 3,4,4:
@@ -214,10 +248,14 @@ class DecodeSession:
             if self.logprobs or self.truncated:
                 self.lm_head_kw["lse_partial"] = self.lse_part
             self.lm_head_kw["sample"] = (self.temperature, self.seed, self.step_idx) if self.do_sample else None
+            if self.row_table is not None:
+                self.lm_head_kw["sample_rows"] = self.row_table
         # (a name, not a bound method: a session that refers to itself is freed by the cycle collector only - at any allocation, another
         # session's graph capture included, where releasing device memory aborts)
-        self.step_end = "truncated" if self.truncated else "logprob" if self.logprobs else "argmax" if self.fused_argmax else "unfused"
-        self._init_penalties(penalties or {})
+        self.step_end = "rows" if self.row_table is not None else "truncated" if self.truncated else "logprob" if self.logprobs else "argmax" if self.fused_argmax else "unfused"
+        # (force: a per-row table holds the penalty values - the scalar ones stay neutral - or reserves the buffers for later rows)
+        force = self.row_table is not None and (rows.get("reserve") or any(p.penalised for p in self.row_params))
+        self._init_penalties(dict(penalties or {}, force=True) if force else (penalties or {}))
         self.steps_done = 0
         self.graph = None
         if use_graph:
@@ -233,7 +271,7 @@ class DecodeSession:
         self.pen = None
         self.pen_count = self.pen_list = self.pen_len = self.pen_bias = None
         context = kw.get("context")
-        if r == 1.0 and p == 0.0 and f == 0.0 and not bias:
+        if r == 1.0 and p == 0.0 and f == 0.0 and not bias and not kw.get("force"):
             return                                  # neutral (a context set alone changes nothing): today's step
         if context is None:
             context = [[] for _ in range(B)]
@@ -284,6 +322,15 @@ class DecodeSession:
     def copy_penalty_history(self, other, slots=None):
         """Take over another session's penalty state for `slots` (default: all) - a re-captured step goes on with those requests.  The
         sessions hold the same slots and biased columns; this one's static section and list may be larger (more room for context)."""
+        if self.row_table is not None:              # the kept slots go on with their parameters, streams and draw counters
+            if other.row_table is None:
+                raise ValueError("copy_penalty_history: the other session has no per-row sampling table")
+            keep = list(range(self.B)) if slots is None else [int(b) for b in slots]
+            if keep:
+                at = torch.tensor(keep, dtype=torch.int64, device=self.dev)
+                self.row_table[at] = other.row_table[at]
+                for b in keep:
+                    self.row_params[b], self.row_streams[b] = other.row_params[b], other.row_streams[b]
         if self.pen is None:
             return
         grow = 0 if other.pen is None else self.pen_static - other.pen_static
@@ -354,8 +401,14 @@ class DecodeSession:
             ops.logit_penalty(self.logits, self.ids, self.pen_count, self.pen_list, self.pen_len, self.pen_static, bias=self.pen_bias,
                               repetition_penalty=r, presence_penalty=p, frequency_penalty=f,
                               temperature=self.temperature if self.do_sample else 0.0, seed=self.seed, step=self.step_idx,
-                              argmax_partial=self.lm_head_kw.get("argmax_partial"), lse_partial=self.lm_head_kw.get("lse_partial"))
-        if self.step_end == "truncated":
+                              argmax_partial=self.lm_head_kw.get("argmax_partial"), lse_partial=self.lm_head_kw.get("lse_partial"),
+                              sample_rows=self.row_table)
+        if self.step_end == "rows":
+            # every row ends the step with its own sampler (the truncated path or the key maximum) and advances its own draw counter
+            ops.decode_step_end_rows(self.tok_slot, self.tok_pos, self.kv_len, self.amax_part, self.ids, self.in_ids, self.pred_ids,
+                                     self.step_idx, self.logits, self.row_table, lse_partial=self.lse_part, logprobs=self.pred_logprobs,
+                                     forced_ids=self.forced_ids, cut_y=self.pred_cut_y, n_kept=self.pred_n_kept)
+        elif self.step_end == "truncated":
             # the fused step end whose pick is the epilogue's only if that column survived the filters (the kept set's Gumbel maximum
             # otherwise), plus pred_cut_y[step] / pred_n_kept[step] - and pred_logprobs[step] when log-probabilities are on
             ops.decode_step_end_truncated(self.tok_slot, self.tok_pos, self.kv_len, self.amax_part, self.ids, self.in_ids, self.pred_ids,
@@ -385,6 +438,8 @@ class DecodeSession:
         state = (self.ids, self.tok_slot, self.tok_pos, self.kv_len, self.step_idx)
         if self.pen is not None:                    # the warm-up step records into the penalty history as well
             state += (self.pen_count, self.pen_list, self.pen_len)
+        if self.row_table is not None:              # ... and advances the rows' draw counters
+            state += (self.row_table,)
         saved = [t.clone() for t in state]
         s = torch.cuda.Stream(device=self.dev)
         s.wait_stream(torch.cuda.current_stream())
@@ -414,9 +469,14 @@ class DecodeSession:
     # ---- continuous batching support (serving.py): the captured step reads these from device memory, so a slot can be
     # re-pointed at a new request between replays without re-capturing
     @ops.on_device
-    def set_slot(self, b, token, kv_len, pos, penalty_context_ids=None):
+    def set_slot(self, b, token, kv_len, pos, penalty_context_ids=None, sampling=None, stream=None, draw=0):
         """Sample b continues from `token` with `kv_len` tokens already in its cache segment and rope position `pos`.  With penalties
-        on, the slot's history starts over: no generated tokens, penalty_context_ids as its context set, `token` as its start token."""
+        on, the slot's history starts over: no generated tokens, penalty_context_ids as its context set, `token` as its start token.
+        sampling (a SamplingParams; sessions with row_sampling): row b of the table is rewritten - the slot decodes with these
+        parameters from the next replay on, its key words (seed, stream - default: the slot's current one -, draw); without it the
+        row, its draw counter included, stays as it is."""
+        if sampling is not None:
+            self._set_row(b, sampling, stream, draw)
         if self.pen is not None:
             self._reset_penalty_slot(b, self._penalty_context(penalty_context_ids))
         self.ids[b:b + 1].fill_(int(token))
@@ -424,10 +484,21 @@ class DecodeSession:
         self.kv_len[b:b + 1].fill_(int(kv_len) + 1)
         self.tok_pos[b:b + 1].fill_(int(pos))
 
+    def _set_row(self, b, params, stream, draw):
+        if self.row_table is None:
+            raise ValueError("set_slot(sampling=...) needs a session built with row_sampling")
+        if self.pen is None and params.penalised:
+            raise ValueError("this session reserved no penalty buffers: build it with row_penalties=True (or a penalised row)")
+        stream = self.row_streams[b] if stream is None else int(stream)
+        row = sampling_mod.to_tensor(sampling_mod.pack_row(params, seed=self.seed, stream=stream, draw=draw), self.dev)
+        self.row_table[b:b + 1].copy_(row)
+        self.row_params[b], self.row_streams[b] = params, stream
+
     @ops.on_device
     def rewind_outputs(self):
         """Start writing in_ids / pred_ids (and pred_logprobs) at row 0 again (the caller has harvested the previous rows).  The
-        penalty history is NOT touched: a request lives across rounds."""
+        penalty history is NOT touched: a request lives across rounds - and neither are the rows' draw counters (row_sampling): a
+        request's noise does not repeat from round to round."""
         self.step_idx.zero_()
         self.in_ids[0].copy_(self.ids)      # the tokens the next step is fed (set_slot may have changed them)
         self.steps_done = 0

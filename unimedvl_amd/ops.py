@@ -265,7 +265,7 @@ def _route(lin, M, splitk=False, norm=False, amax=False, act8=False, out_f32=Fal
 
 
 def _launch(lib, route, x, lin, out, ldo, M, flags=0, residual=None, row_idx=None, norm_w=None, norm_eps=0.0, amax=None, sample=None,
-            k_splits=0, split_stride=0, lse=None):
+            k_splits=0, split_stride=0, lse=None, sample_rows=None):
     """Build the umv_gemm_args of a routed call and launch it.  What only some entries take is set from the route: w_scale; th-row tiles
     and the bound on x's rows (the bf16 kernel and its 13-bit twin, outside split-K); the sampling mode (not the MXFP4 entries, which
     have no argmax keys); every other field is the call's"""
@@ -290,7 +290,12 @@ def _launch(lib, route, x, lin, out, ldo, M, flags=0, residual=None, row_idx=Non
         a.sample_temperature, a.sample_seed, a.sample_step = _sample_fields(sample, amax)
     if lse is not None:
         a.lse_partial = lse
-    if wz is not None:
+    if sample_rows is not None:         # the lm_head call with a per-row table: the entry's *_rows twin, the table behind the struct
+        if wz is not None:
+            check(lib.umv_gemm_z13w_rows(C.byref(a), wz.data_ptr(), sample_rows, _stream()), entry + "_rows")
+        else:
+            check(getattr(lib, entry + "_rows")(C.byref(a), sample_rows, _stream()), entry + "_rows")
+    elif wz is not None:
         check(lib.umv_gemm_z13w(C.byref(a), wz.data_ptr(), _stream()), entry)
     else:
         check(getattr(lib, entry)(C.byref(a), _stream()), entry)
@@ -298,7 +303,7 @@ def _launch(lib, route, x, lin, out, ldo, M, flags=0, residual=None, row_idx=Non
 
 
 def gemm(x, lin, out=None, *, M=None, residual=None, act=None, row_idx=None, out_f32=False, use_bias=True,
-         norm_w=None, norm_eps=1e-6, act8=False, argmax_partial=None, sample=None, z13=None, lse_partial=None):
+         norm_w=None, norm_eps=1e-6, act8=False, argmax_partial=None, sample=None, z13=None, lse_partial=None, sample_rows=None):
     """out = epilogue(x @ W^T).  x [M,K] bf16 (row stride may exceed K).  act in {None,'gelu_tanh','silu'}.
     norm_w: fuse Qwen2RMSNorm(x)*norm_w into the GEMM prologue (M <= 16, K <= 4096).
     act8 (W8A8 mode, needs lin.w8m): the activations are rounded per row through e4m3 - on the fp8 matrix instruction for
@@ -309,6 +314,9 @@ def gemm(x, lin, out=None, *, M=None, residual=None, act=None, row_idx=None, out
     lse_partial (with argmax_partial; fp32 [M, ceil(N/16), 2]): per tile and row the maximum of the value the keys order without noise
     and the sum of exp(value - maximum) - the softmax statistics decode_step_end_logprob turns into the token's log-probability.  It
     rides on the argmax_partial epilogue: without argmax_partial the library refuses it (UMV_ERR_ARG).
+    sample_rows (with argmax_partial, instead of sample; int64 [M, 6] = the per-row table of sampling.to_tensor): row m's keys and
+    statistics are those of ITS temperature (0 = a greedy row) and (seed, draw, stream) - include/unimedvl_hip.h, per-row sampling
+    parameters.  The bf16, 13-bit and e4m3 routes take it; the library refuses it without argmax_partial or above 64 rows.
     z13 (tests and A/B only; leave None): whether a linear's exact 13-bit image is streamed - None = the measured policy of _route,
     True = whenever umv_gemm_z13w serves the call, False = never."""
     lib = _lib.load()
@@ -348,6 +356,11 @@ def gemm(x, lin, out=None, *, M=None, residual=None, act=None, row_idx=None, out
         if not (lse_partial.is_contiguous() and tuple(lse_partial.shape) == (M, (lin.N + 15) // 16, 2)):
             raise _lib.UmvError(f"lse_partial must be a contiguous fp32 [{M}, {(lin.N + 15) // 16}, 2] tensor")
         lse = lse_partial.data_ptr()
+    rows = None
+    if sample_rows is not None:
+        if route[0] not in ("umv_gemm_bf16", "umv_gemm_z13w", "umv_gemm_fp8w"):
+            raise _lib.UmvError(f"gemm: sample_rows rides on the argmax_partial epilogue of the bf16 / 13-bit / e4m3 routes, not {route[0]}")
+        rows = _row_table(sample_rows, M, "gemm")
     if route[0] == "umv_gemm_fp8a8w":
         if lse is not None:
             raise _lib.UmvError("gemm: lse_partial rides on the argmax_partial epilogue of the M <= 64 kernels")
@@ -363,7 +376,8 @@ def gemm(x, lin, out=None, *, M=None, residual=None, act=None, row_idx=None, out
             a8.row_idx = row_idx.data_ptr()
         check(lib.umv_gemm_fp8a8w(C.byref(a8), _stream()), "umv_gemm_fp8a8w")
         return out
-    return _launch(lib, route, x, lin, out, out.stride(0), M, flags, residual, row_idx, norm_w, norm_eps, amax, sample, lse=lse)
+    return _launch(lib, route, x, lin, out, out.stride(0), M, flags, residual, row_idx, norm_w, norm_eps, amax, sample, lse=lse,
+                   sample_rows=rows)
 
 
 def rmsnorm(x, w, eps, out=None, w_gen=None, expert=None):
@@ -422,6 +436,14 @@ def sample(logits, temperature, seed, step=None, out=None):
     check(lib.umv_sample_bf16(_p(logits), logits.stride(0), _p(out), M, V, float(temperature), int(seed) & (2 ** 64 - 1),
                               _p(step), _stream()), "umv_sample_bf16")
     return out
+
+
+def _row_table(rows, M, who):
+    """the device pointer of a per-row sampling table (sampling.to_tensor: int64 [rows >= M, 6], contiguous, 16-byte aligned)"""
+    _req(rows, torch.int64, "sample_rows")
+    if not (rows.dim() == 2 and rows.shape[1] == 6 and rows.shape[0] >= M and rows.is_contiguous() and rows.data_ptr() % 16 == 0):
+        raise _lib.UmvError(f"{who}: sample_rows must be a contiguous, 16-byte aligned int64 [{M}, 6] tensor (sampling.to_tensor)")
+    return rows.data_ptr()
 
 
 def check_truncation(top_k, top_p, min_p):
@@ -490,12 +512,13 @@ def check_penalties(repetition_penalty=1.0, presence_penalty=0.0, frequency_pena
 
 
 def logit_penalty(logits, ids, count, vlist, list_len, n_static, bias=None, repetition_penalty=1.0, presence_penalty=0.0,
-                  frequency_penalty=0.0, temperature=0.0, seed=0, step=None, argmax_partial=None, lse_partial=None):
+                  frequency_penalty=0.0, temperature=0.0, seed=0, step=None, argmax_partial=None, lse_partial=None, sample_rows=None):
     """umv_logit_penalty_bf16 on bf16 logits [M, V], in place: record ids (int64 [M], the tokens this step is fed) in count (int32 [M, V])
     and the visit list vlist (int32 [M, cap], the first n_static entries seeded by the caller, bias fp32 [M, n_static] parallel to them)
     / list_len (int32 [M], -1 = fresh slot), patch the listed columns, and - with argmax_partial ([M, n_tiles] int64, lse_partial
     [M, n_tiles, 2] fp32) - recompute the tiles they sit in as the lm_head call with sample=(temperature, seed, step) leaves them
-    (temperature 0: greedy)."""
+    (temperature 0: greedy).  sample_rows (the per-row table of sampling.to_tensor, int64 [M, 6]): every row takes its three penalty
+    values, its temperature and its sampling key from its own entry; the scalar ones must then be left neutral."""
     lib = _lib.load()
     _req(logits, BF16, "logits")
     _req(ids, torch.int64, "ids")
@@ -528,6 +551,8 @@ def logit_penalty(logits, ids, count, vlist, list_len, n_static, bias=None, repe
         if argmax_partial is not None and not (lse_partial.is_contiguous() and tuple(lse_partial.shape) == tuple(argmax_partial.shape) + (2,)):
             raise _lib.UmvError("logit_penalty: lse_partial must be a contiguous [M, n_tiles, 2] tensor")
         a.lse_partial = lse_partial.data_ptr()
+    if sample_rows is not None:
+        a.rows = _row_table(sample_rows, M, "logit_penalty")
     check(lib.umv_logit_penalty_bf16(C.byref(a), _stream()), "umv_logit_penalty_bf16")
     return logits
 
@@ -829,6 +854,25 @@ def decode_step_end_truncated(tok_slot, tok_pos, kv_len, argmax_partial, ids, in
                                             int(seed) & (2 ** 64 - 1), int(top_k), float(top_p), float(min_p), _p(cut_y), _p(n_kept),
                                             _stream()),
           "umv_decode_step_end_truncated")
+
+
+def decode_step_end_rows(tok_slot, tok_pos, kv_len, argmax_partial, ids, in_ids, pred_ids, step_idx, logits, sample_rows, lse_partial=None,
+                         logprobs=None, forced_ids=None, cut_y=None, n_kept=None):
+    """The step end of a step with a per-row sampling table (include/unimedvl_hip.h; sample_rows = sampling.to_tensor's int64 [B, 6],
+    the table the lm_head call got): per row decode_step_end_truncated with the row's own temperature, filters and (seed, draw, stream)
+    where the row samples with a filter on, the key maximum of decode_step_end_logprob otherwise (cut_y = -inf, n_kept = V).  Adds 1 to
+    every row's draw counter - the only word of the table it writes.  lse_partial with logprobs, forced_ids, cut_y, n_kept as there."""
+    lib = _lib.load()
+    if (lse_partial is None) != (logprobs is None):
+        raise _lib.UmvError("decode_step_end_rows: lse_partial and logprobs go together")
+    B = _check_fused_step_end("decode_step_end_rows", argmax_partial, ids, in_ids, pred_ids, step_idx, lse_partial, logits,
+                              logprobs=(logprobs, torch.float32), forced_ids=(forced_ids, torch.int64), cut_y=(cut_y, torch.float32),
+                              n_kept=(n_kept, torch.int32))
+    rows = None if sample_rows is None else _row_table(sample_rows, B, "decode_step_end_rows")
+    check(lib.umv_decode_step_end_rows(_p(tok_slot), _p(tok_pos), _p(kv_len), _p(argmax_partial), _p(lse_partial), argmax_partial.shape[1],
+                                       _p(ids), _p(in_ids), _p(pred_ids), _p(step_idx), _p(logits), logits.stride(0), logits.shape[1],
+                                       _p(forced_ids), _p(logprobs), B, in_ids.shape[0], rows, _p(cut_y), _p(n_kept), _stream()),
+          "umv_decode_step_end_rows")
 
 
 def token_logprob(logits, ids, temperature=0.0, out=None):

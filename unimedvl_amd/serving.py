@@ -18,6 +18,7 @@ produced <|im_end|> (or hit their token budget) and prefills the next queued req
   * samples are independent rows of every kernel: a request's tokens are the same whichever slot and neighbours it gets
     (tests/test_serving_gpu.py checks this against one-request-at-a-time greedy decoding).
 """
+import dataclasses
 from collections import deque
 from dataclasses import dataclass, field
 from typing import Any, Deque, Dict, List, Optional
@@ -28,6 +29,7 @@ from . import ops
 
 from .decode import DecodeSession
 from .kvcache import NaiveCache, PagedCache
+from .sampling import SamplingParams, derive_seed
 
 
 @dataclass
@@ -39,6 +41,7 @@ class _Request:
     tokens: List[int] = field(default_factory=list)
     logprobs: List[float] = field(default_factory=list)
     prompt_ids: Optional[List[int]] = None      # penalize_prompt: the prompt's tokens, the repetition penalty's context set
+    sampling: Optional[SamplingParams] = None   # per_request_sampling: the request's own parameters (None = the batcher's)
 
 
 class ContinuousBatcher:
@@ -47,7 +50,8 @@ class ContinuousBatcher:
                  use_graph: bool = True, growable: bool = True, context_limit: Optional[int] = None, paged: bool = False,
                  pool_pages: Optional[int] = None, logprobs: bool = False, *, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, penalize_prompt: bool = False,
-                 top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+                 per_request_sampling: bool = False, seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0,
+                 min_p: float = 0.0):
         """max_context: the context (prompt + images) the slots are RESERVED for; with growable=True longer requests enlarge
         the cache (up to context_limit tokens of context when given), with growable=False they are refused.
         paged=True: block-table KV (kvcache.PagedCache) instead of slabs - the slots draw 256-token pages from ONE pool of `pool_pages`
@@ -62,7 +66,14 @@ class ContinuousBatcher:
         penalize_prompt=True: a request's prompt token ids (the text between the bos / eos wrapper, which is NOT part of the set: a
         penalised end token would only make answers longer) are its context set for the repetition penalty.  The session reserves
         room for the longest prompt admitted so far (a power of two, at least 32 distinct tokens) - the penalty kernel walks that
-        reservation every step - and the step is re-captured, histories carried over, when a longer prompt arrives."""
+        reservation every step - and the step is re-captured, histories carried over, when a longer prompt arrives.
+        per_request_sampling=True: every request decodes with its OWN sampling.SamplingParams (submit(..., sampling=)) inside the one
+        captured step (DecodeSession(row_sampling=...)); the sampler keywords above become the default of the requests that give
+        none, logit_bias stays batcher-wide.  A request's sampling key is (its seed, stream 0, its own draw counter from 0): the seed
+        is SamplingParams.seed or, without one, derived on the host from `seed` (None: one draw from the model's generator at the
+        first run()) and the request id - so a request's tokens and log-probabilities depend on neither its slot, its neighbours,
+        the admission order nor check_every, and no noise repeats from round to round.  Needs slots <= 64.  False: nothing changes -
+        one sampler for all, keyed by slot and round-local step."""
         self.top_k, self.top_p, self.min_p = ops.check_truncation(top_k, top_p, min_p)
         if (self.top_k > 0 or self.top_p < 1.0 or self.min_p > 0.0) and not do_sample:
             raise ValueError("top_k / top_p / min_p truncate the sampler: they need do_sample=True")
@@ -72,6 +83,20 @@ class ContinuousBatcher:
                                   ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty, logit_bias,
                                                       vocab=model.cfg.vocab)))
         self.penalize_prompt = bool(penalize_prompt)
+        self.per_request = bool(per_request_sampling)
+        self.seed = None if seed is None else int(seed)
+        if self.per_request:
+            if int(slots) > 64:
+                raise ValueError(f"per_request_sampling rides on the fused step end: at most 64 slots (got {slots})")
+            pen = self.penalties
+            self.default_sampling = SamplingParams(do_sample=bool(do_sample), temperature=temperature if do_sample else 1.0,
+                                                   top_k=self.top_k, top_p=self.top_p, min_p=self.min_p,
+                                                   repetition_penalty=pen["repetition_penalty"], presence_penalty=pen["presence_penalty"],
+                                                   frequency_penalty=pen["frequency_penalty"])
+            # the session reserves the penalty buffers as soon as any request (or the default) is penalised
+            self._row_pen = self.default_sampling.penalised
+        elif seed is not None:
+            raise ValueError("seed goes with per_request_sampling (the batcher-wide sampler draws its key from the model's generator)")
         self._pen_room = 0                              # distinct context tokens per slot the decode session reserves
         self.slots, self.check_every = int(slots), int(check_every)
         self.max_context, self.default_new = int(max_context), int(max_new_tokens)
@@ -95,15 +120,22 @@ class ContinuousBatcher:
         self.stats = {"decode_steps": 0, "prefills": 0, "tokens": 0, "cache_grows": 0}
 
     # ------------------------------------------------------------------ API
-    def submit(self, images, prompt: str, max_new_tokens: Optional[int] = None) -> int:
-        """images: one image / a list of images (PIL or [3,H,W] tensors, as the transform accepts) or None."""
+    def submit(self, images, prompt: str, max_new_tokens: Optional[int] = None, sampling: Optional[SamplingParams] = None) -> int:
+        """images: one image / a list of images (PIL or [3,H,W] tensors, as the transform accepts) or None.
+        sampling (per_request_sampling=True only): the request's own SamplingParams; None = the batcher's defaults."""
+        if sampling is not None:
+            if not self.per_request:
+                raise ValueError("submit(sampling=...) needs ContinuousBatcher(per_request_sampling=True)")
+            if not isinstance(sampling, SamplingParams):
+                raise ValueError(f"sampling must be a SamplingParams, got {type(sampling).__name__}")
+            self._row_pen = self._row_pen or sampling.penalised
         imgs = [] if images is None else (list(images) if isinstance(images, (list, tuple)) else [images])
         budget = self.default_new if max_new_tokens is None else int(max_new_tokens)
         if budget > self.default_new and not self.growable:
             raise ValueError(f"max_new_tokens {budget} exceeds the batcher's reserve of {self.default_new}")
         rid = self._next_id
         self._next_id += 1
-        self.queue.append(_Request(rid, imgs, prompt, budget))
+        self.queue.append(_Request(rid, imgs, prompt, budget, sampling=sampling))
         return rid
 
     @torch.no_grad()
@@ -123,7 +155,16 @@ class ContinuousBatcher:
                 first.append(b)
         for b, st in zip(first, self._prefill_many(first, [active[b] for b in first])):
             state[b] = st
-        seed = m._sampling_seed() if self.do_sample else 0
+        seed = m._sampling_seed() if self.do_sample and not self.per_request else 0
+        if self.per_request and self.seed is None:
+            self.seed = m._sampling_seed()
+
+        def params_of(b):         # the parameters slot b decodes with: its request's (seeded by the request id), the default when idle
+            req = active[b]
+            if req is None:
+                return self.default_sampling
+            p = req.sampling or self.default_sampling
+            return p if p.seed is not None else dataclasses.replace(p, seed=derive_seed(self.seed, req.rid))
 
         def context_of(b):
             return active[b].prompt_ids if active[b] is not None else None
@@ -141,11 +182,15 @@ class ContinuousBatcher:
             start = torch.tensor([s[0] for s in state], dtype=torch.int64)
             pos = torch.tensor([s[2] for s in state], dtype=torch.int64)
             lens_now = list(cache.lens)
+            if self.per_request:    # one table row per slot: stream 0, draw 0 (the kept slots take theirs over from `prev` below)
+                sampler = dict(row_sampling=[params_of(b) for b in range(B)], row_streams=[0] * B, row_penalties=self._row_pen,
+                               logit_bias=self.penalties["logit_bias"])
+            else:
+                sampler = dict(do_sample=self.do_sample, temperature=self.temperature, seed=seed, top_k=self.top_k, top_p=self.top_p,
+                               min_p=self.min_p, **self.penalties)
             sn = DecodeSession(m.language_model, cache, start, pos, self.check_every, use_graph=self.use_graph,
-                               do_sample=self.do_sample, temperature=self.temperature, seed=seed, logprobs=self.want_logprobs,
-                               top_k=self.top_k, top_p=self.top_p, min_p=self.min_p, **self.penalties,
-                               penalty_context_ids=[context_of(b) for b in range(B)],
-                               penalty_context_room=self._pen_room, penalty_history=m.cfg.vocab)
+                               logprobs=self.want_logprobs, penalty_context_ids=[context_of(b) for b in range(B)],
+                               penalty_context_room=self._pen_room, penalty_history=m.cfg.vocab, **sampler)
             if prev is not None:                        # the requests go on: so do their penalty histories
                 sn.copy_penalty_history(prev, keep)
             cache.lens = lens_now                       # the session only reads them; this loop owns the bookkeeping
@@ -207,7 +252,8 @@ class ContinuousBatcher:
                 sess = new_session(sess, [b for b in range(B) if b not in freed])       # than the penalty reservation: new captured step
             else:
                 for b in freed:
-                    sess.set_slot(b, *state[b], penalty_context_ids=context_of(b))
+                    row = dict(sampling=params_of(b), stream=0, draw=0) if self.per_request else {}
+                    sess.set_slot(b, *state[b], penalty_context_ids=context_of(b), **row)
         return dict(self.results)
 
     # ------------------------------------------------------------------ hooks (MixedBatcher)
