@@ -49,7 +49,7 @@ def _variants():
     F = L.ATTN_FORCE
     return L, {
         "tq1": F | L.ATTN_TQ1, "tq2": F | L.ATTN_TQ2, "tq1_whole": F | L.ATTN_TQ1 | L.ATTN_WHOLE_TOKENS,
-        "tq2_whole": F | L.ATTN_TQ2 | L.ATTN_WHOLE_TOKENS, "tq2_pair": F | L.ATTN_TQ2 | L.ATTN_PAIR,
+        "tq2_whole": F | L.ATTN_TQ2 | L.ATTN_WHOLE_TOKENS,
         "exact_tq2": F | L.ATTN_TQ2 | L.ATTN_EXACT, "exact_tq1": F | L.ATTN_TQ1 | L.ATTN_EXACT, "stream": F | L.ATTN_STREAM,
     }
 

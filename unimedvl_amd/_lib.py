@@ -54,7 +54,8 @@ class AttnArgs(C.Structure):
 
 
 # umv_attn_args.variant bits (tests / A-B only): FORCE makes the others replace the library's shape -> kernel policy for one call
-ATTN_FORCE, ATTN_STREAM, ATTN_TQ1, ATTN_TQ2, ATTN_EXACT, ATTN_WHOLE_TOKENS, ATTN_PAIR = 1, 2, 4, 8, 16, 32, 64
+ATTN_FORCE, ATTN_STREAM, ATTN_TQ1, ATTN_TQ2, ATTN_EXACT, ATTN_WHOLE_TOKENS = 1, 2, 4, 8, 16, 32
+ATTN_PAIR = 64      # once: both q-tiles of a wave in one softmax call.  The library ignores the bit now; the name stays so that callers written against it still load
 
 
 class Gemm8Args(C.Structure):

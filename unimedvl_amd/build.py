@@ -27,8 +27,6 @@ FILE_FLAGS = {"attention_prefill.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 # never in the default build
 if os.environ.get("UMV_ATTN_TRACE", "0") not in ("0", ""):      # timing study of the prefill attention (tools/attn_trace.py); never in the default build
     FILE_FLAGS["attention_prefill.hip"] = FILE_FLAGS["attention_prefill.hip"] + ["-DUMV_ATTN_TRACE"]
-if os.environ.get("UMV_ATTN_PAIR_DEBUG", "0") not in ("0", ""):  # bisecting forms of the paired lazy-softmax kernel (tools/attn_pair_debug.py); never in the default build
-    FILE_FLAGS["attention_prefill.hip"] = FILE_FLAGS["attention_prefill.hip"] + ["-DUMV_ATTN_PAIR_DEBUG=1"]
 if os.environ.get("UMV_GEMM_ABLATIONS", "0") not in ("0", ""):
     FILE_FLAGS["gemm_w4.hip"] = ["-DUMV_GEMM_ABLATIONS"]
 

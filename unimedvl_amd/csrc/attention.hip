@@ -11,22 +11,13 @@
 //                             V transposed), B = P^T = the lane's own 8 probabilities
 // so P never moves between lanes, the O rescale factor is lane-local, and no LDS is used.
 // nsplit > 1 splits the key range over workgroups (decode) and a combine kernel merges.
-#include "common.h"
+#include "attention_tile.h"
 #include "attention_combine.h"
-#include "../../include/unimedvl_hip.h"
 
-// attention_prefill.hip: the nsplit == 1 path with K / V^T shared through LDS (bit-identical results)
-bool umv_attn_prefill_enabled(int variant);
-bool umv_attn_prefill_can_take(const umv_attn_args& a);
-int umv_attn_prefill_launch(const umv_attn_args& a, int qtiles, float scale_log2e, hipStream_t s);
-
-__device__ __forceinline__ bf16x8 mask_keys(bf16x8 v, int nvalid) {
-    // keep the first nvalid (0..8) bf16 elements, zero the rest
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = j < nvalid ? v[j] : (short)0;
-    return o;
-}
+// dynamic LDS of attn_kernel's WS > 1 merge: the waves' O accumulators [WS][DT][64] f32x4, then their (m, l) [WS][16][2]
+constexpr int attn_merge_o_floats(int hd, int ws) { return ws * ((hd + 15) / 16) * 64 * 4; }
+constexpr int attn_merge_lds_bytes(int hd, int ws) { return ws > 1 ? (attn_merge_o_floats(hd, ws) + ws * 16 * 2) * (int)sizeof(float) : 0; }
+static_assert(attn_merge_lds_bytes(128, 4) == 33280 && attn_merge_lds_bytes(128, 2) == 16640 && attn_merge_lds_bytes(128, 1) == 0, "LDS of the decode merge");
 
 // WS > 1 (decode: ONE q-tile per (segment, kv head, split)): the workgroup's waves all own that q-tile and split the keys of the
 // workgroup's range among themselves in runs of 32-key blocks; their (O, m, l) triples meet in LDS (merge in wave order 0 .. wsplit-1,
@@ -41,7 +32,7 @@ __global__ __launch_bounds__(256) void attn_kernel(umv_attn_args a, float scale_
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 15, g = lane >> 4;
     const int G = a.nq / a.nkv;
-    const int QPT = 16 / G > 0 ? 16 / G : 1;
+    const int QPT = attn_qpt(G);
     const int s = blockIdx.z;
     const int kh = blockIdx.y % a.nkv;
     const int split = blockIdx.y / a.nkv;
@@ -58,15 +49,11 @@ __global__ __launch_bounds__(256) void attn_kernel(umv_attn_args a, float scale_
     // causal = bottom-right aligned: query qi sees keys <= Lk - Lq + qi
     const int limit = a.causal ? (Lk - Lq + qi) : (Lk - 1);
 
-    // Q fragments (B operand): lane (j,g) holds Q[row j][ks*32 + g*8 .. +8]
     bf16x8 qf[KS];
     {
         const bf16_t* qp = a.q + (int64_t)(q0 + (rvalid ? qi : 0)) * (a.q_row_stride ? a.q_row_stride : (int64_t)a.nq * HD) + head * HD;
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const int d = ks * 32 + g * 8;
-            qf[ks] = (rvalid && d < HD) ? ldg_frag(qp + d) : zero_frag();
-        }
+        for (int ks = 0; ks < KS; ++ks) qf[ks] = attn_q_frag<HD>(qp, g, rvalid, ks);
     }
     // key range of this split, in 32-key blocks
     int kb_begin = 0, kb_end = Lk;
@@ -210,7 +197,7 @@ __global__ __launch_bounds__(256) void attn_kernel(umv_attn_args a, float scale_
     if constexpr (WS > 1) {
         // merge the waves' (O, m, l) in LDS: wave order 0 .. WS-1 (fixed: the result does not depend on which wave finished first)
         f32x4* smO = reinterpret_cast<f32x4*>(attn_sm);                       // [WS][DT][64]
-        float* smML = attn_sm + WS * DT * 64 * 4;                             // [WS][16][2]
+        float* smML = attn_sm + attn_merge_o_floats(HD, WS);                  // [WS][16][2]
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) smO[(wave * DT + dt) * 64 + lane] = o[dt];
         if (g == 0) { smML[(wave * 16 + j) * 2] = m_run; smML[(wave * 16 + j) * 2 + 1] = l_run; }
@@ -245,15 +232,8 @@ __global__ __launch_bounds__(256) void attn_kernel(umv_attn_args a, float scale_
         const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;
         bf16_t* op = a.out + (tok * a.nq + head) * HD;
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-            const int d = dt * 16 + g * 4;
-            if (d + 3 < HD && (WS == 1 || dt % WS == wave)) {
-                u32x2 pk;
-                pk.x = pack2bf(o[dt].x * inv, o[dt].y * inv);
-                pk.y = pack2bf(o[dt].z * inv, o[dt].w * inv);
-                *reinterpret_cast<u32x2*>(op + d) = pk;
-            }
-        }
+        for (int dt = 0; dt < DT; ++dt)
+            if (WS == 1 || dt % WS == wave) attn_store_o<HD>(op, g, dt, o[dt], inv);      // (WS > 1: the d-tiles this wave finished)
     } else {
         float* wsO = reinterpret_cast<float*>(a.workspace);
         const int64_t slotw = (tok * a.nq + head) * a.nsplit + split;
@@ -267,6 +247,18 @@ __global__ __launch_bounds__(256) void attn_kernel(umv_attn_args a, float scale_
     }
 }
 
+
+template <int HD, int WS>
+static void launch_stream(const umv_attn_args& a, dim3 grid, dim3 block, float scale_log2e, hipStream_t s) {
+    constexpr int lds = attn_merge_lds_bytes(HD, WS);
+    if constexpr (HD == 128) {      // paged KV is built for head_dim 128 (the LLM's cache); umv_attn_varlen rejects the others
+        if (a.page_table) {
+            hipLaunchKernelGGL((attn_kernel<HD, WS, true>), grid, block, lds, s, a, scale_log2e);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((attn_kernel<HD, WS, false>), grid, block, lds, s, a, scale_log2e);
+}
 
 extern "C" size_t umv_attn_workspace_bytes(int nseg, int nq, int hd, int max_q, int nsplit) {
     if (nsplit <= 1) return 0;
@@ -286,10 +278,7 @@ extern "C" int umv_attn_varlen(const umv_attn_args* ap, umv_stream_t stream) {
               "attn: packed K (k_key_stride > 0) is the cache-less self-attention form: nsplit = 1, non-causal, kv_len[s] = cu_q[s+1] - cu_q[s]");
     if (a.nseg == 0 || a.max_q == 0) return UMV_OK;
     const int G = a.nq / a.nkv;
-    const int QPT = 16 / G > 0 ? 16 / G : 1;
-    const int qtiles = (a.max_q + QPT - 1) / QPT;
-    // one wave per q-tile, up to four per workgroup: a decode step (max_q = 1) has ONE q-tile per (segment, kv head, split), so its
-    // workgroups are single waves (with 256 threads three of the four waves of each of the 544 workgroups only exited)
+    const int qtiles = attn_qtiles(a.max_q, G);
     const float scale_log2e = 1.4426950408889634f / sqrtf((float)a.hd);
     hipStream_t s = (hipStream_t)stream;
     if (a.page_table) {
@@ -302,23 +291,15 @@ extern "C" int umv_attn_varlen(const umv_attn_args* ap, umv_stream_t stream) {
     // workgroups are single waves (with 256 threads three of the four waves of each of the 544 workgroups only exited)
     const int wpb = ws > 1 ? ws : (qtiles < 4 ? qtiles : 4);
     dim3 grid(ws > 1 ? qtiles : (qtiles + wpb - 1) / wpb, a.nkv * a.nsplit, a.nseg), block(64 * wpb);
-    if (a.nsplit == 1 && qtiles >= 4 && (a.hd == 128 || a.hd == 72) && umv_attn_prefill_enabled(a.variant) && umv_attn_prefill_can_take(a))
-        return umv_attn_prefill_launch(a, qtiles, scale_log2e, s);
-    const bool pg = a.page_table != nullptr;
-    UMV_CHECK(!pg || a.hd == 128, UMV_ERR_UNSUPPORTED, "attn: paged KV is built for head_dim 128 (the LLM's cache); got %d", a.hd);
-#define UMV_ATTN_LAUNCH(HD_, WS_, LDS_)                                                                               \
-    do {                                                                                                               \
-        if (pg) hipLaunchKernelGGL((attn_kernel<HD_, WS_, true>), grid, block, LDS_, s, a, scale_log2e);               \
-        else hipLaunchKernelGGL((attn_kernel<HD_, WS_, false>), grid, block, LDS_, s, a, scale_log2e);                 \
-    } while (0)
-    if (a.hd == 128 && ws == 4) UMV_ATTN_LAUNCH(128, 4, 4 * 8 * 1024 + 4 * 16 * 2 * 4);
-    else if (a.hd == 128 && ws == 2) UMV_ATTN_LAUNCH(128, 2, 2 * 8 * 1024 + 2 * 16 * 2 * 4);
-    else if (a.hd == 128) UMV_ATTN_LAUNCH(128, 1, 0);
-#undef UMV_ATTN_LAUNCH
-    else if (a.hd == 72)
-        hipLaunchKernelGGL((attn_kernel<72, 1, false>), grid, block, 0, s, a, scale_log2e);
+    if (a.nsplit == 1 && umv_attn_prefill_wanted(a.variant, a.hd, qtiles) && umv_attn_prefill_can_take(a))
+        return umv_attn_prefill_launch(a, scale_log2e, s);
+    UMV_CHECK(!a.page_table || a.hd == 128, UMV_ERR_UNSUPPORTED, "attn: paged KV is built for head_dim 128 (the LLM's cache); got %d", a.hd);
+    if (a.hd == 128 && ws == 4) launch_stream<128, 4>(a, grid, block, scale_log2e, s);
+    else if (a.hd == 128 && ws == 2) launch_stream<128, 2>(a, grid, block, scale_log2e, s);
+    else if (a.hd == 128) launch_stream<128, 1>(a, grid, block, scale_log2e, s);
+    else if (a.hd == 72) launch_stream<72, 1>(a, grid, block, scale_log2e, s);
     else if (a.hd == 512 && a.nsplit == 1)   // VAE mid-block attention, single head of 512 (autoencoder.py:50-62)
-        hipLaunchKernelGGL((attn_kernel<512, 1, false>), grid, block, 0, s, a, scale_log2e);
+        launch_stream<512, 1>(a, grid, block, scale_log2e, s);
     else
         UMV_CHECK(false, UMV_ERR_UNSUPPORTED, "attn: head_dim %d unsupported (128, 72, 512)", a.hd);
     UMV_LAUNCH_CHECK();

@@ -13,15 +13,18 @@
 //   * round 5, the shipped form (LAZY): the softmax runs against a lazy reference point (attn_softmax_lazy below) and the q-tiles pack
 //     the (token, head) pairs densely (16 per tile at any group size).  Same softmax, P rounded at another scale than attn_kernel's.
 // With UMV_ATTN_LAZY=0 the kernels keep the exact running maximum: per row the arithmetic and its order are then those of attn_kernel
-// (both call common.h::attn_softmax_block) and the results are bit-identical to it; the lazy kernels (TQ = 1, 2, either packing) are
+// (both call attention_tile.h::attn_softmax_block) and the results are bit-identical to it; the lazy kernels (TQ = 1, 2, either packing) are
 // bit-identical among themselves (tools/attn_ab.py, tests/test_kernel_branches_gpu.py::test_attn_kernel_variants_bit_identical).
-#include "common.h"
-#include "../../include/unimedvl_hip.h"
+#include "attention_tile.h"
 #include <stdlib.h>
 #include <type_traits>
 
 #define ATTN_LAZY_TAU 8.0f       // lazy softmax reference: exponents stay <= ATTN_LAZY_TAU (P <= 256)
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+#ifdef UMV_ATTN_TRACE       // timing study (UMV_ATTN_TRACE=1 python -m unimedvl_amd.build; tools/attn_trace.py): s_memtime stamps per stage -> a.workspace
+#define ATTN_STAMP(t) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0" : "=s"(t)); __builtin_amdgcn_sched_barrier(0); } while (0)
+#else
+#define ATTN_STAMP(t) do { } while (0)
+#endif
 template <int B, int E, class F>
 __device__ __forceinline__ void static_for_attn(F&& f) {
     if constexpr (B < E) {
@@ -42,15 +45,7 @@ constexpr int ATTN_PREFILL_WAVES(int hd, int tq) { return (hd <= 96 && tq == 2) 
 // (a build that spills here is WRONG, not just slow: scratch traffic counts in vmcnt and the loop's waits are counted by hand.
 // tests/test_host_cpu.py::test_attention_prefill_isa_has_no_scratch compiles this file and checks every kernel.)
 
-__device__ __forceinline__ bf16x8 attn_mask_keys(bf16x8 v, int nvalid) {   // keep the first nvalid (0..8) elements
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = j < nvalid ? v[j] : (short)0;
-    return o;
-}
-
-
-// Online softmax of one 32-key block against a LAZY reference point, for the TQ q-tiles of a wave at once (round 5).
+// Online softmax of one 32-key block of one q-tile against a LAZY reference point (round 5).
 // P = 2^(s c - m_ref) with m_ref <= the row's running maximum <= m_ref + ATTN_LAZY_TAU: the reference moves (and O, l are rescaled by
 // alpha) only when some exponent exceeds ATTN_LAZY_TAU = 8 (P <= 256; the softmax is shift invariant, so only the rounding of P changes:
 // mean error against exact fp32 attention 9.2e-5 vs 8.7e-5 with the exact running maximum).  With the exact maximum the rescale fires
@@ -60,97 +55,71 @@ __device__ __forceinline__ bf16x8 attn_mask_keys(bf16x8 v, int nvalid) {   // ke
 // unset: any finite score of a row's first block sets the reference), l.  When the reference moves by d, the exponents already
 // computed are shifted (e - d) instead of recomputed from the scores: one rounding of ~1e-6 in the exponent, and the scores need
 // not stay live.  Returns true (wave-uniform) when the reference moved; alpha is written only then.
-#ifndef UMV_ATTN_PAIR_DEBUG
-#define UMV_ATTN_PAIR_DEBUG 0
-#endif
-template <int TQ, bool MASKED, bool STATS, int DBG = 0>
-__device__ __forceinline__ bool attn_softmax_lazy(const f32x4 (&st)[TQ][2], int kb, int g, const int (&limit)[TQ], const int (&my_end)[TQ], float c,
-                                                  float (&nm_run)[TQ], float (&thr_run)[TQ], float (&l_run)[TQ], float (&alpha)[TQ], bf16x8 (&pf)[TQ],
-                                                  uint32_t (&cnt)[2]) {
+template <bool MASKED, bool STATS>
+__device__ __forceinline__ bool attn_softmax_lazy(const f32x4 (&st)[2], int kb, int g, int limit, int my_end, float c, float& nm_run, float& thr_run,
+                                                  float& l_run, float& alpha, bf16x8& pf, uint32_t (&cnt)[2]) {
     const umv_f32x2_v c2 = {c, c};
-    umv_f32x2_v e[TQ][4];
-    float emax[TQ];
-    bool trig = false;
+    umv_f32x2_v e[4];
+    float v[8];
 #pragma unroll
-    for (int u = 0; u < TQ; ++u) {
-        float v[8];
+    for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                v[t * 4 + r] = st[u][t][r];
-                if constexpr (MASKED) {
-                    const int key = kb + g * 8 + t * 4 + r;
-                    v[t * 4 + r] = (key <= limit[u] && key < my_end[u]) ? v[t * 4 + r] : -INFINITY;
-                }
+        for (int r = 0; r < 4; ++r) {
+            v[t * 4 + r] = st[t][r];
+            if constexpr (MASKED) {
+                const int key = kb + g * 8 + t * 4 + r;
+                v[t * 4 + r] = (key <= limit && key < my_end) ? v[t * 4 + r] : -INFINITY;
             }
-        const umv_f32x2_v n2 = {nm_run[u], nm_run[u]};
+        }
+    const umv_f32x2_v n2 = {nm_run, nm_run};
 #pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) e[u][q4] = __builtin_elementwise_fma((umv_f32x2_v){v[2 * q4], v[2 * q4 + 1]}, c2, n2);   // (-inf) c + n = -inf
-        // Every instruction of this function is COMPILER-VISIBLE (round 6): the exponents are fma results, which the compiler knows to be
-        // canonical, so fmaxf folds into v_max3_f32 without the v_max_f32 x, x it needs on raw MFMA results (the reason common.h's
-        // attn_softmax_block takes its maxima as inline asm) - and the hazard recogniser sees every producer and consumer of the
-        // v_permlane*_swap steps below (VALU write -> swap read needs wait states that it cannot place around inline asm).
-        const float ea = fmaxf(fmaxf(e[u][0][0], e[u][0][1]), e[u][1][0]), eb = fmaxf(fmaxf(e[u][1][1], e[u][2][0]), e[u][2][1]);
-        emax[u] = fmaxf(fmaxf(ea, eb), fmaxf(e[u][3][0], e[u][3][1]));
-        trig = trig || emax[u] > thr_run[u];
-    }
-    if constexpr (DBG == 6 && TQ == 2) {      // bisect: ONE compare for both tiles (thr = -inf while unset: emax - thr = +inf, or NaN for an all-masked row)
-        trig = fmaxf(emax[0] - thr_run[0], emax[1] - thr_run[1]) > 0.f;
-    }
-    const bool moved = DBG == 4 ? true : __any(trig);
+    for (int q4 = 0; q4 < 4; ++q4) e[q4] = __builtin_elementwise_fma((umv_f32x2_v){v[2 * q4], v[2 * q4 + 1]}, c2, n2);   // (-inf) c + n = -inf
+    // Every instruction of this function is COMPILER-VISIBLE (round 6): the exponents are fma results, which the compiler knows to be
+    // canonical, so fmaxf folds into v_max3_f32 without the v_max_f32 x, x it needs on raw MFMA results (the reason attention_tile.h's
+    // attn_softmax_block takes its maxima as inline asm) - and the hazard recogniser sees every producer and consumer of the
+    // v_permlane*_swap steps below (VALU write -> swap read needs wait states that it cannot place around inline asm).
+    const float ea = fmaxf(fmaxf(e[0][0], e[0][1]), e[1][0]), eb = fmaxf(fmaxf(e[1][1], e[2][0]), e[2][1]);
+    const float emax = fmaxf(fmaxf(ea, eb), fmaxf(e[3][0], e[3][1]));
+    const bool moved = __any(emax > thr_run);
     if (moved) {
-        // the rows' cross-lane maxima first, then the selects, branch-free
-        float mxr[TQ];
-#pragma unroll
-        for (int u = 0; u < TQ; ++u) {
-            if constexpr (DBG == 2) mxr[u] = fmaxf(fmaxf(emax[u], __shfl_xor(emax[u], 16, 64)), fmaxf(__shfl_xor(emax[u], 32, 64), __shfl_xor(emax[u], 48, 64)));
-            else mxr[u] = xor32_max(xor16_max(emax[u]));
-        }
+        // the row's cross-lane maximum first, then the selects, branch-free
+        const float mx = xor32_max(xor16_max(emax));
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (DBG == 3) { asm volatile("s_nop 7\n\ts_nop 7" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }
+        const bool unset = thr_run == -INFINITY;
+        // only the rows that crossed their OWN trigger level move (all lanes of a row agree after the cross-lane maximum): a row's
+        // result does not depend on which other rows share its tile - the tile packing below may change without changing a bit
+        const bool need = mx > thr_run;
+        const float d = need ? mx : 0.f;                 // the reference rises by d (an unset row: to its first maximum)
+        const float a2 = umv_exp2(-d);
+        alpha = (need && !unset) ? a2 : 1.0f;            // (an unset row has O = 0, l = 0)
+        l_run *= alpha;
+        nm_run -= d;
+        thr_run = need ? ATTN_LAZY_TAU : thr_run;
+        const umv_f32x2_v d2 = {d, d};
 #pragma unroll
-        for (int u = 0; u < TQ; ++u) {
-            const float mx = mxr[u];
-            const bool unset = thr_run[u] == -INFINITY;
-            // only the rows that crossed their OWN trigger level move (all lanes of a row agree after the cross-lane maximum): a row's
-            // result does not depend on which other rows share its tile - the tile packing below may change without changing a bit
-            const bool need = mx > thr_run[u];
-            const float d = need ? mx : 0.f;                 // the reference rises by d (an unset row: to its first maximum)
-            const float a2 = umv_exp2(-d);
-            alpha[u] = (need && !unset) ? a2 : 1.0f;         // (an unset row has O = 0, l = 0)
-            l_run[u] *= alpha[u];
-            nm_run[u] -= d;
-            thr_run[u] = need ? ATTN_LAZY_TAU : thr_run[u];
-            const umv_f32x2_v d2 = {d, d};
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) e[u][q4] = e[u][q4] - d2;
-            // diagnostics of the parity tests (umv_attn_args.stats, the STATS kernels only): how often each form of the rare path ran.
-            // Wave-uniform counters, added to memory once at the end of the kernel
-            if constexpr (STATS) {
-                cnt[0] += __any(need && !unset) ? 1u : 0u;
-                cnt[1] += __any(need && unset) ? 1u : 0u;
-            }
+        for (int q4 = 0; q4 < 4; ++q4) e[q4] = e[q4] - d2;
+        // diagnostics of the parity tests (umv_attn_args.stats, the STATS kernels only): how often each form of the rare path ran.
+        // Wave-uniform counters, added to memory once at the end of the kernel
+        if constexpr (STATS) {
+            cnt[0] += __any(need && !unset) ? 1u : 0u;
+            cnt[1] += __any(need && unset) ? 1u : 0u;
         }
     }
+    umv_f32x2_v pv[4];
 #pragma unroll
-    for (int u = 0; u < TQ; ++u) {
-        umv_f32x2_v pv[4];
+    for (int q4 = 0; q4 < 4; ++q4) pv[q4] = (umv_f32x2_v){umv_exp2(e[q4][0]), umv_exp2(e[q4][1])};
+    const umv_f32x2_v s2 = (pv[0] + pv[1]) + (pv[2] + pv[3]);
+    l_run += s2[0] + s2[1];
 #pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) pv[q4] = (umv_f32x2_v){umv_exp2(e[u][q4][0]), umv_exp2(e[u][q4][1])};
-        const umv_f32x2_v s2 = (pv[0] + pv[1]) + (pv[2] + pv[3]);
-        l_run[u] += s2[0] + s2[1];
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-            const uint32_t w = pack2bf(pv[q4][0], pv[q4][1]);
-            pf[u][2 * q4] = (short)(w & 0xFFFFu);
-            pf[u][2 * q4 + 1] = (short)(w >> 16);
-        }
+    for (int q4 = 0; q4 < 4; ++q4) {
+        const uint32_t w = pack2bf(pv[q4][0], pv[q4][1]);
+        pf[2 * q4] = (short)(w & 0xFFFFu);
+        pf[2 * q4 + 1] = (short)(w >> 16);
     }
     return moved;
 }
 
-// LAZY: 0 = exact running maximum, 1 = lazy reference (one softmax call per q-tile), 2 = lazy, both tiles in one call.  STATS: the kernel
+// LAZY: 0 = exact running maximum, 1 = lazy reference (one softmax call per q-tile).  STATS: the kernel
 // also counts its rare-path events into umv_attn_args.stats (a separate instantiation, selected when stats != NULL: the counters cost the
 // hd-72 two-tile kernel the last of its 128 registers; same arithmetic, and the tests compare its output with the plain kernel's bit for bit)
 // PAGED: K / V^T are page pools behind umv_attn_args.page_table (a separate instantiation of the shipped lazy kernels: the slab kernels are
@@ -158,6 +127,7 @@ __device__ __forceinline__ bool attn_softmax_lazy(const f32x4 (&st)[TQ][2], int 
 // page base + offset inside the page; a 32-key block (and a two-block stage) never straddles a 256-key page.
 template <int HD, int TQ, int LAZY, bool STATS = false, bool PAGED = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(STATS ? 1 : ATTN_PREFILL_WAVES(HD, TQ)))) void attn_prefill_kernel(umv_attn_args a, float scale_log2e, int dense) {
+    static_assert(LAZY == 0 || LAZY == 1, "the softmax form: exact running maximum or lazy reference");
     constexpr int KS = (HD + 31) / 32;
     constexpr int DT = (HD + 15) / 16;
     constexpr int FK = 2 * KS, FB = FK + DT;   // fragments (1 KiB each) per 32-key block: K then V^T
@@ -168,7 +138,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(STATS ? 1 :
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int j = lane & 15, g = lane >> 4;
     const int G = a.nq / a.nkv;
-    const int QPT = 16 / G > 0 ? 16 / G : 1;
+    const int QPT = attn_qpt(G);
     // the 16 columns of a q-tile are (token, head) pairs of one kv head.  QPT packing: whole tokens, 16 / G of them (G = 7: 14 columns
     // used); DENSE packing (round 5): pairs run on across tile boundaries, PPT = 16 per tile - 12.5 % fewer tiles at G = 7.  Per row
     // nothing changes (same keys, same blocks, its own softmax reference): the two packings give the same bits.
@@ -204,10 +174,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(STATS ? 1 :
         wave_end = max(wave_end, my_end[u]);
         const bf16_t* qp = a.q + (int64_t)(q0 + (rvalid[u] ? qi[u] : 0)) * (a.q_row_stride ? a.q_row_stride : (int64_t)a.nq * HD) + (rvalid[u] ? head[u] : 0) * HD;
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const int d = ks * 32 + g * 8;
-            qf[u][ks] = (rvalid[u] && d < HD) ? ldg_frag(qp + d) : zero_frag();
-        }
+        for (int ks = 0; ks < KS; ++ks) qf[u][ks] = attn_q_frag<HD>(qp, g, rvalid[u], ks);
     }
     int blk_end = Lk;
     if (a.causal) {
@@ -283,11 +250,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(STATS ? 1 :
         for (int dt = 0; dt < DT; ++dt) o[u][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
 
-#ifdef UMV_ATTN_TRACE       // timing study (UMV_ATTN_TRACE=1 python -m unimedvl_amd.build; tools/attn_trace.py): s_memtime stamps per stage -> a.workspace
-#define ATTN_STAMP(t) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0" : "=s"(t)); __builtin_amdgcn_sched_barrier(0); } while (0)
+#ifdef UMV_ATTN_TRACE
     uint64_t ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, ts4 = 0;
-#else
-#define ATTN_STAMP(t) do { } while (0)
 #endif
     stage(0, 0);
     for (int sidx = 0; sidx < nstages; ++sidx) {
@@ -313,15 +277,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(STATS ? 1 :
                     const bf16x8 kf = *reinterpret_cast<const bf16x8*>(fb + (t * KS + ks) * 1024);
 #pragma unroll
                     for (int u = 0; u < TQ; ++u) st[u][t] = mfma16(kf, qf[u][ks], st[u][t]);
-#if UMV_ATTN_PAIR_DEBUG
-                    if constexpr (LAZY == 7) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");      // bisect: keep the next ds_read away from these MFMAs
-#endif
                 }
             ATTN_STAMP(ts2);
             bf16x8 pf[TQ];
             float alpha[TQ];
             bool rescale = false;
-            // Online softmax on the RAW scores (common.h::attn_softmax_block, shared with attn_kernel: same bits); the masked form
+            // Online softmax on the RAW scores (attention_tile.h::attn_softmax_block, shared with attn_kernel: same bits); the masked form
             // of a boundary block is a code path of its own (merging the two forms after the masks cost the interior path 12
             // register copies per tile).
             auto softmax_tile = [&](auto U, auto MASKED) {
@@ -346,51 +307,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(STATS ? 1 :
             bool all_interior = true;
 #pragma unroll
             for (int u = 0; u < TQ; ++u) all_interior = all_interior && (kb + 32 <= my_end[u] && kb + 31 <= min_limit[u]);   // wave uniform
-            if constexpr (LAZY >= 2) {
-                // both q-tiles of the wave in ONE call (one trigger test, one rare path): UMV_ATTN_VARIANT_PAIR, see the note below
-                constexpr int DBG = LAZY - 2;
-                if constexpr (DBG == 1) {
-                    if constexpr (TQ == 2) attn_mfma_guard(st[0][0], st[0][1], st[1][0], st[1][1]);
-                }
-                rescale = all_interior ? attn_softmax_lazy<TQ, false, STATS, DBG>(st, kb, g, limit, my_end, scale_log2e, nm_run, thr_run, l_run, alpha, pf, cnt)
-                                       : attn_softmax_lazy<TQ, true, STATS, DBG>(st, kb, g, limit, my_end, scale_log2e, nm_run, thr_run, l_run, alpha, pf, cnt);
-                if (!rescale) {
-#pragma unroll
-                    for (int u = 0; u < TQ; ++u) alpha[u] = 1.0f;
-                }
-            } else if constexpr (LAZY == 1) {
-                // one call per q-tile.  The two tiles of a wave in ONE call (LAZY >= 2: one trigger test, one rare path for both) is NOT shipped:
-                // that kernel gives wrong rows in the SECOND tile of some waves now and then, never the same twice.  Round 6 bisected it
-                // (profiles/r06_attn_pair_nondeterminism.txt, tools/attn_pair_debug.py): not the inline-asm maxima round 5 suspected (the
-                // function is compiler-visible throughout now), not the v_permlane*_swap steps (a ds_bpermute form fails too), not MFMA ->
-                // VALU wait states (tools/mfma_raw_probe.hip: 7 needed, hipcc places 8, at any occupancy); it needs >= 2 waves per SIMD, it
-                // goes away when the rare path is unconditional, and the per-lane state dump shows tile 1's scores of lanes 48-63 garbage
-                // in one block.  Cause not found; the form is compiled in UMV_ATTN_PAIR_DEBUG builds only.  The per-tile form below is
+            if constexpr (LAZY == 1) {
+                // one call per q-tile.  Both tiles of a wave in ONE call (one trigger test, one rare path) gave wrong rows in the second tile now
+                // and then; the cause was not found (profiles/r06_attn_pair_nondeterminism.txt is the record) and that form is gone.  This one is
                 // held to a determinism stress test on the bench shapes (tests/test_attn_lazy_gpu.py::test_lazy_kernels_are_deterministic).
                 static_for_attn<0, TQ>([&](auto U) {
                     constexpr int u = decltype(U)::value;
-                    float a1[1] = {1.0f};
+                    float a1 = 1.0f;
                     const bool mv = all_interior
-                        ? attn_softmax_lazy<1, false, STATS>(reinterpret_cast<const f32x4 (&)[1][2]>(st[u]), kb, g, reinterpret_cast<const int (&)[1]>(limit[u]),
-                                                      reinterpret_cast<const int (&)[1]>(my_end[u]), scale_log2e, reinterpret_cast<float (&)[1]>(nm_run[u]),
-                                                      reinterpret_cast<float (&)[1]>(thr_run[u]), reinterpret_cast<float (&)[1]>(l_run[u]), a1,
-                                                      reinterpret_cast<bf16x8 (&)[1]>(pf[u]), cnt)
-                        : attn_softmax_lazy<1, true, STATS>(reinterpret_cast<const f32x4 (&)[1][2]>(st[u]), kb, g, reinterpret_cast<const int (&)[1]>(limit[u]),
-                                                     reinterpret_cast<const int (&)[1]>(my_end[u]), scale_log2e, reinterpret_cast<float (&)[1]>(nm_run[u]),
-                                                     reinterpret_cast<float (&)[1]>(thr_run[u]), reinterpret_cast<float (&)[1]>(l_run[u]), a1,
-                                                     reinterpret_cast<bf16x8 (&)[1]>(pf[u]), cnt);
-                    alpha[u] = mv ? a1[0] : 1.0f;
+                        ? attn_softmax_lazy<false, STATS>(st[u], kb, g, limit[u], my_end[u], scale_log2e, nm_run[u], thr_run[u], l_run[u], a1, pf[u], cnt)
+                        : attn_softmax_lazy<true, STATS>(st[u], kb, g, limit[u], my_end[u], scale_log2e, nm_run[u], thr_run[u], l_run[u], a1, pf[u], cnt);
+                    alpha[u] = mv ? a1 : 1.0f;
                     rescale = rescale || mv;
                 });
             } else {
-            if (all_interior) {
-                if constexpr (TQ == 2) attn_mfma_guard(st[0][0], st[0][1], st[1][0], st[1][1]);      // raw accumulators go to asm maxima (common.h)
-                else attn_mfma_guard(st[0][0], st[0][1]);
-                static_for_attn<0, TQ>([&](auto U) { softmax_tile(U, std::false_type{}); });
-            }
-            else static_for_attn<0, TQ>([&](auto U) { softmax_tile(U, std::true_type{}); });
+                if (all_interior) {
+                    if constexpr (TQ == 2) attn_mfma_guard(st[0][0], st[0][1], st[1][0], st[1][1]);      // raw accumulators go to asm maxima (attention_tile.h)
+                    else attn_mfma_guard(st[0][0], st[0][1]);
+                    static_for_attn<0, TQ>([&](auto U) { softmax_tile(U, std::false_type{}); });
+                }
+                else static_for_attn<0, TQ>([&](auto U) { softmax_tile(U, std::true_type{}); });
 #pragma unroll
-            for (int u = 0; u < TQ; ++u) rescale = rescale || __any(alpha[u] != 1.0f);
+                for (int u = 0; u < TQ; ++u) rescale = rescale || __any(alpha[u] != 1.0f);
             }
             // ---- O^T += V^T P^T : one V^T fragment from LDS feeds the TQ tiles
             // Straight-line code: the rescale and the tail mask are hoisted out of the dt loop as wave-uniform branches, so the
@@ -416,7 +354,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(STATS ? 1 :
             }
             if (tail) {
 #pragma unroll
-                for (int dt = 0; dt < H0; ++dt) vfa[dt] = attn_mask_keys(vfa[dt], nvalid);
+                for (int dt = 0; dt < H0; ++dt) vfa[dt] = mask_keys(vfa[dt], nvalid);
             }
             __builtin_amdgcn_sched_barrier(0);
             bf16x8 vfb[DT - H0];
@@ -428,7 +366,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(STATS ? 1 :
                 for (int u = 0; u < TQ; ++u) o[u][dt] = mfma16(vfa[dt], pf[u], o[u][dt]);
             if (tail) {
 #pragma unroll
-                for (int dt = H0; dt < DT; ++dt) vfb[dt - H0] = attn_mask_keys(vfb[dt - H0], nvalid);
+                for (int dt = H0; dt < DT; ++dt) vfb[dt - H0] = mask_keys(vfb[dt - H0], nvalid);
             }
 #pragma unroll
             for (int dt = H0; dt < DT; ++dt)
@@ -444,19 +382,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(STATS ? 1 :
         }
 #endif
     }
-#if UMV_ATTN_PAIR_DEBUG
-    if constexpr (LAZY != 0 && TQ == 2) {      // debug builds: the per-lane softmax state at the end of the key loop -> workspace [wg][wave][u][lane][4]
-        if (a.workspace && a.nsplit == 1) {
-            const int wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-            float* dbg = reinterpret_cast<float*>(a.workspace) + ((int64_t)(wg * 4 + wave) * TQ) * 64 * 4;
-#pragma unroll
-            for (int u = 0; u < TQ; ++u) {
-                float* d4 = dbg + (u * 64 + lane) * 4;
-                d4[0] = nm_run[u]; d4[1] = thr_run[u]; d4[2] = l_run[u]; d4[3] = o[u][0].x;
-            }
-        }
-    }
-#endif
     // LAZY: the row sums were kept as per-lane partials; reduced here, in front of the first divergent store
     if constexpr (LAZY != 0) {
 #pragma unroll
@@ -469,15 +394,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(STATS ? 1 :
         const float inv = l_run[u] > 0.f ? 1.0f / l_run[u] : 0.f;
         bf16_t* op = a.out + ((int64_t)(q0 + qi[u]) * a.nq + head[u]) * HD;
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-            const int d = dt * 16 + g * 4;
-            if (d + 3 < HD) {
-                u32x2 pk;
-                pk.x = pack2bf(o[u][dt].x * inv, o[u][dt].y * inv);
-                pk.y = pack2bf(o[u][dt].z * inv, o[u][dt].w * inv);
-                *reinterpret_cast<u32x2*>(op + d) = pk;
-            }
-        }
+        for (int dt = 0; dt < DT; ++dt) attn_store_o<HD>(op, g, dt, o[u][dt], inv);
     }
     if constexpr (STATS) {
         if (a.stats && lane == 0) {
@@ -491,7 +408,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(STATS ? 1 :
 // ---------------------------------------------------------------------------------------------------------------- host side
 // The process-wide policy is read from the environment ONCE (thread-safe initialisation of a function-local static, immutable
 // afterwards): UMV_ATTN_SHARED=0 = the per-wave streaming kernel everywhere, UMV_ATTN_TQ=1|2 pins the q-tiles per wave,
-// UMV_ATTN_DENSE=0 = whole-token tiles, UMV_ATTN_LAZY=0|1|2 = the softmax form.  A call can replace it for itself through
+// UMV_ATTN_DENSE=0 = whole-token tiles, UMV_ATTN_LAZY=0 = the exact running maximum (anything else: the lazy reference).  A call can replace it for itself through
 // umv_attn_args.variant (UMV_ATTN_VARIANT_FORCE | ...: the parity tests drive every kernel variant in one process that way).
 struct AttnPolicy { int shared, tq, dense, lazy; };
 static const AttnPolicy& attn_env_policy() {
@@ -500,8 +417,7 @@ static const AttnPolicy& attn_env_policy() {
         const char* e = getenv("UMV_ATTN_SHARED"); q.shared = (e && atoi(e) == 0) ? 0 : 1;
         e = getenv("UMV_ATTN_TQ"); q.tq = e ? atoi(e) : 0;
         e = getenv("UMV_ATTN_DENSE"); q.dense = e ? atoi(e) : 1;
-        e = getenv("UMV_ATTN_LAZY"); q.lazy = e ? atoi(e) : 1;
-        if (q.lazy < 0 || q.lazy > 2) q.lazy = 1;
+        e = getenv("UMV_ATTN_LAZY"); q.lazy = (e && atoi(e) == 0) ? 0 : 1;
         return q;
     }();
     return p;
@@ -512,10 +428,11 @@ static AttnPolicy attn_policy(int variant) {
     q.shared = (variant & UMV_ATTN_VARIANT_STREAM) ? 0 : 1;
     q.tq = (variant & UMV_ATTN_VARIANT_TQ1) ? 1 : (variant & UMV_ATTN_VARIANT_TQ2) ? 2 : 0;
     q.dense = (variant & UMV_ATTN_VARIANT_WHOLE_TOKENS) ? 0 : 1;
-    q.lazy = (variant & UMV_ATTN_VARIANT_EXACT) ? 0 : (variant & UMV_ATTN_VARIANT_PAIR) ? 2 : 1;
+    q.lazy = (variant & UMV_ATTN_VARIANT_EXACT) ? 0 : 1;
     return q;
 }
-bool umv_attn_prefill_enabled(int variant) { return attn_policy(variant).shared != 0; }
+// The routing rule: a workgroup's four waves need four q-tiles to share a stage among, and the kernels are built for hd 128 / 72
+bool umv_attn_prefill_wanted(int variant, int hd, int qtiles) { return qtiles >= 4 && (hd == 128 || hd == 72) && attn_policy(variant).shared != 0; }
 
 template <int HD, int TQ, int LAZY, bool STATS = false, bool PAGED = false>
 static int launch_prefill(const umv_attn_args& a, int qtiles, float scale_log2e, int dense, hipStream_t s) {
@@ -540,8 +457,7 @@ static bool prefill_two_qtiles(const AttnPolicy& p, int qtiles, int nkv, int nse
 // pairs per tile instead of 14); UMV_ATTN_DENSE=0 keeps whole tokens per tile (A/B only; same bits either way)
 static bool attn_dense(const AttnPolicy& p, int G) { return p.dense != 0 && (16 % G) != 0 && G < 16; }
 static int prefill_qtiles(const AttnPolicy& p, int max_q, int G) {
-    const int QPT = 16 / G > 0 ? 16 / G : 1;
-    return attn_dense(p, G) ? (max_q * G + 15) / 16 : (max_q + QPT - 1) / QPT;
+    return attn_dense(p, G) ? (max_q * G + 15) / 16 : attn_qtiles(max_q, G);
 }
 
 // Which prefill-attention kernel umv_attn_varlen sends a (nsplit = 1) call to under the process policy: 0 = the per-wave streaming
@@ -550,8 +466,7 @@ extern "C" int umv_attn_prefill_tq(int nseg, int nq, int nkv, int hd, int max_q)
     if (nkv <= 0 || nq % nkv || nseg <= 0 || max_q <= 0) return 0;
     const AttnPolicy& p = attn_env_policy();
     const int G = nq / nkv;
-    const int QPT = 16 / G > 0 ? 16 / G : 1;
-    if (!((max_q + QPT - 1) / QPT >= 4 && (hd == 128 || hd == 72) && p.shared)) return 0;
+    if (!umv_attn_prefill_wanted(0, hd, attn_qtiles(max_q, G))) return 0;
     return prefill_two_qtiles(p, prefill_qtiles(p, max_q, G), nkv, nseg) ? 2 : 1;
 }
 
@@ -567,41 +482,22 @@ bool umv_attn_prefill_can_take(const umv_attn_args& a) {
     return kbytes < (int64_t)0x7FFFFFFF && vbytes < (int64_t)0x7FFFFFFF;
 }
 
-int umv_attn_prefill_launch(const umv_attn_args& a, int /*qtiles of the per-wave kernel*/, float scale_log2e, hipStream_t s) {
+// The form of the <HD, TQ> kernel: paged (hd 128, lazy, not counting: umv_attn_prefill_can_take), exact, lazy counting (stats given), lazy
+template <int HD, int TQ>
+static int launch_form(const umv_attn_args& a, int lazy, int qtiles, float scale_log2e, int dense, hipStream_t s) {
+    if constexpr (HD == 128) {
+        if (a.page_table) return launch_prefill<HD, TQ, 1, false, true>(a, qtiles, scale_log2e, dense, s);
+    }
+    if (!lazy) return launch_prefill<HD, TQ, 0>(a, qtiles, scale_log2e, dense, s);
+    return a.stats ? launch_prefill<HD, TQ, 1, true>(a, qtiles, scale_log2e, dense, s) : launch_prefill<HD, TQ, 1>(a, qtiles, scale_log2e, dense, s);
+}
+
+int umv_attn_prefill_launch(const umv_attn_args& a, float scale_log2e, hipStream_t s) {
     const AttnPolicy p = attn_policy(a.variant);
     const int G = a.nq / a.nkv;
     const int dense = attn_dense(p, G) ? 1 : 0;
     const int qtiles = prefill_qtiles(p, a.max_q, G);
     const bool two = prefill_two_qtiles(p, qtiles, a.nkv, a.nseg);
-    if (a.page_table)
-        return two ? launch_prefill<128, 2, 1, false, true>(a, qtiles, scale_log2e, dense, s) : launch_prefill<128, 1, 1, false, true>(a, qtiles, scale_log2e, dense, s);
-    if (a.stats && p.lazy == 1) {      // the counting instantiations of the shipped (per-tile lazy) kernels
-        if (a.hd == 128) return two ? launch_prefill<128, 2, 1, true>(a, qtiles, scale_log2e, dense, s) : launch_prefill<128, 1, 1, true>(a, qtiles, scale_log2e, dense, s);
-        return two ? launch_prefill<72, 2, 1, true>(a, qtiles, scale_log2e, dense, s) : launch_prefill<72, 1, 1, true>(a, qtiles, scale_log2e, dense, s);
-    }
-    const int key = (a.hd == 128 ? 0 : 8) + (two ? 4 : 0) + p.lazy;
-    switch (key) {
-        case 0: return launch_prefill<128, 1, 0>(a, qtiles, scale_log2e, dense, s);
-        case 1: case 2: return launch_prefill<128, 1, 1>(a, qtiles, scale_log2e, dense, s);     // (one tile per wave: the paired form is the per-tile form)
-        case 4: return launch_prefill<128, 2, 0>(a, qtiles, scale_log2e, dense, s);
-        case 5: return launch_prefill<128, 2, 1>(a, qtiles, scale_log2e, dense, s);
-        case 6:
-#if UMV_ATTN_PAIR_DEBUG
-            switch ((a.variant >> 8) & 7) {          // debug builds only: bits 8..10 of variant pick a bisecting form of the paired kernel
-                case 1: return launch_prefill<128, 2, 3>(a, qtiles, scale_log2e, dense, s);
-                case 2: return launch_prefill<128, 2, 4>(a, qtiles, scale_log2e, dense, s);
-                case 3: return launch_prefill<128, 2, 5>(a, qtiles, scale_log2e, dense, s);
-                case 4: return launch_prefill<128, 2, 6>(a, qtiles, scale_log2e, dense, s);
-                case 5: return launch_prefill<128, 2, 7>(a, qtiles, scale_log2e, dense, s);
-                case 6: return launch_prefill<128, 2, 8>(a, qtiles, scale_log2e, dense, s);
-                default: return launch_prefill<128, 2, 2>(a, qtiles, scale_log2e, dense, s);
-            }
-#else
-            return launch_prefill<128, 2, 1>(a, qtiles, scale_log2e, dense, s);      // the paired form exists in UMV_ATTN_PAIR_DEBUG builds only (see the note in the kernel)
-#endif
-        case 8: return launch_prefill<72, 1, 0>(a, qtiles, scale_log2e, dense, s);
-        case 9: case 10: return launch_prefill<72, 1, 1>(a, qtiles, scale_log2e, dense, s);
-        case 12: return launch_prefill<72, 2, 0>(a, qtiles, scale_log2e, dense, s);
-        default: return launch_prefill<72, 2, 1>(a, qtiles, scale_log2e, dense, s);     // (13, 14: the paired form needs more than the 128 registers of four waves per SIMD at hd 72 - it exists for hd 128 only)
-    }
+    if (a.hd == 128) return two ? launch_form<128, 2>(a, p.lazy, qtiles, scale_log2e, dense, s) : launch_form<128, 1>(a, p.lazy, qtiles, scale_log2e, dense, s);
+    return two ? launch_form<72, 2>(a, p.lazy, qtiles, scale_log2e, dense, s) : launch_form<72, 1>(a, p.lazy, qtiles, scale_log2e, dense, s);
 }
