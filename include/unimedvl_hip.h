@@ -550,6 +550,60 @@ int umv_decode_step_end_rows(int32_t* tok_slot, int32_t* tok_pos, int32_t* kv_le
                              int64_t* step_idx, const uint16_t* logits, int64_t ldo, int V, const int64_t* forced_ids, float* logprob,
                              int B, int max_len, umv_row_sampling* rows, float* cut_y, int32_t* n_kept, umv_stream_t stream);
 
+/* ------------------------------------------------------------------ speculative greedy decode: verify drafts, commit, roll back, draft again
+ * A step of k = draft_len >= 1 processes T = B * (k + 1) <= 64 rows.  Row r0 = b * (k + 1) holds sample b's next input token t0, which is
+ * not in the cache yet; rows r0 + j, j = 1..k, hold its drafts d_j: the first n_draft[b] are real, the rest are FILLERS equal to t0 -
+ * computed, never accepted.  Before the step, tok_slot[r0 + j] = slot0 + j, tok_pos[r0 + j] = pos0 + j and kv_len[b] = len + k + 1, so that
+ * umv_qkv_post appends all k + 1 tokens and umv_attn_varlen (max_q = k + 1, causal) lets row j see the keys 0..len + j.  After the greedy
+ * lm_head call (argmax_partial [T][n_tiles], sample_temperature = 0) this entry ends the step, one workgroup per sample, no word shared
+ * between workgroups.  All of it is integer logic, so the definition is exact:
+ *   1 pick     p_j = column of the maximum key of argmax_partial[r0 + j][0..n_tiles), j = 0..k (umv_decode_step_end_argmax's pick).
+ *   2 accept   n = the largest n <= n_draft[b] with d_j == p_{j-1} for all 1 <= j <= n.
+ *   3 emit     m = min(n + 1, min(limit[b], out_ld) - n_out[b]), at least 0: out_ids[b][n_out[b] + i] = p_i, i < m; n_out[b] += m.
+ *   4 advance  slot0, pos0 and kv_len[b] go up by m: the cache now holds t0, d_1..d_{m-1}.  The K/V of the rejected rows lies above
+ *              the new length and is overwritten by the next step, which writes the slots len..len + k: a rollback is this shorter length.
+ *   5 history  the m emitted tokens are appended to hist[b] (int32 [B][hist_ld]; hist_len[b] += m; a token that finds no room below
+ *              hist_ld is dropped and hist_len[b] stays at hist_ld - later drafts get worse, the output does not change).  If m > 0
+ *              the next input is p_{m-1}, else it stays t0.
+ *   6 draft    by one of two rules; a draft is always a token of [0, V):
+ *              predicted continuation, for a sample with predicted != NULL and pred_len[b] > 0 (predicted int64 [B][pred_ld] is
+ *                aligned with out_ids): d_j = predicted[b][n_out[b] + j - 1], j = 1..k, while that index is < pred_len[b] and the
+ *                entry is in [0, V);
+ *              prompt lookup otherwise: for g = ngram_max down to ngram_min with hist_len[b] > g, the suffix is the last g history
+ *                tokens; the match is the largest i < hist_len[b] - g with hist[b][i..i + g) equal to the suffix, entries < 0 (the
+ *                caller's separators) never match.  The FIRST g that has a match decides: d_j = hist[b][i + g + j - 1], j = 1..k,
+ *                while the index is < hist_len[b] and the entry is in [0, V).  No match for any g: no drafts.
+ *              n_draft[b] = how many that gave.
+ *   7 rows     ids[r0] = the next input, ids[r0 + j] = d_j (fillers: the next input), tok_slot[r0 + j] = slot0 + j,
+ *              tok_pos[r0 + j] = pos0 + j for j = 0..k.
+ *   8 stats    stats[b] = {steps, drafted, accepted} (int32 x 3) += {1, the n_draft[b] this step verified, n}.
+ * draft_only != 0 runs 6 and 7 alone (nothing is read from argmax_partial, which may be NULL): the call that seeds the first step's rows
+ * from the history / the predicted continuation.  UMV_ERR_ARG: k < 1, B * (k + 1) > 64, ngram_min < 1 or ngram_min > ngram_max, V that
+ * is not the column count behind n_tiles, a NULL required pointer (everything but predicted / pred_len, which go together). */
+typedef struct {
+    int32_t* tok_slot;               /* [T] */
+    int32_t* tok_pos;                /* [T] */
+    int32_t* kv_len;                 /* [B] */
+    const uint64_t* argmax_partial;  /* [T][n_tiles] */
+    int n_tiles;
+    int V;
+    int64_t* ids;                    /* [T]: this step's rows in, the next step's out */
+    int64_t* out_ids;                /* [B][out_ld] */
+    int64_t out_ld;
+    int32_t* n_out;                  /* [B] */
+    const int32_t* limit;            /* [B]: emit no token at or beyond out_ids[b][limit[b]] */
+    int32_t* n_draft;                /* [B] */
+    int32_t* hist;                   /* [B][hist_ld] */
+    int64_t hist_ld;
+    int32_t* hist_len;               /* [B] */
+    const int64_t* predicted;        /* optional [B][pred_ld] */
+    int64_t pred_ld;
+    const int32_t* pred_len;         /* [B], with predicted */
+    int32_t* stats;                  /* [B][3] */
+    int B, k, ngram_min, ngram_max, draft_only;
+} umv_spec_step_args;
+int umv_decode_step_end_speculative(const umv_spec_step_args* a, umv_stream_t stream);
+
 
 /* TimestepEmbedder.timestep_embedding (modeling_utils.py:87-109): out[r] = bf16(cat(cos(t[r] * freqs), sin(t[r] * freqs))),
  * out [n, 2*half]; freqs [half] fp32 = exp(-ln(10000) * i / half) from the caller.  The two linears + SiLU of the embedder

@@ -247,6 +247,29 @@ static void bad_arguments() {
     EXPECT_ERR(umv_logit_penalty_bf16(&lp, nullptr));
     lp.rows = nullptr; lp.M = 0;
     EXPECT_OK(umv_logit_penalty_bf16(&lp, nullptr));             // no rows
+    // speculative step end
+    EXPECT_ERR(umv_decode_step_end_speculative(nullptr, nullptr));
+    umv_spec_step_args sp;
+    std::memset(&sp, 0, sizeof sp);
+    EXPECT_ERR(umv_decode_step_end_speculative(&sp, nullptr));
+    sp.tok_slot = dummyi; sp.tok_pos = dummyi; sp.kv_len = dummyi; sp.argmax_partial = (const uint64_t*)dummyl; sp.n_tiles = 4; sp.V = 64;
+    sp.ids = dummyl; sp.out_ids = dummyl; sp.out_ld = 8; sp.n_out = dummyi; sp.limit = dummyi; sp.n_draft = dummyi; sp.hist = dummyi;
+    sp.hist_ld = 8; sp.hist_len = dummyi; sp.stats = dummyi; sp.B = 1; sp.k = 0; sp.ngram_min = 2; sp.ngram_max = 4;
+    EXPECT_ERR(umv_decode_step_end_speculative(&sp, nullptr));   // k < 1
+    sp.k = 3; sp.B = 17;                                          // 68 rows
+    EXPECT_ERR(umv_decode_step_end_speculative(&sp, nullptr));
+    sp.B = 1; sp.ngram_min = 0;
+    EXPECT_ERR(umv_decode_step_end_speculative(&sp, nullptr));
+    sp.ngram_min = 5;                                             // above ngram_max
+    EXPECT_ERR(umv_decode_step_end_speculative(&sp, nullptr));
+    sp.ngram_min = 2; sp.stats = nullptr;
+    EXPECT_ERR(umv_decode_step_end_speculative(&sp, nullptr));
+    sp.stats = dummyi; sp.predicted = dummyl;                     // predicted without pred_len
+    EXPECT_ERR(umv_decode_step_end_speculative(&sp, nullptr));
+    sp.predicted = nullptr; sp.n_tiles = 3;                       // 64 columns are not 3 tiles
+    EXPECT_ERR(umv_decode_step_end_speculative(&sp, nullptr));
+    sp.n_tiles = 4; sp.B = 0;
+    EXPECT_OK(umv_decode_step_end_speculative(&sp, nullptr));    // no samples
     EXPECT_ERR(umv_timestep_embed(nullptr, nullptr, nullptr, 4, 128, nullptr));
     EXPECT_ERR(umv_cfg_renorm_euler(nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 1, 4.0f, 1.5f, 0.f, 0, 0.1f, 64, nullptr));
     // VAE

@@ -85,6 +85,17 @@ class RowSampling(C.Structure):
     ]
 
 
+class SpecStepArgs(C.Structure):
+    """umv_spec_step_args: the step end of a speculative decode step (umv_decode_step_end_speculative)"""
+    _fields_ = [
+        ("tok_slot", C.c_void_p), ("tok_pos", C.c_void_p), ("kv_len", C.c_void_p), ("argmax_partial", C.c_void_p),
+        ("n_tiles", C.c_int), ("V", C.c_int), ("ids", C.c_void_p), ("out_ids", C.c_void_p), ("out_ld", C.c_int64),
+        ("n_out", C.c_void_p), ("limit", C.c_void_p), ("n_draft", C.c_void_p), ("hist", C.c_void_p), ("hist_ld", C.c_int64),
+        ("hist_len", C.c_void_p), ("predicted", C.c_void_p), ("pred_ld", C.c_int64), ("pred_len", C.c_void_p), ("stats", C.c_void_p),
+        ("B", C.c_int), ("k", C.c_int), ("ngram_min", C.c_int), ("ngram_max", C.c_int), ("draft_only", C.c_int),
+    ]
+
+
 # umv_logit_penalty_args.count words: bits 0..29 the count, then "in the context set" and "in the row's visit list"
 PENALTY_COUNT_MASK, PENALTY_CONTEXT, PENALTY_LISTED = 0x3FFFFFFF, 0x40000000, 0x80000000
 
@@ -157,6 +168,7 @@ _SIGS = {
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "umv_logit_penalty_bf16": (C.c_int, [C.POINTER(LogitPenaltyArgs), C.c_void_p]),
+    "umv_decode_step_end_speculative": (C.c_int, [C.POINTER(SpecStepArgs), C.c_void_p]),
     "umv_timestep_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "umv_cfg_renorm_euler": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.c_void_p]),

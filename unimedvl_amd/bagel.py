@@ -312,7 +312,8 @@ class Bagel(BagelPrep):
                       do_sample: bool = False, temperature: float = 1.0, end_token_id: int = None,
                       return_logits: bool = False, per_sample_eos: bool = False, return_logprobs: bool = False, *,
                       repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
-                      logit_bias=None, penalty_context_ids=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+                      logit_bias=None, penalty_context_ids=None, draft_len: int = 0, draft_ngram=(2, 4), draft_context_ids=None,
+                      predicted_ids=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """Greedy decode (bagel.py:1236-1317).  Returns [steps, B] int64 whose row 0 holds the
         start tokens.  Like the reference, the batch stops when SAMPLE 0 emits end_token_id
         (bagel.py:1313); per_sample_eos=True is the batched extension (stops when every sample
@@ -326,7 +327,13 @@ class Bagel(BagelPrep):
         repetition_penalty / presence_penalty / frequency_penalty (1.0 / 0.0 / 0.0 = off) and logit_bias ({token: float}, -inf bans
         a token): the logit penalties of include/unimedvl_hip.h, applied in the captured step before temperature and truncation; ids,
         logits and logprobs are those of the adjusted logits.  penalty_context_ids: per sample a list of tokens (the prompt) that
-        count as seen for the repetition penalty - this call has no token ids of its own, so without it that set is empty."""
+        count as seen for the repetition penalty - this call has no token ids of its own, so without it that set is empty.
+        draft_len > 0: speculative greedy decode (speculative.SpeculativeDecodeSession) - every step verifies draft_len drafted tokens
+        per sample, B * (draft_len + 1) <= 64.  The drafts come from predicted_ids (per sample a predicted continuation of the
+        generated tokens) where given, else from a lookup of the last draft_ngram = (min, max) tokens in draft_context_ids (per sample
+        the prompt's tokens; this call has none of its own) and in what was generated.  Same matrix, same stop rules, same cache
+        lengths as draft_len = 0, fewer passes over the weights where drafts are accepted; self.last_draft_stats keeps the session's
+        [B, 3] (steps, drafted, accepted).  Greedy only: do_sample, return_logits / return_logprobs, penalties and logit_bias raise."""
         top_k, top_p, min_p = ops.check_truncation(top_k, top_p, min_p)
         ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, vocab=self.cfg.vocab)
         # do_sample: softmax(logits / temperature) + multinomial on the device (bagel.py:1297-1299).  The
@@ -343,6 +350,15 @@ class Bagel(BagelPrep):
             if return_logprobs:
                 res += (torch.zeros((0, len(past_key_values.lens)), dtype=torch.float32, device=self.device),)
             return res if len(res) > 1 else out
+        if draft_len:
+            if return_logits or return_logprobs:
+                raise ValueError("speculative decode (draft_len > 0) is greedy only: no return_logits / return_logprobs")
+            return self._generate_text_speculative(past_key_values, packed_start_tokens, packed_query_position_ids, max_length,
+                                                   end_token_id, per_sample_eos, draft_len, draft_ngram, draft_context_ids, predicted_ids,
+                                                   dict(do_sample=do_sample, top_k=top_k, top_p=top_p, min_p=min_p,
+                                                        repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                                                        frequency_penalty=frequency_penalty, logit_bias=logit_bias,
+                                                        penalty_context_ids=penalty_context_ids))
         sess = DecodeSession(self.language_model, past_key_values, packed_start_tokens, packed_query_position_ids,
                              max_length, use_graph=self.decode_use_graph and not return_logits,
                              do_sample=do_sample, temperature=temperature, seed=seed, logprobs=return_logprobs,
@@ -378,18 +394,55 @@ class Bagel(BagelPrep):
             res += (sess.pred_logprobs[:rows].clone(),)
         return res if len(res) > 1 else out
 
+    def _generate_text_speculative(self, cache, start_tokens, positions, max_length, end_token_id, per_sample_eos, draft_len,
+                                   draft_ngram, draft_context_ids, predicted_ids, plain):
+        """generate_text with drafts: the plain call's matrix row s + 1 is a sample's emitted token s.  The plain call stops at row
+        `stop` - sample 0's first end token, or the last of every sample's first - and returns that many rows, leaving as many tokens
+        in the cache; here a sample may be ahead of another, so when the stop row is known every sample's limit is lowered to it and
+        the steps go on until each holds that many tokens."""
+        from .speculative import SpeculativeDecodeSession
+        sess = SpeculativeDecodeSession(self.language_model, cache, start_tokens, positions, max_length, draft_len,
+                                        use_graph=self.decode_use_graph, draft_ngram=draft_ngram, draft_context_ids=draft_context_ids,
+                                        predicted_ids=predicted_ids, **plain)
+        stop = None
+        while True:
+            sess.step(min(self.eos_check_every, max_length - sess.steps_done))
+            n_out = sess.n_out.cpu()
+            if end_token_id is not None and stop is None:
+                out = sess.out_ids.cpu()
+                first = []                       # per sample the row after its first end token, None while it has emitted none
+                for b in range(out.shape[0]):
+                    hit = (out[b, :int(n_out[b])] == end_token_id).nonzero()
+                    first.append(int(hit[0]) + 1 if hit.numel() else None)
+                if per_sample_eos:
+                    stop = max(first) if all(f is not None for f in first) else None
+                else:
+                    stop = first[0]
+                if stop is not None:
+                    sess.limit.fill_(stop)
+            rows = stop if stop is not None else max_length
+            if int(n_out.min()) >= rows or sess.steps_done >= max_length:
+                break
+        sess.commit(rows)
+        self.last_draft_stats = sess.stats.cpu()
+        return torch.cat([start_tokens.to(device=self.device, dtype=torch.int64).reshape(1, -1), sess.out_ids[:, :rows - 1].t()], 0)
+
     # ------------------------------------------------------------------ convenience (evaluation path)
     @torch.no_grad()
     @ops.on_device
     def chat(self, tokenizer, new_token_ids, image_transform, images, prompt, max_length: int,
              do_sample: bool = False, temperature: float = 1.0, return_logprobs: bool = False, *,
              repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None,
-             penalize_prompt: bool = False, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+             penalize_prompt: bool = False, draft_len: int = 0, draft_ngram=(2, 4), predicted_ids=None,
+             top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """ViT-only VQA convenience path (bagel.py:1321-1392).  return_logprobs=True: returns (answer, token_ids, token_logprobs) -
         the generated tokens behind the answer (the end token excluded) and the log-probability of each (generate_text).
         repetition_penalty / presence_penalty / frequency_penalty / logit_bias: the logit penalties of generate_text;
         penalize_prompt=True makes the prompt's token ids the repetition penalty's context set (off: generated tokens only) - the
-        text's own tokens, not the bos / eos wrapper around them: a penalised end token would only make answers longer."""
+        text's own tokens, not the bos / eos wrapper around them: a penalised end token would only make answers longer.
+        draft_len > 0: speculative greedy decode (generate_text) - the same answer from fewer passes over the weights where the answer
+        repeats the prompt's wording or its own; the prompt's text tokens are the lookup's context.  predicted_ids: a predicted answer
+        (a string, or its token ids) to draft from instead."""
         if self.chat_cache_tokens > 0:       # serving: one reserved cache reused by every request (stable slabs -> graph prefill)
             if self._chat_cache is None or self._chat_cache.cap < self.chat_cache_tokens:
                 self._chat_cache = NaiveCache(self.cfg.layers)
@@ -403,14 +456,21 @@ class Bagel(BagelPrep):
             gi, newlens, new_rope = self.prepare_vit_images(newlens, new_rope, [image], image_transform, new_token_ids)
             cache = self.forward_cache_update_vit(cache, **gi)
         gi, newlens, new_rope = self.prepare_prompts(newlens, new_rope, [prompt], tokenizer, new_token_ids)
-        prompt_ids = [gi["packed_text_ids"].tolist()[1:-1]] if penalize_prompt else None        # without the bos / eos wrapper
+        text_ids = gi["packed_text_ids"].tolist()[1:-1]                                          # without the bos / eos wrapper
+        prompt_ids = [text_ids] if penalize_prompt else None
+        draft = {}
+        if draft_len:
+            if isinstance(predicted_ids, str):
+                predicted_ids = tokenizer.encode(predicted_ids)
+            draft = dict(draft_len=draft_len, draft_ngram=draft_ngram, draft_context_ids=[text_ids],
+                         predicted_ids=None if predicted_ids is None else [list(predicted_ids)])
         cache = self.forward_cache_update_text(cache, **gi)
         gi = self.prepare_start_tokens(newlens, new_rope, new_token_ids)
         ids = self.generate_text(past_key_values=cache, max_length=max_length, do_sample=do_sample,
                                  temperature=temperature, end_token_id=new_token_ids["eos_token_id"],
                                  return_logprobs=return_logprobs, top_k=top_k, top_p=top_p, min_p=min_p,
                                  repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-                                 frequency_penalty=frequency_penalty, logit_bias=logit_bias, penalty_context_ids=prompt_ids, **gi)
+                                 frequency_penalty=frequency_penalty, logit_bias=logit_bias, penalty_context_ids=prompt_ids, **draft, **gi)
         if return_logprobs:
             ids, lp = ids
         output = tokenizer.decode(ids[:, 0].cpu())

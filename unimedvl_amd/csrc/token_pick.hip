@@ -1,6 +1,7 @@
 // Next-token picking and the bookkeeping that ends a decode step: argmax and temperature sampling over bf16 logits, the
 // step-end kernels (three of them finish the lm_head GEMM's argmax epilogue: plain, with the token's log-probability, and with
-// top-k / top-p / min-p), the stand-alone token log-probability and the stand-alone truncated sampler.
+// top-k / top-p / min-p), the stand-alone token log-probability, the stand-alone truncated sampler and the step end of a speculative
+// greedy step (verify the drafts, commit, roll back, draft again).
 #include "block_reduce.h"
 #include "token_pick.h"
 #include "truncation.h"
@@ -452,6 +453,114 @@ extern "C" int umv_decode_step_end_rows(int32_t* tok_slot, int32_t* tok_pos, int
     if (B == 0) return UMV_OK;
     hipLaunchKernelGGL(decode_step_end_rows_kernel, dim3(B), dim3(TR_THREADS), 0, (hipStream_t)stream, e, argmax_partial, lse_partial,
                        n_tiles, logits, ldo, V, rows, forced_ids, logprob, cut_y, n_kept);
+    UMV_LAUNCH_CHECK();
+    return UMV_OK;
+}
+
+// ----------------------------------------------------------------------------- speculative greedy decode (include/unimedvl_hip.h)
+// The step end of a step that verified k drafts per sample: steps 1-8 of the header, one workgroup per sample.  The picks are the
+// key maxima of decode_step_end_argmax_kernel, one row after the other; the sample's bookkeeping is thread 0's; the prompt lookup
+// scans the candidate starts thread-strided and takes the largest through the same key maximum.
+__device__ __forceinline__ bool spec_token_ok(int64_t t, int V) { return t >= 0 && t < V; }
+
+__global__ __launch_bounds__(256) void decode_step_end_speculative_kernel(umv_spec_step_args a) {
+    __shared__ uint64_t sm[4];
+    __shared__ int64_t pick[64];
+    __shared__ int32_t s_hist_len, s_n_out;
+    const int b = blockIdx.x, k = a.k, r0 = b * (k + 1);
+    int32_t* hist = a.hist + (int64_t)b * a.hist_ld;
+    if (!a.draft_only) {
+        for (int j = 0; j <= k; ++j) {
+            const uint64_t best = block_max_u64<256, true>(strided_max_key<256>(a.argmax_partial + (int64_t)(r0 + j) * a.n_tiles, a.n_tiles), sm);
+            if (threadIdx.x == 0) pick[j] = argmax_key_column(best);
+            __syncthreads();             // sm is free again, pick[j] is written
+        }
+    }
+    if (threadIdx.x == 0) {
+        int32_t hl = a.hist_len[b], n_out = a.n_out[b];
+        hl = hl < 0 ? 0 : hl > a.hist_ld ? (int32_t)a.hist_ld : hl;      // nothing is read or written outside the row
+        if (!a.draft_only) {
+            const int nd = a.n_draft[b];
+            int n = 0;
+            while (n < nd && n < k && a.ids[r0 + n + 1] == pick[n]) ++n;
+            const int64_t lim = a.limit[b] < a.out_ld ? (int64_t)a.limit[b] : a.out_ld;
+            const int m = (n_out < 0 || lim - n_out <= 0) ? 0 : lim - n_out < n + 1 ? (int)(lim - n_out) : n + 1;
+            for (int i = 0; i < m; ++i) {
+                a.out_ids[(int64_t)b * a.out_ld + n_out + i] = pick[i];
+                if (hl < a.hist_ld) hist[hl++] = (int32_t)pick[i];
+            }
+            n_out += m;
+            a.n_out[b] = n_out;
+            a.hist_len[b] = hl;
+            a.kv_len[b] += m;
+            a.tok_slot[r0] += m;
+            a.tok_pos[r0] += m;
+            if (m > 0) a.ids[r0] = pick[m - 1];
+            a.stats[b * 3 + 0] += 1;
+            a.stats[b * 3 + 1] += nd;
+            a.stats[b * 3 + 2] += n;
+        }
+        s_hist_len = hl;
+        s_n_out = n_out;
+    }
+    __syncthreads();                     // the appended history is visible to the workgroup
+    const int32_t hl = s_hist_len, n_out = s_n_out;
+    const bool use_pred = a.predicted && a.pred_len[b] > 0;
+    int64_t start = -1;                  // the index of hist the drafts are read from; the same in every thread
+    if (!use_pred) {
+        for (int g = a.ngram_max; g >= a.ngram_min && start < 0; --g) {
+            if (hl <= g) continue;
+            const int32_t* suf = hist + hl - g;
+            uint64_t found = 0;          // 1 + the largest matching start of this thread
+            for (int i = threadIdx.x; i < hl - g; i += 256) {
+                bool eq = true;
+                for (int t = 0; t < g && eq; ++t) eq = suf[t] >= 0 && hist[i + t] == suf[t];
+                if (eq) found = (uint64_t)i + 1;
+            }
+            found = block_max_u64<256, true>(found, sm);
+            __syncthreads();             // sm is free again
+            if (found) start = (int64_t)found - 1 + g;
+        }
+    }
+    if (threadIdx.x == 0) {
+        const int64_t t0 = a.ids[r0];
+        const int32_t slot0 = a.tok_slot[r0], pos0 = a.tok_pos[r0];
+        int nd = 0;
+        bool open = true;                // drafts stop at the first index or entry that is out of range
+        for (int j = 1; j <= k; ++j) {
+            int64_t d = -1;
+            if (open && use_pred) {
+                const int64_t at = (int64_t)n_out + j - 1;
+                if (at < a.pred_len[b] && at < a.pred_ld) d = a.predicted[(int64_t)b * a.pred_ld + at];
+            } else if (open && start >= 0) {
+                const int64_t at = start + j - 1;
+                if (at < hl) d = hist[at];
+            }
+            open = open && spec_token_ok(d, a.V);
+            if (open) ++nd;
+            a.ids[r0 + j] = open ? d : t0;
+            a.tok_slot[r0 + j] = slot0 + j;
+            a.tok_pos[r0 + j] = pos0 + j;
+        }
+        a.n_draft[b] = nd;
+    }
+}
+
+extern "C" int umv_decode_step_end_speculative(const umv_spec_step_args* a, umv_stream_t stream) {
+    UMV_CHECK(a, UMV_ERR_ARG, "decode_step_end_speculative: null args");
+    UMV_CHECK(a->k >= 1 && a->B >= 0 && (int64_t)a->B * (a->k + 1) <= 64, UMV_ERR_ARG,
+              "decode_step_end_speculative: k (%d) must be >= 1 and B * (k + 1) (%d x %d) at most 64 rows", a->k, a->B, a->k + 1);
+    UMV_CHECK(a->ngram_min >= 1 && a->ngram_min <= a->ngram_max, UMV_ERR_ARG,
+              "decode_step_end_speculative: 1 <= ngram_min (%d) <= ngram_max (%d)", a->ngram_min, a->ngram_max);
+    UMV_CHECK(a->tok_slot && a->tok_pos && a->kv_len && a->ids && a->out_ids && a->n_out && a->limit && a->n_draft && a->hist &&
+                  a->hist_len && a->stats && (a->argmax_partial || a->draft_only) && a->out_ld > 0 && a->hist_ld > 0,
+              UMV_ERR_ARG, "decode_step_end_speculative: null pointer");
+    UMV_CHECK((a->predicted != nullptr) == (a->pred_len != nullptr) && (!a->predicted || a->pred_ld > 0), UMV_ERR_ARG,
+              "decode_step_end_speculative: predicted and pred_len go together");
+    UMV_CHECK(a->n_tiles > 0, UMV_ERR_ARG, "decode_step_end_speculative: n_tiles must be > 0");
+    if (int rc = tile_columns_ok("decode_step_end_speculative", a->V, a->n_tiles, a->V)) return rc;
+    if (a->B == 0) return UMV_OK;
+    hipLaunchKernelGGL(decode_step_end_speculative_kernel, dim3(a->B), dim3(256), 0, (hipStream_t)stream, *a);
     UMV_LAUNCH_CHECK();
     return UMV_OK;
 }

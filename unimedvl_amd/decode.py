@@ -36,6 +36,8 @@ def _lib_flag(word):
 
 
 class DecodeSession:
+    draft_len = 0       # tokens a step verifies per sample besides its input (speculative.SpeculativeDecodeSession): a step has B * (draft_len + 1) rows
+
     def __init__(self, llm, cache: NaiveCache, start_tokens, positions, max_length, use_graph=True, nsplit=None,
                  do_sample=False, temperature=1.0, seed=0, logprobs=False, forced_ids=None, *,
                  repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, penalty_context_ids=None,
@@ -96,30 +98,39 @@ class DecodeSession:
         B = len(cache.lens)
         self.B = B
         self.max_length = max_length
+        # a step's rows: one per sample, or - with drafts to verify - draft_len + 1 per sample, sample after sample, at consecutive
+        # slots and positions; every buffer and routing rule below that went by the sample count goes by the row count R
+        k = self.draft_len
+        R = self.rows = B * (k + 1)
         nq, nkv, hd, H = cfg.heads, cfg.kv_heads, cfg.head_dim, cfg.hidden
         if hasattr(cache, "ensure_tokens"):      # paged cache: pages for every slot's own decode horizon (the captured step reads the table)
-            cache.ensure_tokens([n + max_length + 1 for n in cache.lens], nkv, hd, dev)
+            cache.ensure_tokens([n + max_length + 1 + k for n in cache.lens], nkv, hd, dev)
         else:
-            cache.ensure(B, max(cache.lens) + max_length + 1, nkv, hd, dev)
+            cache.ensure(B, max(cache.lens) + max_length + 1 + k, nkv, hd, dev)
         self.lens0 = list(cache.lens)
         i32 = dict(dtype=torch.int32, device=dev)
+
+        def per_row(t):      # a per-sample vector -> per row, the row's offset inside its sample added
+            return t if k == 0 else t.repeat_interleave(k + 1) + torch.arange(k + 1, dtype=t.dtype, device=t.device).repeat(B)
         self.ids = start_tokens.to(device=dev, dtype=torch.int64).clone()
-        self.tok_seg = torch.arange(B, **i32)
-        self.tok_slot = torch.tensor(cache.lens, dtype=torch.int32).to(dev)
+        if k:
+            self.ids = self.ids.repeat_interleave(k + 1)
+        self.tok_seg = torch.arange(B, **i32) if k == 0 else torch.arange(B, **i32).repeat_interleave(k + 1)
+        self.tok_slot = per_row(torch.tensor(cache.lens, dtype=torch.int32).to(dev))
         pmax = int(positions.max()) if positions.numel() else 0
-        if (int(positions.min()) if positions.numel() else 0) < 0 or pmax + max_length >= cfg.max_position:
-            raise ValueError(f"decode would reach rope position {pmax + max_length} >= max_position_embeddings {cfg.max_position}")
-        self.tok_pos = positions.to(device=dev, dtype=torch.int32).clone()
-        self.kv_len = self.tok_slot + 1
-        self.cu_q = torch.arange(B + 1, **i32)
+        if (int(positions.min()) if positions.numel() else 0) < 0 or pmax + max_length + k >= cfg.max_position:
+            raise ValueError(f"decode would reach rope position {pmax + max_length + k} >= max_position_embeddings {cfg.max_position}")
+        self.tok_pos = per_row(positions.to(device=dev, dtype=torch.int32).clone())
+        self.kv_len = torch.tensor(cache.lens, dtype=torch.int32).to(dev) + (k + 1)
+        self.cu_q = torch.arange(B + 1, **i32) * (k + 1)
         self.in_ids = torch.zeros((max_length, B), dtype=torch.int64, device=dev)    # token fed at each step
         self.pred_ids = torch.zeros((max_length, B), dtype=torch.int64, device=dev)  # token predicted at each step
-        if max_length > 0:
+        if max_length > 0 and k == 0:       # (a session with drafts logs its tokens per sample: out_ids / n_out)
             self.in_ids[0].copy_(self.ids)
         # step counter(s): entry 0 is THE counter (sampling, the unfused step end); the fused argmax step end keeps one per sample
         # so that its workgroups share no word (umv_decode_step_end_argmax)
         self.step_idx = torch.zeros(max(B, 1), dtype=torch.int64, device=dev)
-        max_kv = max(cache.lens) + max_length + 1
+        max_kv = max(cache.lens) + max_length + 1 + k
         # split the key range so that every wavefront walks ~2 blocks of 32 keys (latency bound otherwise)
         if nsplit is None and os.environ.get("UMV_DECODE_NSPLIT"):
             nsplit = int(os.environ["UMV_DECODE_NSPLIT"])   # tuning only
@@ -129,30 +140,30 @@ class DecodeSession:
         # 4 splits 4.046, 12 splits 4.064; B = 8, context 1060: 24 splits 3.116, 17 splits 3.125, 28 splits 3.131 -> ~768 waves at
         # 9 .. 32 samples (1024 otherwise: unmeasured, unchanged) and ~48 keys per split up to 8 samples
         if nsplit is None:
-            keys = 48 if B <= 8 else 64
-            nsplit = max(1, min(32, (max_kv + keys - 1) // keys, max(1, (768 if 8 < B <= 32 else 1024) // (B * nkv))))
+            keys = 48 if R <= 8 else 64
+            nsplit = max(1, min(32, (max_kv + keys - 1) // keys, max(1, (768 if 8 < R <= 32 else 1024) // (R * nkv))))
         self.nsplit = nsplit
         # waves per attention workgroup splitting its key range with an LDS merge (umv_attn_args.wave_split: 0 = single-wave workgroups);
         # UMV_DECODE_WSPLIT=2|4 for the A/B of profiles/r06_decode_wave_split.txt
         self.wave_split = int(os.environ.get("UMV_DECODE_WSPLIT", "0") or 0)
-        self.ws = ops.attn_workspace(B, nq, hd, 1, self.nsplit, dev) if self.nsplit > 1 else None
+        self.ws = ops.attn_workspace(B, nq, hd, k + 1, self.nsplit, dev) if self.nsplit > 1 else None
         self.max_kv = max_kv
         # static activations
-        self.seq = torch.empty((B, H), dtype=BF16, device=dev)
-        self.x = torch.empty((B, H), dtype=BF16, device=dev)
-        self.qkv = torch.empty((B, (nq + 2 * nkv) * hd), dtype=BF16, device=dev)
-        self.q = torch.empty((B, nq, hd), dtype=BF16, device=dev)
-        self.o = torch.empty((B, nq * hd), dtype=BF16, device=dev)
-        self.act = torch.empty((B, cfg.inter), dtype=BF16, device=dev)
-        self.hn = torch.empty((B, H), dtype=BF16, device=dev)
-        self.logits = torch.empty((B, cfg.vocab), dtype=BF16, device=dev)
+        self.seq = torch.empty((R, H), dtype=BF16, device=dev)
+        self.x = torch.empty((R, H), dtype=BF16, device=dev)
+        self.qkv = torch.empty((R, (nq + 2 * nkv) * hd), dtype=BF16, device=dev)
+        self.q = torch.empty((R, nq, hd), dtype=BF16, device=dev)
+        self.o = torch.empty((R, nq * hd), dtype=BF16, device=dev)
+        self.act = torch.empty((R, cfg.inter), dtype=BF16, device=dev)
+        self.hn = torch.empty((R, H), dtype=BF16, device=dev)
+        self.logits = torch.empty((R, cfg.vocab), dtype=BF16, device=dev)
         # greedy: the argmax rides on the lm_head epilogue (one key per 16-column tile and row) and is finished by the
         # step-end kernel - the separate 25 us argmax launch over the logits is gone (UMV_DECODE_FUSED_ARGMAX=0 restores it)
         # sampling rides the same way (round 5): the keys order bf16(logit / T) + Gumbel noise, their maximum is one draw from the softmax -
         # the sampled step has the greedy step's two-launch tail (lm_head -> sample -> step_end was 3.29 ms against 3.12)
-        self.fused_argmax = B <= 64 and os.environ.get("UMV_DECODE_FUSED_ARGMAX", "1") not in ("0", "")
+        self.fused_argmax = R <= 64 and os.environ.get("UMV_DECODE_FUSED_ARGMAX", "1") not in ("0", "")
         if self.fused_argmax:
-            self.amax_part = torch.zeros((B, (cfg.vocab + 15) // 16), dtype=torch.int64, device=dev)
+            self.amax_part = torch.zeros((R, (cfg.vocab + 15) // 16), dtype=torch.int64, device=dev)
 
         def need_fused(what):
             if not self.fused_argmax:
@@ -214,17 +225,17 @@ class DecodeSession:
             # MXFP4 weights take both branches: up to 64 rows the split partials of umv_gemm_mxfp4w; 65..128 rows the same K ranges on
             # the tiled MXFP4 kernel (umv_gemm_mxfp4t) when the linears carry no bf16 image of their dequantised weights
             # (llm_fp4_keep_bf16=False), else umv_gemm_bf16 on that image - ops.gemm_splitk routes by rows and by what the linear holds
-            sk = "3,4,4" if B <= 64 else ("6,8,8" if B <= 128 and not getattr(w, "fp8", False) else "0")
+            sk = "3,4,4" if R <= 64 else ("6,8,8" if R <= 128 and not getattr(w, "fp8", False) else "0")
         self.sk = (1, 1, 1) if sk in ("0", "") else tuple(max(1, int(v)) for v in sk.split(","))
         if len(self.sk) != 3 or any(v > 64 for v in self.sk):
             raise ValueError(f"UMV_DECODE_SPLITK={sk!r}: expected 'q,o,d' with 1 <= splits <= 64")
-        if self.sk != (1, 1, 1) and B > 128:
+        if self.sk != (1, 1, 1) and R > 128:
             raise ValueError("split-K decode mode serves at most 128 samples per step")
         sq, so, sd = self.sk
-        self.p_qkv = torch.empty((sq, B, (nq + 2 * nkv) * hd), dtype=torch.float32, device=dev) if sq > 1 else None
-        self.p_h = torch.empty((max(so, sd), B, H), dtype=torch.float32, device=dev) if max(so, sd) > 1 else None
+        self.p_qkv = torch.empty((sq, R, (nq + 2 * nkv) * hd), dtype=torch.float32, device=dev) if sq > 1 else None
+        self.p_h = torch.empty((max(so, sd), R, H), dtype=torch.float32, device=dev) if max(so, sd) > 1 else None
         # decode-only weight copies with exact-partition tiles (N/256 rows per tile) for the GEMMs that run without a split
-        exact = os.environ.get("UMV_DECODE_EXACT_TILES", "1") not in ("0", "") and B <= 64
+        exact = os.environ.get("UMV_DECODE_EXACT_TILES", "1") not in ("0", "") and R <= 64
         need = (sq == 1, so == 1, sd == 1)
         if exact and any(need):
             if not hasattr(w, "decode_copies"):
@@ -374,7 +385,7 @@ class DecodeSession:
                 part = {}
             ops.qkv_post(None if part else self.qkv, self.q, c.slabs[l], self.tok_seg, self.tok_slot, self.tok_pos, nq, nkv, hd,
                          cfg.rms_eps, lw.q_norm, lw.k_norm, cos_tab=w.cos, sin_tab=w.sin, **part)
-            ops.attention(self.q, self.o, c.slabs[l], self.cu_q, self.kv_len, nq, nkv, hd, True, 1, self.max_kv,
+            ops.attention(self.q, self.o, c.slabs[l], self.cu_q, self.kv_len, nq, nkv, hd, True, self.draft_len + 1, self.max_kv,
                           self.nsplit, self.ws, wave_split=self.wave_split)
             # ---- o_proj + residual, then the post-attention norm
             if so > 1:
@@ -403,6 +414,10 @@ class DecodeSession:
                               temperature=self.temperature if self.do_sample else 0.0, seed=self.seed, step=self.step_idx,
                               argmax_partial=self.lm_head_kw.get("argmax_partial"), lse_partial=self.lm_head_kw.get("lse_partial"),
                               sample_rows=self.row_table)
+        self._step_end()
+
+    def _step_end(self):
+        """the launch that closes the step: the pick (where the lm_head epilogue left keys) and the bookkeeping"""
         if self.step_end == "rows":
             # every row ends the step with its own sampler (the truncated path or the key maximum) and advances its own draw counter
             ops.decode_step_end_rows(self.tok_slot, self.tok_pos, self.kv_len, self.amax_part, self.ids, self.in_ids, self.pred_ids,
@@ -432,14 +447,19 @@ class DecodeSession:
             # pred_ids[step] = in_ids[step + 1] = ids; slot / position / kv_len / step += 1: one launch
             ops.decode_step_end(self.tok_slot, self.tok_pos, self.kv_len, self.ids, self.in_ids, self.pred_ids, self.step_idx)
 
-    def _capture(self):
-        # the captured step appends at slot = lens0 and bumps the counters; warm up on a side
-        # stream first (lazy module loading), then restore the counters so capture sees a clean state
+    def _state(self):
+        """every tensor a step writes that the next one reads"""
         state = (self.ids, self.tok_slot, self.tok_pos, self.kv_len, self.step_idx)
-        if self.pen is not None:                    # the warm-up step records into the penalty history as well
+        if self.pen is not None:                    # a step records into the penalty history as well
             state += (self.pen_count, self.pen_list, self.pen_len)
         if self.row_table is not None:              # ... and advances the rows' draw counters
             state += (self.row_table,)
+        return state
+
+    def _capture(self):
+        # the captured step appends at slot = lens0 and bumps the counters; warm up on a side
+        # stream first (lazy module loading), then restore the counters so capture sees a clean state
+        state = self._state()
         saved = [t.clone() for t in state]
         s = torch.cuda.Stream(device=self.dev)
         s.wait_stream(torch.cuda.current_stream())

@@ -35,6 +35,11 @@ def _penalties(repetition_penalty, presence_penalty, frequency_penalty, logit_bi
                 logit_bias=logit_bias)
 
 
+def _drafts(draft_len, draft_ngram, predicted_ids):
+    """the text_draft_len / text_draft_ngram / text_predicted_ids keywords of a pipeline as gen_text's keywords (none when off)"""
+    return dict(draft_len=draft_len, draft_ngram=draft_ngram, predicted_ids=predicted_ids) if draft_len else {}
+
+
 class InterleaveInferencer:
     def __init__(self, model, vae_model, tokenizer, vae_transform, vit_transform, new_token_ids):
         self.model = model
@@ -141,8 +146,11 @@ class InterleaveInferencer:
     @torch.no_grad()
     def gen_text(self, gen_context, max_length: int = 500, do_sample: bool = True, temperature: float = 1.0, *,
                  repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None,
-                 top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+                 draft_len: int = 0, draft_ngram=(2, 4), predicted_ids=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         # top_k / top_p / min_p: truncated sampling (Bagel.generate_text), off by default as in the reference
+        # draft_len > 0 (with do_sample=False): speculative greedy decode (Bagel.generate_text) - the same text from fewer passes over
+        # the weights; a context holds no token ids, so the drafts come from predicted_ids (a string or token ids) or from the
+        # generated text's own repetitions
         # repetition_penalty / presence_penalty / frequency_penalty / logit_bias: the logit penalties of Bagel.generate_text, off by
         # default (the reference has none); a context holds no token ids, so the penalties see the generated tokens only
         # the reference decodes on a deepcopy so that the context keeps its length (inferencer.py:261); here the decode
@@ -155,12 +163,24 @@ class InterleaveInferencer:
                                            temperature=temperature, end_token_id=self.new_token_ids["eos_token_id"],
                                            top_k=top_k, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
                                            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
-                                           logit_bias=logit_bias, **gi)
+                                           logit_bias=logit_bias, **self._draft_kw(draft_len, draft_ngram, predicted_ids, 1), **gi)
         finally:
             if cache.slabs is not None:
                 cache.lens = lens0
         output = self.tokenizer.decode(ids[:, 0].cpu())
         return output.split("<|im_end|>")[0].split("<|im_start|>")[1]
+
+    def _draft_kw(self, draft_len, draft_ngram, predicted_ids, n):
+        """generate_text's speculative keywords for n samples; predicted_ids: per sample (or, for one sample, directly) a string or
+        a list of token ids"""
+        if not draft_len:
+            return {}
+        pred = predicted_ids
+        if pred is not None:
+            if n == 1 and (isinstance(pred, str) or (len(pred) > 0 and isinstance(pred[0], int))):
+                pred = [pred]
+            pred = [self.tokenizer.encode(p) if isinstance(p, str) else [int(t) for t in p] for p in pred]
+        return dict(draft_len=draft_len, draft_ngram=draft_ngram, predicted_ids=pred)
 
     # ------------------------------------------------------------------ pipelines
     @torch.no_grad()
@@ -169,11 +189,14 @@ class InterleaveInferencer:
                              cfg_img_scale=1.5, cfg_interval=(0.4, 1.0), timestep_shift=3.0, num_timesteps=50,
                              cfg_renorm_min=0.0, cfg_renorm_type="global", image_shapes=(1024, 1024), *,
                              text_repetition_penalty=1.0, text_presence_penalty=0.0, text_frequency_penalty=0.0, text_logit_bias=None,
+                             text_draft_len=0, text_draft_ngram=(2, 4), text_predicted_ids=None,
                              text_top_k=0, text_top_p=1.0, text_min_p=0.0) -> List[Union[str, Image.Image]]:
         """inferencer.py:552-638.  text_top_k / text_top_p / text_min_p: truncated sampling of the text passes (gen_text);
-        text_repetition_penalty / text_presence_penalty / text_frequency_penalty / text_logit_bias: their logit penalties."""
+        text_repetition_penalty / text_presence_penalty / text_frequency_penalty / text_logit_bias: their logit penalties;
+        text_draft_len / text_draft_ngram / text_predicted_ids: their speculative greedy decode (do_sample=False)."""
         filters = dict(top_k=text_top_k, top_p=text_top_p, min_p=text_min_p,
-                       **_penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias))
+                       **_penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias),
+                       **_drafts(text_draft_len, text_draft_ngram, text_predicted_ids))
         output_list = []
         need_cfg = not understanding_output
         gen_context = self.init_gen_context()
@@ -229,7 +252,8 @@ class InterleaveInferencer:
             cfg_interval: list = (0.4, 1.0), timestep_shift: float = 3.0, num_timesteps: int = 50,
             cfg_renorm_min: float = 0.0, cfg_renorm_type: str = "global", image_shapes: tuple = (1024, 1024),
             *, text_repetition_penalty: float = 1.0, text_presence_penalty: float = 0.0, text_frequency_penalty: float = 0.0,
-            text_logit_bias=None, text_top_k: int = 0, text_top_p: float = 1.0, text_min_p: float = 0.0
+            text_logit_bias=None, text_draft_len: int = 0, text_draft_ngram=(2, 4), text_predicted_ids=None,
+            text_top_k: int = 0, text_top_p: float = 1.0, text_min_p: float = 0.0
     ) -> List[Union[str, Image.Image]]:
         """VQA, then optionally reconstruct every input image from the answer (inferencer.py:282-362)."""
         output_list = []
@@ -246,8 +270,8 @@ class InterleaveInferencer:
                 raise ValueError(f"Unsupported input type: {type(input_term)}")
         vqa_answer = self.gen_text(vqa_context, do_sample=do_sample, temperature=text_temperature,
                                    max_length=max_think_token_n, top_k=text_top_k, top_p=text_top_p, min_p=text_min_p,
-                                   repetition_penalty=text_repetition_penalty, presence_penalty=text_presence_penalty,
-                                   frequency_penalty=text_frequency_penalty, logit_bias=text_logit_bias)
+                                   **_penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias),
+                                   **_drafts(text_draft_len, text_draft_ngram, text_predicted_ids))
         output_list.append(vqa_answer)
         if not reconstruct_image or not vqa_answer or not vqa_answer.strip():
             return output_list
@@ -313,14 +337,16 @@ class InterleaveInferencer:
             cfg_interval: list = (0.4, 1.0), timestep_shift: float = 3.0, num_timesteps: int = 50,
             cfg_renorm_min: float = 0.0, cfg_renorm_type: str = "global", image_shapes: tuple = (1024, 1024),
             *, text_repetition_penalty: float = 1.0, text_presence_penalty: float = 0.0, text_frequency_penalty: float = 0.0,
-            text_logit_bias=None, text_top_k: int = 0, text_top_p: float = 1.0, text_min_p: float = 0.0
+            text_logit_bias=None, text_draft_len: int = 0, text_draft_ngram=(2, 4), text_predicted_ids=None,
+            text_top_k: int = 0, text_top_p: float = 1.0, text_min_p: float = 0.0
     ) -> List[Union[str, Image.Image]]:
         """inferencer.py:366-463: VQA, then one reconstruction per input image.  (cfg_*_scale / think / image_shapes are
         accepted and ignored, as in the reference.)"""
         return self._vqa_then_rebuild(input_lists, reconstruct_image, False, do_sample, text_temperature, max_think_token_n,
                                       cfg_interval, timestep_shift, num_timesteps, cfg_renorm_min, cfg_renorm_type,
                                       text_top_k, text_top_p, text_min_p,
-                                      _penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias))
+                                      dict(_penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias),
+                                           **_drafts(text_draft_len, text_draft_ngram, text_predicted_ids)))
 
     @torch.no_grad()
     def interleave_inference_for_vqa_reconstruction_ver0(
@@ -330,13 +356,15 @@ class InterleaveInferencer:
             cfg_interval: list = (0.4, 1.0), timestep_shift: float = 3.0, num_timesteps: int = 50,
             cfg_renorm_min: float = 0.0, cfg_renorm_type: str = "global", image_shapes: tuple = (1024, 1024),
             *, text_repetition_penalty: float = 1.0, text_presence_penalty: float = 0.0, text_frequency_penalty: float = 0.0,
-            text_logit_bias=None, text_top_k: int = 0, text_top_p: float = 1.0, text_min_p: float = 0.0
+            text_logit_bias=None, text_draft_len: int = 0, text_draft_ngram=(2, 4), text_predicted_ids=None,
+            text_top_k: int = 0, text_top_p: float = 1.0, text_min_p: float = 0.0
     ) -> List[Union[str, Image.Image]]:
         """inferencer.py:466-549: VQA, then a reconstruction of the FIRST input image only."""
         return self._vqa_then_rebuild(input_lists, reconstruct_image, True, do_sample, text_temperature, max_think_token_n,
                                       cfg_interval, timestep_shift, num_timesteps, cfg_renorm_min, cfg_renorm_type,
                                       text_top_k, text_top_p, text_min_p,
-                                      _penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias))
+                                      dict(_penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias),
+                                           **_drafts(text_draft_len, text_draft_ngram, text_predicted_ids)))
 
     # ------------------------------------------------------------------ batch extension (additive; SURVEY.md section 8b B1)
     # The reference runs one sample per call (contexts are lists of length 1).  Samples are independent segments of
@@ -369,8 +397,10 @@ class InterleaveInferencer:
     @torch.no_grad()
     def gen_text_batch(self, ctx, max_length: int = 500, do_sample: bool = True, temperature: float = 1.0, *,
                        repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None,
+                       draft_len: int = 0, draft_ngram=(2, 4), predicted_ids=None,
                        top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0) -> List[str]:
-        """gen_text for every sample of a batched context; each answer ends at that sample's own EOS."""
+        """gen_text for every sample of a batched context; each answer ends at that sample's own EOS.  draft_len / draft_ngram /
+        predicted_ids (one entry per sample): speculative greedy decode as in gen_text, B * (draft_len + 1) <= 64."""
         cache = ctx["past_key_values"]
         eos = self.new_token_ids["eos_token_id"]
         gi = self.model.prepare_start_tokens(ctx["kv_lens"], ctx["ropes"], self.new_token_ids)
@@ -380,7 +410,8 @@ class InterleaveInferencer:
                                            temperature=temperature, end_token_id=eos, per_sample_eos=True,
                                            top_k=top_k, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
                                            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
-                                           logit_bias=logit_bias, **gi).cpu()
+                                           logit_bias=logit_bias,
+                                           **self._draft_kw(draft_len, draft_ngram, predicted_ids, len(cache.lens)), **gi).cpu()
         finally:
             if cache.slabs is not None:
                 cache.lens = lens0
@@ -427,8 +458,8 @@ class InterleaveInferencer:
                                    cfg_text_scale=3.0, cfg_img_scale=1.5, cfg_interval=(0.4, 1.0), timestep_shift=3.0,
                                    num_timesteps=50, cfg_renorm_min=0.0, cfg_renorm_type="global", image_shapes=(1024, 1024),
                                    *, text_repetition_penalty=1.0, text_presence_penalty=0.0, text_frequency_penalty=0.0,
-                                   text_logit_bias=None, text_top_k=0, text_top_p=1.0,
-                                   text_min_p=0.0) -> List[List[Union[str, Image.Image]]]:
+                                   text_logit_bias=None, text_draft_len=0, text_draft_ngram=(2, 4), text_predicted_ids=None,
+                                   text_top_k=0, text_top_p=1.0, text_min_p=0.0) -> List[List[Union[str, Image.Image]]]:
         """interleave_inference (inferencer.py:552-638) over B samples at once.  Every sample must have the same
         sequence of item types; lengths (prompt tokens, image sizes) may differ.  Returns one output list per sample."""
         n = len(input_lists)
@@ -463,7 +494,8 @@ class InterleaveInferencer:
                 if need_cfg:
                     cfg_text_ctx = self._snap(ctx)
         outputs = [[] for _ in range(n)]
-        penalties = _penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias)
+        penalties = dict(_penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias),
+                         **_drafts(text_draft_len, text_draft_ngram, text_predicted_ids))
         if understanding_output:
             for o, t in zip(outputs, self.gen_text_batch(ctx, do_sample=do_sample, temperature=text_temperature,
                                                          max_length=max_think_token_n, top_k=text_top_k, top_p=text_top_p,

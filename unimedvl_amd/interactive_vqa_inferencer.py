@@ -45,6 +45,9 @@ DEFAULT_CONFIG = {
     "frequency_penalty": 0.0,
     "logit_bias": None,
     "penalize_prompt": False,       # True: the prompt's own tokens (not the bos / eos wrapper) count as seen for repetition_penalty
+    # speculative greedy decode (not reference keys; off = one token per step): Bagel.chat - needs "do_sample": False
+    "draft_len": 0,                 # drafted tokens verified per step (prompt lookup over the question and the answer so far)
+    "draft_ngram": (2, 4),
 }
 
 # codes/data/default.yaml vlm_sft.image_transform_args (read by eval/vlm/utils.py:486-502)
@@ -155,7 +158,7 @@ class VQAInferencer:
 
     def infer_single(self, image_path, prompt, temperature=None, max_new_tokens=None, do_sample=None, show_image=False, *,
                      repetition_penalty=None, presence_penalty=None, frequency_penalty=None, logit_bias=None, penalize_prompt=None,
-                     top_k=None, top_p=None, min_p=None):
+                     draft_len=None, draft_ngram=None, predicted_ids=None, top_k=None, top_p=None, min_p=None):
         if not self.loaded:
             raise RuntimeError("Model not loaded, please call load_model() first")
         temperature = temperature if temperature is not None else self.config["temperature"]
@@ -179,6 +182,10 @@ class VQAInferencer:
         # tokens behind the answer and the log-probability of each (Bagel.generate_text).  Without it the result is the reference's.
         want_lp = bool(self.config.get("return_logprobs", False))
         extra = {"return_logprobs": True} if want_lp else {}
+        draft_len = draft_len if draft_len is not None else self.config.get("draft_len", 0)
+        if draft_len:       # predicted_ids: a predicted answer (a string or token ids) to draft from instead of the lookup
+            extra.update(draft_len=draft_len, draft_ngram=draft_ngram if draft_ngram is not None else self.config.get("draft_ngram", (2, 4)),
+                         predicted_ids=predicted_ids)
         answer = self.model.chat(self.tokenizer, self.new_token_ids, self.image_transform, images=images,
                                  prompt=conversation, max_length=max_new_tokens, do_sample=do_sample,
                                  temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, **penalties, **extra)

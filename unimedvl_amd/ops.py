@@ -875,6 +875,42 @@ def decode_step_end_rows(tok_slot, tok_pos, kv_len, argmax_partial, ids, in_ids,
           "umv_decode_step_end_rows")
 
 
+def decode_step_end_speculative(tok_slot, tok_pos, kv_len, argmax_partial, ids, out_ids, n_out, limit, n_draft, hist, hist_len, stats,
+                                draft_len, vocab, ngram=(2, 4), predicted=None, pred_len=None, draft_only=False):
+    """The step end of a speculative greedy step (include/unimedvl_hip.h): per sample verify the draft_len drafts of this step's rows
+    against the picks behind argmax_partial ([T, n_tiles], T = B * (draft_len + 1) rows), emit the accepted tokens plus one into
+    out_ids [B, max] / n_out up to limit, advance slot / position / kv_len by as many, append them to hist / hist_len, draft the next
+    rows (predicted [B, n] int64 + pred_len where a row has one, prompt lookup with ngram = (min, max) otherwise) and write them to
+    ids / tok_slot / tok_pos [T] and n_draft; stats [B, 3] += (steps, drafted, accepted).  draft_only: only draft and write the rows."""
+    lib = _lib.load()
+    k, B = int(draft_len), kv_len.numel()
+    T = B * (k + 1)
+    n_tiles = (int(vocab) + 15) // 16
+    i32 = [(tok_slot, "tok_slot", T), (tok_pos, "tok_pos", T), (kv_len, "kv_len", B), (n_out, "n_out", B), (limit, "limit", B),
+           (n_draft, "n_draft", B), (hist_len, "hist_len", B), (stats, "stats", 3 * B), (hist, "hist", None)]
+    if pred_len is not None:
+        i32.append((pred_len, "pred_len", B))
+    i64 = [(ids, "ids", T), (out_ids, "out_ids", None), (argmax_partial, "argmax_partial", T * n_tiles)]
+    if predicted is not None:
+        i64.append((predicted, "predicted", None))
+    for group, dt in ((i32, torch.int32), (i64, torch.int64)):
+        for t, name, n in group:
+            _req(t, dt, name)
+            if not t.is_contiguous() or (n is not None and t.numel() != n) or (n is None and (t.dim() != 2 or t.shape[0] != B)):
+                raise _lib.UmvError(f"decode_step_end_speculative: {name} must be contiguous with {'[B, n]' if n is None else n} entries "
+                                    f"(B = {B}, draft_len = {k}), got {tuple(t.shape)}")
+    if (predicted is None) != (pred_len is None):
+        raise _lib.UmvError("decode_step_end_speculative: predicted and pred_len go together")
+    a = _lib.SpecStepArgs(
+        tok_slot=tok_slot.data_ptr(), tok_pos=tok_pos.data_ptr(), kv_len=kv_len.data_ptr(), argmax_partial=argmax_partial.data_ptr(),
+        n_tiles=n_tiles, V=int(vocab), ids=ids.data_ptr(), out_ids=out_ids.data_ptr(), out_ld=out_ids.shape[1], n_out=n_out.data_ptr(),
+        limit=limit.data_ptr(), n_draft=n_draft.data_ptr(), hist=hist.data_ptr(), hist_ld=hist.shape[1], hist_len=hist_len.data_ptr(),
+        predicted=None if predicted is None else predicted.data_ptr(), pred_ld=0 if predicted is None else predicted.shape[1],
+        pred_len=None if pred_len is None else pred_len.data_ptr(), stats=stats.data_ptr(), B=B, k=k, ngram_min=int(ngram[0]),
+        ngram_max=int(ngram[1]), draft_only=int(bool(draft_only)))
+    check(lib.umv_decode_step_end_speculative(C.byref(a), _stream()), "umv_decode_step_end_speculative")
+
+
 def token_logprob(logits, ids, temperature=0.0, out=None):
     """out[m] = log_softmax(y[m])[ids[m]] in fp32 for bf16 logits [M, V] (any row stride): y = the logits (temperature 0: greedy) or
     bf16(logits / temperature), the value sampling orders.  For callers who hold logits - return_logits=True, a prefill's last rows."""
