@@ -550,6 +550,45 @@ int umv_decode_step_end_rows(int32_t* tok_slot, int32_t* tok_pos, int32_t* kv_le
                              int64_t* step_idx, const uint16_t* logits, int64_t ldo, int V, const int64_t* forced_ids, float* logprob,
                              int B, int max_len, umv_row_sampling* rows, float* cut_y, int32_t* n_kept, umv_stream_t stream);
 
+/* ------------------------------------------------------------------ top-n alternative tokens and token ranks
+ * For row b of a decode step take y[c] exactly as the token log-probabilities define it: greedy (temperature 0) y[c] = float(bf16
+ * logit), temperature T > 0 y[c] = bf16_round(logit / T) - with a per-row table the row's own temperature - and -0 == +0.  The logits
+ * are the stored ones, so after umv_logit_penalty_bf16 the adjusted ones; the alternatives are those of the UNTRUNCATED softmax, like
+ * the log-probabilities.  Order the columns by (y descending, column ascending): argmax_key's order applied to y without noise.
+ *   top_ids[j], j = 0..n-1: the j-th column in that order.
+ *   top_logprobs[j] = (y[top_ids[j]] - ref) - logf(S), with (ref, S) the row's merged statistics, merged in exactly the order of the
+ *     step end that ended the step - so wherever the fed token is one of the n, its entry equals that step end's logprob bit for bit.
+ *   rank = 1 + the number of columns before the FED token in that order, int32, 1-based.  The fed token is the one the step end left
+ *     for the next step (ids[b] = in_ids[s + 1][b]): the pick, or the forced token where one was fed.  0 where the forced token was
+ *     outside the vocabulary (forced_ids[s][b] >= V) or the stand-alone id is outside [0, V).
+ * Ties are split by column, never by the logit: at T > 0 two different logits can share one y (3.015625 and 3.03125 both give 2.015625
+ * at T = 1.5), and then the lower column comes first even if its logit is the smaller one.  -inf columns are ordinary: last in the
+ * order, log-probability -inf.  A row whose merged S is NaN (a NaN logit) gives NaN in every top_logprobs entry, -1 in every top_ids
+ * entry and rank 0.  All comparisons are integer or exact bf16: a row's ids and ranks never depend on the batch it sits in, and neither
+ * do its log-probabilities under the condition the token log-probabilities have.  1 <= n <= UMV_TOP_LOGPROBS_MAX and n <= V,
+ * UMV_ERR_ARG otherwise, as for a NULL output.
+ *
+ * umv_decode_top_logprobs: one launch AFTER the step end of a step (umv_decode_step_end_logprob, _truncated or _rows), one workgroup
+ * per sample, no word shared between workgroups.  The step just ended is s = step_idx[b] - 1; row s of top_ids (int32
+ * [max_len][B][n]), top_logprobs (fp32 [max_len][B][n]) and rank (int32 [max_len][B]) is written; s outside [0, max_len) writes
+ * nothing.  logits / ldo / V / lse_partial / n_tiles / forced_ids: what the step end got.  ids [B]: the tokens the step end left for
+ * the next step.  temperature: the scalar one (0 = greedy), ignored where rows (optional, the table of umv_decode_step_end_rows) is
+ * given - then row b's own temperature applies.  merge_order names the step end whose order the statistics are merged in:
+ * UMV_TOP_AFTER_LOGPROB or UMV_TOP_AFTER_TRUNCATED; with rows it is ignored and the row's own is taken (a sampled row with a filter on:
+ * the truncated one).
+ *
+ * umv_top_logprobs_bf16: the stand-alone form over bf16 logits [M][V] (row stride ld elements) with ids [M], whose rank is wanted; the
+ * statistics come from the logits as umv_token_logprob_bf16 takes them (its bits), outputs are [M][n] / [M][n] / [M]. */
+#define UMV_TOP_LOGPROBS_MAX 20
+#define UMV_TOP_AFTER_LOGPROB 0
+#define UMV_TOP_AFTER_TRUNCATED 1
+int umv_decode_top_logprobs(const uint16_t* logits, int64_t ldo, int V, const float* lse_partial, int n_tiles, float temperature,
+                            const umv_row_sampling* rows, int merge_order, const int64_t* ids, const int64_t* step_idx,
+                            const int64_t* forced_ids, int B, int max_len, int n, int32_t* top_ids, float* top_logprobs, int32_t* rank,
+                            umv_stream_t stream);
+int umv_top_logprobs_bf16(const uint16_t* logits, int64_t ld, const int64_t* ids, int M, int V, float temperature, int n,
+                          int32_t* top_ids, float* top_logprobs, int32_t* rank, umv_stream_t stream);
+
 /* ------------------------------------------------------------------ speculative greedy decode: verify drafts, commit, roll back, draft again
  * A step of k = draft_len >= 1 processes T = B * (k + 1) <= 64 rows.  Row r0 = b * (k + 1) holds sample b's next input token t0, which is
  * not in the cache yet; rows r0 + j, j = 1..k, hold its drafts d_j: the first n_draft[b] are real, the rest are FILLERS equal to t0 -

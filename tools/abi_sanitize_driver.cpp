@@ -174,6 +174,25 @@ static void bad_arguments() {
     EXPECT_ERR(umv_token_logprob_bf16(dummy16, 32, dummyl, dummyf, 1, 64, 0.f, nullptr));         // row stride below V
     EXPECT_ERR(umv_token_logprob_bf16(dummy16, 64, dummyl, dummyf, 1, 64, -1.f, nullptr));        // negative temperature
     EXPECT_OK(umv_token_logprob_bf16(dummy16, 64, dummyl, dummyf, 0, 64, 0.f, nullptr));          // no rows
+    EXPECT_ERR(umv_decode_top_logprobs(nullptr, 152064, 152064, nullptr, 9504, 0.f, nullptr, UMV_TOP_AFTER_LOGPROB, nullptr, nullptr, nullptr, 8,
+                                       16, 5, nullptr, nullptr, nullptr, nullptr));
+    EXPECT_ERR(umv_decode_top_logprobs(dummy16, 64, 64, dummyf, 4, 0.f, nullptr, UMV_TOP_AFTER_LOGPROB, dummyl, dummyl, nullptr, 1, 16, 0, dummyi,
+                                       dummyf, dummyi, nullptr));                                 // n = 0
+    EXPECT_ERR(umv_decode_top_logprobs(dummy16, 64, 64, dummyf, 4, 0.f, nullptr, UMV_TOP_AFTER_LOGPROB, dummyl, dummyl, nullptr, 1, 16,
+                                       UMV_TOP_LOGPROBS_MAX + 1, dummyi, dummyf, dummyi, nullptr));
+    EXPECT_ERR(umv_decode_top_logprobs(dummy16, 64, 64, dummyf, 4, 0.f, nullptr, UMV_TOP_AFTER_LOGPROB, dummyl, dummyl, nullptr, 1, 16, 5, dummyi,
+                                       nullptr, dummyi, nullptr));                                // an output missing
+    EXPECT_ERR(umv_decode_top_logprobs(dummy16, 64, 100, dummyf, 4, 0.f, nullptr, UMV_TOP_AFTER_LOGPROB, dummyl, dummyl, nullptr, 1, 16, 5, dummyi,
+                                       dummyf, dummyi, nullptr));                                 // 100 columns are not 4 tiles
+    EXPECT_ERR(umv_decode_top_logprobs(dummy16, 64, 64, dummyf, 4, 0.f, nullptr, 7, dummyl, dummyl, nullptr, 1, 16, 5, dummyi, dummyf, dummyi,
+                                       nullptr));                                                 // no such step end
+    EXPECT_OK(umv_decode_top_logprobs(dummy16, 64, 64, dummyf, 4, 0.f, nullptr, UMV_TOP_AFTER_TRUNCATED, dummyl, dummyl, nullptr, 0, 16, 5, dummyi,
+                                      dummyf, dummyi, nullptr));                                  // no rows
+    EXPECT_ERR(umv_top_logprobs_bf16(nullptr, 0, nullptr, 8, 152064, 0.f, 5, nullptr, nullptr, nullptr, nullptr));
+    EXPECT_ERR(umv_top_logprobs_bf16(dummy16, 64, dummyl, 1, 64, 0.f, UMV_TOP_LOGPROBS_MAX + 1, dummyi, dummyf, dummyi, nullptr));
+    EXPECT_ERR(umv_top_logprobs_bf16(dummy16, 12, dummyl, 1, 12, 0.f, 13, dummyi, dummyf, dummyi, nullptr));    // n > V
+    EXPECT_ERR(umv_top_logprobs_bf16(dummy16, 64, dummyl, 1, 64, -1.f, 5, dummyi, dummyf, dummyi, nullptr));    // negative temperature
+    EXPECT_OK(umv_top_logprobs_bf16(dummy16, 64, dummyl, 0, 64, 0.f, 5, dummyi, dummyf, dummyi, nullptr));      // no rows
     EXPECT_ERR(umv_sample_truncated_bf16(nullptr, 0, nullptr, 8, 152064, 1.0f, 1, nullptr, 50, 0.9f, 0.05f, nullptr, nullptr, nullptr));
     EXPECT_ERR(umv_sample_truncated_bf16(dummy16, 64, dummyl, 1, 64, 0.0f, 1, nullptr, 50, 0.9f, 0.f, nullptr, nullptr, nullptr));   // temperature 0
     EXPECT_ERR(umv_sample_truncated_bf16(dummy16, 64, dummyl, 1, 64, 1.0f, 1, nullptr, -1, 0.9f, 0.f, nullptr, nullptr, nullptr));   // top_k < 0

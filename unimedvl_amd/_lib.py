@@ -98,6 +98,8 @@ class SpecStepArgs(C.Structure):
 
 # umv_logit_penalty_args.count words: bits 0..29 the count, then "in the context set" and "in the row's visit list"
 PENALTY_COUNT_MASK, PENALTY_CONTEXT, PENALTY_LISTED = 0x3FFFFFFF, 0x40000000, 0x80000000
+# umv_decode_top_logprobs: the most alternatives a row can ask for, and the step end whose merge order the statistics take
+TOP_LOGPROBS_MAX, TOP_AFTER_LOGPROB, TOP_AFTER_TRUNCATED = 20, 0, 1
 
 
 _SIGS = {
@@ -167,6 +169,10 @@ _SIGS = {
     "umv_decode_step_end_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "umv_decode_top_logprobs": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "umv_top_logprobs_bf16": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
     "umv_logit_penalty_bf16": (C.c_int, [C.POINTER(LogitPenaltyArgs), C.c_void_p]),
     "umv_decode_step_end_speculative": (C.c_int, [C.POINTER(SpecStepArgs), C.c_void_p]),
     "umv_timestep_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

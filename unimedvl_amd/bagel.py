@@ -13,6 +13,7 @@ The prepare_* functions build the same packed index tensors on the host (they ar
 boundary's data format); the forward_* functions consume what they need of them and
 run everything else on the GPU through libunimedvl_hip.so.
 """
+from collections import namedtuple
 from types import SimpleNamespace
 from typing import List, Optional, Tuple
 
@@ -27,6 +28,9 @@ from .kvcache import NaiveCache
 from .llm import Qwen2MoT
 from .vit import SiglipVisionModel
 from .weights import GlueWeights, LLMWeights, ViTWeights
+
+# what top_logprobs=n adds to a result (generate_text: tensors [rows, B, n] / [rows, B, n] / [rows, B]; chat: per-token lists)
+TopLogprobs = namedtuple("TopLogprobs", ["ids", "logprobs", "rank"])
 
 BF16 = torch.bfloat16
 
@@ -313,7 +317,7 @@ class Bagel(BagelPrep):
                       return_logits: bool = False, per_sample_eos: bool = False, return_logprobs: bool = False, *,
                       repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
                       logit_bias=None, penalty_context_ids=None, draft_len: int = 0, draft_ngram=(2, 4), draft_context_ids=None,
-                      predicted_ids=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+                      predicted_ids=None, top_logprobs: int = 0, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """Greedy decode (bagel.py:1236-1317).  Returns [steps, B] int64 whose row 0 holds the
         start tokens.  Like the reference, the batch stops when SAMPLE 0 emits end_token_id
         (bagel.py:1313); per_sample_eos=True is the batched extension (stops when every sample
@@ -324,6 +328,10 @@ class Bagel(BagelPrep):
         in the captured graph.
         top_k / top_p / min_p (0 / 1.0 / 0.0 = off; with do_sample): truncated sampling as include/unimedvl_hip.h defines it, in the
         captured step (DecodeSession); B <= 64.  The log-probabilities stay those of the untruncated softmax.
+        top_logprobs=n (1..20; implies return_logprobs): one more element at the end of the returned tuple, a TopLogprobs named tuple
+        (ids int32 [rows, B, n], logprobs fp32 [rows, B, n], rank int32 [rows, B]): per step the n most likely tokens of the
+        untruncated softmax with their log-probabilities, most likely first, and the 1-based rank of the token that was fed; row s
+        belongs to ids[s + 1], as for logprobs (include/unimedvl_hip.h, top-n alternative tokens).
         repetition_penalty / presence_penalty / frequency_penalty (1.0 / 0.0 / 0.0 = off) and logit_bias ({token: float}, -inf bans
         a token): the logit penalties of include/unimedvl_hip.h, applied in the captured step before temperature and truncation; ids,
         logits and logprobs are those of the adjusted logits.  penalty_context_ids: per sample a list of tokens (the prompt) that
@@ -335,6 +343,8 @@ class Bagel(BagelPrep):
         lengths as draft_len = 0, fewer passes over the weights where drafts are accepted; self.last_draft_stats keeps the session's
         [B, 3] (steps, drafted, accepted).  Greedy only: do_sample, return_logits / return_logprobs, penalties and logit_bias raise."""
         top_k, top_p, min_p = ops.check_truncation(top_k, top_p, min_p)
+        top_logprobs = ops.check_top_logprobs(top_logprobs, self.cfg.vocab)
+        return_logprobs = bool(return_logprobs) or top_logprobs > 0
         ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, vocab=self.cfg.vocab)
         # do_sample: softmax(logits / temperature) + multinomial on the device (bagel.py:1297-1299).  The
         # draw is keyed by a seed derived from torch.initial_seed(), so torch.manual_seed(s) makes runs
@@ -349,10 +359,15 @@ class Bagel(BagelPrep):
                 res += (torch.zeros((0, len(past_key_values.lens), self.cfg.vocab), dtype=BF16, device=self.device),)
             if return_logprobs:
                 res += (torch.zeros((0, len(past_key_values.lens)), dtype=torch.float32, device=self.device),)
+            if top_logprobs:
+                shape = (0, len(past_key_values.lens), top_logprobs)
+                res += (TopLogprobs(torch.zeros(shape, dtype=torch.int32, device=self.device),
+                                    torch.zeros(shape, dtype=torch.float32, device=self.device),
+                                    torch.zeros(shape[:2], dtype=torch.int32, device=self.device)),)
             return res if len(res) > 1 else out
         if draft_len:
             if return_logits or return_logprobs:
-                raise ValueError("speculative decode (draft_len > 0) is greedy only: no return_logits / return_logprobs")
+                raise ValueError("speculative decode (draft_len > 0) is greedy only: no return_logits / return_logprobs / top_logprobs")
             return self._generate_text_speculative(past_key_values, packed_start_tokens, packed_query_position_ids, max_length,
                                                    end_token_id, per_sample_eos, draft_len, draft_ngram, draft_context_ids, predicted_ids,
                                                    dict(do_sample=do_sample, top_k=top_k, top_p=top_p, min_p=min_p,
@@ -364,7 +379,7 @@ class Bagel(BagelPrep):
                              do_sample=do_sample, temperature=temperature, seed=seed, logprobs=return_logprobs,
                              top_k=top_k, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
                              presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, logit_bias=logit_bias,
-                             penalty_context_ids=penalty_context_ids)
+                             penalty_context_ids=penalty_context_ids, top_logprobs=top_logprobs)
         logits = []
         steps = 0
         stop = None
@@ -392,6 +407,8 @@ class Bagel(BagelPrep):
             res += (torch.stack(logits[:rows], 0),)
         if return_logprobs:
             res += (sess.pred_logprobs[:rows].clone(),)
+        if top_logprobs:
+            res += (TopLogprobs(sess.pred_top_ids[:rows].clone(), sess.pred_top_logprobs[:rows].clone(), sess.pred_rank[:rows].clone()),)
         return res if len(res) > 1 else out
 
     def _generate_text_speculative(self, cache, start_tokens, positions, max_length, end_token_id, per_sample_eos, draft_len,
@@ -434,9 +451,11 @@ class Bagel(BagelPrep):
              do_sample: bool = False, temperature: float = 1.0, return_logprobs: bool = False, *,
              repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None,
              penalize_prompt: bool = False, draft_len: int = 0, draft_ngram=(2, 4), predicted_ids=None,
-             top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+             top_logprobs: int = 0, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """ViT-only VQA convenience path (bagel.py:1321-1392).  return_logprobs=True: returns (answer, token_ids, token_logprobs) -
         the generated tokens behind the answer (the end token excluded) and the log-probability of each (generate_text).
+        top_logprobs=n (implies return_logprobs): a fourth element, a TopLogprobs named tuple of per-token lists - ids and logprobs
+        (n entries per token, most likely first) and rank (the token's own 1-based rank).
         repetition_penalty / presence_penalty / frequency_penalty / logit_bias: the logit penalties of generate_text;
         penalize_prompt=True makes the prompt's token ids the repetition penalty's context set (off: generated tokens only) - the
         text's own tokens, not the bos / eos wrapper around them: a penalised end token would only make answers longer.
@@ -468,16 +487,22 @@ class Bagel(BagelPrep):
         gi = self.prepare_start_tokens(newlens, new_rope, new_token_ids)
         ids = self.generate_text(past_key_values=cache, max_length=max_length, do_sample=do_sample,
                                  temperature=temperature, end_token_id=new_token_ids["eos_token_id"],
-                                 return_logprobs=return_logprobs, top_k=top_k, top_p=top_p, min_p=min_p,
+                                 return_logprobs=return_logprobs, top_k=top_k, top_p=top_p, min_p=min_p, top_logprobs=top_logprobs,
                                  repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                                  frequency_penalty=frequency_penalty, logit_bias=logit_bias, penalty_context_ids=prompt_ids, **draft, **gi)
-        if return_logprobs:
+        top = None
+        if top_logprobs:
+            ids, lp, top = ids
+        elif return_logprobs:
             ids, lp = ids
         output = tokenizer.decode(ids[:, 0].cpu())
         answer = output.split("<|im_end|>")[0].split("<|im_start|>")[1]
-        if return_logprobs:          # lp[s] belongs to ids[s + 1]
+        if return_logprobs or top is not None:          # lp[s] belongs to ids[s + 1]
             n = max(ids.shape[0] - 1, 0)
-            return answer, ids[1:, 0].tolist(), lp[:n, 0].tolist()
+            res = (answer, ids[1:, 0].tolist(), lp[:n, 0].tolist())
+            if top is not None:
+                res += (TopLogprobs(top.ids[:n, 0].tolist(), top.logprobs[:n, 0].tolist(), top.rank[:n, 0].tolist()),)
+            return res
         return answer
 
     @torch.no_grad()
@@ -491,7 +516,23 @@ class Bagel(BagelPrep):
         tokens, EOS included), token_logprobs (one fp32 value per token) and logprob (their sum, added in fp64 on the host).
         Samples are independent rows of every kernel, so a candidate's values do not depend on the others.
         Forced decoding costs one decode step per token - the right trade for answers of a few tokens; long continuations want a
-        prefill-time scorer, which this is not."""
+        prefill-time scorer, which this is not.  score_top_logprobs adds every token's rank and alternatives."""
+        return self._score(tokenizer, new_token_ids, image_transform, images, prompt, candidates, append_eos, None)
+
+    @torch.no_grad()
+    @ops.on_device
+    def score_top_logprobs(self, tokenizer, new_token_ids, image_transform, images, prompt, candidates, append_eos: bool = True,
+                           top_logprobs: int = 0):
+        """`score` whose dicts also carry token_ranks - per token its 1-based rank among the vocabulary at its step ("was the right
+        answer's token in the top 5?") - and, with top_logprobs = n > 0 (at most 20), top_logprobs: per token a list of n (id, logprob)
+        pairs, most likely first (include/unimedvl_hip.h, top-n alternative tokens).  The other entries are `score`'s own bits.
+        (n = 0 still costs a one-alternative launch per step: the rank comes from the same kernel.)  A method of its own because
+        `score`'s parameter list is pinned."""
+        return self._score(tokenizer, new_token_ids, image_transform, images, prompt, candidates, append_eos, top_logprobs)
+
+    def _score(self, tokenizer, new_token_ids, image_transform, images, prompt, candidates, append_eos, top_logprobs):
+        ranks = top_logprobs is not None
+        want_top = ops.check_top_logprobs(top_logprobs, self.cfg.vocab) if ranks else 0
         cands = list(candidates)
         if not 1 <= len(cands) <= 64:
             raise ValueError(f"score takes 1..64 candidates, got {len(cands)}")
@@ -517,13 +558,19 @@ class Bagel(BagelPrep):
         for b, t in enumerate(toks):
             forced[:len(t), b] = torch.tensor(t, dtype=torch.int64)
         sess = DecodeSession(self.language_model, many, gi["packed_start_tokens"].repeat(n), gi["packed_query_position_ids"].repeat(n),
-                             steps, use_graph=self.decode_use_graph, forced_ids=forced)
+                             steps, use_graph=self.decode_use_graph, forced_ids=forced, top_logprobs=max(want_top, 1) if ranks else 0)
         sess.step(steps)
         lp = sess.pred_logprobs.cpu()
+        if ranks:
+            rk, tid, tlp = sess.pred_rank.cpu(), sess.pred_top_ids.cpu(), sess.pred_top_logprobs.cpu()
         out = []
         for b, t in enumerate(toks):
             vals = lp[:len(t), b]
             out.append({"token_ids": t, "token_logprobs": vals.tolist(), "logprob": float(vals.double().sum())})
+            if ranks:
+                out[-1]["token_ranks"] = rk[:len(t), b].tolist()
+            if want_top:
+                out[-1]["top_logprobs"] = [list(zip(tid[s, b, :want_top].tolist(), tlp[s, b, :want_top].tolist())) for s in range(len(t))]
         return out
 
 

@@ -29,6 +29,28 @@ __device__ __forceinline__ float block_reduce_max(float v, float* sm) {
 // exp(-inf - 0) = 0, not exp(-inf + inf) = NaN.
 __device__ __forceinline__ float softmax_ref(float M) { return (M == -INFINITY) ? 0.f : M; }
 
+// The merge of a sample's per-tile softmax statistics (m_t, s_t) into (ref, S), in every thread: M = max m_t, ref = softmax_ref(M),
+// S = sum s_t exp(m_t - ref).  Two passes over the 8 n_tiles bytes (L2 resident: the GEMM has just written them), each thread-strided
+// by T, then the wave tree, then the waves in order - a fixed order for a given T, so a sample's bits do not depend on the batch it
+// sits in.  A tile of -inf only is (-inf, 0) and adds 0 * exp(-inf) = 0; a NaN s_t makes S NaN.  smf: one float per wave.
+// TA < T: only the first TA threads take tiles, in TA's order - the other waves add +0 behind them, so a workgroup of T threads gets
+// the bits a workgroup of TA threads gets (the per-row step end and the top-n kernel run the 256-thread kernels' merge in their 512
+// threads).  Used by the step ends of token_pick.hip and by top_logprobs.hip, which must merge in the order the step end did.
+template <int T, int TA = T>
+__device__ __forceinline__ void merge_tile_stats(const umv_f32x2* __restrict__ st, int n_tiles, float* smf, float& ref, float& S) {
+    const int c_first = (TA == T || (int)threadIdx.x < TA) ? (int)threadIdx.x : n_tiles;
+    float M = -INFINITY;
+    for (int c = c_first; c < n_tiles; c += TA) M = fmaxf(M, st[c].x);
+    M = block_reduce_max(M, smf);
+    ref = softmax_ref(M);
+    S = 0.f;
+    for (int c = c_first; c < n_tiles; c += TA) {
+        const umv_f32x2 v = st[c];
+        S += v.y * expf(v.x - ref);
+    }
+    S = block_reduce_sum(S, smf);
+}
+
 // The maximum of a 64-bit value (an argmax key, token_pick.h) over a workgroup of T threads: complete in every thread (ALL) or in
 // thread 0 only.  sm: one word per wave, not in use by anything before this call; an ALL caller that reuses it puts a barrier behind.
 template <int T, bool ALL>

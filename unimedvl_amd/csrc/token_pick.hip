@@ -164,26 +164,7 @@ __device__ __forceinline__ uint64_t strided_max_key(const uint64_t* __restrict__
     return best;
 }
 
-// The merge of a sample's per-tile softmax statistics (m_t, s_t) into (ref, S), in every thread: M = max m_t, ref = softmax_ref(M),
-// S = sum s_t exp(m_t - ref).  Two passes over the 8 n_tiles bytes (L2 resident: the GEMM has just written them), each thread-strided
-// by T, then the wave tree, then the waves in order (block_reduce.h) - a fixed order for a given T, so a sample's bits do not depend
-// on the batch it sits in.  A tile of -inf only is (-inf, 0) and adds 0 * exp(-inf) = 0; a NaN s_t makes S NaN.  smf: one float per wave.
-// TA < T: only the first TA threads take tiles, in TA's order - the other waves add +0 behind them, so a workgroup of T threads gets
-// the bits a workgroup of TA threads gets (the per-row step end runs the 256-thread kernels' merge in its 512 threads).
-template <int T, int TA = T>
-__device__ __forceinline__ void merge_tile_stats(const umv_f32x2* __restrict__ st, int n_tiles, float* smf, float& ref, float& S) {
-    const int c_first = (TA == T || (int)threadIdx.x < TA) ? (int)threadIdx.x : n_tiles;
-    float M = -INFINITY;
-    for (int c = c_first; c < n_tiles; c += TA) M = fmaxf(M, st[c].x);
-    M = block_reduce_max(M, smf);
-    ref = softmax_ref(M);
-    S = 0.f;
-    for (int c = c_first; c < n_tiles; c += TA) {
-        const umv_f32x2 v = st[c];
-        S += v.y * expf(v.x - ref);
-    }
-    S = block_reduce_sum(S, smf);
-}
+// (the merge of a sample's per-tile softmax statistics: block_reduce.h::merge_tile_stats, shared with top_logprobs.hip)
 
 // Thread 0's tail for sample b at step s, id the pick.  The token the next step is fed is the forced one where there is one inside
 // the vocabulary (a forced token outside it is never fed: the pick is, with a NaN log-probability).  Row s of lp.out / co.cut_y /

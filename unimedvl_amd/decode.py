@@ -42,7 +42,7 @@ class DecodeSession:
                  do_sample=False, temperature=1.0, seed=0, logprobs=False, forced_ids=None, *,
                  repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, penalty_context_ids=None,
                  penalty_context_room=None, penalty_history=None, row_sampling=None, row_streams=None, row_penalties=False,
-                 top_k=0, top_p=1.0, min_p=0.0):
+                 top_logprobs=0, top_k=0, top_p=1.0, min_p=0.0):
         """logprobs: also record pred_logprobs (fp32 [max_length, B]) - row s is the log-probability of in_ids[s + 1], the token step s
         picked (include/unimedvl_hip.h, token log-probabilities: of softmax(logits) in greedy decoding, of softmax(bf16(logits / T))
         when sampling).  forced_ids (int64 [max_length, B]): where an entry is >= 0 that token is fed to the next step instead of the
@@ -71,7 +71,13 @@ class DecodeSession:
         set_slot(b, ..., sampling=, stream=, draw=) gives a slot new parameters between replays without a re-capture.  pred_cut_y /
         pred_n_kept are always recorded (a row without a filter: -inf / vocab).  The penalty buffers are allocated only if a row is
         not neutral, a bias is given, or row_penalties=True reserves them for later set_slot calls.  Rides on the fused step end
-        (B <= 64).  Without row_sampling nothing is allocated and the step is today's, launch for launch."""
+        (B <= 64).  Without row_sampling nothing is allocated and the step is today's, launch for launch.
+        top_logprobs (n, 0 = off, at most 20): also record, per step, the n most likely tokens with their log-probabilities and the rank
+        of the token fed next (include/unimedvl_hip.h, top-n alternative tokens) - pred_top_ids (int32) / pred_top_logprobs (fp32),
+        both [max_length, B, n], and pred_rank (int32 [max_length, B]); row s belongs to in_ids[s + 1] like pred_logprobs.  One
+        umv_decode_top_logprobs launch behind the step end, in the same graph; implies logprobs.  The alternatives are those of the
+        untruncated softmax of the stored (adjusted) logits, whatever sampler, filters, penalties or forced tokens the step runs with.
+        Off: nothing is allocated, nothing is launched."""
         if row_sampling is not None:
             given = dict(do_sample=do_sample is not False, temperature=temperature != 1.0, top_k=top_k != 0, top_p=top_p != 1.0,
                          min_p=min_p != 0.0, repetition_penalty=repetition_penalty != 1.0, presence_penalty=presence_penalty != 0.0,
@@ -80,19 +86,22 @@ class DecodeSession:
                 raise ValueError(f"row_sampling excludes the scalar sampler keywords (got {[k for k, v in given.items() if v]})")
         elif row_streams is not None or row_penalties:
             raise ValueError("row_streams / row_penalties go with row_sampling")
+        top_logprobs = ops.check_top_logprobs(top_logprobs, llm.cfg.vocab)
+        if top_logprobs and self.draft_len:
+            raise ValueError("top_logprobs is not available with draft_len > 0 (speculative decode)")
         with ops.device_scope(llm.device):
             self._init(llm, cache, start_tokens, positions, max_length, use_graph, nsplit, do_sample, temperature, seed, logprobs,
                        forced_ids, top_k, top_p, min_p,
                        dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
                             logit_bias=logit_bias, context=penalty_context_ids, room=penalty_context_room, history=penalty_history),
-                       dict(params=row_sampling, streams=row_streams, reserve=bool(row_penalties)))
+                       dict(params=row_sampling, streams=row_streams, reserve=bool(row_penalties)), top_logprobs)
 
     @property
     def device(self):
         return self.dev
 
     def _init(self, llm, cache, start_tokens, positions, max_length, use_graph, nsplit, do_sample, temperature, seed, logprobs=False,
-              forced_ids=None, top_k=0, top_p=1.0, min_p=0.0, penalties=None, rows=None):
+              forced_ids=None, top_k=0, top_p=1.0, min_p=0.0, penalties=None, rows=None, top_logprobs=0):
         cfg, dev = llm.cfg, llm.device
         self.llm, self.cache, self.cfg, self.dev = llm, cache, cfg, dev
         B = len(cache.lens)
@@ -171,7 +180,8 @@ class DecodeSession:
                                  f"(got B={B}, UMV_DECODE_FUSED_ARGMAX={os.environ.get('UMV_DECODE_FUSED_ARGMAX', '1')!r})")
         # token log-probabilities / forced tokens: the lm_head epilogue also leaves the softmax statistics of every tile, and the step
         # ends with umv_decode_step_end_logprob instead - same launch count, still one graph
-        self.logprobs = bool(logprobs) or forced_ids is not None
+        self.top_logprobs = int(top_logprobs)
+        self.logprobs = bool(logprobs) or forced_ids is not None or self.top_logprobs > 0
         self.forced_ids = self.pred_logprobs = self.lse_part = None
         if self.logprobs:
             need_fused("logprobs / forced_ids")
@@ -184,6 +194,13 @@ class DecodeSession:
                 self.forced_ids = f.to(dev).contiguous()
             self.lse_part = torch.zeros((B, (cfg.vocab + 15) // 16, 2), dtype=torch.float32, device=dev)
             self.pred_logprobs = torch.zeros((max_length, B), dtype=torch.float32, device=dev)
+        # top-n alternatives: one more launch behind the step end, over the logits and the statistics that one read
+        self.pred_top_ids = self.pred_top_logprobs = self.pred_rank = None
+        if self.top_logprobs:
+            n = self.top_logprobs
+            self.pred_top_ids = torch.zeros((max_length, B, n), dtype=torch.int32, device=dev)
+            self.pred_top_logprobs = torch.zeros((max_length, B, n), dtype=torch.float32, device=dev)
+            self.pred_rank = torch.zeros((max_length, B), dtype=torch.int32, device=dev)
         # truncated sampling: the lm_head call stays the sampling call; the step end finds the cutoff from the logits it stored
         self.top_k, self.top_p, self.min_p = ops.check_truncation(top_k, top_p, min_p)
         self.truncated = self.top_k > 0 or self.top_p < 1.0 or self.min_p > 0.0
@@ -415,6 +432,11 @@ class DecodeSession:
                               argmax_partial=self.lm_head_kw.get("argmax_partial"), lse_partial=self.lm_head_kw.get("lse_partial"),
                               sample_rows=self.row_table)
         self._step_end()
+        if self.top_logprobs:
+            # the n best columns of the (adjusted) logits and the rank of the token just fed, with the statistics merged as the step end did
+            ops.decode_top_logprobs(self.logits, self.lse_part, self.ids, self.step_idx, self.pred_top_ids, self.pred_top_logprobs,
+                                    self.pred_rank, temperature=self.temperature if self.do_sample else 0.0, sample_rows=self.row_table,
+                                    truncated=self.step_end == "truncated", forced_ids=self.forced_ids)
 
     def _step_end(self):
         """the launch that closes the step: the pick (where the lm_head epilogue left keys) and the bookkeeping"""

@@ -180,8 +180,13 @@ class VQAInferencer:
         images, conversation = process_conversation([input_image], prompt)
         # "return_logprobs" (not a reference key; default off): the result also carries "token_ids" and "token_logprobs", the generated
         # tokens behind the answer and the log-probability of each (Bagel.generate_text).  Without it the result is the reference's.
-        want_lp = bool(self.config.get("return_logprobs", False))
+        # "top_logprobs" (n, default 0 = off; implies "return_logprobs"): the result also carries "top_logprobs" - per token its n most
+        # likely alternatives as (id, logprob) pairs - and "token_ranks", each token's own 1-based rank (Bagel.generate_text).
+        n_top = int(self.config.get("top_logprobs", 0) or 0)
+        want_lp = bool(self.config.get("return_logprobs", False)) or n_top > 0
         extra = {"return_logprobs": True} if want_lp else {}
+        if n_top:
+            extra["top_logprobs"] = n_top
         draft_len = draft_len if draft_len is not None else self.config.get("draft_len", 0)
         if draft_len:       # predicted_ids: a predicted answer (a string or token ids) to draft from instead of the lookup
             extra.update(draft_len=draft_len, draft_ngram=draft_ngram if draft_ngram is not None else self.config.get("draft_ngram", (2, 4)),
@@ -189,20 +194,29 @@ class VQAInferencer:
         answer = self.model.chat(self.tokenizer, self.new_token_ids, self.image_transform, images=images,
                                  prompt=conversation, max_length=max_new_tokens, do_sample=do_sample,
                                  temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, **penalties, **extra)
-        if want_lp:
+        top = None
+        if n_top:
+            answer, token_ids, token_logprobs, top = answer
+        elif want_lp:
             answer, token_ids, token_logprobs = answer
         result = {"answer": answer, "input_image": input_image, "time": time.time() - start, "image_path": image_path,
                   "prompt": prompt, "timestamp": datetime.now().strftime("%Y-%m-%d %H:%M:%S")}
         if want_lp:
             result.update(token_ids=token_ids, token_logprobs=token_logprobs)
+        if top is not None:
+            result.update(top_logprobs=[list(zip(i, l)) for i, l in zip(top.ids, top.logprobs)], token_ranks=top.rank)
         return result
 
     def score(self, image, question, candidates, append_eos=True):
         """Closed-set answering (Bagel.score): one dict per candidate - token_ids, token_logprobs, logprob - for the answers
-        `candidates` (strings or token-id lists, at most 64) to `question` about `image` (a PIL image or a path)."""
+        `candidates` (strings or token-id lists, at most 64) to `question` about `image` (a PIL image or a path).  With the config key
+        "top_logprobs" set (n, 0 included) every dict also carries token_ranks and, for n > 0, top_logprobs (Bagel.score)."""
         if not self.loaded:
             raise RuntimeError("Model not loaded, please call load_model() first")
         input_image = image.convert("RGB") if isinstance(image, Image.Image) else Image.open(image).convert("RGB")
         images, conversation = process_conversation([input_image], question)
+        if self.config.get("top_logprobs") is not None:
+            return self.model.score_top_logprobs(self.tokenizer, self.new_token_ids, self.image_transform, images, conversation, candidates,
+                                                 append_eos=append_eos, top_logprobs=self.config["top_logprobs"])
         return self.model.score(self.tokenizer, self.new_token_ids, self.image_transform, images, conversation, candidates,
                                 append_eos=append_eos)

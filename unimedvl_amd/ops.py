@@ -931,6 +931,81 @@ def token_logprob(logits, ids, temperature=0.0, out=None):
     return out
 
 
+def check_top_logprobs(n, vocab=None):
+    """The number of alternatives per token as an int: 0 = off, at most _lib.TOP_LOGPROBS_MAX and the vocabulary; ValueError otherwise."""
+    if isinstance(n, bool) or int(n) != n or n < 0 or n > _lib.TOP_LOGPROBS_MAX:
+        raise ValueError(f"top_logprobs must be an integer in [0, {_lib.TOP_LOGPROBS_MAX}] (0 = off), got {n!r}")
+    if vocab is not None and n > vocab:
+        raise ValueError(f"top_logprobs ({n}) exceeds the vocabulary ({vocab})")
+    return int(n)
+
+
+def _top_n(who, n, V):
+    if isinstance(n, bool) or int(n) != n or not 1 <= n <= min(_lib.TOP_LOGPROBS_MAX, V):
+        raise _lib.UmvError(f"{who}: n must be an integer in [1, {_lib.TOP_LOGPROBS_MAX}] and at most V = {V}, got {n!r}")
+    return int(n)
+
+
+def decode_top_logprobs(logits, lse_partial, ids, step_idx, top_ids, top_logprobs, rank, temperature=0.0, sample_rows=None,
+                        truncated=False, forced_ids=None):
+    """After a fused step end (include/unimedvl_hip.h, top-n alternative tokens): row s = step_idx - 1 of top_ids (int32 [max_len, B, n]),
+    top_logprobs (fp32, same shape) and rank (int32 [max_len, B]) - the n best columns of every sample by (y descending, column
+    ascending) with their log-probabilities, and the 1-based rank of the token the step end left in ids.  logits / lse_partial /
+    temperature / sample_rows / forced_ids: what the step end got; truncated: the step end was decode_step_end_truncated (the order its
+    statistics were merged in; with sample_rows the row's own is taken)."""
+    lib = _lib.load()
+    _req(logits, BF16, "logits")
+    _req(lse_partial, torch.float32, "lse_partial")
+    _req(ids, torch.int64, "ids")
+    _req(step_idx, torch.int64, "step_idx")
+    _req(top_ids, torch.int32, "top_ids")
+    _req(top_logprobs, torch.float32, "top_logprobs")
+    _req(rank, torch.int32, "rank")
+    B = ids.numel()
+    if top_ids.dim() != 3:
+        raise _lib.UmvError("decode_top_logprobs: top_ids must be [max_len, B, n]")
+    max_len, _, n = top_ids.shape
+    if logits.dim() != 2 or logits.shape[0] < B or logits.stride(1) != 1:
+        raise _lib.UmvError("decode_top_logprobs: logits must be [B, V] with unit column stride")
+    V = logits.shape[1]
+    n = _top_n("decode_top_logprobs", n, V)
+    if not (top_ids.is_contiguous() and top_logprobs.is_contiguous() and rank.is_contiguous() and tuple(top_ids.shape) == (max_len, B, n)
+            and top_logprobs.shape == top_ids.shape and tuple(rank.shape) == (max_len, B) and ids.is_contiguous() and step_idx.numel() >= B):
+        raise _lib.UmvError("decode_top_logprobs: top_ids / top_logprobs [max_len, B, n], rank [max_len, B], ids [B], step_idx [B], all contiguous")
+    if not (lse_partial.is_contiguous() and lse_partial.dim() == 3 and lse_partial.shape[0] == B and lse_partial.shape[2] == 2):
+        raise _lib.UmvError("decode_top_logprobs: lse_partial must be a contiguous [B, n_tiles, 2] tensor")
+    if forced_ids is not None:
+        _req(forced_ids, torch.int64, "forced_ids")
+        if not (forced_ids.is_contiguous() and tuple(forced_ids.shape) == (max_len, B)):
+            raise _lib.UmvError("decode_top_logprobs: forced_ids must be a contiguous [max_len, B] tensor")
+    rows = None if sample_rows is None else _row_table(sample_rows, B, "decode_top_logprobs")
+    order = _lib.TOP_AFTER_TRUNCATED if truncated else _lib.TOP_AFTER_LOGPROB
+    check(lib.umv_decode_top_logprobs(_p(logits), logits.stride(0), V, _p(lse_partial), lse_partial.shape[1], float(temperature), rows, order,
+                                      _p(ids), _p(step_idx), _p(forced_ids), B, max_len, n, _p(top_ids), _p(top_logprobs), _p(rank),
+                                      _stream()),
+          "umv_decode_top_logprobs")
+
+
+def top_logprobs(logits, ids, n, temperature=0.0):
+    """The n best columns of every row of bf16 logits [M, V] (any row stride) by (y descending, column ascending), y as token_logprob's:
+    (top_ids int32 [M, n], top_logprobs fp32 [M, n], rank int32 [M]) - rank the 1-based place of ids[m] in that order, 0 for an id outside
+    the vocabulary.  Where ids[m] is among the n, its entry is token_logprob's value bit for bit."""
+    if logits.dim() != 2 or logits.stride(1) != 1 or ids.numel() != logits.shape[0] or not ids.is_contiguous():
+        raise _lib.UmvError("top_logprobs: logits [M, V] with unit column stride, ids a contiguous int64 [M]")
+    M, V = logits.shape
+    n = _top_n("top_logprobs", n, V)                    # (refused on the host, before anything touches the library)
+    lib = _lib.load()
+    _req(logits, BF16, "logits")
+    _req(ids, torch.int64, "ids")
+    top_ids = torch.empty((M, n), dtype=torch.int32, device=logits.device)
+    top_lp = torch.empty((M, n), dtype=torch.float32, device=logits.device)
+    rank = torch.empty((M,), dtype=torch.int32, device=logits.device)
+    check(lib.umv_top_logprobs_bf16(_p(logits), logits.stride(0), _p(ids), M, V, float(temperature), n, _p(top_ids), _p(top_lp), _p(rank),
+                                    _stream()),
+          "umv_top_logprobs_bf16")
+    return top_ids, top_lp, rank
+
+
 def timestep_embed(t, freqs):
     """[n] fp32 timesteps (device) x [half] fp32 frequencies -> [n, 2*half] bf16 sinusoid (cos | sin)"""
     lib = _lib.load()

@@ -40,6 +40,8 @@ class _Request:
     max_new_tokens: int
     tokens: List[int] = field(default_factory=list)
     logprobs: List[float] = field(default_factory=list)
+    top: List[Any] = field(default_factory=list)        # top_logprobs: per emitted token its n (id, logprob) pairs
+    ranks: List[int] = field(default_factory=list)      # ... and the token's own rank
     prompt_ids: Optional[List[int]] = None      # penalize_prompt: the prompt's tokens, the repetition penalty's context set
     sampling: Optional[SamplingParams] = None   # per_request_sampling: the request's own parameters (None = the batcher's)
 
@@ -50,8 +52,8 @@ class ContinuousBatcher:
                  use_graph: bool = True, growable: bool = True, context_limit: Optional[int] = None, paged: bool = False,
                  pool_pages: Optional[int] = None, logprobs: bool = False, *, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, penalize_prompt: bool = False,
-                 per_request_sampling: bool = False, seed: Optional[int] = None, top_k: int = 0, top_p: float = 1.0,
-                 min_p: float = 0.0):
+                 per_request_sampling: bool = False, seed: Optional[int] = None, top_logprobs: int = 0, top_k: int = 0,
+                 top_p: float = 1.0, min_p: float = 0.0):
         """max_context: the context (prompt + images) the slots are RESERVED for; with growable=True longer requests enlarge
         the cache (up to context_limit tokens of context when given), with growable=False they are refused.
         paged=True: block-table KV (kvcache.PagedCache) instead of slabs - the slots draw 256-token pages from ONE pool of `pool_pages`
@@ -60,6 +62,9 @@ class ContinuousBatcher:
         its pages.  Same answers as the slab cache (tests/test_paged_kv_gpu.py).
         logprobs=True: self.logprobs[rid] holds one float per emitted token of the request - the token's log-probability as
         DecodeSession(logprobs=True) records it - cut at EOS or the budget exactly as the tokens are.  Needs slots <= 64.
+        top_logprobs=n (1..20, batcher-wide: the buffer size is captured; implies logprobs): self.top_logprobs[rid] holds per emitted
+        token a list of its n most likely alternatives as (id, logprob) pairs, most likely first, and self.ranks[rid] the token's own
+        1-based rank (DecodeSession(top_logprobs=n)), both cut exactly as the tokens are.  Works with per_request_sampling.
         top_k / top_p / min_p: truncated sampling (DecodeSession), batcher-wide like temperature; they need do_sample and slots <= 64.
         repetition_penalty / presence_penalty / frequency_penalty / logit_bias: the logit penalties (DecodeSession), batcher-wide like
         temperature; a slot's history starts over when a request is admitted to it and lives across the rounds of that request.
@@ -114,8 +119,11 @@ class ContinuousBatcher:
         self.cache.reserve(self.slots, per_slot, cfg.kv_heads, cfg.head_dim, model.device)
         self.queue: Deque[_Request] = deque()
         self.results: Dict[int, str] = {}
-        self.want_logprobs = bool(logprobs)
+        self.n_top = ops.check_top_logprobs(top_logprobs, cfg.vocab)
+        self.want_logprobs = bool(logprobs) or self.n_top > 0
         self.logprobs: Dict[int, List[float]] = {}
+        self.top_logprobs: Dict[int, List[Any]] = {}
+        self.ranks: Dict[int, List[int]] = {}
         self._next_id = 0
         self.stats = {"decode_steps": 0, "prefills": 0, "tokens": 0, "cache_grows": 0}
 
@@ -189,7 +197,7 @@ class ContinuousBatcher:
                 sampler = dict(do_sample=self.do_sample, temperature=self.temperature, seed=seed, top_k=self.top_k, top_p=self.top_p,
                                min_p=self.min_p, **self.penalties)
             sn = DecodeSession(m.language_model, cache, start, pos, self.check_every, use_graph=self.use_graph,
-                               logprobs=self.want_logprobs, penalty_context_ids=[context_of(b) for b in range(B)],
+                               logprobs=self.want_logprobs, top_logprobs=self.n_top, penalty_context_ids=[context_of(b) for b in range(B)],
                                penalty_context_room=self._pen_room, penalty_history=m.cfg.vocab, **sampler)
             if prev is not None:                        # the requests go on: so do their penalty histories
                 sn.copy_penalty_history(prev, keep)
@@ -212,6 +220,8 @@ class ContinuousBatcher:
             self.stats["decode_steps"] += k
             ids = sess.pred_ids[:k].cpu()               # [k, B]; the only host sync of the round
             lps = sess.pred_logprobs[:k].cpu() if self.want_logprobs else None
+            if self.n_top:
+                tids, tlps, rks = sess.pred_top_ids[:k].cpu(), sess.pred_top_logprobs[:k].cpu(), sess.pred_rank[:k].cpu()
             freed = []
             for b in range(B):
                 req = active[b]
@@ -229,6 +239,10 @@ class ContinuousBatcher:
                     req.tokens.append(int(t))
                 if lps is not None:                     # one value per token emitted this round
                     req.logprobs.extend(lps[:len(req.tokens) - n_before, b].tolist())
+                if self.n_top:
+                    for s in range(len(req.tokens) - n_before):
+                        req.top.append(list(zip(tids[s, b].tolist(), tlps[s, b].tolist())))
+                    req.ranks.extend(rks[:len(req.tokens) - n_before, b].tolist())
                 if len(req.tokens) >= req.max_new_tokens:
                     done = True
                 if not done:
@@ -382,6 +396,9 @@ class ContinuousBatcher:
         self.results[req.rid] = text.split("<|im_end|>")[0].split("<|im_start|>")[1]   # inferencer.py:277-278
         if self.want_logprobs:
             self.logprobs[req.rid] = list(req.logprobs)
+        if self.n_top:
+            self.top_logprobs[req.rid] = list(req.top)
+            self.ranks[req.rid] = list(req.ranks)
         self.stats["tokens"] += len(req.tokens)
 
 

@@ -32,7 +32,7 @@ def _token_lists(value, B, what):
 # (temperature and seed mean nothing without do_sample and are ignored.)
 _NEUTRAL = dict(do_sample=False, logprobs=False, forced_ids=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
                 logit_bias=None, penalty_context_ids=None, penalty_context_room=None, penalty_history=None, row_sampling=None,
-                row_streams=None, row_penalties=False, top_k=0, top_p=1.0, min_p=0.0)
+                row_streams=None, row_penalties=False, top_k=0, top_p=1.0, min_p=0.0, top_logprobs=0)
 _IGNORED = ("temperature", "seed")
 
 
