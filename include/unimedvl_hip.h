@@ -643,6 +643,45 @@ typedef struct {
 } umv_spec_step_args;
 int umv_decode_step_end_speculative(const umv_spec_step_args* a, umv_stream_t stream);
 
+/* ------------------------------------------------------------------ speculative decode with sampling: verify drafts against the seeded draw
+ * A request's noise is keyed by its own (seed, stream, draw) - "per-row sampling parameters" - not by the step or the row it sits in, so
+ * token i of a request is a fixed function of the logits its prefix produces and of draw = i.  A speculative step therefore gives row
+ * r0 + j of sample b a table entry with the sample's parameters, seed and stream and draw = d0 + j (d0 = the number of tokens emitted so
+ * far): the lm_head epilogue (the per-row call over T = B * (k + 1) rows) and the pick below then produce, for that row, exactly the token
+ * the plain per-row step would pick after the prefix t0, d_1..d_j, and draft d_{j+1} is accepted exactly when it equals that pick.  No
+ * rejection-sampling arithmetic and no residual distribution: a deterministic draft is accepted with the probability the (truncated)
+ * softmax gives it, and the emitted sequence is the plain per-row session's, token for token (up to the last bit of a logit: the
+ * attention's key split depends on the segment length).  A greedy row (temperature <= 0) is the greedy speculative step's row.
+ * The step ends in two launches:
+ *
+ * umv_decode_pick_rows: one workgroup per ROW, T <= 64.  The pick part of umv_decode_step_end_rows with the row's own values, and
+ * nothing else: picks[r] (int64) = the truncated pick on a sampled row with a filter on (the fused pick if it survived, else the kept
+ * set's Gumbel maximum with regenerated noise), the key maximum otherwise; logprob[r] (fp32, with lse_partial or neither) = the pick's
+ * own log-probability, the statistics merged in the order umv_decode_step_end_rows uses for that kind of row (NaN for a pick outside
+ * [0, V)); cut_y[r] / n_kept[r] (optional) = the row's cutoff and kept count (-inf / V without a filter).  It advances no slot,
+ * position or length and only READS the table.  UMV_ERR_ARG as umv_decode_step_end_rows has it, plus T > 64 and a NULL picks.
+ *
+ * umv_decode_step_end_speculative_rows: steps 2-8 of "speculative greedy decode" unchanged, one workgroup per sample, with
+ *   1 pick     p_j = picks[r0 + j] (what umv_decode_pick_rows left) instead of the key maxima; step.argmax_partial is not read;
+ *   9 draws    with d0 = rows[r0].draw before the step and m the number emitted: rows[r0 + j].draw = d0 + m + j, j = 0..k - so m = 0
+ *              leaves the draws alone.  The only words of the table the launch writes;
+ *   logprobs   with row_logprob [T] and out_logprobs [B][step.out_ld] (both or neither): out_logprobs[b][n_out + i] = row_logprob[r0 + i]
+ *              for the m emitted tokens (n_out before the step).
+ * step.draft_only != 0 touches neither the table nor the log-probabilities (the host packs the first draws).  UMV_ERR_ARG: what
+ * umv_decode_step_end_speculative refuses (argmax_partial may be NULL), a NULL picks (unless draft_only), a NULL or misaligned table,
+ * row_logprob without out_logprobs or the reverse. */
+int umv_decode_pick_rows(const uint64_t* argmax_partial, const float* lse_partial, int n_tiles, const uint16_t* logits, int64_t ldo, int V,
+                         const umv_row_sampling* rows, int T, int64_t* picks, float* logprob, float* cut_y, int32_t* n_kept,
+                         umv_stream_t stream);
+typedef struct {
+    umv_spec_step_args step;         /* as for umv_decode_step_end_speculative; argmax_partial is not read */
+    const int64_t* picks;            /* [T] */
+    umv_row_sampling* rows;          /* [T]: only `draw` is written */
+    const float* row_logprob;        /* optional [T] */
+    float* out_logprobs;             /* optional [B][step.out_ld], with row_logprob */
+} umv_spec_rows_step_args;
+int umv_decode_step_end_speculative_rows(const umv_spec_rows_step_args* a, umv_stream_t stream);
+
 
 /* TimestepEmbedder.timestep_embedding (modeling_utils.py:87-109): out[r] = bf16(cat(cos(t[r] * freqs), sin(t[r] * freqs))),
  * out [n, 2*half]; freqs [half] fp32 = exp(-ln(10000) * i / half) from the caller.  The two linears + SiLU of the embedder

@@ -289,6 +289,33 @@ static void bad_arguments() {
     EXPECT_ERR(umv_decode_step_end_speculative(&sp, nullptr));
     sp.n_tiles = 4; sp.B = 0;
     EXPECT_OK(umv_decode_step_end_speculative(&sp, nullptr));    // no samples
+    // sampled speculative step end: the pick launch and the commit launch
+    EXPECT_ERR(umv_decode_pick_rows(nullptr, nullptr, 4, nullptr, 64, 64, nullptr, 1, nullptr, nullptr, nullptr, nullptr, nullptr));
+    EXPECT_ERR(umv_decode_pick_rows((const uint64_t*)dummyl, nullptr, 4, dummy16, 64, 64, nullptr, 1, dummyl, nullptr, dummyf, dummyi,
+                                    nullptr));                                                                  // no table
+    EXPECT_ERR(umv_decode_pick_rows((const uint64_t*)dummyl, nullptr, 4, dummy16, 64, 64, rows, 1, dummyl, dummyf, dummyf, dummyi,
+                                    nullptr));                                                                  // logprob without lse_partial
+    EXPECT_ERR(umv_decode_pick_rows((const uint64_t*)dummyl, nullptr, 3, dummy16, 64, 64, rows, 1, dummyl, nullptr, dummyf, dummyi,
+                                    nullptr));                                                                  // 64 columns are not 3 tiles
+    EXPECT_ERR(umv_decode_pick_rows((const uint64_t*)dummyl, nullptr, 4, dummy16, 64, 64, rows, 65, dummyl, nullptr, dummyf, dummyi,
+                                    nullptr));                                                                  // 65 rows
+    EXPECT_OK(umv_decode_pick_rows((const uint64_t*)dummyl, nullptr, 4, dummy16, 64, 64, rows, 0, dummyl, nullptr, dummyf, dummyi,
+                                   nullptr));                                                                   // no rows
+    EXPECT_ERR(umv_decode_step_end_speculative_rows(nullptr, nullptr));
+    umv_spec_rows_step_args sr;
+    std::memset(&sr, 0, sizeof sr);
+    EXPECT_ERR(umv_decode_step_end_speculative_rows(&sr, nullptr));
+    sr.step = sp; sr.step.B = 1; sr.step.argmax_partial = nullptr;       // the keys are not read
+    sr.picks = dummyl;
+    EXPECT_ERR(umv_decode_step_end_speculative_rows(&sr, nullptr));     // no table
+    sr.rows = rows; sr.picks = nullptr;
+    EXPECT_ERR(umv_decode_step_end_speculative_rows(&sr, nullptr));     // no picks
+    sr.picks = dummyl; sr.row_logprob = dummyf;                          // row_logprob without out_logprobs
+    EXPECT_ERR(umv_decode_step_end_speculative_rows(&sr, nullptr));
+    sr.row_logprob = nullptr; sr.step.k = 64;                            // 65 rows
+    EXPECT_ERR(umv_decode_step_end_speculative_rows(&sr, nullptr));
+    sr.step.k = 3; sr.step.B = 0;
+    EXPECT_OK(umv_decode_step_end_speculative_rows(&sr, nullptr));      // no samples
     EXPECT_ERR(umv_timestep_embed(nullptr, nullptr, nullptr, 4, 128, nullptr));
     EXPECT_ERR(umv_cfg_renorm_euler(nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 1, 4.0f, 1.5f, 0.f, 0, 0.1f, 64, nullptr));
     // VAE

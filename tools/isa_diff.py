@@ -3,7 +3,9 @@
 revision, with the file's flags from unimedvl_amd/build.py, and prints per kernel: VGPRs / occupancy / scratch on both sides and whether
 the instruction streams are identical (comments, .loc / .file / .cfi lines dropped, basic-block labels renumbered).
 
-usage: python tools/isa_diff.py attention_prefill.hip [--rev HEAD] [--must-match REGEX]     exit 1 when a --must-match kernel differs"""
+usage: python tools/isa_diff.py attention_prefill.hip [--rev HEAD] [--must-match REGEX]     exit 1 when a --must-match kernel differs
+       --renamed OLD=NEW (repeatable): a kernel whose symbol changed - one that became a template instantiation, say - is compared
+       under its two names (each a regex that matches exactly one symbol of its side) and must be identical"""
 import argparse
 import os
 import re
@@ -40,6 +42,7 @@ def main():
     ap.add_argument("source", help="file name under unimedvl_amd/csrc/")
     ap.add_argument("--rev", default="HEAD")
     ap.add_argument("--must-match", default=None, help="regex over kernel symbols whose instruction streams must be identical")
+    ap.add_argument("--renamed", action="append", default=[], metavar="OLD=NEW", help="compare a kernel of the revision with a differently named one of the tree")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         subprocess.check_call("git archive %s unimedvl_amd/csrc include | tar -x -C %s" % (a.rev, tmp), shell=True, cwd=ROOT)
@@ -54,6 +57,16 @@ def main():
         must = a.must_match is not None and re.search(a.must_match, name) is not None
         bad += must and verdict != "identical"
         print("%-9s %-14s %-14s %s%s" % (verdict, old.get(name, (0, "-"))[1], new.get(name, (0, "-"))[1], name, "  (must match)" if must else ""))
+    for pair in a.renamed:
+        sides = []
+        for rx, side in zip(pair.split("=", 1), (old, new)):
+            hit = [n for n in side if re.search(rx, n)]
+            if len(hit) != 1:
+                sys.exit("--renamed %s: %r matches %d kernels" % (pair, rx, len(hit)))
+            sides.append((hit[0], [ln.replace(hit[0], "<kernel>") for ln in side[hit[0]][0] if not re.match(r"\.(text|section)\b", ln)], side[hit[0]][1]))
+        same = sides[0][1] == sides[1][1]
+        bad += not same
+        print("%-9s %-14s %-14s %s -> %s  (renamed, must match)" % ("identical" if same else "differs", sides[0][2], sides[1][2], sides[0][0], sides[1][0]))
     return 1 if bad else 0
 
 

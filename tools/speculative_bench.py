@@ -16,7 +16,14 @@ deeper in the context than the plain one (up to steps * (k + 1) tokens), which i
 Per arm: ms per step (median, min - max), tokens per step, ms per emitted token next to the plain arm's min - max, and the break-even:
 the tokens per step at which ms per token equals the plain arm's median.
 
-    python tools/speculative_bench.py [--steps 64] [--warmup 8] [--repeats 3] [--out FILE]"""
+--sampled runs the sampled arms instead (speculative decode with sampling, SpeculativeDecodeSession(sampling=...)): B = 1 with k = 3 and
+k = 7, B = 8 with k = 1, each with plain sampling (T = 1), with top_p = 0.9 and with log-probabilities.  A step's time does not depend on
+what is accepted, so the predictions are the random ones (0 %).  Per arm, in the same process and alternating: the greedy speculative
+step at the same (B, k), the plain per-row session at the same sampler, the plain scalar session; reported: the sampled step over the
+greedy one, the rows session over the scalar one, what the sampled step costs beyond those two (the commit launch and the T - B extra
+pick workgroups), and the break-even tokens per step against the plain per-row session.
+
+    python tools/speculative_bench.py [--steps 64] [--warmup 8] [--repeats 3] [--sampled] [--out FILE]"""
 import argparse
 import gc
 import json
@@ -29,6 +36,9 @@ import torch  # noqa: E402
 
 CTX = 1060
 ARMS = {1: (3, 7), 8: (1, 3)}          # batch size -> draft lengths
+SAMPLED_ARMS = {1: (3, 7), 8: (1,)}
+SAMPLERS = {"sample": (dict(do_sample=True, temperature=1.0), False), "top_p": (dict(do_sample=True, temperature=1.0, top_p=0.9), False),
+            "sample_logprobs": (dict(do_sample=True, temperature=1.0), True)}
 
 
 def _timed(sess, n):
@@ -44,7 +54,9 @@ def _timed(sess, n):
 class Arm:
     """a session that can be put back to its first state"""
 
-    def __init__(self, llm, B, k, total):
+    def __init__(self, llm, B, k, total, sampling=None, logprobs=False, rows=False):
+        """sampling (SamplingParams keywords): the sampled speculative session (k > 0), or with k = 0 the plain per-row session
+        (rows=True) / the plain scalar session at the same sampler"""
         from unimedvl_amd.decode import DecodeSession
         from unimedvl_amd.kvcache import NaiveCache
         from unimedvl_amd.speculative import SpeculativeDecodeSession
@@ -56,12 +68,19 @@ class Arm:
         cache.lens = [CTX] * B
         start = torch.randint(1000, 100000, (B,), generator=torch.Generator().manual_seed(5))
         pos = torch.full((B,), CTX, dtype=torch.int64)
+        extra = {}
+        if sampling is not None:
+            from unimedvl_amd.sampling import SamplingParams
+            par = [SamplingParams(seed=77 + b, **sampling) for b in range(B)]
+            extra = dict(sampling=par, logprobs=logprobs) if k else dict(row_sampling=par, logprobs=logprobs) if rows else \
+                dict(sampling, seed=77, logprobs=logprobs)
         if k:
             g = torch.Generator().manual_seed(6 + k)
             self.garbage = torch.randint(1000, 100000, (B, self.room), generator=g).to(dev)
-            self.sess = SpeculativeDecodeSession(llm, cache, start, pos, self.room, k, use_graph=True, predicted_ids=self.garbage.cpu())
+            self.sess = SpeculativeDecodeSession(llm, cache, start, pos, self.room, k, use_graph=True, predicted_ids=self.garbage.cpu(),
+                                                 **extra)
         else:
-            self.sess = DecodeSession(llm, cache, start, pos, self.room + 1, use_graph=True)
+            self.sess = DecodeSession(llm, cache, start, pos, self.room + 1, use_graph=True, **extra)
         self.first = [t.clone() for t in self.sess._state()]
 
     def reset(self, predicted=None):
@@ -145,12 +164,42 @@ def batch_leg(llm, B, steps, warmup, repeats):
     return res
 
 
+def sampled_leg(llm, B, steps, warmup, repeats):
+    """the sampled arms of one batch size: per (k, sampler) four sessions timed alternating, `repeats` times"""
+    total = warmup + steps
+    out = {}
+    for k in SAMPLED_ARMS[B]:
+        greedy = Arm(llm, B, k, total)
+        for name, (par, lp) in SAMPLERS.items():
+            runs = [("sampled_spec", Arm(llm, B, k, total, par, lp)), ("greedy_spec", greedy), ("plain_rows", Arm(llm, B, 0, total, par, lp, rows=True)),
+                    ("plain_scalar", Arm(llm, B, 0, total, par, lp))]
+            times = {n: [] for n, _ in runs}
+            for _ in range(repeats):
+                for n, arm in runs:
+                    arm.reset(arm.garbage if arm.k else None)
+                    arm.sess.step(warmup)
+                    times[n].append(_timed(arm.sess, steps))
+            med = {n: statistics.median(t) for n, t in times.items()}
+            r = {n: dict(ms_per_step=round(med[n], 4), min_ms=round(min(t), 4), max_ms=round(max(t), 4)) for n, t in times.items()}
+            r.update(rows=B * (k + 1), sampled_minus_greedy_spec_us=round(1e3 * (med["sampled_spec"] - med["greedy_spec"]), 2),
+                     rows_minus_scalar_us=round(1e3 * (med["plain_rows"] - med["plain_scalar"]), 2),
+                     beyond_both_us=round(1e3 * (med["sampled_spec"] - med["greedy_spec"] - (med["plain_rows"] - med["plain_scalar"])), 2),
+                     break_even_tokens_per_step=round(med["sampled_spec"] / med["plain_rows"], 3))
+            out[f"k{k}_{name}"] = r
+            del runs
+            gc.collect()
+    res = dict(B=B, context=CTX, steps=steps, warmup=warmup, repeats=repeats, decode="hipGraph", arms=out)
+    print(json.dumps(res), flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--batches", default="1,8")
+    ap.add_argument("--sampled", action="store_true", help="the sampled arms (B = 1: k = 3, 7; B = 8: k = 1) instead of the greedy ones")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -164,7 +213,8 @@ def main():
                "lookup accepts nothing on random text, so real-text acceptance is not measured here")
     with torch.no_grad():
         for B in (int(v) for v in args.batches.split(",")):
-            res[f"B{B}"] = batch_leg(model.language_model, B, args.steps, args.warmup, args.repeats)
+            leg = sampled_leg if args.sampled else batch_leg
+            res[f"B{B}"] = leg(model.language_model, B, args.steps, args.warmup, args.repeats)
             gc.collect()
     if args.out:
         with open(args.out, "w") as f:

@@ -96,6 +96,13 @@ class SpecStepArgs(C.Structure):
     ]
 
 
+class SpecRowsStepArgs(C.Structure):
+    """umv_spec_rows_step_args: the commit launch of a sampled speculative step (umv_decode_step_end_speculative_rows)"""
+    _fields_ = [
+        ("step", SpecStepArgs), ("picks", C.c_void_p), ("rows", C.c_void_p), ("row_logprob", C.c_void_p), ("out_logprobs", C.c_void_p),
+    ]
+
+
 # umv_logit_penalty_args.count words: bits 0..29 the count, then "in the context set" and "in the row's visit list"
 PENALTY_COUNT_MASK, PENALTY_CONTEXT, PENALTY_LISTED = 0x3FFFFFFF, 0x40000000, 0x80000000
 # umv_decode_top_logprobs: the most alternatives a row can ask for, and the step end whose merge order the statistics take
@@ -175,6 +182,9 @@ _SIGS = {
                                         C.c_void_p, C.c_void_p]),
     "umv_logit_penalty_bf16": (C.c_int, [C.POINTER(LogitPenaltyArgs), C.c_void_p]),
     "umv_decode_step_end_speculative": (C.c_int, [C.POINTER(SpecStepArgs), C.c_void_p]),
+    "umv_decode_pick_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "umv_decode_step_end_speculative_rows": (C.c_int, [C.POINTER(SpecRowsStepArgs), C.c_void_p]),
     "umv_timestep_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "umv_cfg_renorm_euler": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.c_void_p]),

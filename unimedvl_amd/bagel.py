@@ -23,6 +23,7 @@ from . import ops
 from .config import UniMedVLConfig
 from .data_utils import (PackedVitImages, get_flattened_position_ids_extrapolate, get_flattened_position_ids_interpolate, patchify)
 from .decode import DecodeSession
+from .sampling import SamplingParams
 from .prep import BagelPrep
 from .kvcache import NaiveCache
 from .llm import Qwen2MoT
@@ -317,7 +318,7 @@ class Bagel(BagelPrep):
                       return_logits: bool = False, per_sample_eos: bool = False, return_logprobs: bool = False, *,
                       repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
                       logit_bias=None, penalty_context_ids=None, draft_len: int = 0, draft_ngram=(2, 4), draft_context_ids=None,
-                      predicted_ids=None, top_logprobs: int = 0, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+                      predicted_ids=None, sampling=None, top_logprobs: int = 0, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """Greedy decode (bagel.py:1236-1317).  Returns [steps, B] int64 whose row 0 holds the
         start tokens.  Like the reference, the batch stops when SAMPLE 0 emits end_token_id
         (bagel.py:1313); per_sample_eos=True is the batched extension (stops when every sample
@@ -341,7 +342,24 @@ class Bagel(BagelPrep):
         generated tokens) where given, else from a lookup of the last draft_ngram = (min, max) tokens in draft_context_ids (per sample
         the prompt's tokens; this call has none of its own) and in what was generated.  Same matrix, same stop rules, same cache
         lengths as draft_len = 0, fewer passes over the weights where drafts are accepted; self.last_draft_stats keeps the session's
-        [B, 3] (steps, drafted, accepted).  Greedy only: do_sample, return_logits / return_logprobs, penalties and logit_bias raise."""
+        [B, 3] (steps, drafted, accepted).  Greedy only: do_sample, return_logits / return_logprobs, penalties and logit_bias raise.
+        sampling (one sampling.SamplingParams, or a list of B): per-request sampling - every sample decodes with its own sampler and
+        its own seeded noise (DecodeSession(row_sampling=...); a seed of None is derived from _sampling_seed(), the stream word is the
+        sample index).  It excludes the scalar sampler keywords: do_sample, top_k / top_p / min_p, the three penalty keywords and a
+        temperature other than 1.0 raise ValueError.  With draft_len > 0 it is sampled speculative decode
+        (SpeculativeDecodeSession(sampling=...)): the drafts are verified against each request's own draw, so the matrix is the
+        draft_len = 0 matrix (up to the last bit of a logit); return_logprobs is allowed there ([rows, B], aligned as in the plain
+        call), while return_logits, top_logprobs, penalised params and logit_bias raise."""
+        if sampling is not None:
+            given = dict(do_sample=do_sample is not False, temperature=temperature != 1.0, top_k=top_k != 0, top_p=top_p != 1.0,
+                         min_p=min_p != 0.0, repetition_penalty=repetition_penalty != 1.0, presence_penalty=presence_penalty != 0.0,
+                         frequency_penalty=frequency_penalty != 0.0)
+            if any(given.values()):
+                raise ValueError(f"sampling excludes the scalar sampler keywords (got {[k for k, v in given.items() if v]})")
+            B = len(past_key_values.lens)
+            sampling = [sampling] * B if isinstance(sampling, SamplingParams) else list(sampling)
+            if len(sampling) != B or any(not isinstance(p, SamplingParams) for p in sampling):
+                raise ValueError(f"sampling must be one SamplingParams or a list of one per sample ({B})")
         top_k, top_p, min_p = ops.check_truncation(top_k, top_p, min_p)
         top_logprobs = ops.check_top_logprobs(top_logprobs, self.cfg.vocab)
         return_logprobs = bool(return_logprobs) or top_logprobs > 0
@@ -349,7 +367,7 @@ class Bagel(BagelPrep):
         # do_sample: softmax(logits / temperature) + multinomial on the device (bagel.py:1297-1299).  The
         # draw is keyed by a seed derived from torch.initial_seed(), so torch.manual_seed(s) makes runs
         # reproducible; the stream itself is not torch's (no device can reproduce another's RNG).
-        seed = self._sampling_seed() if do_sample else 0
+        seed = self._sampling_seed() if do_sample or (sampling and any(p.do_sample and p.seed is None for p in sampling)) else 0
         if key_values_lens is not None and [int(v) for v in key_values_lens.tolist()] != list(past_key_values.lens):
             raise ValueError("key_values_lens disagree with the cache")
         if max_length <= 0:   # nothing to decode (the reference would fail on torch.stack([]) here, bagel.py:1316)
@@ -365,6 +383,14 @@ class Bagel(BagelPrep):
                                     torch.zeros(shape, dtype=torch.float32, device=self.device),
                                     torch.zeros(shape[:2], dtype=torch.int32, device=self.device)),)
             return res if len(res) > 1 else out
+        if draft_len and sampling is not None:
+            if return_logits or top_logprobs:
+                raise ValueError("sampled speculative decode (draft_len > 0 with sampling) has no return_logits / top_logprobs")
+            if logit_bias:
+                raise ValueError("sampled speculative decode (draft_len > 0 with sampling) takes no logit_bias")
+            return self._generate_text_speculative(past_key_values, packed_start_tokens, packed_query_position_ids, max_length,
+                                                   end_token_id, per_sample_eos, draft_len, draft_ngram, draft_context_ids, predicted_ids,
+                                                   dict(sampling=sampling, seed=seed, logprobs=return_logprobs))
         if draft_len:
             if return_logits or return_logprobs:
                 raise ValueError("speculative decode (draft_len > 0) is greedy only: no return_logits / return_logprobs / top_logprobs")
@@ -374,12 +400,13 @@ class Bagel(BagelPrep):
                                                         repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                                                         frequency_penalty=frequency_penalty, logit_bias=logit_bias,
                                                         penalty_context_ids=penalty_context_ids))
+        sampler = dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p,
+                       repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty)
+        if sampling is not None:             # every sample its own sampler and key; the stream word is the sample index
+            sampler = dict(row_sampling=sampling)
         sess = DecodeSession(self.language_model, past_key_values, packed_start_tokens, packed_query_position_ids,
-                             max_length, use_graph=self.decode_use_graph and not return_logits,
-                             do_sample=do_sample, temperature=temperature, seed=seed, logprobs=return_logprobs,
-                             top_k=top_k, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
-                             presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, logit_bias=logit_bias,
-                             penalty_context_ids=penalty_context_ids, top_logprobs=top_logprobs)
+                             max_length, use_graph=self.decode_use_graph and not return_logits, seed=seed, logprobs=return_logprobs,
+                             logit_bias=logit_bias, penalty_context_ids=penalty_context_ids, top_logprobs=top_logprobs, **sampler)
         logits = []
         steps = 0
         stop = None
@@ -442,7 +469,10 @@ class Bagel(BagelPrep):
                 break
         sess.commit(rows)
         self.last_draft_stats = sess.stats.cpu()
-        return torch.cat([start_tokens.to(device=self.device, dtype=torch.int64).reshape(1, -1), sess.out_ids[:, :rows - 1].t()], 0)
+        out = torch.cat([start_tokens.to(device=self.device, dtype=torch.int64).reshape(1, -1), sess.out_ids[:, :rows - 1].t()], 0)
+        if sess.out_logprobs is not None:        # row s: the log-probability of emitted token s = out[s + 1], as the plain call has it
+            return out, sess.out_logprobs[:, :rows].t().contiguous()
+        return out
 
     # ------------------------------------------------------------------ convenience (evaluation path)
     @torch.no_grad()
@@ -451,7 +481,7 @@ class Bagel(BagelPrep):
              do_sample: bool = False, temperature: float = 1.0, return_logprobs: bool = False, *,
              repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None,
              penalize_prompt: bool = False, draft_len: int = 0, draft_ngram=(2, 4), predicted_ids=None,
-             top_logprobs: int = 0, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+             sampling=None, top_logprobs: int = 0, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """ViT-only VQA convenience path (bagel.py:1321-1392).  return_logprobs=True: returns (answer, token_ids, token_logprobs) -
         the generated tokens behind the answer (the end token excluded) and the log-probability of each (generate_text).
         top_logprobs=n (implies return_logprobs): a fourth element, a TopLogprobs named tuple of per-token lists - ids and logprobs
@@ -461,7 +491,9 @@ class Bagel(BagelPrep):
         text's own tokens, not the bos / eos wrapper around them: a penalised end token would only make answers longer.
         draft_len > 0: speculative greedy decode (generate_text) - the same answer from fewer passes over the weights where the answer
         repeats the prompt's wording or its own; the prompt's text tokens are the lookup's context.  predicted_ids: a predicted answer
-        (a string, or its token ids) to draft from instead."""
+        (a string, or its token ids) to draft from instead.
+        sampling (a sampling.SamplingParams): the request's own sampler and seed instead of the scalar sampler keywords
+        (generate_text) - with draft_len > 0 sampled speculative decode, the same answer as with draft_len = 0."""
         if self.chat_cache_tokens > 0:       # serving: one reserved cache reused by every request (stable slabs -> graph prefill)
             if self._chat_cache is None or self._chat_cache.cap < self.chat_cache_tokens:
                 self._chat_cache = NaiveCache(self.cfg.layers)
@@ -489,7 +521,8 @@ class Bagel(BagelPrep):
                                  temperature=temperature, end_token_id=new_token_ids["eos_token_id"],
                                  return_logprobs=return_logprobs, top_k=top_k, top_p=top_p, min_p=min_p, top_logprobs=top_logprobs,
                                  repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-                                 frequency_penalty=frequency_penalty, logit_bias=logit_bias, penalty_context_ids=prompt_ids, **draft, **gi)
+                                 frequency_penalty=frequency_penalty, logit_bias=logit_bias, penalty_context_ids=prompt_ids,
+                                 sampling=sampling, **draft, **gi)
         top = None
         if top_logprobs:
             ids, lp, top = ids

@@ -1,10 +1,11 @@
 // Next-token picking and the bookkeeping that ends a decode step: argmax and temperature sampling over bf16 logits, the
 // step-end kernels (three of them finish the lm_head GEMM's argmax epilogue: plain, with the token's log-probability, and with
 // top-k / top-p / min-p), the stand-alone token log-probability, the stand-alone truncated sampler and the step end of a speculative
-// greedy step (verify the drafts, commit, roll back, draft again).
+// greedy step (verify the drafts, commit, roll back, draft again) and the two launches that end a sampled speculative step.
 #include "block_reduce.h"
 #include "token_pick.h"
 #include "truncation.h"
+#include <type_traits>
 #include "../../include/unimedvl_hip.h"
 
 // ----------------------------------------------------------------------------- argmax (bf16 logits, lowest index wins)
@@ -381,15 +382,24 @@ extern "C" int umv_decode_step_end_truncated(int32_t* tok_slot, int32_t* tok_pos
 // decode_step_end_truncated_kernel's path with the row's temperature, filters and (seed, draw, stream), or the key maximum of
 // decode_step_end_logprob_kernel (a greedy row, or a sampled one with no filter on), its statistics merged in that kernel's 256-thread
 // order.  Thread 0 then advances the row's own draw counter: the one word of the table this launch writes, read by nobody else in it.
-__global__ __launch_bounds__(TR_THREADS) void decode_step_end_rows_kernel(StepEnd e, const uint64_t* __restrict__ part,
+// The kernel is a template on what ends it, so that there is one copy of the pick: E = StepEnd is the step end just described (row b is
+// sample b); E = PickOnly is umv_decode_pick_rows - the same pick, row b's outputs at entry b of picks / logprob / cut_y / n_kept, the
+// pick's own log-probability, and nothing else written: no bookkeeping, no draw.
+struct PickOnly {
+    int64_t* picks;
+};
+template <class E>
+__global__ __launch_bounds__(TR_THREADS) void decode_step_end_rows_kernel(E e, const uint64_t* __restrict__ part,
                                                                           const float* __restrict__ lse, int n_tiles,
                                                                           const bf16_t* __restrict__ logits, int64_t ldo, int V,
                                                                           umv_row_sampling* rows, const int64_t* __restrict__ forced,
                                                                           float* logprob, float* cut_y, int32_t* n_kept) {
     __shared__ uint32_t hist[TR_BINS];
     __shared__ TruncShared sh;
+    constexpr bool STEP_END = std::is_same<E, StepEnd>::value;
     const int b = blockIdx.x;
-    const int64_t s = e.step_idx[b];
+    int64_t s = 0;
+    if constexpr (STEP_END) s = e.step_idx[b];
     const bf16_t* row = logits + (int64_t)b * ldo;
     const float temp = row_sampling_temp(rows, b);
     const int top_k = rows[b].top_k;
@@ -413,9 +423,17 @@ __global__ __launch_bounds__(TR_THREADS) void decode_step_end_rows_kernel(StepEn
         if (truncated) merge_tile_stats<TR_THREADS>(st, n_tiles, sh.smf, ref, S);
         else merge_tile_stats<TR_THREADS, 256>(st, n_tiles, sh.smf, ref, S);
     }
-    if (threadIdx.x == 0) {
-        step_end_finish(e, b, s, argmax_key_column(best), forced, {row, V, temp, ref, S, logprob}, {cut, kept, cut_y, n_kept});
-        rows[b].draw = draw + 1;
+    if constexpr (STEP_END) {
+        if (threadIdx.x == 0) {
+            step_end_finish(e, b, s, argmax_key_column(best), forced, {row, V, temp, ref, S, logprob}, {cut, kept, cut_y, n_kept});
+            rows[b].draw = draw + 1;
+        }
+    } else if (threadIdx.x == 0) {
+        const int64_t id = argmax_key_column(best);
+        e.picks[b] = id;
+        if (logprob) logprob[b] = (id >= 0 && id < V) ? logprob_finish(pick_value(bf2f(row[id]), temp), ref, S) : NAN;
+        if (cut_y) cut_y[b] = cut;
+        if (n_kept) n_kept[b] = (int32_t)kept;
     }
 }
 
@@ -432,7 +450,7 @@ extern "C" int umv_decode_step_end_rows(int32_t* tok_slot, int32_t* tok_pos, int
               "decode_step_end_rows: logprob and lse_partial go together (both or neither)");
     if (int rc = tile_columns_ok("decode_step_end_rows", V, n_tiles, ldo)) return rc;
     if (B == 0) return UMV_OK;
-    hipLaunchKernelGGL(decode_step_end_rows_kernel, dim3(B), dim3(TR_THREADS), 0, (hipStream_t)stream, e, argmax_partial, lse_partial,
+    hipLaunchKernelGGL(decode_step_end_rows_kernel<StepEnd>, dim3(B), dim3(TR_THREADS), 0, (hipStream_t)stream, e, argmax_partial, lse_partial,
                        n_tiles, logits, ldo, V, rows, forced_ids, logprob, cut_y, n_kept);
     UMV_LAUNCH_CHECK();
     return UMV_OK;
@@ -444,13 +462,24 @@ extern "C" int umv_decode_step_end_rows(int32_t* tok_slot, int32_t* tok_pos, int
 // scans the candidate starts thread-strided and takes the largest through the same key maximum.
 __device__ __forceinline__ bool spec_token_ok(int64_t t, int V) { return t >= 0 && t < V; }
 
-__global__ __launch_bounds__(256) void decode_step_end_speculative_kernel(umv_spec_step_args a) {
+// One body for two kernels, a template on the arguments: umv_spec_step_args is the greedy step end (the picks are the key maxima);
+// umv_spec_rows_step_args is umv_decode_step_end_speculative_rows (ROWS) - the picks are read from r.picks, step 9 advances the draw
+// counters of the sample's table rows and the emitted tokens take their rows' log-probabilities.
+__device__ __forceinline__ const umv_spec_step_args& spec_step_of(const umv_spec_step_args& x) { return x; }
+__device__ __forceinline__ const umv_spec_step_args& spec_step_of(const umv_spec_rows_step_args& x) { return x.step; }
+template <class Args>
+__global__ __launch_bounds__(256) void decode_step_end_speculative_kernel(Args r) {
+    constexpr bool ROWS = std::is_same<Args, umv_spec_rows_step_args>::value;
+    const umv_spec_step_args& a = spec_step_of(r);
     __shared__ uint64_t sm[4];
     __shared__ int64_t pick[64];
     __shared__ int32_t s_hist_len, s_n_out;
     const int b = blockIdx.x, k = a.k, r0 = b * (k + 1);
     int32_t* hist = a.hist + (int64_t)b * a.hist_ld;
-    if (!a.draft_only) {
+    if constexpr (ROWS) {
+        if (!a.draft_only && (int)threadIdx.x <= k) pick[threadIdx.x] = r.picks[r0 + threadIdx.x];
+        __syncthreads();                 // pick[0..k] is written
+    } else if (!a.draft_only) {
         for (int j = 0; j <= k; ++j) {
             const uint64_t best = block_max_u64<256, true>(strided_max_key<256>(a.argmax_partial + (int64_t)(r0 + j) * a.n_tiles, a.n_tiles), sm);
             if (threadIdx.x == 0) pick[j] = argmax_key_column(best);
@@ -469,6 +498,14 @@ __global__ __launch_bounds__(256) void decode_step_end_speculative_kernel(umv_sp
             for (int i = 0; i < m; ++i) {
                 a.out_ids[(int64_t)b * a.out_ld + n_out + i] = pick[i];
                 if (hl < a.hist_ld) hist[hl++] = (int32_t)pick[i];
+                if constexpr (ROWS)
+                    if (r.out_logprobs) r.out_logprobs[(int64_t)b * a.out_ld + n_out + i] = r.row_logprob[r0 + i];
+            }
+            if constexpr (ROWS) {
+                if (m > 0) {             // the draws: row j of the next step is the sample's token n_out + m + j
+                    const int64_t d0 = r.rows[r0].draw;
+                    for (int j = 0; j <= k; ++j) r.rows[r0 + j].draw = d0 + m + j;
+                }
             }
             n_out += m;
             a.n_out[b] = n_out;
@@ -527,21 +564,61 @@ __global__ __launch_bounds__(256) void decode_step_end_speculative_kernel(umv_sp
     }
 }
 
+// What the two entries check alike.  keys: the entry reads argmax_partial (unless draft_only).
+static int spec_step_args_ok(const char* who, const umv_spec_step_args* a, bool keys) {
+    UMV_CHECK(a->k >= 1 && a->B >= 0 && (int64_t)a->B * (a->k + 1) <= 64, UMV_ERR_ARG,
+              "%s: k (%d) must be >= 1 and B * (k + 1) (%d x %d) at most 64 rows", who, a->k, a->B, a->k + 1);
+    UMV_CHECK(a->ngram_min >= 1 && a->ngram_min <= a->ngram_max, UMV_ERR_ARG, "%s: 1 <= ngram_min (%d) <= ngram_max (%d)", who,
+              a->ngram_min, a->ngram_max);
+    UMV_CHECK(a->tok_slot && a->tok_pos && a->kv_len && a->ids && a->out_ids && a->n_out && a->limit && a->n_draft && a->hist &&
+                  a->hist_len && a->stats && (!keys || a->argmax_partial || a->draft_only) && a->out_ld > 0 && a->hist_ld > 0,
+              UMV_ERR_ARG, "%s: null pointer", who);
+    UMV_CHECK((a->predicted != nullptr) == (a->pred_len != nullptr) && (!a->predicted || a->pred_ld > 0), UMV_ERR_ARG,
+              "%s: predicted and pred_len go together", who);
+    UMV_CHECK(a->n_tiles > 0, UMV_ERR_ARG, "%s: n_tiles must be > 0", who);
+    return tile_columns_ok(who, a->V, a->n_tiles, a->V);
+}
+
 extern "C" int umv_decode_step_end_speculative(const umv_spec_step_args* a, umv_stream_t stream) {
     UMV_CHECK(a, UMV_ERR_ARG, "decode_step_end_speculative: null args");
-    UMV_CHECK(a->k >= 1 && a->B >= 0 && (int64_t)a->B * (a->k + 1) <= 64, UMV_ERR_ARG,
-              "decode_step_end_speculative: k (%d) must be >= 1 and B * (k + 1) (%d x %d) at most 64 rows", a->k, a->B, a->k + 1);
-    UMV_CHECK(a->ngram_min >= 1 && a->ngram_min <= a->ngram_max, UMV_ERR_ARG,
-              "decode_step_end_speculative: 1 <= ngram_min (%d) <= ngram_max (%d)", a->ngram_min, a->ngram_max);
-    UMV_CHECK(a->tok_slot && a->tok_pos && a->kv_len && a->ids && a->out_ids && a->n_out && a->limit && a->n_draft && a->hist &&
-                  a->hist_len && a->stats && (a->argmax_partial || a->draft_only) && a->out_ld > 0 && a->hist_ld > 0,
-              UMV_ERR_ARG, "decode_step_end_speculative: null pointer");
-    UMV_CHECK((a->predicted != nullptr) == (a->pred_len != nullptr) && (!a->predicted || a->pred_ld > 0), UMV_ERR_ARG,
-              "decode_step_end_speculative: predicted and pred_len go together");
-    UMV_CHECK(a->n_tiles > 0, UMV_ERR_ARG, "decode_step_end_speculative: n_tiles must be > 0");
-    if (int rc = tile_columns_ok("decode_step_end_speculative", a->V, a->n_tiles, a->V)) return rc;
+    if (int rc = spec_step_args_ok("decode_step_end_speculative", a, true)) return rc;
     if (a->B == 0) return UMV_OK;
-    hipLaunchKernelGGL(decode_step_end_speculative_kernel, dim3(a->B), dim3(256), 0, (hipStream_t)stream, *a);
+    hipLaunchKernelGGL(decode_step_end_speculative_kernel<umv_spec_step_args>, dim3(a->B), dim3(256), 0, (hipStream_t)stream, *a);
+    UMV_LAUNCH_CHECK();
+    return UMV_OK;
+}
+
+// ----------------------------------------------------------------------------- speculative decode with sampling (include/unimedvl_hip.h)
+// Two launches end a sampled speculative step: every row's pick with its own sampler (decode_step_end_rows_kernel<PickOnly>, the T
+// workgroups sweeping their rows in parallel), then the commit per sample (decode_step_end_speculative_kernel on the rows arguments).
+extern "C" int umv_decode_pick_rows(const uint64_t* argmax_partial, const float* lse_partial, int n_tiles, const uint16_t* logits, int64_t ldo,
+                                    int V, const umv_row_sampling* rows, int T, int64_t* picks, float* logprob, float* cut_y, int32_t* n_kept,
+                                    umv_stream_t stream) {
+    UMV_CHECK(argmax_partial && logits && picks && n_tiles > 0 && T >= 0, UMV_ERR_ARG, "decode_pick_rows: bad args");
+    UMV_CHECK(T <= 64, UMV_ERR_ARG, "decode_pick_rows: at most 64 rows (got %d)", T);
+    UMV_CHECK(rows && ((uintptr_t)rows % 16) == 0, UMV_ERR_ARG, "decode_pick_rows: rows (the per-row sampling table) must be set and "
+              "16-byte aligned");
+    UMV_CHECK((logprob != nullptr) == (lse_partial != nullptr), UMV_ERR_ARG,
+              "decode_pick_rows: logprob and lse_partial go together (both or neither)");
+    if (int rc = tile_columns_ok("decode_pick_rows", V, n_tiles, ldo)) return rc;
+    if (T == 0) return UMV_OK;
+    hipLaunchKernelGGL(decode_step_end_rows_kernel<PickOnly>, dim3(T), dim3(TR_THREADS), 0, (hipStream_t)stream, PickOnly{picks},
+                       argmax_partial, lse_partial, n_tiles, logits, ldo, V, const_cast<umv_row_sampling*>(rows), (const int64_t*)nullptr,
+                       logprob, cut_y, n_kept);
+    UMV_LAUNCH_CHECK();
+    return UMV_OK;
+}
+
+extern "C" int umv_decode_step_end_speculative_rows(const umv_spec_rows_step_args* a, umv_stream_t stream) {
+    UMV_CHECK(a, UMV_ERR_ARG, "decode_step_end_speculative_rows: null args");
+    if (int rc = spec_step_args_ok("decode_step_end_speculative_rows", &a->step, false)) return rc;
+    UMV_CHECK(a->picks || a->step.draft_only, UMV_ERR_ARG, "decode_step_end_speculative_rows: picks must be set");
+    UMV_CHECK(a->rows && ((uintptr_t)a->rows % 16) == 0, UMV_ERR_ARG, "decode_step_end_speculative_rows: rows (the per-row sampling table) "
+              "must be set and 16-byte aligned");
+    UMV_CHECK((a->row_logprob != nullptr) == (a->out_logprobs != nullptr), UMV_ERR_ARG,
+              "decode_step_end_speculative_rows: row_logprob and out_logprobs go together (both or neither)");
+    if (a->step.B == 0) return UMV_OK;
+    hipLaunchKernelGGL(decode_step_end_speculative_kernel<umv_spec_rows_step_args>, dim3(a->step.B), dim3(256), 0, (hipStream_t)stream, *a);
     UMV_LAUNCH_CHECK();
     return UMV_OK;
 }

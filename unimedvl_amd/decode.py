@@ -192,8 +192,9 @@ class DecodeSession:
                 if f.numel() and int(f.max()) >= cfg.vocab:
                     raise ValueError(f"forced_ids holds token {int(f.max())} >= vocab {cfg.vocab}")
                 self.forced_ids = f.to(dev).contiguous()
-            self.lse_part = torch.zeros((B, (cfg.vocab + 15) // 16, 2), dtype=torch.float32, device=dev)
-            self.pred_logprobs = torch.zeros((max_length, B), dtype=torch.float32, device=dev)
+            # (one tile statistic per ROW; a session with drafts logs per sample: out_logprobs, speculative.py)
+            self.lse_part = torch.zeros((R, (cfg.vocab + 15) // 16, 2), dtype=torch.float32, device=dev)
+            self.pred_logprobs = torch.zeros((max_length, B), dtype=torch.float32, device=dev) if k == 0 else None
         # top-n alternatives: one more launch behind the step end, over the logits and the statistics that one read
         self.pred_top_ids = self.pred_top_logprobs = self.pred_rank = None
         if self.top_logprobs:
@@ -223,9 +224,21 @@ class DecodeSession:
             if len(params) != B or len(streams) != B:
                 raise ValueError(f"row_sampling / row_streams must hold one entry per sample ({B}), got {len(params)} / {len(streams)}")
             self.row_params, self.row_streams = params, streams
-            self.row_table = sampling_mod.to_tensor(sampling_mod.pack(params, seed=int(seed), streams=streams), dev)
-            self.pred_cut_y = torch.zeros((max_length, B), dtype=torch.float32, device=dev)
-            self.pred_n_kept = torch.zeros((max_length, B), dtype=torch.int32, device=dev)
+            if k == 0:
+                self.row_table = sampling_mod.to_tensor(sampling_mod.pack(params, seed=int(seed), streams=streams), dev)
+                self.pred_cut_y = torch.zeros((max_length, B), dtype=torch.float32, device=dev)
+                self.pred_n_kept = torch.zeros((max_length, B), dtype=torch.int32, device=dev)
+            else:
+                # with drafts the table has one entry per ROW: sample b's k + 1 rows repeat its parameters, seed and stream, and row j
+                # draws with the key of the sample's token n_out + j (include/unimedvl_hip.h, speculative decode with sampling); what
+                # the pick launch leaves is per row as well
+                self.row_table = sampling_mod.to_tensor(sampling_mod.pack(
+                    [p for p in params for _ in range(k + 1)], seed=int(seed), streams=[v for v in streams for _ in range(k + 1)],
+                    draws=list(range(k + 1)) * B), dev)
+                self.row_picks = torch.zeros((R,), dtype=torch.int64, device=dev)
+                self.row_logprob = torch.zeros((R,), dtype=torch.float32, device=dev) if self.logprobs else None
+                self.row_cut_y = torch.zeros((R,), dtype=torch.float32, device=dev)
+                self.row_n_kept = torch.zeros((R,), dtype=torch.int32, device=dev)
         w = llm.w
         # K splits of the QKV / o / down GEMMs: "q,o,d" (1 = that GEMM is not split), "0" = none, "auto" by batch / weights.
         # Measured on MI355X (bench.py --batch B, ms per step), no split -> 3,4,4:

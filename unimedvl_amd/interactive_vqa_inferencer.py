@@ -48,6 +48,10 @@ DEFAULT_CONFIG = {
     # speculative greedy decode (not reference keys; off = one token per step): Bagel.chat - needs "do_sample": False
     "draft_len": 0,                 # drafted tokens verified per step (prompt lookup over the question and the answer so far)
     "draft_ngram": (2, 4),
+    # per-request sampling (not a reference key; None = the scalar keys above): a sampling.SamplingParams, or a dict of its fields - the
+    # request's own sampler and seed (Bagel.chat(sampling=...)).  It REPLACES "do_sample" / "temperature" / "top_k" / "top_p" / "min_p"
+    # and the three penalty keys, which are then not passed on; with "draft_len" > 0 it is sampled speculative decode
+    "sampling": None,
 }
 
 # codes/data/default.yaml vlm_sft.image_transform_args (read by eval/vlm/utils.py:486-502)
@@ -161,6 +165,7 @@ class VQAInferencer:
                      draft_len=None, draft_ngram=None, predicted_ids=None, top_k=None, top_p=None, min_p=None):
         if not self.loaded:
             raise RuntimeError("Model not loaded, please call load_model() first")
+        temperature_arg, do_sample_arg, top_k_arg, top_p_arg, min_p_arg = temperature, do_sample, top_k, top_p, min_p
         temperature = temperature if temperature is not None else self.config["temperature"]
         max_new_tokens = max_new_tokens if max_new_tokens is not None else self.config["max_new_tokens"]
         do_sample = do_sample if do_sample is not None else self.config["do_sample"]
@@ -191,9 +196,16 @@ class VQAInferencer:
         if draft_len:       # predicted_ids: a predicted answer (a string or token ids) to draft from instead of the lookup
             extra.update(draft_len=draft_len, draft_ngram=draft_ngram if draft_ngram is not None else self.config.get("draft_ngram", (2, 4)),
                          predicted_ids=predicted_ids)
+        sampler = dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, **penalties)
+        sampling = self.config.get("sampling")
+        if sampling is not None:    # the config's scalar sampler keys step aside; one given to this call explicitly is passed on (and refused)
+            from .sampling import SamplingParams
+            passed = dict(temperature=temperature_arg, do_sample=do_sample_arg, top_k=top_k_arg, top_p=top_p_arg, min_p=min_p_arg, **given)
+            sampler = {k: v for k, v in passed.items() if v is not None and k not in ("logit_bias", "penalize_prompt")}
+            sampler.update(sampling=sampling if isinstance(sampling, SamplingParams) else SamplingParams(**sampling),
+                           logit_bias=penalties["logit_bias"], penalize_prompt=penalties["penalize_prompt"])
         answer = self.model.chat(self.tokenizer, self.new_token_ids, self.image_transform, images=images,
-                                 prompt=conversation, max_length=max_new_tokens, do_sample=do_sample,
-                                 temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, **penalties, **extra)
+                                 prompt=conversation, max_length=max_new_tokens, **sampler, **extra)
         top = None
         if n_top:
             answer, token_ids, token_logprobs, top = answer

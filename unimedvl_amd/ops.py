@@ -875,6 +875,39 @@ def decode_step_end_rows(tok_slot, tok_pos, kv_len, argmax_partial, ids, in_ids,
           "umv_decode_step_end_rows")
 
 
+def _spec_step_args(who, tok_slot, tok_pos, kv_len, argmax_partial, ids, out_ids, n_out, limit, n_draft, hist, hist_len, stats, draft_len,
+                    vocab, ngram, predicted, pred_len, draft_only):
+    """umv_spec_step_args from the tensors of a speculative step, checked (argmax_partial may be None where the entry does not read it)"""
+    k, B = int(draft_len), kv_len.numel()
+    T = B * (k + 1)
+    n_tiles = (int(vocab) + 15) // 16
+    i32 = [(tok_slot, "tok_slot", T), (tok_pos, "tok_pos", T), (kv_len, "kv_len", B), (n_out, "n_out", B), (limit, "limit", B),
+           (n_draft, "n_draft", B), (hist_len, "hist_len", B), (stats, "stats", 3 * B), (hist, "hist", None)]
+    if pred_len is not None:
+        i32.append((pred_len, "pred_len", B))
+    i64 = [(ids, "ids", T), (out_ids, "out_ids", None)]
+    if argmax_partial is not None:
+        i64.append((argmax_partial, "argmax_partial", T * n_tiles))
+    if predicted is not None:
+        i64.append((predicted, "predicted", None))
+    for group, dt in ((i32, torch.int32), (i64, torch.int64)):
+        for t, name, n in group:
+            _req(t, dt, name)
+            if not t.is_contiguous() or (n is not None and t.numel() != n) or (n is None and (t.dim() != 2 or t.shape[0] != B)):
+                raise _lib.UmvError(f"{who}: {name} must be contiguous with {'[B, n]' if n is None else n} entries "
+                                    f"(B = {B}, draft_len = {k}), got {tuple(t.shape)}")
+    if (predicted is None) != (pred_len is None):
+        raise _lib.UmvError(f"{who}: predicted and pred_len go together")
+    return _lib.SpecStepArgs(
+        tok_slot=tok_slot.data_ptr(), tok_pos=tok_pos.data_ptr(), kv_len=kv_len.data_ptr(),
+        argmax_partial=None if argmax_partial is None else argmax_partial.data_ptr(),
+        n_tiles=n_tiles, V=int(vocab), ids=ids.data_ptr(), out_ids=out_ids.data_ptr(), out_ld=out_ids.shape[1], n_out=n_out.data_ptr(),
+        limit=limit.data_ptr(), n_draft=n_draft.data_ptr(), hist=hist.data_ptr(), hist_ld=hist.shape[1], hist_len=hist_len.data_ptr(),
+        predicted=None if predicted is None else predicted.data_ptr(), pred_ld=0 if predicted is None else predicted.shape[1],
+        pred_len=None if pred_len is None else pred_len.data_ptr(), stats=stats.data_ptr(), B=B, k=k, ngram_min=int(ngram[0]),
+        ngram_max=int(ngram[1]), draft_only=int(bool(draft_only)))
+
+
 def decode_step_end_speculative(tok_slot, tok_pos, kv_len, argmax_partial, ids, out_ids, n_out, limit, n_draft, hist, hist_len, stats,
                                 draft_len, vocab, ngram=(2, 4), predicted=None, pred_len=None, draft_only=False):
     """The step end of a speculative greedy step (include/unimedvl_hip.h): per sample verify the draft_len drafts of this step's rows
@@ -883,32 +916,66 @@ def decode_step_end_speculative(tok_slot, tok_pos, kv_len, argmax_partial, ids, 
     rows (predicted [B, n] int64 + pred_len where a row has one, prompt lookup with ngram = (min, max) otherwise) and write them to
     ids / tok_slot / tok_pos [T] and n_draft; stats [B, 3] += (steps, drafted, accepted).  draft_only: only draft and write the rows."""
     lib = _lib.load()
-    k, B = int(draft_len), kv_len.numel()
-    T = B * (k + 1)
-    n_tiles = (int(vocab) + 15) // 16
-    i32 = [(tok_slot, "tok_slot", T), (tok_pos, "tok_pos", T), (kv_len, "kv_len", B), (n_out, "n_out", B), (limit, "limit", B),
-           (n_draft, "n_draft", B), (hist_len, "hist_len", B), (stats, "stats", 3 * B), (hist, "hist", None)]
-    if pred_len is not None:
-        i32.append((pred_len, "pred_len", B))
-    i64 = [(ids, "ids", T), (out_ids, "out_ids", None), (argmax_partial, "argmax_partial", T * n_tiles)]
-    if predicted is not None:
-        i64.append((predicted, "predicted", None))
-    for group, dt in ((i32, torch.int32), (i64, torch.int64)):
-        for t, name, n in group:
-            _req(t, dt, name)
-            if not t.is_contiguous() or (n is not None and t.numel() != n) or (n is None and (t.dim() != 2 or t.shape[0] != B)):
-                raise _lib.UmvError(f"decode_step_end_speculative: {name} must be contiguous with {'[B, n]' if n is None else n} entries "
-                                    f"(B = {B}, draft_len = {k}), got {tuple(t.shape)}")
-    if (predicted is None) != (pred_len is None):
-        raise _lib.UmvError("decode_step_end_speculative: predicted and pred_len go together")
-    a = _lib.SpecStepArgs(
-        tok_slot=tok_slot.data_ptr(), tok_pos=tok_pos.data_ptr(), kv_len=kv_len.data_ptr(), argmax_partial=argmax_partial.data_ptr(),
-        n_tiles=n_tiles, V=int(vocab), ids=ids.data_ptr(), out_ids=out_ids.data_ptr(), out_ld=out_ids.shape[1], n_out=n_out.data_ptr(),
-        limit=limit.data_ptr(), n_draft=n_draft.data_ptr(), hist=hist.data_ptr(), hist_ld=hist.shape[1], hist_len=hist_len.data_ptr(),
-        predicted=None if predicted is None else predicted.data_ptr(), pred_ld=0 if predicted is None else predicted.shape[1],
-        pred_len=None if pred_len is None else pred_len.data_ptr(), stats=stats.data_ptr(), B=B, k=k, ngram_min=int(ngram[0]),
-        ngram_max=int(ngram[1]), draft_only=int(bool(draft_only)))
+    a = _spec_step_args("decode_step_end_speculative", tok_slot, tok_pos, kv_len, argmax_partial, ids, out_ids, n_out, limit, n_draft, hist,
+                        hist_len, stats, draft_len, vocab, ngram, predicted, pred_len, draft_only)
     check(lib.umv_decode_step_end_speculative(C.byref(a), _stream()), "umv_decode_step_end_speculative")
+
+
+def decode_pick_rows(argmax_partial, logits, sample_rows, picks, lse_partial=None, logprob=None, cut_y=None, n_kept=None):
+    """Every row's pick with its own sampler and nothing else (include/unimedvl_hip.h, speculative decode with sampling): picks [T] int64
+    from the keys the per-row lm_head call left in argmax_partial [T, n_tiles], the logits [T, V] it stored and the table sample_rows
+    (sampling.to_tensor, [T, 6]) - decode_step_end_rows' pick, without its bookkeeping and without touching the table.  logprob (fp32
+    [T], with lse_partial [T, n_tiles, 2]): the pick's own log-probability; cut_y (fp32 [T]) / n_kept (int32 [T]): the row's cutoff."""
+    lib = _lib.load()
+    _req(argmax_partial, torch.int64, "argmax_partial")
+    _req(logits, BF16, "logits")
+    _req(picks, torch.int64, "picks")
+    T = picks.numel()
+    if (lse_partial is None) != (logprob is None):
+        raise _lib.UmvError("decode_pick_rows: lse_partial and logprob go together")
+    if not (argmax_partial.dim() == 2 and argmax_partial.is_contiguous() and argmax_partial.shape[0] == T and picks.is_contiguous()
+            and logits.dim() == 2 and logits.shape[0] >= T and logits.stride(1) == 1):
+        raise _lib.UmvError("decode_pick_rows: argmax_partial [T, n_tiles] and picks [T] contiguous, logits [T, V] with unit column stride")
+    if lse_partial is not None:
+        _req(lse_partial, torch.float32, "lse_partial")
+        if not (lse_partial.is_contiguous() and tuple(lse_partial.shape) == tuple(argmax_partial.shape) + (2,)):
+            raise _lib.UmvError("decode_pick_rows: lse_partial must be a contiguous [T, n_tiles, 2] tensor")
+    for t, dt, name in ((logprob, torch.float32, "logprob"), (cut_y, torch.float32, "cut_y"), (n_kept, torch.int32, "n_kept")):
+        if t is not None:
+            _req(t, dt, name)
+            if not (t.is_contiguous() and t.numel() == T):
+                raise _lib.UmvError(f"decode_pick_rows: {name} must be a contiguous tensor of {T} entries")
+    rows = _row_table(sample_rows, T, "decode_pick_rows")
+    check(lib.umv_decode_pick_rows(_p(argmax_partial), _p(lse_partial), argmax_partial.shape[1], _p(logits), logits.stride(0), logits.shape[1],
+                                   rows, T, _p(picks), _p(logprob), _p(cut_y), _p(n_kept), _stream()), "umv_decode_pick_rows")
+
+
+def decode_step_end_speculative_rows(tok_slot, tok_pos, kv_len, picks, sample_rows, ids, out_ids, n_out, limit, n_draft, hist, hist_len, stats,
+                                     draft_len, vocab, ngram=(2, 4), predicted=None, pred_len=None, draft_only=False, row_logprob=None,
+                                     out_logprobs=None):
+    """The commit launch of a sampled speculative step: decode_step_end_speculative whose picks are read from picks [T] (decode_pick_rows)
+    instead of key maxima, which also sets the draw counters of the sample's table rows to d0 + m + j (m tokens emitted, row j) and, with
+    row_logprob [T] / out_logprobs [B, max] (both or neither), copies the emitted tokens' log-probabilities next to out_ids.
+    draft_only: only draft and write the rows; the table and the log-probabilities are not touched."""
+    lib = _lib.load()
+    who = "decode_step_end_speculative_rows"
+    step = _spec_step_args(who, tok_slot, tok_pos, kv_len, None, ids, out_ids, n_out, limit, n_draft, hist, hist_len, stats, draft_len, vocab,
+                           ngram, predicted, pred_len, draft_only)
+    T = ids.numel()
+    _req(picks, torch.int64, "picks")
+    if not (picks.is_contiguous() and picks.numel() == T):
+        raise _lib.UmvError(f"{who}: picks must be a contiguous tensor of {T} entries")
+    if (row_logprob is None) != (out_logprobs is None):
+        raise _lib.UmvError(f"{who}: row_logprob and out_logprobs go together")
+    if row_logprob is not None:
+        _req(row_logprob, torch.float32, "row_logprob")
+        _req(out_logprobs, torch.float32, "out_logprobs")
+        if not (row_logprob.is_contiguous() and row_logprob.numel() == T and out_logprobs.is_contiguous()
+                and out_logprobs.shape == out_ids.shape):
+            raise _lib.UmvError(f"{who}: row_logprob [{T}] and out_logprobs {tuple(out_ids.shape)} (as out_ids), contiguous")
+    a = _lib.SpecRowsStepArgs(step=step, picks=picks.data_ptr(), rows=_row_table(sample_rows, T, who), row_logprob=None if row_logprob is None else row_logprob.data_ptr(),
+                              out_logprobs=None if out_logprobs is None else out_logprobs.data_ptr())
+    check(lib.umv_decode_step_end_speculative_rows(C.byref(a), _stream()), "umv_decode_step_end_speculative_rows")
 
 
 def token_logprob(logits, ids, temperature=0.0, out=None):

@@ -8,8 +8,11 @@ epilogue leaves every row's argmax keys - and umv_decode_step_end_speculative en
 length by what was accepted (the rejected rows' K/V stays above the length and is overwritten by the next step), append to the
 history, draft again.  So the whole step still replays as one graph with no host round trip.
 
-Greedy only: a verified token is the argmax of the logits its row computed.  The rows of a step see the same keys a plain step would,
-but the attention's key split depends on the segment's length, so a logit may differ from the plain step's in the last bit."""
+Greedy: a verified token is the argmax of the logits its row computed.  Sampled (sampling=): a request's noise is keyed by its own
+(seed, stream, draw), so row j of a sample draws with the key of the token it would emit, its pick is the plain per-row session's pick
+after the same prefix, and a draft is accepted exactly when it equals that pick - no rejection-sampling arithmetic.  Either way the
+rows of a step see the same keys a plain step would, but the attention's key split depends on the segment's length, so a logit may
+differ from the plain step's in the last bit."""
 import os
 
 import torch
@@ -47,16 +50,42 @@ def _neutral(name, v):
 
 class SpeculativeDecodeSession(DecodeSession):
     def __init__(self, llm, cache, start_tokens, positions, max_length, draft_len, use_graph=True, nsplit=None, *, draft_ngram=(2, 4),
-                 draft_context_ids=None, predicted_ids=None, **plain):
+                 draft_context_ids=None, predicted_ids=None, sampling=None, sampling_streams=None, **plain):
         """max_length: tokens to emit per sample at the most (out_ids [B, max_length] int64, n_out [B] int32: how many of a row are
         valid).  limit ([B] int32, device, starts at max_length): a sample stops emitting at out_ids[b][limit[b]] - the host may
         rewrite it between replays.  stats ([B, 3] int32): steps, drafts verified, drafts accepted.  draft_ngram = (min, max): the
         suffix lengths the prompt lookup tries, longest first.  draft_context_ids: per sample the tokens that precede the start token
         (the prompt; negative entries are separators nothing matches) - the history the lookup searches, which the emitted tokens
         extend.  predicted_ids: per sample a predicted continuation (what out_ids is expected to hold); a sample that has one drafts
-        from it instead of the lookup.  Any sampler, log-probability, forced-token, penalty or per-row keyword raises ValueError."""
+        from it instead of the lookup.
+        sampling (one sampling.SamplingParams, or a list of B): sampled speculative decode - every request verifies its drafts against
+        its own seeded draw (include/unimedvl_hip.h, speculative decode with sampling), so out_ids is what
+        DecodeSession(row_sampling=sampling, row_streams=sampling_streams, seed=seed) emits, token for token (up to the last bit of a
+        logit: the attention's key split depends on the segment length).  The table has B * (draft_len + 1) entries; the step ends with
+        umv_decode_pick_rows and umv_decode_step_end_speculative_rows.  sampling_streams: the `stream` word of every sample's key
+        (default: the sample index, DecodeSession's default); seed: the seed of the params that carry none.  Greedy entries
+        (SamplingParams()) are legal and may be mixed with sampled ones.  logprobs=True (with sampling): out_logprobs (fp32
+        [B, max_length]) holds every emitted token's log-probability next to out_ids.  Penalised params, logit_bias, forced_ids and
+        top_logprobs raise ValueError.
+        Without sampling, any sampler, log-probability, forced-token, penalty or per-row keyword raises ValueError."""
         k = int(draft_len)
         B = len(cache.lens)
+        params, logprobs, seed = None, False, 0
+        if sampling is not None:
+            from .sampling import SamplingParams
+            params = [sampling] * B if isinstance(sampling, SamplingParams) else list(sampling)
+            if len(params) != B or any(not isinstance(p, SamplingParams) for p in params):
+                raise ValueError(f"sampling must be one SamplingParams or a list of one per sample ({B})")
+            if any(p.penalised for p in params):
+                raise ValueError("sampled speculative decode takes no penalties (a penalised SamplingParams)")
+            logprobs, seed = bool(plain.pop("logprobs", False)), int(plain.get("seed", 0))
+            on = [name for name, v in plain.items() if name not in _IGNORED and not _neutral(name, v)]
+            if on:
+                raise ValueError(f"sampled speculative decode takes its samplers from sampling=: no scalar sampler keywords, forced_ids, "
+                                 f"penalties / logit_bias, top_logprobs or row_sampling (got {on})")
+        elif sampling_streams is not None:
+            raise ValueError("sampling_streams goes with sampling")
+        mode = "speculative decode is greedy only and" if params is None else "sampled speculative decode"
         on = [name for name, v in plain.items() if name not in _IGNORED and not _neutral(name, v)]
         if on:
             raise ValueError(f"speculative decode is greedy only: no sampling, logprobs / forced_ids, penalties / logit_bias or "
@@ -64,16 +93,16 @@ class SpeculativeDecodeSession(DecodeSession):
         if k < 1:
             raise ValueError(f"speculative decode needs draft_len >= 1 (got {draft_len})")
         if B * (k + 1) > 64:
-            raise ValueError(f"speculative decode is greedy only and rides on the fused step end: B * (draft_len + 1) = {B} x {k + 1} "
-                             "rows exceed its 64")
+            raise ValueError(f"{mode} rides on the fused step end: B * (draft_len + 1) = {B} x {k + 1} rows exceed its 64")
         if os.environ.get("UMV_DECODE_FUSED_ARGMAX", "1") in ("0", ""):
-            raise ValueError("speculative decode is greedy only and rides on the fused step end: UMV_DECODE_FUSED_ARGMAX=0 excludes it")
+            raise ValueError(f"{mode} rides on the fused step end: UMV_DECODE_FUSED_ARGMAX=0 excludes it")
         lo, hi = (int(v) for v in draft_ngram)
         if not 1 <= lo <= hi:
             raise ValueError(f"draft_ngram = (min, max) with 1 <= min <= max, got {draft_ngram!r}")
         self.draft_len, self.draft_ngram = k, (lo, hi)
         with ops.device_scope(llm.device):
-            self._init(llm, cache, start_tokens, positions, max_length, False, nsplit, False, 1.0, 0)
+            self._init(llm, cache, start_tokens, positions, max_length, False, nsplit, False, 1.0, seed, logprobs,
+                       rows=dict(params=params, streams=sampling_streams))
             self._init_drafts(_token_lists(draft_context_ids, B, "draft_context_ids"), predicted_ids)
             if use_graph:
                 self._capture()
@@ -87,6 +116,7 @@ class SpeculativeDecodeSession(DecodeSession):
         self.limit = torch.full((B,), self.max_length, **i32)
         self.n_draft = torch.zeros((B,), **i32)
         self.stats = torch.zeros((B, 3), **i32)
+        self.out_logprobs = torch.zeros((B, room), dtype=torch.float32, device=dev) if self.logprobs else None
         # the history: the context, the start token, then what is emitted
         start = self.ids[::k + 1].tolist()
         rows = [c + [t] for c, t in zip(context, start)]
@@ -108,9 +138,19 @@ class SpeculativeDecodeSession(DecodeSession):
         self._step_end(draft_only=True)          # the first step's drafts
 
     def _step_end(self, draft_only=False):
-        ops.decode_step_end_speculative(self.tok_slot, self.tok_pos, self.kv_len, self.amax_part, self.ids, self.out_ids, self.n_out,
-                                        self.limit, self.n_draft, self.hist, self.hist_len, self.stats, self.draft_len, self.cfg.vocab,
-                                        ngram=self.draft_ngram, predicted=self.predicted, pred_len=self.pred_len, draft_only=draft_only)
+        spec = (self.ids, self.out_ids, self.n_out, self.limit, self.n_draft, self.hist, self.hist_len, self.stats, self.draft_len,
+                self.cfg.vocab)
+        kw = dict(ngram=self.draft_ngram, predicted=self.predicted, pred_len=self.pred_len, draft_only=draft_only)
+        if self.row_table is None:
+            ops.decode_step_end_speculative(self.tok_slot, self.tok_pos, self.kv_len, self.amax_part, *spec, **kw)
+            return
+        # sampled: every row's own pick (T workgroups sweep their rows in parallel), then the commit per sample - which also moves the
+        # rows' draw counters to the sample's new token count and logs the emitted tokens' log-probabilities
+        if not draft_only:
+            ops.decode_pick_rows(self.amax_part, self.logits, self.row_table, self.row_picks, lse_partial=self.lse_part,
+                                 logprob=self.row_logprob, cut_y=self.row_cut_y, n_kept=self.row_n_kept)
+        ops.decode_step_end_speculative_rows(self.tok_slot, self.tok_pos, self.kv_len, self.row_picks, self.row_table, *spec, **kw,
+                                             row_logprob=self.row_logprob, out_logprobs=self.out_logprobs)
 
     def _state(self):
         return super()._state() + (self.out_ids, self.n_out, self.n_draft, self.hist, self.hist_len, self.stats)
