@@ -589,6 +589,65 @@ int umv_decode_top_logprobs(const uint16_t* logits, int64_t ldo, int V, const fl
 int umv_top_logprobs_bf16(const uint16_t* logits, int64_t ld, const int64_t* ids, int M, int V, float temperature, int n,
                           int32_t* top_ids, float* top_logprobs, int32_t* rank, umv_stream_t stream);
 
+/* ------------------------------------------------------------------ token automata: constrained decoding
+ * Which tokens a row may be fed next, as a function of what it was fed so far: a deterministic automaton over token ids in CSR form,
+ * read-only device memory.  State s owns the edges row_ptr[s] .. row_ptr[s + 1] - 1; edge e carries the token edge_token[e] and the
+ * state edge_next[e] the row is in after that token.  Within a state the tokens are strictly ascending (sorted, distinct).  Each row
+ * carries one int32 state word in device memory (state [M]).  A word that is negative or >= n_states marks a FREE row: unconstrained.
+ * UMV_CONSTRAINT_FREE as an edge_next releases the row; UMV_CONSTRAINT_LEFT is what the word becomes when the row is fed a token its
+ * state has no edge for (a forced token, say) - unconstrained from then on, and told apart from a released row.
+ *
+ * umv_logit_constrain_bf16: between the lm_head GEMM and whatever picks, after umv_logit_penalty_bf16 when that runs; grid (chunk of
+ * UMV_CONSTRAIN_CHUNK columns, row).  For row b with s = state[b]:
+ *   free     s < 0 or s >= n_states: no byte of the row's logits, keys or statistics is written.
+ *   masked   otherwise let A be the tokens of s's edges that lie in [0, V) (an edge token >= V is ignored).  Every column outside A
+ *            becomes bf16 -inf (0xFF80) - a NaN outside A too -, every column in A keeps its bits, NaN included.  The masked row
+ *            REPLACES the logits in memory, as the penalties' l' does, and everything downstream is defined on it in the words used
+ *            above: the greedy pick, y = bf16(l / T) and its Gumbel key, the truncation classes, the token log-probabilities - now
+ *            those of the softmax renormalised over A -, the top-n alternatives.
+ *   tiles    with argmax_partial (and lse_partial when given) EVERY tile of a masked row holds the bits the lm_head epilogue of
+ *            umv_gemm_bf16 leaves for the masked logits: greedy keys when temperature = 0, the sampling keys of (temperature, seed,
+ *            *step) otherwise - with rows, of rows[b]'s temperature and (seed, draw, stream); the statistics in epi_lse_tile's
+ *            order.  A tile without an allowed column holds the key of -inf at its lowest column and (-inf, 0).  argmax_partial =
+ *            NULL: the logits only (the unfused step).
+ *   empty A  legal: the row of -inf only, which behaves as such a row does everywhere above.
+ * The kernel only reads state.  UMV_ERR_ARG: what umv_logit_penalty_bf16 rejects of the fields the two share (temperature < 0 or
+ * not finite, lse_partial without argmax_partial, n_tiles that is not ceil(V / 16) with argmax_partial, rows with a scalar
+ * temperature other than 0, a misaligned table), a NULL state, row_ptr or - with n_edges > 0 - edge array, n_states <= 0,
+ * n_edges < 0.  The automaton's CONTENTS are the caller's: nothing is validated on the device; what the kernels guarantee for a
+ * malformed table is only that they read nothing outside its n_edges edges and write nothing outside the row.
+ *
+ * umv_constraint_advance: after the step end (and after umv_decode_top_logprobs), one thread per row and a binary search.  ids [M]:
+ * the token the step end left to be fed next, picked or forced.  A row whose word is negative or >= n_states keeps it; otherwise
+ * state[b] becomes the edge_next of state[b]'s edge for ids[b], or UMV_CONSTRAINT_LEFT when there is none.  state[b] is the only word
+ * written, and this entry the only writer: a constrained step is lm_head, [penalty], constrain, step end, [top-logprobs], advance -
+ * one graph, no host round trip, no word shared between workgroups. */
+#define UMV_CONSTRAINT_FREE (-1)
+#define UMV_CONSTRAINT_LEFT (-2)
+#define UMV_CONSTRAIN_CHUNK 4096
+typedef struct {
+    const int32_t* row_ptr;     /* [n_states + 1], ascending, row_ptr[0] = 0 */
+    const int32_t* edge_token;  /* [n_edges]; within a state strictly ascending */
+    const int32_t* edge_next;   /* [n_edges]; a state, or UMV_CONSTRAINT_FREE */
+    int n_states, n_edges;
+} umv_token_automaton;
+typedef struct {
+    uint16_t* logits;          /* [M][V] bf16, row stride ld elements; masked in place */
+    int64_t ld;
+    int M, V;
+    umv_token_automaton automaton;
+    const int32_t* state;      /* [M] */
+    float temperature;         /* as given to the lm_head GEMM: 0 = greedy keys and y = l */
+    uint64_t* argmax_partial;  /* optional [M][n_tiles] */
+    float* lse_partial;        /* optional [M][n_tiles][2], only with argmax_partial */
+    int n_tiles;
+    uint64_t seed;             /* sample_seed / sample_step of the lm_head call (temperature > 0) */
+    const int64_t* step;
+    const umv_row_sampling* rows; /* optional [M]: row b's temperature and (seed, draw, stream); the scalar temperature must be 0 */
+} umv_logit_constrain_args;
+int umv_logit_constrain_bf16(const umv_logit_constrain_args* a, umv_stream_t stream);
+int umv_constraint_advance(const umv_token_automaton* automaton, int32_t* state, const int64_t* ids, int M, umv_stream_t stream);
+
 /* ------------------------------------------------------------------ speculative greedy decode: verify drafts, commit, roll back, draft again
  * A step of k = draft_len >= 1 processes T = B * (k + 1) <= 64 rows.  Row r0 = b * (k + 1) holds sample b's next input token t0, which is
  * not in the cache yet; rows r0 + j, j = 1..k, hold its drafts d_j: the first n_draft[b] are real, the rest are FILLERS equal to t0 -

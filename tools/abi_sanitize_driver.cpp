@@ -266,6 +266,42 @@ static void bad_arguments() {
     EXPECT_ERR(umv_logit_penalty_bf16(&lp, nullptr));
     lp.rows = nullptr; lp.M = 0;
     EXPECT_OK(umv_logit_penalty_bf16(&lp, nullptr));             // no rows
+    // token automata: the mask and the state advance
+    EXPECT_ERR(umv_logit_constrain_bf16(nullptr, nullptr));
+    umv_logit_constrain_args lc;
+    std::memset(&lc, 0, sizeof lc);
+    EXPECT_ERR(umv_logit_constrain_bf16(&lc, nullptr));
+    lc.logits = dummy16; lc.ld = 64; lc.M = 1; lc.V = 64; lc.state = dummyi;
+    EXPECT_ERR(umv_logit_constrain_bf16(&lc, nullptr));          // no automaton
+    lc.automaton.row_ptr = dummyi; lc.automaton.edge_token = dummyi; lc.automaton.edge_next = dummyi;
+    lc.automaton.n_states = 0; lc.automaton.n_edges = 2;         // no state
+    EXPECT_ERR(umv_logit_constrain_bf16(&lc, nullptr));
+    lc.automaton.n_states = 1; lc.automaton.n_edges = -1;        // a negative edge count
+    EXPECT_ERR(umv_logit_constrain_bf16(&lc, nullptr));
+    lc.automaton.n_edges = 2; lc.automaton.edge_next = nullptr;  // edges without their next states
+    EXPECT_ERR(umv_logit_constrain_bf16(&lc, nullptr));
+    lc.automaton.edge_next = dummyi; lc.state = nullptr;         // no state words
+    EXPECT_ERR(umv_logit_constrain_bf16(&lc, nullptr));
+    lc.state = dummyi; lc.temperature = -1.f;                    // negative temperature
+    EXPECT_ERR(umv_logit_constrain_bf16(&lc, nullptr));
+    lc.temperature = 0.f; lc.lse_partial = dummyf;               // lse_partial without argmax_partial
+    EXPECT_ERR(umv_logit_constrain_bf16(&lc, nullptr));
+    lc.lse_partial = nullptr; lc.argmax_partial = (uint64_t*)dummyl; lc.n_tiles = 3;     // 64 columns are not 3 tiles
+    EXPECT_ERR(umv_logit_constrain_bf16(&lc, nullptr));
+    lc.n_tiles = 4; lc.ld = 32;                                  // a row stride below V
+    EXPECT_ERR(umv_logit_constrain_bf16(&lc, nullptr));
+    lc.ld = 64; lc.rows = rows; lc.temperature = 0.7f;           // a scalar temperature next to the per-row table
+    EXPECT_ERR(umv_logit_constrain_bf16(&lc, nullptr));
+    lc.rows = nullptr; lc.temperature = 0.f; lc.M = 0;
+    EXPECT_OK(umv_logit_constrain_bf16(&lc, nullptr));           // no rows
+    EXPECT_ERR(umv_constraint_advance(nullptr, dummyi, dummyl, 1, nullptr));
+    EXPECT_ERR(umv_constraint_advance(&lc.automaton, nullptr, dummyl, 1, nullptr));
+    EXPECT_ERR(umv_constraint_advance(&lc.automaton, dummyi, nullptr, 1, nullptr));
+    EXPECT_ERR(umv_constraint_advance(&lc.automaton, dummyi, dummyl, -1, nullptr));
+    lc.automaton.row_ptr = nullptr;
+    EXPECT_ERR(umv_constraint_advance(&lc.automaton, dummyi, dummyl, 1, nullptr));
+    lc.automaton.row_ptr = dummyi;
+    EXPECT_OK(umv_constraint_advance(&lc.automaton, dummyi, dummyl, 0, nullptr));         // no rows
     // speculative step end
     EXPECT_ERR(umv_decode_step_end_speculative(nullptr, nullptr));
     umv_spec_step_args sp;

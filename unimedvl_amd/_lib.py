@@ -76,6 +76,21 @@ class LogitPenaltyArgs(C.Structure):
     ]
 
 
+class TokenAutomatonArgs(C.Structure):
+    """umv_token_automaton: a token automaton in CSR form, device pointers (constraints.TokenAutomaton.to_device)"""
+    _fields_ = [
+        ("row_ptr", C.c_void_p), ("edge_token", C.c_void_p), ("edge_next", C.c_void_p), ("n_states", C.c_int), ("n_edges", C.c_int),
+    ]
+
+
+class LogitConstrainArgs(C.Structure):
+    _fields_ = [
+        ("logits", C.c_void_p), ("ld", C.c_int64), ("M", C.c_int), ("V", C.c_int), ("automaton", TokenAutomatonArgs),
+        ("state", C.c_void_p), ("temperature", C.c_float), ("argmax_partial", C.c_void_p), ("lse_partial", C.c_void_p),
+        ("n_tiles", C.c_int), ("seed", C.c_uint64), ("step", C.c_void_p), ("rows", C.c_void_p),
+    ]
+
+
 class RowSampling(C.Structure):
     """umv_row_sampling: one row of the per-row sampling table (device memory; sampling.ROW_DTYPE is the same layout for numpy)"""
     _fields_ = [
@@ -107,6 +122,9 @@ class SpecRowsStepArgs(C.Structure):
 PENALTY_COUNT_MASK, PENALTY_CONTEXT, PENALTY_LISTED = 0x3FFFFFFF, 0x40000000, 0x80000000
 # umv_decode_top_logprobs: the most alternatives a row can ask for, and the step end whose merge order the statistics take
 TOP_LOGPROBS_MAX, TOP_AFTER_LOGPROB, TOP_AFTER_TRUNCATED = 20, 0, 1
+# token automata: the state words of a released row and of a row that was fed a token outside its state's edges; the columns one
+# workgroup of umv_logit_constrain_bf16 masks (UMV_CONSTRAIN_CHUNK)
+CONSTRAINT_FREE, CONSTRAINT_LEFT, CONSTRAIN_CHUNK = -1, -2, 4096
 
 
 _SIGS = {
@@ -181,6 +199,8 @@ _SIGS = {
     "umv_top_logprobs_bf16": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
     "umv_logit_penalty_bf16": (C.c_int, [C.POINTER(LogitPenaltyArgs), C.c_void_p]),
+    "umv_logit_constrain_bf16": (C.c_int, [C.POINTER(LogitConstrainArgs), C.c_void_p]),
+    "umv_constraint_advance": (C.c_int, [C.POINTER(TokenAutomatonArgs), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "umv_decode_step_end_speculative": (C.c_int, [C.POINTER(SpecStepArgs), C.c_void_p]),
     "umv_decode_pick_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

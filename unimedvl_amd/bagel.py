@@ -318,7 +318,8 @@ class Bagel(BagelPrep):
                       return_logits: bool = False, per_sample_eos: bool = False, return_logprobs: bool = False, *,
                       repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
                       logit_bias=None, penalty_context_ids=None, draft_len: int = 0, draft_ngram=(2, 4), draft_context_ids=None,
-                      predicted_ids=None, sampling=None, top_logprobs: int = 0, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+                      predicted_ids=None, sampling=None, top_logprobs: int = 0, constraint=None, constraint_states=None,
+                      top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """Greedy decode (bagel.py:1236-1317).  Returns [steps, B] int64 whose row 0 holds the
         start tokens.  Like the reference, the batch stops when SAMPLE 0 emits end_token_id
         (bagel.py:1313); per_sample_eos=True is the batched extension (stops when every sample
@@ -349,7 +350,14 @@ class Bagel(BagelPrep):
         temperature other than 1.0 raise ValueError.  With draft_len > 0 it is sampled speculative decode
         (SpeculativeDecodeSession(sampling=...)): the drafts are verified against each request's own draw, so the matrix is the
         draft_len = 0 matrix (up to the last bit of a logit); return_logprobs is allowed there ([rows, B], aligned as in the plain
-        call), while return_logits, top_logprobs, penalised params and logit_bias raise."""
+        call), while return_logits, top_logprobs, penalised params and logit_bias raise.
+        constraint (a constraints.TokenAutomaton) / constraint_states (one start state per sample, default 0, -1 = free): constrained
+        decoding in the captured step (DecodeSession) - a sample is only ever fed tokens its automaton state has an edge for; ids,
+        logits, logprobs and top_logprobs are those of the masked logits.  With draft_len > 0 it raises."""
+        if constraint is None and constraint_states is not None:
+            raise ValueError("constraint_states goes with constraint")
+        if constraint is not None and draft_len:
+            raise ValueError("constraint is not available with draft_len > 0 (speculative decode)")
         if sampling is not None:
             given = dict(do_sample=do_sample is not False, temperature=temperature != 1.0, top_k=top_k != 0, top_p=top_p != 1.0,
                          min_p=min_p != 0.0, repetition_penalty=repetition_penalty != 1.0, presence_penalty=presence_penalty != 0.0,
@@ -406,7 +414,8 @@ class Bagel(BagelPrep):
             sampler = dict(row_sampling=sampling)
         sess = DecodeSession(self.language_model, past_key_values, packed_start_tokens, packed_query_position_ids,
                              max_length, use_graph=self.decode_use_graph and not return_logits, seed=seed, logprobs=return_logprobs,
-                             logit_bias=logit_bias, penalty_context_ids=penalty_context_ids, top_logprobs=top_logprobs, **sampler)
+                             logit_bias=logit_bias, penalty_context_ids=penalty_context_ids, top_logprobs=top_logprobs,
+                             constraint=constraint, constraint_states=constraint_states, **sampler)
         logits = []
         steps = 0
         stop = None
@@ -481,7 +490,8 @@ class Bagel(BagelPrep):
              do_sample: bool = False, temperature: float = 1.0, return_logprobs: bool = False, *,
              repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None,
              penalize_prompt: bool = False, draft_len: int = 0, draft_ngram=(2, 4), predicted_ids=None,
-             sampling=None, top_logprobs: int = 0, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+             sampling=None, top_logprobs: int = 0, choices=None, choices_after: str = "stop",
+             top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """ViT-only VQA convenience path (bagel.py:1321-1392).  return_logprobs=True: returns (answer, token_ids, token_logprobs) -
         the generated tokens behind the answer (the end token excluded) and the log-probability of each (generate_text).
         top_logprobs=n (implies return_logprobs): a fourth element, a TopLogprobs named tuple of per-token lists - ids and logprobs
@@ -493,7 +503,16 @@ class Bagel(BagelPrep):
         repeats the prompt's wording or its own; the prompt's text tokens are the lookup's context.  predicted_ids: a predicted answer
         (a string, or its token ids) to draft from instead.
         sampling (a sampling.SamplingParams): the request's own sampler and seed instead of the scalar sampler keywords
-        (generate_text) - with draft_len > 0 sampled speculative decode, the same answer as with draft_len = 0."""
+        (generate_text) - with draft_len > 0 sampled speculative decode, the same answer as with draft_len = 0.
+        choices (strings, tokenised as `score` tokenises its candidates, or lists of token ids): guided choice - the answer is one of
+        them (constraints.TokenAutomaton.from_choices; generate_text(constraint=)), picked by the sampler the other keywords set, the
+        end token after it.  choices_after="free": the answer STARTS with one of them and goes on as free text.  `score` ranks a closed
+        set exactly at one forced row per candidate; choices costs one row, samples, and returns the sampler's pick."""
+        constraint = None
+        if choices is not None:
+            from .constraints import TokenAutomaton
+            constraint = TokenAutomaton.from_choices([tokenizer.encode(c) if isinstance(c, str) else [int(v) for v in c] for c in choices],
+                                                     int(new_token_ids["eos_token_id"]), after=choices_after)
         if self.chat_cache_tokens > 0:       # serving: one reserved cache reused by every request (stable slabs -> graph prefill)
             if self._chat_cache is None or self._chat_cache.cap < self.chat_cache_tokens:
                 self._chat_cache = NaiveCache(self.cfg.layers)
@@ -522,7 +541,7 @@ class Bagel(BagelPrep):
                                  return_logprobs=return_logprobs, top_k=top_k, top_p=top_p, min_p=min_p, top_logprobs=top_logprobs,
                                  repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                                  frequency_penalty=frequency_penalty, logit_bias=logit_bias, penalty_context_ids=prompt_ids,
-                                 sampling=sampling, **draft, **gi)
+                                 sampling=sampling, constraint=constraint, **draft, **gi)
         top = None
         if top_logprobs:
             ids, lp, top = ids

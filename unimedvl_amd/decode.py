@@ -42,7 +42,7 @@ class DecodeSession:
                  do_sample=False, temperature=1.0, seed=0, logprobs=False, forced_ids=None, *,
                  repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, penalty_context_ids=None,
                  penalty_context_room=None, penalty_history=None, row_sampling=None, row_streams=None, row_penalties=False,
-                 top_logprobs=0, top_k=0, top_p=1.0, min_p=0.0):
+                 top_logprobs=0, constraint=None, constraint_states=None, top_k=0, top_p=1.0, min_p=0.0):
         """logprobs: also record pred_logprobs (fp32 [max_length, B]) - row s is the log-probability of in_ids[s + 1], the token step s
         picked (include/unimedvl_hip.h, token log-probabilities: of softmax(logits) in greedy decoding, of softmax(bf16(logits / T))
         when sampling).  forced_ids (int64 [max_length, B]): where an entry is >= 0 that token is fed to the next step instead of the
@@ -77,7 +77,20 @@ class DecodeSession:
         both [max_length, B, n], and pred_rank (int32 [max_length, B]); row s belongs to in_ids[s + 1] like pred_logprobs.  One
         umv_decode_top_logprobs launch behind the step end, in the same graph; implies logprobs.  The alternatives are those of the
         untruncated softmax of the stored (adjusted) logits, whatever sampler, filters, penalties or forced tokens the step runs with.
-        Off: nothing is allocated, nothing is launched."""
+        Off: nothing is allocated, nothing is launched.
+        constraint (a constraints.TokenAutomaton): constrained decoding (include/unimedvl_hip.h, token automata) - every sample carries
+        a state word on the device; one umv_logit_constrain_bf16 launch behind the lm_head call (and the penalty kernel) masks the
+        stored logits of a sample to the tokens its state has an edge for, and one umv_constraint_advance launch at the very end of the
+        step moves the word along the token that will be fed next - the pick, or the forced token.  Picks, pred_logprobs (those of the
+        softmax renormalised over the allowed set), truncation, top_logprobs and `logits` are all those of the masked logits.
+        constraint_states: one start state per sample (default: state 0 for all), -1 leaves a sample free - its step is today's, bit
+        for bit.  The session owns the device tables and the words: set_slot(constraint_state=) rewrites one, rewind_outputs keeps
+        them.  Works on the fused and the unfused step and with every keyword above; not with draft_len > 0 (ValueError).  None:
+        today's step, launch for launch, no buffer allocated."""
+        if constraint is None and constraint_states is not None:
+            raise ValueError("constraint_states goes with constraint")
+        if constraint is not None and self.draft_len:
+            raise ValueError("constraint is not available with draft_len > 0 (speculative decode)")
         if row_sampling is not None:
             given = dict(do_sample=do_sample is not False, temperature=temperature != 1.0, top_k=top_k != 0, top_p=top_p != 1.0,
                          min_p=min_p != 0.0, repetition_penalty=repetition_penalty != 1.0, presence_penalty=presence_penalty != 0.0,
@@ -94,14 +107,15 @@ class DecodeSession:
                        forced_ids, top_k, top_p, min_p,
                        dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
                             logit_bias=logit_bias, context=penalty_context_ids, room=penalty_context_room, history=penalty_history),
-                       dict(params=row_sampling, streams=row_streams, reserve=bool(row_penalties)), top_logprobs)
+                       dict(params=row_sampling, streams=row_streams, reserve=bool(row_penalties)), top_logprobs,
+                       None if constraint is None else dict(automaton=constraint, states=constraint_states))
 
     @property
     def device(self):
         return self.dev
 
     def _init(self, llm, cache, start_tokens, positions, max_length, use_graph, nsplit, do_sample, temperature, seed, logprobs=False,
-              forced_ids=None, top_k=0, top_p=1.0, min_p=0.0, penalties=None, rows=None, top_logprobs=0):
+              forced_ids=None, top_k=0, top_p=1.0, min_p=0.0, penalties=None, rows=None, top_logprobs=0, constraint=None):
         cfg, dev = llm.cfg, llm.device
         self.llm, self.cache, self.cfg, self.dev = llm, cache, cfg, dev
         B = len(cache.lens)
@@ -297,6 +311,7 @@ class DecodeSession:
         # (force: a per-row table holds the penalty values - the scalar ones stay neutral - or reserves the buffers for later rows)
         force = self.row_table is not None and (rows.get("reserve") or any(p.penalised for p in self.row_params))
         self._init_penalties(dict(penalties or {}, force=True) if force else (penalties or {}))
+        self._init_constraint(constraint)
         self.steps_done = 0
         self.graph = None
         if use_graph:
@@ -332,6 +347,41 @@ class DecodeSession:
         self.pen_bias = torch.zeros((B, self.pen_static), dtype=torch.float32, device=dev) if self.pen_static else None
         for b in range(B):
             self._reset_penalty_slot(b, context[b])
+
+    # ---- constrained decoding (include/unimedvl_hip.h, token automata): the automaton's tables and one state word per sample
+    def _init_constraint(self, kw):
+        self.constraint = self.con_dev = self.con_state = None
+        if kw is None:
+            return
+        from .constraints import TokenAutomaton
+        automaton, states = kw["automaton"], kw.get("states")
+        if not isinstance(automaton, TokenAutomaton):
+            raise ValueError(f"constraint must be a constraints.TokenAutomaton, got {type(automaton).__name__}")
+        states = [0] * self.B if states is None else [self._constraint_state(automaton, s) for s in states]
+        if len(states) != self.B:
+            raise ValueError(f"constraint_states must hold one start state per sample ({self.B}), got {len(states)}")
+        self.constraint = automaton
+        self.con_dev = automaton.to_device(self.dev)
+        self.con_state = torch.tensor(states, dtype=torch.int32).to(self.dev)
+
+    @staticmethod
+    def _constraint_state(automaton, s):
+        if isinstance(s, bool) or int(s) != s or not -1 <= int(s) < automaton.n_states:
+            raise ValueError(f"a constraint state must be an integer in [-1, {automaton.n_states}) (-1 = unconstrained), got {s!r}")
+        return int(s)
+
+    @ops.on_device
+    def copy_constraint_states(self, other, slots=None):
+        """Take over another session's state words for `slots` (default: all) - a re-captured step goes on with those requests.  The
+        sessions were built with the same automaton."""
+        if self.con_state is None:
+            return
+        if other.con_state is None or other.constraint is not self.constraint:
+            raise ValueError("copy_constraint_states: the sessions do not share an automaton")
+        rows = list(range(self.B)) if slots is None else [int(b) for b in slots]
+        if rows:
+            at = torch.tensor(rows, dtype=torch.int64, device=self.dev)
+            self.con_state[at] = other.con_state[at]
 
     def _penalty_context(self, tokens):
         """distinct tokens of a context list, in order of first appearance"""
@@ -444,12 +494,20 @@ class DecodeSession:
                               temperature=self.temperature if self.do_sample else 0.0, seed=self.seed, step=self.step_idx,
                               argmax_partial=self.lm_head_kw.get("argmax_partial"), lse_partial=self.lm_head_kw.get("lse_partial"),
                               sample_rows=self.row_table)
+        if self.con_state is not None:
+            # mask the (adjusted) logits of every constrained sample to its state's tokens and rewrite its tiles' keys and statistics,
+            # again with what the lm_head call got: the step end picks from, and normalises over, the allowed set
+            ops.logit_constrain(self.logits, self.con_dev, self.con_state, temperature=self.temperature if self.do_sample else 0.0,
+                                seed=self.seed, step=self.step_idx, argmax_partial=self.lm_head_kw.get("argmax_partial"),
+                                lse_partial=self.lm_head_kw.get("lse_partial"), sample_rows=self.row_table)
         self._step_end()
         if self.top_logprobs:
             # the n best columns of the (adjusted) logits and the rank of the token just fed, with the statistics merged as the step end did
             ops.decode_top_logprobs(self.logits, self.lse_part, self.ids, self.step_idx, self.pred_top_ids, self.pred_top_logprobs,
                                     self.pred_rank, temperature=self.temperature if self.do_sample else 0.0, sample_rows=self.row_table,
                                     truncated=self.step_end == "truncated", forced_ids=self.forced_ids)
+        if self.con_state is not None:
+            ops.constraint_advance(self.con_dev, self.con_state, self.ids)     # along the token the next step is fed: picked or forced
 
     def _step_end(self):
         """the launch that closes the step: the pick (where the lm_head epilogue left keys) and the bookkeeping"""
@@ -489,6 +547,8 @@ class DecodeSession:
             state += (self.pen_count, self.pen_list, self.pen_len)
         if self.row_table is not None:              # ... and advances the rows' draw counters
             state += (self.row_table,)
+        if self.con_state is not None:              # ... and the constraint states
+            state += (self.con_state,)
         return state
 
     def _capture(self):
@@ -524,12 +584,18 @@ class DecodeSession:
     # ---- continuous batching support (serving.py): the captured step reads these from device memory, so a slot can be
     # re-pointed at a new request between replays without re-capturing
     @ops.on_device
-    def set_slot(self, b, token, kv_len, pos, penalty_context_ids=None, sampling=None, stream=None, draw=0):
+    def set_slot(self, b, token, kv_len, pos, penalty_context_ids=None, sampling=None, stream=None, draw=0, constraint_state=None):
         """Sample b continues from `token` with `kv_len` tokens already in its cache segment and rope position `pos`.  With penalties
         on, the slot's history starts over: no generated tokens, penalty_context_ids as its context set, `token` as its start token.
         sampling (a SamplingParams; sessions with row_sampling): row b of the table is rewritten - the slot decodes with these
         parameters from the next replay on, its key words (seed, stream - default: the slot's current one -, draw); without it the
-        row, its draw counter included, stays as it is."""
+        row, its draw counter included, stays as it is.
+        constraint_state (sessions with constraint): the slot's state word becomes this state of the automaton (-1 = unconstrained)
+        from the next replay on; without it the word stays as it is."""
+        if constraint_state is not None:
+            if self.con_state is None:
+                raise ValueError("set_slot(constraint_state=...) needs a session built with constraint")
+            self.con_state[b:b + 1].fill_(self._constraint_state(self.constraint, constraint_state))
         if sampling is not None:
             self._set_row(b, sampling, stream, draw)
         if self.pen is not None:
@@ -553,7 +619,7 @@ class DecodeSession:
     def rewind_outputs(self):
         """Start writing in_ids / pred_ids (and pred_logprobs) at row 0 again (the caller has harvested the previous rows).  The
         penalty history is NOT touched: a request lives across rounds - and neither are the rows' draw counters (row_sampling): a
-        request's noise does not repeat from round to round."""
+        request's noise does not repeat from round to round - nor the constraint states: a request is where it is in its automaton."""
         self.step_idx.zero_()
         self.in_ids[0].copy_(self.ids)      # the tokens the next step is fed (set_slot may have changed them)
         self.steps_done = 0

@@ -52,6 +52,11 @@ DEFAULT_CONFIG = {
     # request's own sampler and seed (Bagel.chat(sampling=...)).  It REPLACES "do_sample" / "temperature" / "top_k" / "top_p" / "min_p"
     # and the three penalty keys, which are then not passed on; with "draft_len" > 0 it is sampled speculative decode
     "sampling": None,
+    # guided choice (not a reference key; None = free text): a list of answers (strings or token-id lists) - the answer is one of them,
+    # picked by the sampler the keys above set (Bagel.chat(choices=...)); "choices_after": "free" makes them answer PREFIXES.  `score`
+    # ranks the same closed set exactly, at one forced row per candidate; this costs one row and returns the sampler's pick
+    "choices": None,
+    "choices_after": "stop",
 }
 
 # codes/data/default.yaml vlm_sft.image_transform_args (read by eval/vlm/utils.py:486-502)
@@ -162,7 +167,7 @@ class VQAInferencer:
 
     def infer_single(self, image_path, prompt, temperature=None, max_new_tokens=None, do_sample=None, show_image=False, *,
                      repetition_penalty=None, presence_penalty=None, frequency_penalty=None, logit_bias=None, penalize_prompt=None,
-                     draft_len=None, draft_ngram=None, predicted_ids=None, top_k=None, top_p=None, min_p=None):
+                     draft_len=None, draft_ngram=None, predicted_ids=None, choices=None, top_k=None, top_p=None, min_p=None):
         if not self.loaded:
             raise RuntimeError("Model not loaded, please call load_model() first")
         temperature_arg, do_sample_arg, top_k_arg, top_p_arg, min_p_arg = temperature, do_sample, top_k, top_p, min_p
@@ -196,6 +201,9 @@ class VQAInferencer:
         if draft_len:       # predicted_ids: a predicted answer (a string or token ids) to draft from instead of the lookup
             extra.update(draft_len=draft_len, draft_ngram=draft_ngram if draft_ngram is not None else self.config.get("draft_ngram", (2, 4)),
                          predicted_ids=predicted_ids)
+        choices = choices if choices is not None else self.config.get("choices")
+        if choices is not None:     # the answer is one of these (this call's list, else the config's); not with drafts (Bagel.generate_text)
+            extra.update(choices=choices, choices_after=self.config.get("choices_after", "stop"))
         sampler = dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, **penalties)
         sampling = self.config.get("sampling")
         if sampling is not None:    # the config's scalar sampler keys step aside; one given to this call explicitly is passed on (and refused)

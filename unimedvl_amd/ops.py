@@ -8,7 +8,7 @@ import torch
 
 from . import _lib
 from ._lib import (EPI_BIAS, EPI_GELU_TANH, EPI_OUT_F32, EPI_RESIDUAL, EPI_SILU, EPI_SWIGLU, AttnArgs, GemmArgs,
-                   LogitPenaltyArgs, QkvPostArgs, check)
+                   LogitConstrainArgs, LogitPenaltyArgs, QkvPostArgs, TokenAutomatonArgs, check)
 
 BF16 = torch.bfloat16
 
@@ -555,6 +555,73 @@ def logit_penalty(logits, ids, count, vlist, list_len, n_static, bias=None, repe
         a.rows = _row_table(sample_rows, M, "logit_penalty")
     check(lib.umv_logit_penalty_bf16(C.byref(a), _stream()), "umv_logit_penalty_bf16")
     return logits
+
+
+CONSTRAIN_CHUNK = _lib.CONSTRAIN_CHUNK      # columns one workgroup of umv_logit_constrain_bf16 masks (UMV_CONSTRAIN_CHUNK)
+
+
+def _automaton_args(automaton, who):
+    """umv_token_automaton of a constraints.DeviceAutomaton on the current tensors' device"""
+    for t, name, n in ((automaton.row_ptr, "row_ptr", automaton.n_states + 1), (automaton.edge_token, "edge_token", automaton.n_edges),
+                       (automaton.edge_next, "edge_next", automaton.n_edges)):
+        _req(t, torch.int32, f"automaton.{name}")
+        if not (t.is_contiguous() and t.dim() == 1 and t.numel() == n):
+            raise _lib.UmvError(f"{who}: automaton.{name} must be a contiguous int32 [{n}] tensor")
+    t = TokenAutomatonArgs()
+    t.row_ptr, t.edge_token, t.edge_next = automaton.row_ptr.data_ptr(), automaton.edge_token.data_ptr() or None, \
+        automaton.edge_next.data_ptr() or None
+    t.n_states, t.n_edges = int(automaton.n_states), int(automaton.n_edges)
+    return t
+
+
+def logit_constrain(logits, automaton, state, temperature=0.0, seed=0, step=None, argmax_partial=None, lse_partial=None, sample_rows=None):
+    """umv_logit_constrain_bf16 on bf16 logits [M, V], in place: row b in state state[b] (int32 [M]) of `automaton` (a
+    constraints.DeviceAutomaton) keeps the bits of the columns its state has an edge for, every other column becomes -inf; a row whose
+    word is negative or >= n_states is not touched.  With argmax_partial ([M, n_tiles] int64, lse_partial [M, n_tiles, 2] fp32) every
+    tile of a masked row is recomputed as the lm_head call with sample=(temperature, seed, step) leaves it for the masked logits
+    (temperature 0: greedy); sample_rows (the per-row table, int64 [M, 6]): with every row's own temperature and key, the scalar
+    temperature left at 0.  Runs after logit_penalty when that runs, before whatever picks."""
+    lib = _lib.load()
+    _req(logits, BF16, "logits")
+    _req(state, torch.int32, "state")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise _lib.UmvError("logit_constrain: logits [M, V] with unit column stride")
+    M, V = logits.shape
+    if not (state.is_contiguous() and state.numel() == M):
+        raise _lib.UmvError("logit_constrain: state must be a contiguous int32 [M] tensor")
+    a = LogitConstrainArgs()
+    a.logits, a.ld, a.M, a.V = logits.data_ptr(), logits.stride(0), M, V
+    a.automaton = _automaton_args(automaton, "logit_constrain")
+    a.state = state.data_ptr()
+    a.temperature, a.seed, a.step = float(temperature), int(seed) & (2 ** 64 - 1), None if step is None else step.data_ptr()
+    if argmax_partial is not None:
+        _req(argmax_partial, torch.int64, "argmax_partial")
+        if not (argmax_partial.is_contiguous() and argmax_partial.dim() == 2 and argmax_partial.shape[0] == M):
+            raise _lib.UmvError("logit_constrain: argmax_partial must be a contiguous [M, n_tiles] tensor")
+        a.argmax_partial, a.n_tiles = argmax_partial.data_ptr(), argmax_partial.shape[1]
+    if lse_partial is not None:
+        _req(lse_partial, torch.float32, "lse_partial")
+        if argmax_partial is not None and not (lse_partial.is_contiguous() and tuple(lse_partial.shape) == tuple(argmax_partial.shape) + (2,)):
+            raise _lib.UmvError("logit_constrain: lse_partial must be a contiguous [M, n_tiles, 2] tensor")
+        a.lse_partial = lse_partial.data_ptr()
+    if sample_rows is not None:
+        a.rows = _row_table(sample_rows, M, "logit_constrain")
+    check(lib.umv_logit_constrain_bf16(C.byref(a), _stream()), "umv_logit_constrain_bf16")
+    return logits
+
+
+def constraint_advance(automaton, state, ids):
+    """umv_constraint_advance: state (int32 [M]) moves along the edge of ids (int64 [M], the tokens the step end left to be fed next) -
+    to that edge's next state, to CONSTRAINT_LEFT where the row's state has no such edge; a free row keeps its word."""
+    lib = _lib.load()
+    _req(state, torch.int32, "state")
+    _req(ids, torch.int64, "ids")
+    M = state.numel()
+    if not (state.is_contiguous() and ids.is_contiguous() and ids.numel() == M):
+        raise _lib.UmvError("constraint_advance: state int32 [M] and ids int64 [M], both contiguous")
+    t = _automaton_args(automaton, "constraint_advance")
+    check(lib.umv_constraint_advance(C.byref(t), _p(state), _p(ids), M, _stream()), "umv_constraint_advance")
+    return state
 
 
 def cast_pad(x, Kp):

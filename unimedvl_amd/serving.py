@@ -44,6 +44,7 @@ class _Request:
     ranks: List[int] = field(default_factory=list)      # ... and the token's own rank
     prompt_ids: Optional[List[int]] = None      # penalize_prompt: the prompt's tokens, the repetition penalty's context set
     sampling: Optional[SamplingParams] = None   # per_request_sampling: the request's own parameters (None = the batcher's)
+    constraint: Optional[str] = None            # the name of the automaton (ContinuousBatcher(constraints=)) the request decodes under
 
 
 class ContinuousBatcher:
@@ -52,8 +53,8 @@ class ContinuousBatcher:
                  use_graph: bool = True, growable: bool = True, context_limit: Optional[int] = None, paged: bool = False,
                  pool_pages: Optional[int] = None, logprobs: bool = False, *, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, penalize_prompt: bool = False,
-                 per_request_sampling: bool = False, seed: Optional[int] = None, top_logprobs: int = 0, top_k: int = 0,
-                 top_p: float = 1.0, min_p: float = 0.0):
+                 per_request_sampling: bool = False, seed: Optional[int] = None, top_logprobs: int = 0, constraints=None,
+                 top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """max_context: the context (prompt + images) the slots are RESERVED for; with growable=True longer requests enlarge
         the cache (up to context_limit tokens of context when given), with growable=False they are refused.
         paged=True: block-table KV (kvcache.PagedCache) instead of slabs - the slots draw 256-token pages from ONE pool of `pool_pages`
@@ -78,7 +79,17 @@ class ContinuousBatcher:
         is SamplingParams.seed or, without one, derived on the host from `seed` (None: one draw from the model's generator at the
         first run()) and the request id - so a request's tokens and log-probabilities depend on neither its slot, its neighbours,
         the admission order nor check_every, and no noise repeats from round to round.  Needs slots <= 64.  False: nothing changes -
-        one sampler for all, keyed by slot and round-local step."""
+        one sampler for all, keyed by slot and round-local step.
+        constraints ({name: constraints.TokenAutomaton}): constrained decoding (DecodeSession(constraint=)) - submit(..., constraint=name)
+        decodes that request under the named automaton from its state 0; a request without one is free and decodes as it does in a
+        batcher without constraints.  The automata are merged ONCE, here (TokenAutomaton.union), so the device tables have a captured
+        size and never move; admission writes the request's start state into its slot's state word, and a re-captured session takes
+        the live slots' words over as it takes the penalty histories over.  An automaton per request, compiled at submit, is not
+        offered: the tables would have to grow under a captured step."""
+        self.constraint, self.constraint_start = None, {}
+        if constraints:
+            from .constraints import TokenAutomaton
+            self.constraint, self.constraint_start = TokenAutomaton.union(dict(constraints))
         self.top_k, self.top_p, self.min_p = ops.check_truncation(top_k, top_p, min_p)
         if (self.top_k > 0 or self.top_p < 1.0 or self.min_p > 0.0) and not do_sample:
             raise ValueError("top_k / top_p / min_p truncate the sampler: they need do_sample=True")
@@ -128,9 +139,13 @@ class ContinuousBatcher:
         self.stats = {"decode_steps": 0, "prefills": 0, "tokens": 0, "cache_grows": 0}
 
     # ------------------------------------------------------------------ API
-    def submit(self, images, prompt: str, max_new_tokens: Optional[int] = None, sampling: Optional[SamplingParams] = None) -> int:
+    def submit(self, images, prompt: str, max_new_tokens: Optional[int] = None, sampling: Optional[SamplingParams] = None,
+               constraint: Optional[str] = None) -> int:
         """images: one image / a list of images (PIL or [3,H,W] tensors, as the transform accepts) or None.
-        sampling (per_request_sampling=True only): the request's own SamplingParams; None = the batcher's defaults."""
+        sampling (per_request_sampling=True only): the request's own SamplingParams; None = the batcher's defaults.
+        constraint: the name of one of the batcher's automata (ContinuousBatcher(constraints=)); None = free text."""
+        if constraint is not None and constraint not in self.constraint_start:
+            raise ValueError(f"submit(constraint={constraint!r}): the batcher holds {sorted(self.constraint_start) or 'no automata'}")
         if sampling is not None:
             if not self.per_request:
                 raise ValueError("submit(sampling=...) needs ContinuousBatcher(per_request_sampling=True)")
@@ -143,7 +158,7 @@ class ContinuousBatcher:
             raise ValueError(f"max_new_tokens {budget} exceeds the batcher's reserve of {self.default_new}")
         rid = self._next_id
         self._next_id += 1
-        self.queue.append(_Request(rid, imgs, prompt, budget, sampling=sampling))
+        self.queue.append(_Request(rid, imgs, prompt, budget, sampling=sampling, constraint=constraint))
         return rid
 
     @torch.no_grad()
@@ -177,6 +192,12 @@ class ContinuousBatcher:
         def context_of(b):
             return active[b].prompt_ids if active[b] is not None else None
 
+        def guided(b):            # set_slot's keyword for slot b: its request's start state, -1 for a free request or an idle slot
+            if self.constraint is None:
+                return {}
+            req = active[b]
+            return dict(constraint_state=-1 if req is None or req.constraint is None else self.constraint_start[req.constraint])
+
         def room_short(slots):    # does a prompt of these slots hold more distinct tokens than the session reserves?  Then reserve more.
             need = max([len(set(context_of(b) or ())) for b in slots] + [0])
             if not self.penalize_prompt or need <= self._pen_room:
@@ -198,9 +219,12 @@ class ContinuousBatcher:
                                min_p=self.min_p, **self.penalties)
             sn = DecodeSession(m.language_model, cache, start, pos, self.check_every, use_graph=self.use_graph,
                                logprobs=self.want_logprobs, top_logprobs=self.n_top, penalty_context_ids=[context_of(b) for b in range(B)],
-                               penalty_context_room=self._pen_room, penalty_history=m.cfg.vocab, **sampler)
-            if prev is not None:                        # the requests go on: so do their penalty histories
+                               penalty_context_room=self._pen_room, penalty_history=m.cfg.vocab, constraint=self.constraint,
+                               constraint_states=[guided(b)["constraint_state"] for b in range(B)] if self.constraint is not None else None,
+                               **sampler)
+            if prev is not None:                        # the requests go on: so do their penalty histories and constraint states
                 sn.copy_penalty_history(prev, keep)
+                sn.copy_constraint_states(prev, keep)
             cache.lens = lens_now                       # the session only reads them; this loop owns the bookkeeping
             self._grew = False
             return sn
@@ -226,7 +250,7 @@ class ContinuousBatcher:
             for b in range(B):
                 req = active[b]
                 if req is None:
-                    sess.set_slot(b, bos, 0, 0)         # idle slot: keep it parked at the start of its segment
+                    sess.set_slot(b, bos, 0, 0, **guided(b))         # idle slot: keep it parked at the start of its segment
                     state[b] = (bos, 0, 0)
                     continue
                 col = ids[:, b].tolist()
@@ -256,7 +280,7 @@ class ContinuousBatcher:
                     active[b] = self.queue.popleft()
                     freed.append(b)
                 else:
-                    sess.set_slot(b, bos, 0, 0)
+                    sess.set_slot(b, bos, 0, 0, **guided(b))
                     state[b] = (bos, 0, 0)
             # every slot that was freed this round is refilled by ONE batched prefill (images of the new requests share the
             # ViT and LLM forward; the other slots take part with zero query tokens)
@@ -267,7 +291,7 @@ class ContinuousBatcher:
             else:
                 for b in freed:
                     row = dict(sampling=params_of(b), stream=0, draw=0) if self.per_request else {}
-                    sess.set_slot(b, *state[b], penalty_context_ids=context_of(b), **row)
+                    sess.set_slot(b, *state[b], penalty_context_ids=context_of(b), **row, **guided(b))
         return dict(self.results)
 
     # ------------------------------------------------------------------ hooks (MixedBatcher)

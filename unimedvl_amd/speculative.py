@@ -35,7 +35,8 @@ def _token_lists(value, B, what):
 # (temperature and seed mean nothing without do_sample and are ignored.)
 _NEUTRAL = dict(do_sample=False, logprobs=False, forced_ids=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
                 logit_bias=None, penalty_context_ids=None, penalty_context_room=None, penalty_history=None, row_sampling=None,
-                row_streams=None, row_penalties=False, top_k=0, top_p=1.0, min_p=0.0, top_logprobs=0)
+                row_streams=None, row_penalties=False, top_k=0, top_p=1.0, min_p=0.0, top_logprobs=0, constraint=None,
+                constraint_states=None)
 _IGNORED = ("temperature", "seed")
 
 
@@ -65,9 +66,9 @@ class SpeculativeDecodeSession(DecodeSession):
         umv_decode_pick_rows and umv_decode_step_end_speculative_rows.  sampling_streams: the `stream` word of every sample's key
         (default: the sample index, DecodeSession's default); seed: the seed of the params that carry none.  Greedy entries
         (SamplingParams()) are legal and may be mixed with sampled ones.  logprobs=True (with sampling): out_logprobs (fp32
-        [B, max_length]) holds every emitted token's log-probability next to out_ids.  Penalised params, logit_bias, forced_ids and
-        top_logprobs raise ValueError.
-        Without sampling, any sampler, log-probability, forced-token, penalty or per-row keyword raises ValueError."""
+        [B, max_length]) holds every emitted token's log-probability next to out_ids.  Penalised params, logit_bias, forced_ids,
+        top_logprobs and constraint raise ValueError.
+        Without sampling, any sampler, log-probability, forced-token, penalty, per-row or constraint keyword raises ValueError."""
         k = int(draft_len)
         B = len(cache.lens)
         params, logprobs, seed = None, False, 0
@@ -82,14 +83,14 @@ class SpeculativeDecodeSession(DecodeSession):
             on = [name for name, v in plain.items() if name not in _IGNORED and not _neutral(name, v)]
             if on:
                 raise ValueError(f"sampled speculative decode takes its samplers from sampling=: no scalar sampler keywords, forced_ids, "
-                                 f"penalties / logit_bias, top_logprobs or row_sampling (got {on})")
+                                 f"penalties / logit_bias, top_logprobs, constraint or row_sampling (got {on})")
         elif sampling_streams is not None:
             raise ValueError("sampling_streams goes with sampling")
         mode = "speculative decode is greedy only and" if params is None else "sampled speculative decode"
         on = [name for name, v in plain.items() if name not in _IGNORED and not _neutral(name, v)]
         if on:
-            raise ValueError(f"speculative decode is greedy only: no sampling, logprobs / forced_ids, penalties / logit_bias or "
-                             f"row_sampling (got {on})")
+            raise ValueError(f"speculative decode is greedy only: no sampling, logprobs / forced_ids, penalties / logit_bias, "
+                             f"constraint or row_sampling (got {on})")
         if k < 1:
             raise ValueError(f"speculative decode needs draft_len >= 1 (got {draft_len})")
         if B * (k + 1) > 64:
