@@ -11,7 +11,6 @@ or tmp<k> for the k-th tensor allocated inside the call), the row count becomes 
                                                         rewrites tests/golden/gemm_routing.json; refuses to record from this tree
     python tests/test_gemm_routing_cpu.py --host-cost   microseconds per ops.gemm call under the recorder (profiles/gemm_routing_refactor.txt)
 """
-import contextlib
 import ctypes as C
 import functools
 import json
@@ -20,6 +19,8 @@ import sys
 import timeit
 
 import torch
+
+from abi_recorder import _seams, render
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "gemm_routing.json")
@@ -31,45 +32,6 @@ VARIANTS = ("plain", "bias", "swiglu")
 FORMS = ("plain", "no_bias", "residual", "gelu_tanh", "silu", "out_f32", "row_idx", "norm_w", "argmax", "argmax_sample", "act8", "splitk")
 IMAGES = ("wp", "w8", "scale", "w8m", "w4", "wz", "bias")
 M_ARG = {"umv_quantize_act_fp8": 8}       # the position of the row count among the plain arguments of a recorded function
-
-
-class _Recorder:
-    def __init__(self, calls):
-        self._calls = calls
-
-    def __getattr__(self, name):
-        def fn(*args):
-            if self._calls is not None:
-                self._calls.append((name, args))
-            return 64 if name.endswith(("_bytes", "_elems")) else 0      # a size, so that every image has an address of its own
-        return fn
-
-
-def _req_dtype_only(t, dtype, name):
-    if t.dtype != dtype:
-        raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
-    return t
-
-
-@contextlib.contextmanager
-def _seams(calls, made=None):
-    """ops behind the three seams; `made` collects the tensors the call allocates (kept alive, so no address is used twice)"""
-    from unimedvl_amd import _lib, ops
-    saved = _lib.load, ops._stream, ops._req, torch.empty, torch.empty_like
-    rec = _Recorder(calls)
-
-    def keep(fn):
-        def wrapped(*a, **kw):
-            made.append(fn(*a, **kw))
-            return made[-1]
-        return wrapped
-    _lib.load, ops._stream, ops._req = (lambda: rec), (lambda: None), _req_dtype_only
-    if made is not None:
-        torch.empty, torch.empty_like = keep(saved[3]), keep(saved[4])
-    try:
-        yield ops
-    finally:
-        _lib.load, ops._stream, ops._req, torch.empty, torch.empty_like = saved
 
 
 def _linear(ops, kind, variant):
@@ -158,25 +120,12 @@ def _record(ops, calls, made, kind, variant, form, z13, M):
     def rows(v):
         return "M" if v == M else f"M+{v - M}"
 
-    items = []
-    for name, args in calls:
-        out = []
-        for i, v in enumerate(args):
-            if hasattr(v, "_obj"):          # byref(structure)
-                s, fields = v._obj, []
-                for f, ty in s._fields_:
-                    fv = getattr(s, f)
-                    if not fv:
-                        continue
-                    if f == "split_stride" and fv % M == 0:
-                        fv = f"M*{fv // M}"
-                    fields.append(f"{f}={ptr(fv) if ty is C.c_void_p else rows(fv) if f in ('M', 'x_rows') else fv}")
-                out.append("{" + " ".join(fields) + "}")
-            elif v is None or isinstance(v, C.c_void_p) or v in names:
-                out.append(ptr(v))
-            else:
-                out.append(rows(v) if M_ARG.get(name) == i else str(v))
-        items.append(f"{name}({', '.join(out)})")
+    def field(f, fv):
+        if f == "split_stride" and fv % M == 0:
+            return f"M*{fv // M}"
+        return rows(fv) if f in ("M", "x_rows") else fv
+
+    items = render(calls, ptr, lambda v: v in names, field, lambda fn, i, v: rows(v) if M_ARG.get(fn) == i else str(v))
     return " ; ".join(items + raised)
 
 

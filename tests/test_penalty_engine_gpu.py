@@ -226,8 +226,8 @@ def test_batcher_reserves_room_for_the_longest_prompt_only(model, monkeypatch):
     rooms = []
     real = decode.DecodeSession._init_penalties
 
-    def spy(self, kw):
-        real(self, kw)
+    def spy(self, *args, **kw):
+        real(self, *args, **kw)
         rooms.append((self.pen_room, self.pen_static))
     monkeypatch.setattr(decode.DecodeSession, "_init_penalties", spy)
     srv = ContinuousBatcher(model, tok, NEW_TOKEN_IDS, ident, slots=2, max_context=256, max_new_tokens=14, check_every=4,

@@ -23,7 +23,7 @@ from . import ops
 from .config import UniMedVLConfig
 from .data_utils import (PackedVitImages, get_flattened_position_ids_extrapolate, get_flattened_position_ids_interpolate, patchify)
 from .decode import DecodeSession
-from .sampling import SamplingParams
+from .sampling import off_neutral, per_sample
 from .prep import BagelPrep
 from .kvcache import NaiveCache
 from .llm import Qwen2MoT
@@ -359,15 +359,10 @@ class Bagel(BagelPrep):
         if constraint is not None and draft_len:
             raise ValueError("constraint is not available with draft_len > 0 (speculative decode)")
         if sampling is not None:
-            given = dict(do_sample=do_sample is not False, temperature=temperature != 1.0, top_k=top_k != 0, top_p=top_p != 1.0,
-                         min_p=min_p != 0.0, repetition_penalty=repetition_penalty != 1.0, presence_penalty=presence_penalty != 0.0,
-                         frequency_penalty=frequency_penalty != 0.0)
-            if any(given.values()):
-                raise ValueError(f"sampling excludes the scalar sampler keywords (got {[k for k, v in given.items() if v]})")
-            B = len(past_key_values.lens)
-            sampling = [sampling] * B if isinstance(sampling, SamplingParams) else list(sampling)
-            if len(sampling) != B or any(not isinstance(p, SamplingParams) for p in sampling):
-                raise ValueError(f"sampling must be one SamplingParams or a list of one per sample ({B})")
+            scalar = off_neutral(locals())
+            if scalar:
+                raise ValueError(f"sampling excludes the scalar sampler keywords (got {scalar})")
+            sampling = per_sample(sampling, len(past_key_values.lens))
         top_k, top_p, min_p = ops.check_truncation(top_k, top_p, min_p)
         top_logprobs = ops.check_top_logprobs(top_logprobs, self.cfg.vocab)
         return_logprobs = bool(return_logprobs) or top_logprobs > 0

@@ -92,30 +92,32 @@ class DecodeSession:
         if constraint is not None and self.draft_len:
             raise ValueError("constraint is not available with draft_len > 0 (speculative decode)")
         if row_sampling is not None:
-            given = dict(do_sample=do_sample is not False, temperature=temperature != 1.0, top_k=top_k != 0, top_p=top_p != 1.0,
-                         min_p=min_p != 0.0, repetition_penalty=repetition_penalty != 1.0, presence_penalty=presence_penalty != 0.0,
-                         frequency_penalty=frequency_penalty != 0.0)
-            if any(given.values()):
-                raise ValueError(f"row_sampling excludes the scalar sampler keywords (got {[k for k, v in given.items() if v]})")
+            scalar = sampling_mod.off_neutral(locals())
+            if scalar:
+                raise ValueError(f"row_sampling excludes the scalar sampler keywords (got {scalar})")
         elif row_streams is not None or row_penalties:
             raise ValueError("row_streams / row_penalties go with row_sampling")
         top_logprobs = ops.check_top_logprobs(top_logprobs, llm.cfg.vocab)
         if top_logprobs and self.draft_len:
             raise ValueError("top_logprobs is not available with draft_len > 0 (speculative decode)")
         with ops.device_scope(llm.device):
-            self._init(llm, cache, start_tokens, positions, max_length, use_graph, nsplit, do_sample, temperature, seed, logprobs,
-                       forced_ids, top_k, top_p, min_p,
-                       dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
-                            logit_bias=logit_bias, context=penalty_context_ids, room=penalty_context_room, history=penalty_history),
-                       dict(params=row_sampling, streams=row_streams, reserve=bool(row_penalties)), top_logprobs,
-                       None if constraint is None else dict(automaton=constraint, states=constraint_states))
+            self._init(llm, cache, start_tokens, positions, max_length, use_graph=use_graph, nsplit=nsplit, do_sample=do_sample,
+                       temperature=temperature, seed=seed, logprobs=logprobs, forced_ids=forced_ids,
+                       repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+                       logit_bias=logit_bias, penalty_context_ids=penalty_context_ids, penalty_context_room=penalty_context_room,
+                       penalty_history=penalty_history, row_sampling=row_sampling, row_streams=row_streams, row_penalties=row_penalties,
+                       top_logprobs=top_logprobs, constraint=constraint, constraint_states=constraint_states, top_k=top_k, top_p=top_p,
+                       min_p=min_p)
 
     @property
     def device(self):
         return self.dev
 
-    def _init(self, llm, cache, start_tokens, positions, max_length, use_graph, nsplit, do_sample, temperature, seed, logprobs=False,
-              forced_ids=None, top_k=0, top_p=1.0, min_p=0.0, penalties=None, rows=None, top_logprobs=0, constraint=None):
+    def _init(self, llm, cache, start_tokens, positions, max_length, *, use_graph, nsplit=None, do_sample=False, temperature=1.0, seed=0,
+              logprobs=False, forced_ids=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None,
+              penalty_context_ids=None, penalty_context_room=None, penalty_history=None, row_sampling=None, row_streams=None,
+              row_penalties=False, top_logprobs=0, constraint=None, constraint_states=None, top_k=0, top_p=1.0, min_p=0.0):
+        """the constructor's keywords under the constructor's names, already checked against each other (__init__)"""
         cfg, dev = llm.cfg, llm.device
         self.llm, self.cache, self.cfg, self.dev = llm, cache, cfg, dev
         B = len(cache.lens)
@@ -226,22 +228,17 @@ class DecodeSession:
             if float(temperature) <= 0.0:
                 raise ValueError(f"truncated sampling needs temperature > 0 (got {temperature})")
             need_fused("top_k / top_p / min_p")
-            self.pred_cut_y = torch.zeros((max_length, B), dtype=torch.float32, device=dev)
-            self.pred_n_kept = torch.zeros((max_length, B), dtype=torch.int32, device=dev)
         # per-row sampling parameters: the table the lm_head epilogue, the penalty kernel and the step end read
         self.row_table = self.row_params = self.row_streams = None
-        rows = rows or {}
-        if rows.get("params") is not None:
+        if row_sampling is not None:
             need_fused("row_sampling")
-            params = list(rows["params"])
-            streams = list(range(B)) if rows.get("streams") is None else [int(v) for v in rows["streams"]]
+            params = list(row_sampling)
+            streams = list(range(B)) if row_streams is None else [int(v) for v in row_streams]
             if len(params) != B or len(streams) != B:
                 raise ValueError(f"row_sampling / row_streams must hold one entry per sample ({B}), got {len(params)} / {len(streams)}")
             self.row_params, self.row_streams = params, streams
             if k == 0:
                 self.row_table = sampling_mod.to_tensor(sampling_mod.pack(params, seed=int(seed), streams=streams), dev)
-                self.pred_cut_y = torch.zeros((max_length, B), dtype=torch.float32, device=dev)
-                self.pred_n_kept = torch.zeros((max_length, B), dtype=torch.int32, device=dev)
             else:
                 # with drafts the table has one entry per ROW: sample b's k + 1 rows repeat its parameters, seed and stream, and row j
                 # draws with the key of the sample's token n_out + j (include/unimedvl_hip.h, speculative decode with sampling); what
@@ -253,6 +250,10 @@ class DecodeSession:
                 self.row_logprob = torch.zeros((R,), dtype=torch.float32, device=dev) if self.logprobs else None
                 self.row_cut_y = torch.zeros((R,), dtype=torch.float32, device=dev)
                 self.row_n_kept = torch.zeros((R,), dtype=torch.int32, device=dev)
+        # each step's cutoff value and kept-column count: a truncated step records them, a step with a per-row table always does
+        if self.truncated or (self.row_table is not None and k == 0):
+            self.pred_cut_y = torch.zeros((max_length, B), dtype=torch.float32, device=dev)
+            self.pred_n_kept = torch.zeros((max_length, B), dtype=torch.int32, device=dev)
         w = llm.w
         # K splits of the QKV / o / down GEMMs: "q,o,d" (1 = that GEMM is not split), "0" = none, "auto" by batch / weights.
         # Measured on MI355X (bench.py --batch B, ms per step), no split -> 3,4,4:
@@ -305,13 +306,19 @@ class DecodeSession:
             self.lm_head_kw["sample"] = (self.temperature, self.seed, self.step_idx) if self.do_sample else None
             if self.row_table is not None:
                 self.lm_head_kw["sample_rows"] = self.row_table
+        # what every launch between the lm_head call and the step end is given, so that it rewrites the tiles as that call left them:
+        # the temperature as the lm_head call sampled (0 when greedy), its seed and step counter, its keys and statistics, its table
+        self.step_kw = dict(temperature=self.temperature if self.do_sample else 0.0, seed=self.seed, step=self.step_idx,
+                            argmax_partial=self.lm_head_kw.get("argmax_partial"), lse_partial=self.lm_head_kw.get("lse_partial"),
+                            sample_rows=self.row_table)
         # (a name, not a bound method: a session that refers to itself is freed by the cycle collector only - at any allocation, another
         # session's graph capture included, where releasing device memory aborts)
         self.step_end = "rows" if self.row_table is not None else "truncated" if self.truncated else "logprob" if self.logprobs else "argmax" if self.fused_argmax else "unfused"
         # (force: a per-row table holds the penalty values - the scalar ones stay neutral - or reserves the buffers for later rows)
-        force = self.row_table is not None and (rows.get("reserve") or any(p.penalised for p in self.row_params))
-        self._init_penalties(dict(penalties or {}, force=True) if force else (penalties or {}))
-        self._init_constraint(constraint)
+        force = self.row_table is not None and (bool(row_penalties) or any(p.penalised for p in self.row_params))
+        self._init_penalties(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, penalty_context_ids,
+                             penalty_context_room, penalty_history, force)
+        self._init_constraint(constraint, constraint_states)
         self.steps_done = 0
         self.graph = None
         if use_graph:
@@ -319,23 +326,23 @@ class DecodeSession:
 
     # ---- logit penalties (include/unimedvl_hip.h): per slot a count word per column, the list of columns to visit (static entries
     # first: the context and the biased columns, seeded here; then the generated ones, appended by the kernel) and its length
-    def _init_penalties(self, kw):
+    def _init_penalties(self, repetition_penalty, presence_penalty, frequency_penalty, logit_bias, penalty_context_ids,
+                        penalty_context_room, penalty_history, force):
         cfg, dev, B = self.cfg, self.dev, self.B
-        r, p, f, bias = ops.check_penalties(kw.get("repetition_penalty", 1.0), kw.get("presence_penalty", 0.0),
-                                            kw.get("frequency_penalty", 0.0), kw.get("logit_bias"), vocab=cfg.vocab)
+        r, p, f, bias = ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, vocab=cfg.vocab)
         bias = {t: v for t, v in bias.items() if v != 0.0}
         self.pen = None
         self.pen_count = self.pen_list = self.pen_len = self.pen_bias = None
-        context = kw.get("context")
-        if r == 1.0 and p == 0.0 and f == 0.0 and not bias and not kw.get("force"):
+        context = penalty_context_ids
+        if r == 1.0 and p == 0.0 and f == 0.0 and not bias and not force:
             return                                  # neutral (a context set alone changes nothing): today's step
         if context is None:
             context = [[] for _ in range(B)]
         if len(context) != B:
             raise ValueError(f"penalty_context_ids must hold one token list per sample ({B}), got {len(context)}")
         context = [self._penalty_context(c) for c in context]
-        room = max([len(c) for c in context] + [0]) if kw.get("room") is None else int(kw["room"])
-        history = self.max_length if kw.get("history") is None else int(kw["history"])
+        room = max([len(c) for c in context] + [0]) if penalty_context_room is None else int(penalty_context_room)
+        history = self.max_length if penalty_history is None else int(penalty_history)
         self.pen_bias_cols = bias
         self.pen_room = room
         self.pen_static = min(room, cfg.vocab) + len(bias)
@@ -349,12 +356,11 @@ class DecodeSession:
             self._reset_penalty_slot(b, context[b])
 
     # ---- constrained decoding (include/unimedvl_hip.h, token automata): the automaton's tables and one state word per sample
-    def _init_constraint(self, kw):
+    def _init_constraint(self, automaton, states):
         self.constraint = self.con_dev = self.con_state = None
-        if kw is None:
+        if automaton is None:
             return
         from .constraints import TokenAutomaton
-        automaton, states = kw["automaton"], kw.get("states")
         if not isinstance(automaton, TokenAutomaton):
             raise ValueError(f"constraint must be a constraints.TokenAutomaton, got {type(automaton).__name__}")
         states = [0] * self.B if states is None else [self._constraint_state(automaton, s) for s in states]
@@ -378,10 +384,14 @@ class DecodeSession:
             return
         if other.con_state is None or other.constraint is not self.constraint:
             raise ValueError("copy_constraint_states: the sessions do not share an automaton")
-        rows = list(range(self.B)) if slots is None else [int(b) for b in slots]
+        rows, at = self._slot_index(slots)
         if rows:
-            at = torch.tensor(rows, dtype=torch.int64, device=self.dev)
             self.con_state[at] = other.con_state[at]
+
+    def _slot_index(self, slots):
+        """`slots` (default: all) as a list and as an index tensor on the device"""
+        rows = list(range(self.B)) if slots is None else [int(b) for b in slots]
+        return rows, torch.tensor(rows, dtype=torch.int64, device=self.dev)
 
     def _penalty_context(self, tokens):
         """distinct tokens of a context list, in order of first appearance"""
@@ -416,9 +426,8 @@ class DecodeSession:
         if self.row_table is not None:              # the kept slots go on with their parameters, streams and draw counters
             if other.row_table is None:
                 raise ValueError("copy_penalty_history: the other session has no per-row sampling table")
-            keep = list(range(self.B)) if slots is None else [int(b) for b in slots]
+            keep, at = self._slot_index(slots)
             if keep:
-                at = torch.tensor(keep, dtype=torch.int64, device=self.dev)
                 self.row_table[at] = other.row_table[at]
                 for b in keep:
                     self.row_params[b], self.row_streams[b] = other.row_params[b], other.row_streams[b]
@@ -428,10 +437,9 @@ class DecodeSession:
         if other.pen is None or other.pen_count.shape != self.pen_count.shape or other.pen_bias_cols != self.pen_bias_cols or grow < 0 or \
                 other.pen_list.shape[1] + grow > self.pen_list.shape[1]:
             raise ValueError("copy_penalty_history: the sessions do not share a penalty layout")
-        rows = list(range(self.B)) if slots is None else [int(b) for b in slots]
+        rows, at = self._slot_index(slots)
         if not rows:
             return
-        at = torch.tensor(rows, dtype=torch.int64, device=self.dev)
         old, n_gen = other.pen_static, other.pen_list.shape[1] - other.pen_static
         self.pen_count[at] = other.pen_count[at]
         lst = torch.full((len(rows), self.pen_list.shape[1]), -1, dtype=torch.int32, device=self.dev)
@@ -490,21 +498,16 @@ class DecodeSession:
             # the (temperature, seed, step) the lm_head call got, so whichever step end follows reads the adjusted distribution
             r, p, f = self.pen
             ops.logit_penalty(self.logits, self.ids, self.pen_count, self.pen_list, self.pen_len, self.pen_static, bias=self.pen_bias,
-                              repetition_penalty=r, presence_penalty=p, frequency_penalty=f,
-                              temperature=self.temperature if self.do_sample else 0.0, seed=self.seed, step=self.step_idx,
-                              argmax_partial=self.lm_head_kw.get("argmax_partial"), lse_partial=self.lm_head_kw.get("lse_partial"),
-                              sample_rows=self.row_table)
+                              repetition_penalty=r, presence_penalty=p, frequency_penalty=f, **self.step_kw)
         if self.con_state is not None:
             # mask the (adjusted) logits of every constrained sample to its state's tokens and rewrite its tiles' keys and statistics,
             # again with what the lm_head call got: the step end picks from, and normalises over, the allowed set
-            ops.logit_constrain(self.logits, self.con_dev, self.con_state, temperature=self.temperature if self.do_sample else 0.0,
-                                seed=self.seed, step=self.step_idx, argmax_partial=self.lm_head_kw.get("argmax_partial"),
-                                lse_partial=self.lm_head_kw.get("lse_partial"), sample_rows=self.row_table)
+            ops.logit_constrain(self.logits, self.con_dev, self.con_state, **self.step_kw)
         self._step_end()
         if self.top_logprobs:
             # the n best columns of the (adjusted) logits and the rank of the token just fed, with the statistics merged as the step end did
             ops.decode_top_logprobs(self.logits, self.lse_part, self.ids, self.step_idx, self.pred_top_ids, self.pred_top_logprobs,
-                                    self.pred_rank, temperature=self.temperature if self.do_sample else 0.0, sample_rows=self.row_table,
+                                    self.pred_rank, temperature=self.step_kw["temperature"], sample_rows=self.step_kw["sample_rows"],
                                     truncated=self.step_end == "truncated", forced_ids=self.forced_ids)
         if self.con_state is not None:
             ops.constraint_advance(self.con_dev, self.con_state, self.ids)     # along the token the next step is fed: picked or forced

@@ -344,23 +344,11 @@ def gemm(x, lin, out=None, *, M=None, residual=None, act=None, row_idx=None, out
     route = _route(lin, M, False, norm_w is not None, argmax_partial is not None, act8, out_f32, act is not None, z13)
     if act8 and M <= 64:
         x = fake_quantize_act(x, M, row_idx)
-    amax = None
-    if argmax_partial is not None:
-        _req(argmax_partial, torch.int64, "argmax_partial")
-        if not (argmax_partial.is_contiguous() and tuple(argmax_partial.shape) == (M, (lin.N + 15) // 16)):
-            raise _lib.UmvError(f"argmax_partial must be a contiguous int64 [{M}, {(lin.N + 15) // 16}] tensor")
-        amax = argmax_partial.data_ptr()
-    lse = None
-    if lse_partial is not None:
-        _req(lse_partial, torch.float32, "lse_partial")
-        if not (lse_partial.is_contiguous() and tuple(lse_partial.shape) == (M, (lin.N + 15) // 16, 2)):
-            raise _lib.UmvError(f"lse_partial must be a contiguous fp32 [{M}, {(lin.N + 15) // 16}, 2] tensor")
-        lse = lse_partial.data_ptr()
-    rows = None
-    if sample_rows is not None:
-        if route[0] not in ("umv_gemm_bf16", "umv_gemm_z13w", "umv_gemm_fp8w"):
-            raise _lib.UmvError(f"gemm: sample_rows rides on the argmax_partial epilogue of the bf16 / 13-bit / e4m3 routes, not {route[0]}")
-        rows = _row_table(sample_rows, M, "gemm")
+    if sample_rows is not None and route[0] not in ("umv_gemm_bf16", "umv_gemm_z13w", "umv_gemm_fp8w"):
+        raise _lib.UmvError(f"gemm: sample_rows rides on the argmax_partial epilogue of the bf16 / 13-bit / e4m3 routes, not {route[0]}")
+    amax = lse = rows = None
+    if argmax_partial is not None or lse_partial is not None or sample_rows is not None:        # (a plain GEMM pays no call for them)
+        amax, lse, rows, _ = _tile_keys("gemm", M, argmax_partial, lse_partial, sample_rows, (lin.N + 15) // 16)
     if route[0] == "umv_gemm_fp8a8w":
         if lse is not None:
             raise _lib.UmvError("gemm: lse_partial rides on the argmax_partial epilogue of the M <= 64 kernels")
@@ -433,8 +421,8 @@ def sample(logits, temperature, seed, step=None, out=None):
     _req(logits, BF16, "logits")
     M, V = logits.shape
     out = torch.empty((M,), dtype=torch.int64, device=logits.device) if out is None else out
-    check(lib.umv_sample_bf16(_p(logits), logits.stride(0), _p(out), M, V, float(temperature), int(seed) & (2 ** 64 - 1),
-                              _p(step), _stream()), "umv_sample_bf16")
+    check(lib.umv_sample_bf16(_p(logits), logits.stride(0), _p(out), M, V, float(temperature), _seed64(seed), _p(step), _stream()),
+          "umv_sample_bf16")
     return out
 
 
@@ -444,6 +432,56 @@ def _row_table(rows, M, who):
     if not (rows.dim() == 2 and rows.shape[1] == 6 and rows.shape[0] >= M and rows.is_contiguous() and rows.data_ptr() % 16 == 0):
         raise _lib.UmvError(f"{who}: sample_rows must be a contiguous, 16-byte aligned int64 [{M}, 6] tensor (sampling.to_tensor)")
     return rows.data_ptr()
+
+
+def _seed64(seed):
+    """a seed as the 64-bit word the kernels key their noise with"""
+    return int(seed) & (2 ** 64 - 1)
+
+
+def _logits_shape(who, logits, M=None):
+    """logits [>= M, V] (M = None: every row) with unit column stride -> (M, V)"""
+    if logits.dim() != 2 or logits.stride(1) != 1 or (M is not None and logits.shape[0] < M):
+        raise _lib.UmvError(f"{who}: logits must be [{'M' if M is None else M}, V] with unit column stride")
+    return logits.shape[0] if M is None else M, logits.shape[1]
+
+
+def _row_outputs(who, n, **outs):
+    """the optional per-row outputs of a wrapper (name -> (tensor or None, dtype)): each a contiguous tensor of n entries"""
+    for name, (t, dt) in outs.items():
+        if t is not None:
+            _req(t, dt, name)
+            if not (t.is_contiguous() and t.numel() == n):
+                raise _lib.UmvError(f"{who}: {name} must be a contiguous {dt} tensor of {n} entries")
+
+
+def _tile_keys(who, M, argmax_partial=None, lse_partial=None, sample_rows=None, n_tiles=None):
+    """What the lm_head epilogue leaves per 16-column tile for M rows, and the table it sampled by, checked for the wrapper `who`:
+    argmax_partial int64 [M, n_tiles], lse_partial fp32 [M, n_tiles, 2], both contiguous and of one n_tiles - the caller's where it
+    knows it, else the tensors' own -, and sample_rows through _row_table.  Returns the three pointers (None for what was not given)
+    and n_tiles (0 without keys or statistics)."""
+    amax = lse = rows = None
+    if argmax_partial is not None:
+        _req(argmax_partial, torch.int64, "argmax_partial")
+        if not (argmax_partial.is_contiguous() and argmax_partial.dim() == 2 and argmax_partial.shape[0] == M
+                and n_tiles in (None, argmax_partial.shape[1])):
+            raise _lib.UmvError(f"{who}: argmax_partial must be a contiguous int64 [{M}, {'n_tiles' if n_tiles is None else n_tiles}] tensor")
+        amax, n_tiles = argmax_partial.data_ptr(), argmax_partial.shape[1]
+    if lse_partial is not None:
+        _req(lse_partial, torch.float32, "lse_partial")
+        if not (lse_partial.is_contiguous() and lse_partial.dim() == 3 and lse_partial.shape[0] == M and lse_partial.shape[2] == 2
+                and n_tiles in (None, lse_partial.shape[1])):
+            raise _lib.UmvError(f"{who}: lse_partial must be a contiguous fp32 [{M}, {'n_tiles' if n_tiles is None else n_tiles}, 2] tensor")
+        lse, n_tiles = lse_partial.data_ptr(), lse_partial.shape[1]
+    if sample_rows is not None:
+        rows = _row_table(sample_rows, M, who)
+    return amax, lse, rows, n_tiles or 0
+
+
+def _fill_tile_keys(a, who, M, temperature, seed, step, argmax_partial, lse_partial, sample_rows):
+    """the seven fields umv_logit_penalty_args and umv_logit_constrain_args share: how the lm_head call sampled, and the tiles to rewrite"""
+    a.temperature, a.seed, a.step = float(temperature), _seed64(seed), None if step is None else step.data_ptr()
+    a.argmax_partial, a.lse_partial, a.rows, a.n_tiles = _tile_keys(who, M, argmax_partial, lse_partial, sample_rows)
 
 
 def check_truncation(top_k, top_p, min_p):
@@ -463,19 +501,10 @@ def sample_truncated(logits, temperature, seed, step=None, top_k=0, top_p=1.0, m
     cut_y (fp32 [M]) / n_kept (int32 [M]), if given, receive the cutoff value and the number of kept columns."""
     lib = _lib.load()
     _req(logits, BF16, "logits")
-    if logits.dim() != 2 or logits.stride(1) != 1:
-        raise _lib.UmvError("sample_truncated: logits [M, V] with unit column stride")
-    M, V = logits.shape
+    M, V = _logits_shape("sample_truncated", logits)
     out = torch.empty((M,), dtype=torch.int64, device=logits.device) if out is None else out
-    _req(out, torch.int64, "out")
-    for t, dt, name in ((cut_y, torch.float32, "cut_y"), (n_kept, torch.int32, "n_kept")):
-        if t is not None:
-            _req(t, dt, name)
-            if not (t.is_contiguous() and t.numel() == M):
-                raise _lib.UmvError(f"sample_truncated: {name} must be a contiguous [M] tensor")
-    if not (out.is_contiguous() and out.numel() == M):
-        raise _lib.UmvError("sample_truncated: out must be a contiguous int64 [M] tensor")
-    check(lib.umv_sample_truncated_bf16(_p(logits), logits.stride(0), _p(out), M, V, float(temperature), int(seed) & (2 ** 64 - 1), _p(step),
+    _row_outputs("sample_truncated", M, out=(out, torch.int64), cut_y=(cut_y, torch.float32), n_kept=(n_kept, torch.int32))
+    check(lib.umv_sample_truncated_bf16(_p(logits), logits.stride(0), _p(out), M, V, float(temperature), _seed64(seed), _p(step),
                                         int(top_k), float(top_p), float(min_p), _p(cut_y), _p(n_kept), _stream()),
           "umv_sample_truncated_bf16")
     return out
@@ -524,9 +553,7 @@ def logit_penalty(logits, ids, count, vlist, list_len, n_static, bias=None, repe
     _req(ids, torch.int64, "ids")
     for t, name in ((count, "count"), (vlist, "list"), (list_len, "list_len")):
         _req(t, torch.int32, name)
-    if logits.dim() != 2 or logits.stride(1) != 1:
-        raise _lib.UmvError("logit_penalty: logits [M, V] with unit column stride")
-    M, V = logits.shape
+    M, V = _logits_shape("logit_penalty", logits)
     if not (ids.is_contiguous() and ids.numel() == M and list_len.is_contiguous() and list_len.numel() == M and count.is_contiguous()
             and tuple(count.shape) == (M, V) and vlist.is_contiguous() and vlist.dim() == 2 and vlist.shape[0] == M):
         raise _lib.UmvError("logit_penalty: ids [M], count [M, V], list [M, cap], list_len [M], all contiguous")
@@ -540,19 +567,7 @@ def logit_penalty(logits, ids, count, vlist, list_len, n_static, bias=None, repe
     a.bias = None if bias is None else bias.data_ptr()
     a.M, a.V, a.cap, a.n_static = M, V, vlist.shape[1], int(n_static)
     a.repetition_penalty, a.presence_penalty, a.frequency_penalty = float(repetition_penalty), float(presence_penalty), float(frequency_penalty)
-    a.temperature, a.seed, a.step = float(temperature), int(seed) & (2 ** 64 - 1), None if step is None else step.data_ptr()
-    if argmax_partial is not None:
-        _req(argmax_partial, torch.int64, "argmax_partial")
-        if not (argmax_partial.is_contiguous() and argmax_partial.dim() == 2 and argmax_partial.shape[0] == M):
-            raise _lib.UmvError("logit_penalty: argmax_partial must be a contiguous [M, n_tiles] tensor")
-        a.argmax_partial, a.n_tiles = argmax_partial.data_ptr(), argmax_partial.shape[1]
-    if lse_partial is not None:
-        _req(lse_partial, torch.float32, "lse_partial")
-        if argmax_partial is not None and not (lse_partial.is_contiguous() and tuple(lse_partial.shape) == tuple(argmax_partial.shape) + (2,)):
-            raise _lib.UmvError("logit_penalty: lse_partial must be a contiguous [M, n_tiles, 2] tensor")
-        a.lse_partial = lse_partial.data_ptr()
-    if sample_rows is not None:
-        a.rows = _row_table(sample_rows, M, "logit_penalty")
+    _fill_tile_keys(a, "logit_penalty", M, temperature, seed, step, argmax_partial, lse_partial, sample_rows)
     check(lib.umv_logit_penalty_bf16(C.byref(a), _stream()), "umv_logit_penalty_bf16")
     return logits
 
@@ -584,28 +599,14 @@ def logit_constrain(logits, automaton, state, temperature=0.0, seed=0, step=None
     lib = _lib.load()
     _req(logits, BF16, "logits")
     _req(state, torch.int32, "state")
-    if logits.dim() != 2 or logits.stride(1) != 1:
-        raise _lib.UmvError("logit_constrain: logits [M, V] with unit column stride")
-    M, V = logits.shape
+    M, V = _logits_shape("logit_constrain", logits)
     if not (state.is_contiguous() and state.numel() == M):
         raise _lib.UmvError("logit_constrain: state must be a contiguous int32 [M] tensor")
     a = LogitConstrainArgs()
     a.logits, a.ld, a.M, a.V = logits.data_ptr(), logits.stride(0), M, V
     a.automaton = _automaton_args(automaton, "logit_constrain")
     a.state = state.data_ptr()
-    a.temperature, a.seed, a.step = float(temperature), int(seed) & (2 ** 64 - 1), None if step is None else step.data_ptr()
-    if argmax_partial is not None:
-        _req(argmax_partial, torch.int64, "argmax_partial")
-        if not (argmax_partial.is_contiguous() and argmax_partial.dim() == 2 and argmax_partial.shape[0] == M):
-            raise _lib.UmvError("logit_constrain: argmax_partial must be a contiguous [M, n_tiles] tensor")
-        a.argmax_partial, a.n_tiles = argmax_partial.data_ptr(), argmax_partial.shape[1]
-    if lse_partial is not None:
-        _req(lse_partial, torch.float32, "lse_partial")
-        if argmax_partial is not None and not (lse_partial.is_contiguous() and tuple(lse_partial.shape) == tuple(argmax_partial.shape) + (2,)):
-            raise _lib.UmvError("logit_constrain: lse_partial must be a contiguous [M, n_tiles, 2] tensor")
-        a.lse_partial = lse_partial.data_ptr()
-    if sample_rows is not None:
-        a.rows = _row_table(sample_rows, M, "logit_constrain")
+    _fill_tile_keys(a, "logit_constrain", M, temperature, seed, step, argmax_partial, lse_partial, sample_rows)
     check(lib.umv_logit_constrain_bf16(C.byref(a), _stream()), "umv_logit_constrain_bf16")
     return logits
 
@@ -734,7 +735,7 @@ def _sample_fields(sample, amax):
     t, seed, step = sample
     if not float(t) > 0.0:
         raise _lib.UmvError(f"gemm: sampling temperature must be > 0 (got {t})")
-    return float(t), int(seed) & (2 ** 64 - 1), None if step is None else step.data_ptr()
+    return float(t), _seed64(seed), None if step is None else step.data_ptr()
 
 
 def gemm_splitk(x, lin, partials, k_splits, *, M=None, z13=None):
@@ -854,18 +855,14 @@ def _check_fused_step_end(who, argmax_partial, ids, in_ids, pred_ids, step_idx, 
     """What the decode_step_end_* wrappers below check alike, under the wrapper's name: int64 keys / ids / counters, one counter per sample,
     contiguous in_ids / pred_ids [max_len, B] and argmax_partial [B, n_tiles], lse_partial [B, n_tiles, 2] where there is one, the
     optional [max_len, B] tensors in `rows` (name -> (tensor or None, dtype)) and bf16 logits [B, V].  Returns B."""
-    for t, name in ((argmax_partial, "argmax_partial"), (ids, "ids"), (in_ids, "in_ids"), (pred_ids, "pred_ids"), (step_idx, "step_idx")):
+    for t, name in ((ids, "ids"), (in_ids, "in_ids"), (pred_ids, "pred_ids"), (step_idx, "step_idx")):
         _req(t, torch.int64, name)
     B = ids.numel()
     if step_idx.numel() < B:
         raise _lib.UmvError(f"{who}: step_idx holds {step_idx.numel()} counters for {B} samples")
-    if not (in_ids.is_contiguous() and pred_ids.is_contiguous() and in_ids.shape == pred_ids.shape and in_ids.shape[1] == B
-            and argmax_partial.is_contiguous() and argmax_partial.shape[0] == B):
-        raise _lib.UmvError(f"{who}: in_ids / pred_ids [max_len, B], argmax_partial [B, n_tiles], all contiguous")
-    if lse_partial is not None:
-        _req(lse_partial, torch.float32, "lse_partial")
-        if not (lse_partial.is_contiguous() and tuple(lse_partial.shape) == tuple(argmax_partial.shape) + (2,)):
-            raise _lib.UmvError(f"{who}: lse_partial must be a contiguous [B, n_tiles, 2] tensor")
+    if not (in_ids.is_contiguous() and pred_ids.is_contiguous() and in_ids.shape == pred_ids.shape and in_ids.shape[1] == B):
+        raise _lib.UmvError(f"{who}: in_ids / pred_ids must be contiguous [max_len, B]")
+    _tile_keys(who, B, _req(argmax_partial, torch.int64, "argmax_partial"), lse_partial)
     for name, (t, dt) in rows.items():
         if t is not None:
             _req(t, dt, name)
@@ -873,8 +870,7 @@ def _check_fused_step_end(who, argmax_partial, ids, in_ids, pred_ids, step_idx, 
                 raise _lib.UmvError(f"{who}: {name} must be a contiguous [max_len, B] tensor")
     if logits is not None:
         _req(logits, BF16, "logits")
-        if logits.dim() != 2 or logits.shape[0] < B or logits.stride(1) != 1:
-            raise _lib.UmvError(f"{who}: logits must be [B, V] with unit column stride")
+        _logits_shape(who, logits, B)
     return B
 
 
@@ -918,7 +914,7 @@ def decode_step_end_truncated(tok_slot, tok_pos, kv_len, argmax_partial, ids, in
     check(lib.umv_decode_step_end_truncated(_p(tok_slot), _p(tok_pos), _p(kv_len), _p(argmax_partial), _p(lse_partial), argmax_partial.shape[1],
                                             _p(ids), _p(in_ids), _p(pred_ids), _p(step_idx), _p(logits), logits.stride(0), logits.shape[1],
                                             float(temperature), _p(forced_ids), _p(logprobs), B, in_ids.shape[0],
-                                            int(seed) & (2 ** 64 - 1), int(top_k), float(top_p), float(min_p), _p(cut_y), _p(n_kept),
+                                            _seed64(seed), int(top_k), float(top_p), float(min_p), _p(cut_y), _p(n_kept),
                                             _stream()),
           "umv_decode_step_end_truncated")
 
@@ -994,27 +990,18 @@ def decode_pick_rows(argmax_partial, logits, sample_rows, picks, lse_partial=Non
     (sampling.to_tensor, [T, 6]) - decode_step_end_rows' pick, without its bookkeeping and without touching the table.  logprob (fp32
     [T], with lse_partial [T, n_tiles, 2]): the pick's own log-probability; cut_y (fp32 [T]) / n_kept (int32 [T]): the row's cutoff."""
     lib = _lib.load()
-    _req(argmax_partial, torch.int64, "argmax_partial")
     _req(logits, BF16, "logits")
     _req(picks, torch.int64, "picks")
     T = picks.numel()
     if (lse_partial is None) != (logprob is None):
         raise _lib.UmvError("decode_pick_rows: lse_partial and logprob go together")
-    if not (argmax_partial.dim() == 2 and argmax_partial.is_contiguous() and argmax_partial.shape[0] == T and picks.is_contiguous()
-            and logits.dim() == 2 and logits.shape[0] >= T and logits.stride(1) == 1):
-        raise _lib.UmvError("decode_pick_rows: argmax_partial [T, n_tiles] and picks [T] contiguous, logits [T, V] with unit column stride")
-    if lse_partial is not None:
-        _req(lse_partial, torch.float32, "lse_partial")
-        if not (lse_partial.is_contiguous() and tuple(lse_partial.shape) == tuple(argmax_partial.shape) + (2,)):
-            raise _lib.UmvError("decode_pick_rows: lse_partial must be a contiguous [T, n_tiles, 2] tensor")
-    for t, dt, name in ((logprob, torch.float32, "logprob"), (cut_y, torch.float32, "cut_y"), (n_kept, torch.int32, "n_kept")):
-        if t is not None:
-            _req(t, dt, name)
-            if not (t.is_contiguous() and t.numel() == T):
-                raise _lib.UmvError(f"decode_pick_rows: {name} must be a contiguous tensor of {T} entries")
-    rows = _row_table(sample_rows, T, "decode_pick_rows")
-    check(lib.umv_decode_pick_rows(_p(argmax_partial), _p(lse_partial), argmax_partial.shape[1], _p(logits), logits.stride(0), logits.shape[1],
-                                   rows, T, _p(picks), _p(logprob), _p(cut_y), _p(n_kept), _stream()), "umv_decode_pick_rows")
+    if not picks.is_contiguous():
+        raise _lib.UmvError("decode_pick_rows: picks must be a contiguous int64 [T] tensor")
+    _, V = _logits_shape("decode_pick_rows", logits, T)
+    _, _, rows, n_tiles = _tile_keys("decode_pick_rows", T, argmax_partial, lse_partial, sample_rows)
+    _row_outputs("decode_pick_rows", T, logprob=(logprob, torch.float32), cut_y=(cut_y, torch.float32), n_kept=(n_kept, torch.int32))
+    check(lib.umv_decode_pick_rows(_p(argmax_partial), _p(lse_partial), n_tiles, _p(logits), logits.stride(0), V, rows, T, _p(picks),
+                                   _p(logprob), _p(cut_y), _p(n_kept), _stream()), "umv_decode_pick_rows")
 
 
 def decode_step_end_speculative_rows(tok_slot, tok_pos, kv_len, picks, sample_rows, ids, out_ids, n_out, limit, n_draft, hist, hist_len, stats,
@@ -1050,16 +1037,9 @@ def token_logprob(logits, ids, temperature=0.0, out=None):
     bf16(logits / temperature), the value sampling orders.  For callers who hold logits - return_logits=True, a prefill's last rows."""
     lib = _lib.load()
     _req(logits, BF16, "logits")
-    _req(ids, torch.int64, "ids")
-    if logits.dim() != 2 or logits.stride(1) != 1 or ids.numel() != logits.shape[0] or not ids.is_contiguous():
-        raise _lib.UmvError("token_logprob: logits [M, V] with unit column stride, ids a contiguous int64 [M]")
-    M, V = logits.shape
-    if out is None:
-        out = torch.empty((M,), dtype=torch.float32, device=logits.device)
-    else:
-        _req(out, torch.float32, "out")
-        if not (out.is_contiguous() and out.numel() == M):
-            raise _lib.UmvError("token_logprob: out must be a contiguous fp32 [M] tensor")
+    M, V = _logits_shape("token_logprob", logits)
+    out = torch.empty((M,), dtype=torch.float32, device=logits.device) if out is None else out
+    _row_outputs("token_logprob", M, ids=(ids, torch.int64), out=(out, torch.float32))
     check(lib.umv_token_logprob_bf16(_p(logits), logits.stride(0), _p(ids), _p(out), M, V, float(temperature), _stream()),
           "umv_token_logprob_bf16")
     return out
@@ -1089,7 +1069,6 @@ def decode_top_logprobs(logits, lse_partial, ids, step_idx, top_ids, top_logprob
     statistics were merged in; with sample_rows the row's own is taken)."""
     lib = _lib.load()
     _req(logits, BF16, "logits")
-    _req(lse_partial, torch.float32, "lse_partial")
     _req(ids, torch.int64, "ids")
     _req(step_idx, torch.int64, "step_idx")
     _req(top_ids, torch.int32, "top_ids")
@@ -1099,22 +1078,18 @@ def decode_top_logprobs(logits, lse_partial, ids, step_idx, top_ids, top_logprob
     if top_ids.dim() != 3:
         raise _lib.UmvError("decode_top_logprobs: top_ids must be [max_len, B, n]")
     max_len, _, n = top_ids.shape
-    if logits.dim() != 2 or logits.shape[0] < B or logits.stride(1) != 1:
-        raise _lib.UmvError("decode_top_logprobs: logits must be [B, V] with unit column stride")
-    V = logits.shape[1]
+    _, V = _logits_shape("decode_top_logprobs", logits, B)
     n = _top_n("decode_top_logprobs", n, V)
     if not (top_ids.is_contiguous() and top_logprobs.is_contiguous() and rank.is_contiguous() and tuple(top_ids.shape) == (max_len, B, n)
             and top_logprobs.shape == top_ids.shape and tuple(rank.shape) == (max_len, B) and ids.is_contiguous() and step_idx.numel() >= B):
         raise _lib.UmvError("decode_top_logprobs: top_ids / top_logprobs [max_len, B, n], rank [max_len, B], ids [B], step_idx [B], all contiguous")
-    if not (lse_partial.is_contiguous() and lse_partial.dim() == 3 and lse_partial.shape[0] == B and lse_partial.shape[2] == 2):
-        raise _lib.UmvError("decode_top_logprobs: lse_partial must be a contiguous [B, n_tiles, 2] tensor")
+    _, _, rows, n_tiles = _tile_keys("decode_top_logprobs", B, None, _req(lse_partial, torch.float32, "lse_partial"), sample_rows)
     if forced_ids is not None:
         _req(forced_ids, torch.int64, "forced_ids")
         if not (forced_ids.is_contiguous() and tuple(forced_ids.shape) == (max_len, B)):
             raise _lib.UmvError("decode_top_logprobs: forced_ids must be a contiguous [max_len, B] tensor")
-    rows = None if sample_rows is None else _row_table(sample_rows, B, "decode_top_logprobs")
     order = _lib.TOP_AFTER_TRUNCATED if truncated else _lib.TOP_AFTER_LOGPROB
-    check(lib.umv_decode_top_logprobs(_p(logits), logits.stride(0), V, _p(lse_partial), lse_partial.shape[1], float(temperature), rows, order,
+    check(lib.umv_decode_top_logprobs(_p(logits), logits.stride(0), V, _p(lse_partial), n_tiles, float(temperature), rows, order,
                                       _p(ids), _p(step_idx), _p(forced_ids), B, max_len, n, _p(top_ids), _p(top_logprobs), _p(rank),
                                       _stream()),
           "umv_decode_top_logprobs")
@@ -1124,9 +1099,9 @@ def top_logprobs(logits, ids, n, temperature=0.0):
     """The n best columns of every row of bf16 logits [M, V] (any row stride) by (y descending, column ascending), y as token_logprob's:
     (top_ids int32 [M, n], top_logprobs fp32 [M, n], rank int32 [M]) - rank the 1-based place of ids[m] in that order, 0 for an id outside
     the vocabulary.  Where ids[m] is among the n, its entry is token_logprob's value bit for bit."""
-    if logits.dim() != 2 or logits.stride(1) != 1 or ids.numel() != logits.shape[0] or not ids.is_contiguous():
-        raise _lib.UmvError("top_logprobs: logits [M, V] with unit column stride, ids a contiguous int64 [M]")
-    M, V = logits.shape
+    M, V = _logits_shape("top_logprobs", logits)
+    if not (ids.is_contiguous() and ids.numel() == M):
+        raise _lib.UmvError("top_logprobs: ids must be a contiguous int64 [M] tensor")
     n = _top_n("top_logprobs", n, V)                    # (refused on the host, before anything touches the library)
     lib = _lib.load()
     _req(logits, BF16, "logits")

@@ -4,7 +4,7 @@ umv_row_sampling).
 One captured decode step serves rows with different samplers: the lm_head epilogue, the penalty kernel and umv_decode_step_end_rows take
 a row's temperature, filters, penalties and the three words of its sampling key - (seed, draw, stream) - from one 48-byte entry per row
 in device memory.  This module validates the values on the host (a C entry cannot look into device memory) and packs them."""
-from dataclasses import dataclass
+from dataclasses import dataclass, fields
 from typing import Optional
 
 import numpy as np
@@ -64,6 +64,30 @@ class SamplingParams:
     @property
     def penalised(self):
         return self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
+
+
+# the scalar sampler keywords of DecodeSession, Bagel.generate_text and ContinuousBatcher: SamplingParams' own fields but the seed
+_NEUTRAL = {f.name: f.default for f in fields(SamplingParams) if f.name != "seed"}
+
+
+def off_neutral(given):
+    """The scalar sampler keywords that `given` (a mapping holding every one of them, e.g. a function's locals()) has off its neutral
+    value - SamplingParams' default; for do_sample anything but False - in field order"""
+    return [k for k, neutral in _NEUTRAL.items() if (given[k] is not False if k == "do_sample" else given[k] != neutral)]
+
+
+def per_sample(sampling, B):
+    """one SamplingParams for all, or a sequence of one per sample -> a list of B SamplingParams"""
+    params = [sampling] * B if isinstance(sampling, SamplingParams) else list(sampling)
+    if len(params) != B or any(not isinstance(p, SamplingParams) for p in params):
+        raise ValueError(f"sampling must be one SamplingParams or a list of one per sample ({B})")
+    return params
+
+
+def from_keywords(do_sample=False, temperature=1.0, **rest):
+    """The SamplingParams that the scalar sampler keywords describe (a temperature means nothing without do_sample); ValueError as
+    SamplingParams raises it - a filter without do_sample among them"""
+    return SamplingParams(do_sample=bool(do_sample), temperature=temperature if do_sample else 1.0, **rest)
 
 
 def derive_seed(base, rid):

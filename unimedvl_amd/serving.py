@@ -29,7 +29,7 @@ from . import ops
 
 from .decode import DecodeSession
 from .kvcache import NaiveCache, PagedCache
-from .sampling import SamplingParams, derive_seed
+from .sampling import SamplingParams, derive_seed, from_keywords
 
 
 @dataclass
@@ -90,9 +90,12 @@ class ContinuousBatcher:
         if constraints:
             from .constraints import TokenAutomaton
             self.constraint, self.constraint_start = TokenAutomaton.union(dict(constraints))
-        self.top_k, self.top_p, self.min_p = ops.check_truncation(top_k, top_p, min_p)
-        if (self.top_k > 0 or self.top_p < 1.0 or self.min_p > 0.0) and not do_sample:
-            raise ValueError("top_k / top_p / min_p truncate the sampler: they need do_sample=True")
+        # the batcher-wide sampler keywords as one SamplingParams: checked here (a filter needs do_sample), and the default of the
+        # requests that give none under per_request_sampling
+        self.default_sampling = from_keywords(do_sample, temperature, top_k=top_k, top_p=top_p, min_p=min_p,
+                                              repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                                              frequency_penalty=frequency_penalty)
+        self.top_k, self.top_p, self.min_p = self.default_sampling.top_k, self.default_sampling.top_p, self.default_sampling.min_p
         self.model, self.tokenizer, self.new_token_ids, self.image_transform = model, tokenizer, new_token_ids, image_transform
         self.device = model.device
         self.penalties = dict(zip(("repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias"),
@@ -104,11 +107,6 @@ class ContinuousBatcher:
         if self.per_request:
             if int(slots) > 64:
                 raise ValueError(f"per_request_sampling rides on the fused step end: at most 64 slots (got {slots})")
-            pen = self.penalties
-            self.default_sampling = SamplingParams(do_sample=bool(do_sample), temperature=temperature if do_sample else 1.0,
-                                                   top_k=self.top_k, top_p=self.top_p, min_p=self.min_p,
-                                                   repetition_penalty=pen["repetition_penalty"], presence_penalty=pen["presence_penalty"],
-                                                   frequency_penalty=pen["frequency_penalty"])
             # the session reserves the penalty buffers as soon as any request (or the default) is penalised
             self._row_pen = self.default_sampling.penalised
         elif seed is not None:

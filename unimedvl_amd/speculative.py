@@ -13,12 +13,14 @@ Greedy: a verified token is the argmax of the logits its row computed.  Sampled 
 after the same prefix, and a draft is accepted exactly when it equals that pick - no rejection-sampling arithmetic.  Either way the
 rows of a step see the same keys a plain step would, but the attention's key split depends on the segment's length, so a logit may
 differ from the plain step's in the last bit."""
+import inspect
 import os
 
 import torch
 
 from . import ops
 from .decode import DecodeSession
+from .sampling import per_sample
 
 
 def _token_lists(value, B, what):
@@ -31,13 +33,11 @@ def _token_lists(value, B, what):
     return [[int(t) for t in r] for r in rows]
 
 
-# DecodeSession's keywords that pick a sampler, log, force or penalise: all of them must be at their neutral value here.
-# (temperature and seed mean nothing without do_sample and are ignored.)
-_NEUTRAL = dict(do_sample=False, logprobs=False, forced_ids=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
-                logit_bias=None, penalty_context_ids=None, penalty_context_room=None, penalty_history=None, row_sampling=None,
-                row_streams=None, row_penalties=False, top_k=0, top_p=1.0, min_p=0.0, top_logprobs=0, constraint=None,
-                constraint_states=None)
+# DecodeSession's keywords that pick a sampler, log, force, penalise or constrain - every parameter behind nsplit, with its default:
+# all of them must be at their neutral value here.  (temperature and seed mean nothing without do_sample and are ignored.)
 _IGNORED = ("temperature", "seed")
+_NEUTRAL = {name: p.default for name, p in inspect.signature(DecodeSession.__init__).parameters.items()}
+_NEUTRAL = {name: _NEUTRAL[name] for name in list(_NEUTRAL)[list(_NEUTRAL).index("nsplit") + 1:] if name not in _IGNORED}
 
 
 def _neutral(name, v):
@@ -73,24 +73,19 @@ class SpeculativeDecodeSession(DecodeSession):
         B = len(cache.lens)
         params, logprobs, seed = None, False, 0
         if sampling is not None:
-            from .sampling import SamplingParams
-            params = [sampling] * B if isinstance(sampling, SamplingParams) else list(sampling)
-            if len(params) != B or any(not isinstance(p, SamplingParams) for p in params):
-                raise ValueError(f"sampling must be one SamplingParams or a list of one per sample ({B})")
+            params = per_sample(sampling, B)
             if any(p.penalised for p in params):
                 raise ValueError("sampled speculative decode takes no penalties (a penalised SamplingParams)")
             logprobs, seed = bool(plain.pop("logprobs", False)), int(plain.get("seed", 0))
-            on = [name for name, v in plain.items() if name not in _IGNORED and not _neutral(name, v)]
-            if on:
-                raise ValueError(f"sampled speculative decode takes its samplers from sampling=: no scalar sampler keywords, forced_ids, "
-                                 f"penalties / logit_bias, top_logprobs, constraint or row_sampling (got {on})")
         elif sampling_streams is not None:
             raise ValueError("sampling_streams goes with sampling")
         mode = "speculative decode is greedy only and" if params is None else "sampled speculative decode"
         on = [name for name, v in plain.items() if name not in _IGNORED and not _neutral(name, v)]
         if on:
-            raise ValueError(f"speculative decode is greedy only: no sampling, logprobs / forced_ids, penalties / logit_bias, "
-                             f"constraint or row_sampling (got {on})")
+            raise ValueError(("speculative decode is greedy only: no sampling, logprobs / forced_ids, penalties / logit_bias, constraint or "
+                              "row_sampling" if params is None else
+                              "sampled speculative decode takes its samplers from sampling=: no scalar sampler keywords, forced_ids, "
+                              "penalties / logit_bias, top_logprobs, constraint or row_sampling") + f" (got {on})")
         if k < 1:
             raise ValueError(f"speculative decode needs draft_len >= 1 (got {draft_len})")
         if B * (k + 1) > 64:
@@ -102,8 +97,8 @@ class SpeculativeDecodeSession(DecodeSession):
             raise ValueError(f"draft_ngram = (min, max) with 1 <= min <= max, got {draft_ngram!r}")
         self.draft_len, self.draft_ngram = k, (lo, hi)
         with ops.device_scope(llm.device):
-            self._init(llm, cache, start_tokens, positions, max_length, False, nsplit, False, 1.0, seed, logprobs,
-                       rows=dict(params=params, streams=sampling_streams))
+            self._init(llm, cache, start_tokens, positions, max_length, use_graph=False, nsplit=nsplit, seed=seed, logprobs=logprobs,
+                       row_sampling=params, row_streams=sampling_streams)
             self._init_drafts(_token_lists(draft_context_ids, B, "draft_context_ids"), predicted_ids)
             if use_graph:
                 self._capture()
