@@ -763,7 +763,10 @@ int umv_cfg_renorm_euler(float* x_t, const uint16_t* v_t, const uint16_t* v_text
  * autoencoder.py:95,65) as an MFMA implicit GEMM:
  *   mode 0: stride 1, pad (k-1)/2            (autoencoder.py:76,78,80,138,167,214,238)
  *   mode 1: nearest 2x upsample then 3x3     (Upsample, autoencoder.py:116-118)
- *   mode 2: F.pad(0,1,0,1) then 3x3 stride 2 (Downsample, autoencoder.py:104-107) */
+ *   mode 2: F.pad(0,1,0,1) then 3x3 stride 2 (Downsample, autoencoder.py:104-107): floor(H/2) x floor(W/2) outputs, so an input
+ *           of one row or one column gives an empty result (UMV_OK, nothing written)
+ * k is 3, or 1 with mode 0 (modes 1 and 2 with k = 1: UMV_ERR_UNSUPPORTED).  UMV_ERR_ARG: a NULL x / wp / out, Cin no positive
+ * multiple of 8, Cout <= 0, a negative B, Hin or Win. */
 int umv_conv2d_nhwc_bf16(const uint16_t* x, const uint16_t* wp, const uint16_t* bias, const uint16_t* residual,
                          uint16_t* out, int B, int Cin, int Hin, int Win, int Cout, int ksize, int mode,
                          umv_stream_t stream);

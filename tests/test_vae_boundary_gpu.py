@@ -1,6 +1,6 @@
-"""Every kernel of csrc/vae.hip other than the convolutions, one small launch per case, against the explicit models of
-tests/vae_ref.py (fp64 per operation, bf16 roundings where the kernels' comments put them; tests/test_vae_ref_cpu.py checks the models
-themselves).  Scalar chains are walked over EVERY bf16 value; layouts at h != w, crops of the latent and b > 0.  Outputs are prefilled
+"""Every kernel of csrc/vae.hip, one small launch per case, against the explicit models of tests/vae_ref.py (the convolutions of
+csrc/vae_conv.hip are held to the same file's conv2d in tests/test_vae_conv_gpu.py).  The models: fp64 per operation, bf16 roundings
+where the kernels' comments put them; tests/test_vae_ref_cpu.py checks the models themselves.  Scalar chains are walked over EVERY bf16 value; layouts at h != w, crops of the latent and b > 0.  Outputs are prefilled
 with a NaN pattern and framed by guard elements: nothing outside the result may be written.
 
 Where exact equality of bits is not the contract, the bound is derived, not measured:
@@ -14,12 +14,11 @@ import pytest
 import torch
 
 import vae_ref as R
+from guarded import Guarded
 
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
 SCALE, SHIFT = 0.3611, 0.1159
-GUARD = 64
-_PATTERN = {BF16: (torch.int16, 0x7FA5), torch.uint8: (torch.uint8, 0xA5), torch.float32: (torch.int32, 0x7FC00A5A)}
 
 
 def _lib():
@@ -27,29 +26,6 @@ def _lib():
         pytest.fail("GPU tests need a GPU")
     from unimedvl_amd import _lib, ops
     return _lib.load(), ops._stream
-
-
-class Guarded:
-    """an output buffer of n elements prefilled with a NaN / sentinel pattern, with GUARD elements of the same pattern on either side"""
-
-    def __init__(self, n, dtype):
-        self.itype, self.pat = _PATTERN[dtype]
-        self.n, self.dtype = n, dtype
-        self.raw = torch.full((n + 2 * GUARD,), self.pat, dtype=self.itype, device="cuda")
-
-    def ptr(self):
-        return self.raw[GUARD:].data_ptr()
-
-    def fetch(self):
-        """(typed result, its raw patterns) on the host, after checking both guards"""
-        torch.cuda.synchronize()
-        h = self.raw.cpu()
-        assert bool((h[:GUARD] == self.pat).all()) and bool((h[GUARD + self.n:] == self.pat).all()), "wrote outside the output"
-        body = h[GUARD:GUARD + self.n].clone()
-        return (body if self.dtype == torch.uint8 else body.view(self.dtype)), body
-
-    def untouched(self):
-        return bool((self.fetch()[1] == self.pat).all())
 
 
 def _randn(shape, seed, dtype=torch.float32):

@@ -1,4 +1,4 @@
-"""Explicit reference models of the kernels in csrc/vae.hip other than the convolutions, on CPU tensors.
+"""Explicit reference models of the kernels in csrc/vae.hip and of the convolutions in csrc/vae_conv.hip (conv2d), on CPU tensors.
 
 Every operation is computed in fp64 on bf16-rounded operands and rounded to bf16 exactly where the kernel's comment says a rounding
 happens.  The rounding goes fp64 -> fp32 -> bf16, which is what the kernels do (one fp32 operation, then f2bf): the exact result of a
@@ -137,6 +137,61 @@ def groupnorm_fp32_allowance(x, gamma, beta, eps):
     mean, rstd = groupnorm_stats(x, eps)
     t = (x.to(F64).abs() + mean.abs()) * rstd * gamma.to(F64).abs()
     return 3.25 * 2.0 ** -20 * torch.maximum(t, beta.to(F64).abs().expand_as(t))
+
+
+def conv2d_out_hw(Hin, Win, ks, mode):
+    """mode 0: the input's size; mode 1: twice it; mode 2: floor((n + 1 - 3) / 2) + 1 per axis, none for a single row or column"""
+    if mode == 0:
+        return Hin, Win
+    if mode == 1:
+        return 2 * Hin, 2 * Win
+    return max((Hin + 1 - 3) // 2 + 1, 0), max((Win + 1 - 3) // 2 + 1, 0)
+
+
+def conv2d_parts(x, w, bias=None, residual=None, mode=0):
+    """umv_conv2d_nhwc_bf16 with the value before each rounding: (out bf16 [B,Hout,Wout,Cout], acc + bias fp64, . + residual fp64 or None).
+    x [B,Hin,Win,Cin] bf16 NHWC, w [Cout,Cin,k,k] bf16 (as vae._Conv takes it), bias [Cout] bf16 or None, residual as the output or None.
+    mode 0: stride 1, pad (k - 1) / 2.  mode 1: nearest 2x upsample, then pad 1.  mode 2: F.pad(0, 1, 0, 1), then stride 2 without padding.
+    The sum runs in fp64 on the bf16 operands; the roundings are the kernels' (conv_epilogue4 and conv3x3_patch_kernel's copy of it):
+    rbf(acc + bias), then rbf(. + residual) if there is a residual.  The sum itself is NOT rounded to fp32 here: the model is the kernels'
+    bit for bit where the fp32 sum is exact in every order (tests/conv_cases.py builds such inputs), the exact convolution otherwise."""
+    Cout, Cin, ks, _ = w.shape
+    B, Hin, Win, _ = x.shape
+    assert x.shape[3] == Cin and w.shape[2] == w.shape[3] and mode in (0, 1, 2)
+    Hout, Wout = conv2d_out_hw(Hin, Win, ks, mode)
+    if B * Hout * Wout == 0:
+        return torch.zeros((B, Hout, Wout, Cout), dtype=BF16), torch.zeros((B, Hout, Wout, Cout), dtype=F64), None
+    xc, w64 = x.to(F64).permute(0, 3, 1, 2), w.to(F64)
+    if mode == 0:
+        acc = torch.nn.functional.conv2d(xc, w64, padding=(ks - 1) // 2)
+    elif mode == 1:
+        acc = torch.nn.functional.conv2d(xc.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3), w64, padding=1)
+    else:
+        acc = torch.nn.functional.conv2d(torch.nn.functional.pad(xc, (0, 1, 0, 1)), w64, stride=2)
+    acc = acc.permute(0, 2, 3, 1)
+    assert tuple(acc.shape) == (B, Hout, Wout, Cout)
+    pre1 = acc + (bias.to(F64) if bias is not None else 0.0)
+    v = rbf(pre1)
+    pre2 = None
+    if residual is not None:
+        pre2 = v + residual.to(F64)
+        v = rbf(pre2)
+    return v.to(BF16).contiguous(), pre1, pre2
+
+
+def conv2d(x, w, bias=None, residual=None, mode=0):
+    """the model of umv_conv2d_nhwc_bf16: conv2d_parts' first result"""
+    return conv2d_parts(x, w, bias, residual, mode)[0]
+
+
+def bf16_inexact(v64):
+    """mask of the fp64 values that are no bf16 value: rounding them changes them"""
+    return rbf(v64) != v64
+
+
+def bf16_tie(v64):
+    """mask of the fp64 values exactly half way between two neighbouring bf16 values, where round-to-nearest-even decides"""
+    return (rbf(v64) - v64).abs() * 2 == bf16_ulp(v64)
 
 
 def softmax_rows(S, scale):

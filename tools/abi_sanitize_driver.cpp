@@ -357,6 +357,11 @@ static void bad_arguments() {
     // VAE
     EXPECT_ERR(umv_conv2d_nhwc_bf16(nullptr, nullptr, nullptr, nullptr, nullptr, 1, 128, 32, 32, 128, 3, 0, nullptr));
     EXPECT_ERR(umv_conv2d_nhwc_bf16(dummy16, dummy16, nullptr, nullptr, dummy16, 1, 128, 32, 32, 128, 5, 0, nullptr));   // 5 x 5
+    EXPECT_ERR(umv_conv2d_nhwc_bf16(dummy16, dummy16, nullptr, nullptr, dummy16, 1, 128, 32, 32, 128, 1, 1, nullptr));   // 1 x 1 upsample
+    EXPECT_ERR(umv_conv2d_nhwc_bf16(dummy16, dummy16, nullptr, nullptr, dummy16, 1, 128, 32, 32, 128, 1, 2, nullptr));   // 1 x 1 downsample
+    EXPECT_ERR(umv_conv2d_nhwc_bf16(dummy16, dummy16, nullptr, nullptr, dummy16, -1, 128, -32, 32, 128, 3, 0, nullptr));
+    EXPECT_ERR(umv_conv2d_nhwc_bf16(dummy16, dummy16, nullptr, nullptr, dummy16, 1, 128, 32, 32, 0, 3, 0, nullptr));
+    EXPECT_OK(umv_conv2d_nhwc_bf16(dummy16, dummy16, nullptr, nullptr, dummy16, 1, 128, 1, 32, 128, 3, 2, nullptr));     // one row: empty
     EXPECT_ERR(umv_groupnorm_nhwc_bf16(nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1024, 128, 1e-6f, 1, nullptr));
     EXPECT_ERR(umv_nchw_f32_to_nhwc_bf16(nullptr, nullptr, 1, 3, 32, 32, 8, nullptr));
     EXPECT_ERR(umv_unpatchify_latent(nullptr, nullptr, 16, 16, 2, 16, 0.36f, 0.11f, nullptr));

@@ -422,16 +422,19 @@ extern "C" int umv_conv2d_nhwc_bf16(const uint16_t* x, const uint16_t* wp, const
                                     uint16_t* out, int B, int Cin, int Hin, int Win, int Cout, int ksize, int mode,
                                     umv_stream_t stream) {
     UMV_CHECK(x && wp && out, UMV_ERR_ARG, "conv2d: null pointer");
-    UMV_CHECK(Cin % 8 == 0, UMV_ERR_ARG, "conv2d: Cin (%d) must be a multiple of 8 (pad the input channels)", Cin);
+    UMV_CHECK(Cin > 0 && Cin % 8 == 0, UMV_ERR_ARG, "conv2d: Cin (%d) must be a positive multiple of 8 (pad the input channels)", Cin);
+    UMV_CHECK(B >= 0 && Hin >= 0 && Win >= 0 && Cout > 0, UMV_ERR_ARG, "conv2d: B %d Hin %d Win %d Cout %d", B, Hin, Win, Cout);
     const int force = mode & ~3;       // tests / A-B: | 16 = the input-stationary 3x3 kernel whatever the grid, | 32 = the gather kernel
     mode &= 3;
     UMV_CHECK((ksize == 3 || ksize == 1) && mode >= 0 && mode <= 2 && (force == 0 || force == 16 || force == 32), UMV_ERR_ARG,
               "conv2d: ksize %d mode %d", ksize, mode | force);
+    // the up- and downsample are 3x3 only (Upsample / Downsample of the reference): the gather's mode 1 / 2 arithmetic has the 3-wide window built in
+    UMV_CHECK(ksize == 3 || mode == 0, UMV_ERR_UNSUPPORTED, "conv2d: mode %d needs ksize 3 (got %d)", mode, ksize);
     ConvGeom geo;
     geo.B = B; geo.Cin = Cin; geo.Hin = Hin; geo.Win = Win; geo.Cout = Cout; geo.ks = ksize; geo.mode = mode;
     if (mode == 0) { geo.Hout = Hin; geo.Wout = Win; }
     else if (mode == 1) { geo.Hout = 2 * Hin; geo.Wout = 2 * Win; }
-    else { geo.Hout = (Hin + 1 - 3) / 2 + 1; geo.Wout = (Win + 1 - 3) / 2 + 1; }
+    else { geo.Hout = Hin / 2; geo.Wout = Win / 2; }       // floor((Hin + 1 - 3) / 2) + 1 for Hin >= 0: one row or column gives none, not one
     const int M = B * geo.Hout * geo.Wout;
     if (M == 0) return UMV_OK;
     const int K = ksize * ksize * Cin;
