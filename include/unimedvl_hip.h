@@ -648,6 +648,56 @@ typedef struct {
 int umv_logit_constrain_bf16(const umv_logit_constrain_args* a, umv_stream_t stream);
 int umv_constraint_advance(const umv_token_automaton* automaton, int32_t* state, const int64_t* ids, int M, umv_stream_t stream);
 
+/* ------------------------------------------------------------------ no-repeat n-grams
+ * no_repeat_ngram_size: a row may not emit a token that would complete an n-gram its history already holds.  Row b owns an ordered
+ * history h[0..L): hist [M][hist_ld] int32 with its length in hist_len[b].  The caller seeds it with an optional context (the prompt's
+ * tokens; negative entries are separators); the kernel appends the token the step is fed, ids[b] - the start token and any forced
+ * token included (an id outside [0, 2^31) is recorded as -1).  Let L be the length after the append and n the row's size: row_n[b]
+ * where that optional int32 [M] array is given, else the scalar n.  A row with n outside 1..UMV_NGRAM_MAX is recorded but not banned.
+ *   banned set  Ban = { h[i + n - 1] : 0 <= i <= L - n, h[i .. i + n - 1) == h[L - n + 1 .. L) element for element }.  All compared
+ *               entries must lie in [0, V): a separator or an out-of-range id never matches.  A follower outside [0, V) is not banned.
+ *               n = 1 bans every history token; L < n bans nothing; the candidate i = L - n overlaps the suffix and counts (history
+ *               a a, n = 2: a is banned).  This is HF's NoRepeatNGramLogitsProcessor applied to the sequence h.
+ *   column      a banned column becomes bf16 -inf (0xFF80), also where it held NaN; a column already -inf stays -inf; every other
+ *               column keeps its bits.  The banned row REPLACES the logits in memory, as the penalties' l' and the constraint mask do,
+ *               and everything downstream is defined on it in the words used above: the greedy pick, y = bf16(l / T) and its Gumbel
+ *               key, the truncation classes, the token log-probabilities (renormalised), the top-n alternatives.
+ *   order       a step is lm_head, [penalty], ngram ban, [constrain], step end, [top-logprobs], [advance]: HF's processor order.
+ *   off         hist_len[b] < 0 is a row switched off: nothing recorded, nothing banned, no byte of the row written.
+ *   full        a row whose history is full at record time (hist_len[b] == hist_ld) gets hist_len[b] = UMV_NGRAM_FULL and is off
+ *               from then on; nothing is ever written at or beyond hist_ld.  (Callers size hist_ld so that this cannot happen: it is
+ *               the kernel's defined behaviour, not a supported mode.)
+ *   tiles       with argmax_partial every tile that holds a banned column carries the bits the lm_head epilogue of umv_gemm_bf16 would
+ *               leave for the banned logits: greedy keys when temperature = 0, the sampling keys of (temperature, seed, *step)
+ *               otherwise - with rows, of rows[b]'s temperature and (seed, draw, stream); lse_partial, when given, the statistics in
+ *               epi_lse_tile's order.  A row with an empty ban set gets no write to its logits, keys or statistics.  argmax_partial =
+ *               NULL: record and ban only (the unfused step).
+ * umv_logit_ngram_ban_bf16: one workgroup per row, no word shared between workgroups; a row's result depends only on its own logits
+ * and history.  UMV_ERR_ARG: what umv_logit_penalty_bf16 rejects of the fields the two share (temperature < 0 or not finite,
+ * lse_partial without argmax_partial, n_tiles that is not ceil(V / 16) with argmax_partial, rows with a scalar temperature other than
+ * 0, a misaligned table), a NULL hist, hist_len or ids, hist_ld < 1, a scalar n < 0 or > UMV_NGRAM_MAX. */
+#define UMV_NGRAM_MAX 16
+#define UMV_NGRAM_FULL (-2)
+typedef struct {
+    uint16_t* logits;          /* [M][V] bf16, row stride ld elements; banned in place */
+    int64_t ld;
+    const int64_t* ids;        /* [M]: the token each row is fed at this step */
+    int32_t* hist;             /* [M][hist_ld] */
+    int64_t hist_ld;
+    int32_t* hist_len;         /* [M]; negative = the row is off */
+    const int32_t* row_n;      /* optional [M]: the size of each row; NULL = the scalar n for all */
+    int M, V;
+    int n;                     /* 0 = record only */
+    float temperature;         /* as given to the lm_head GEMM: 0 = greedy keys and y = l */
+    uint64_t* argmax_partial;  /* optional [M][n_tiles] */
+    float* lse_partial;        /* optional [M][n_tiles][2], only with argmax_partial */
+    int n_tiles;
+    uint64_t seed;             /* sample_seed / sample_step of the lm_head call (temperature > 0) */
+    const int64_t* step;
+    const umv_row_sampling* rows; /* optional [M]: row b's temperature and (seed, draw, stream); the scalar temperature must be 0 */
+} umv_ngram_ban_args;
+int umv_logit_ngram_ban_bf16(const umv_ngram_ban_args* a, umv_stream_t stream);
+
 /* ------------------------------------------------------------------ speculative greedy decode: verify drafts, commit, roll back, draft again
  * A step of k = draft_len >= 1 processes T = B * (k + 1) <= 64 rows.  Row r0 = b * (k + 1) holds sample b's next input token t0, which is
  * not in the cache yet; rows r0 + j, j = 1..k, hold its drafts d_j: the first n_draft[b] are real, the rest are FILLERS equal to t0 -

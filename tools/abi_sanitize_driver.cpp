@@ -302,6 +302,36 @@ static void bad_arguments() {
     EXPECT_ERR(umv_constraint_advance(&lc.automaton, dummyi, dummyl, 1, nullptr));
     lc.automaton.row_ptr = dummyi;
     EXPECT_OK(umv_constraint_advance(&lc.automaton, dummyi, dummyl, 0, nullptr));         // no rows
+    // no-repeat n-grams
+    EXPECT_ERR(umv_logit_ngram_ban_bf16(nullptr, nullptr));
+    umv_ngram_ban_args ng;
+    std::memset(&ng, 0, sizeof ng);
+    EXPECT_ERR(umv_logit_ngram_ban_bf16(&ng, nullptr));
+    ng.logits = dummy16; ng.ld = 64; ng.ids = dummyl; ng.hist = dummyi; ng.hist_ld = 8; ng.hist_len = dummyi; ng.M = 1; ng.V = 64; ng.n = 3;
+    ng.hist = nullptr;                                           // no history
+    EXPECT_ERR(umv_logit_ngram_ban_bf16(&ng, nullptr));
+    ng.hist = dummyi; ng.hist_len = nullptr;                     // no length words
+    EXPECT_ERR(umv_logit_ngram_ban_bf16(&ng, nullptr));
+    ng.hist_len = dummyi; ng.ids = nullptr;                      // no fed tokens
+    EXPECT_ERR(umv_logit_ngram_ban_bf16(&ng, nullptr));
+    ng.ids = dummyl; ng.hist_ld = 0;                             // no room for a history
+    EXPECT_ERR(umv_logit_ngram_ban_bf16(&ng, nullptr));
+    ng.hist_ld = 8; ng.n = -1;                                   // a negative size
+    EXPECT_ERR(umv_logit_ngram_ban_bf16(&ng, nullptr));
+    ng.n = UMV_NGRAM_MAX + 1;                                    // a size above the maximum
+    EXPECT_ERR(umv_logit_ngram_ban_bf16(&ng, nullptr));
+    ng.n = 3; ng.temperature = -1.f;                             // negative temperature
+    EXPECT_ERR(umv_logit_ngram_ban_bf16(&ng, nullptr));
+    ng.temperature = 0.f; ng.lse_partial = dummyf;               // lse_partial without argmax_partial
+    EXPECT_ERR(umv_logit_ngram_ban_bf16(&ng, nullptr));
+    ng.lse_partial = nullptr; ng.argmax_partial = (uint64_t*)dummyl; ng.n_tiles = 3;     // 64 columns are not 3 tiles
+    EXPECT_ERR(umv_logit_ngram_ban_bf16(&ng, nullptr));
+    ng.n_tiles = 4; ng.ld = 32;                                  // a row stride below V
+    EXPECT_ERR(umv_logit_ngram_ban_bf16(&ng, nullptr));
+    ng.ld = 64; ng.rows = rows; ng.temperature = 0.7f;           // a scalar temperature next to the per-row table
+    EXPECT_ERR(umv_logit_ngram_ban_bf16(&ng, nullptr));
+    ng.rows = nullptr; ng.temperature = 0.f; ng.M = 0;
+    EXPECT_OK(umv_logit_ngram_ban_bf16(&ng, nullptr));           // no rows
     // speculative step end
     EXPECT_ERR(umv_decode_step_end_speculative(nullptr, nullptr));
     umv_spec_step_args sp;

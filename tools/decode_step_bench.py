@@ -10,6 +10,9 @@ about 5 us) in a kernel trace of a decode run: --trace-arm NAME runs that arm of
   constraint    a off | b all rows on a 4-choice trie, greedy | c b with do_sample, top_p 0.9, logprobs (c0: that sampler, constraint
                 off) | d one constrained row of 8 | e an allowed set of 10 000 tokens on all rows.  (A masked row costs the same in
                 every state: every tile of it is rewritten.)
+  ngram         a off | b greedy, no_repeat_ngram_size 3, generated history only | c b plus a 1024-token seeded context per row (the
+                scan walks about 1.2 k int32 per row) | d do_sample, top_p 0.9, logprobs, repetition_penalty 1.1 and the same n = 3 (d0: that
+                sampler and penalty, n-gram ban off)
   logprobs      off | on, greedy; plus a `score` leg: one Bagel.score call (a 448 x 448 image, a 32-token question, four candidates of
                 eight tokens) next to one Bagel.chat call with max_length = 9, each run twice - the warm time is the one to read
   top_logprobs  a greedy logprobs | b a + top 5 | c a + top 20 | s do_sample | d s + top_k 50: the yardstick - the selection runs the
@@ -169,6 +172,30 @@ CONSTRAINT = Suite(
     spread=[("a_off", "a_spread_ms"), ("c0_sample_top_p_logprobs_off", "c0_spread_ms")], hook=_constraint_states)
 
 
+# ---- no-repeat n-grams
+def _ngram_context(cfg):
+    g = torch.Generator().manual_seed(5)
+    return dict(NGRAM, ngram_context_ids=[torch.randint(1000, 100000, (1024,), generator=g).tolist() for _ in range(B)])
+
+
+def _ngram_histories(run, res):
+    for arm, s in run.sessions.items():
+        if s.ng_hist is not None:
+            res[arm]["history_length_at_end"] = [int(v) for v in s.ng_len.tolist()]
+            res[arm]["history_room"] = int(s.ng_hist.shape[1])
+
+
+NGRAM = dict(no_repeat_ngram_size=3)
+NGRAM_SAMPLED = dict(REP, do_sample=True, temperature=1.0, seed=SEED, top_p=0.9, logprobs=True)
+NGRAM_SUITE = Suite(
+    arms={"a_off": {}, "b_ngram3": dict(NGRAM), "c_ngram3_context": _ngram_context,
+          "d_sample_top_p_logprobs_penalty": dict(NGRAM, **NGRAM_SAMPLED), "d0_sample_top_p_logprobs_penalty_off": dict(NGRAM_SAMPLED)},
+    over=[(arm, "a_off", "over_a_us") for arm in ("b_ngram3", "c_ngram3_context", "d_sample_top_p_logprobs_penalty",
+                                                  "d0_sample_top_p_logprobs_penalty_off")]
+    + [("d_sample_top_p_logprobs_penalty", "d0_sample_top_p_logprobs_penalty_off", "over_d0_us")],
+    spread=[("a_off", "a_spread_ms"), ("d0_sample_top_p_logprobs_penalty_off", "d0_spread_ms")], hook=_ngram_histories)
+
+
 # ---- logprobs
 def _logprob_values(run, res):
     n = run.args.warmup + run.args.repeats * run.args.steps
@@ -305,7 +332,7 @@ PER_REQUEST = Suite(arms=_per_request_arms(), over=[(name + "_rows", name + "_sc
                     + [("mixed_rows", "all_scalar", "over_all_scalar_us"), ("mixed_rows", "greedy_scalar", "over_greedy_scalar_us")],
                     spread=[], head=dict(table_bytes=48 * B), hook=_same_tokens)
 
-SUITES = {"penalties": PENALTIES, "constraint": CONSTRAINT, "logprobs": LOGPROBS, "top_logprobs": TOP_LOGPROBS, "truncated": TRUNCATED,
+SUITES = {"penalties": PENALTIES, "constraint": CONSTRAINT, "ngram": NGRAM_SUITE, "logprobs": LOGPROBS, "top_logprobs": TOP_LOGPROBS, "truncated": TRUNCATED,
           "per_request": PER_REQUEST}
 
 

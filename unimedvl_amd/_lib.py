@@ -91,6 +91,16 @@ class LogitConstrainArgs(C.Structure):
     ]
 
 
+class NgramBanArgs(C.Structure):
+    """umv_ngram_ban_args: no_repeat_ngram_size on the stored logits of a step (umv_logit_ngram_ban_bf16)"""
+    _fields_ = [
+        ("logits", C.c_void_p), ("ld", C.c_int64), ("ids", C.c_void_p), ("hist", C.c_void_p), ("hist_ld", C.c_int64),
+        ("hist_len", C.c_void_p), ("row_n", C.c_void_p), ("M", C.c_int), ("V", C.c_int), ("n", C.c_int), ("temperature", C.c_float),
+        ("argmax_partial", C.c_void_p), ("lse_partial", C.c_void_p), ("n_tiles", C.c_int), ("seed", C.c_uint64), ("step", C.c_void_p),
+        ("rows", C.c_void_p),
+    ]
+
+
 class RowSampling(C.Structure):
     """umv_row_sampling: one row of the per-row sampling table (device memory; sampling.ROW_DTYPE is the same layout for numpy)"""
     _fields_ = [
@@ -125,6 +135,8 @@ TOP_LOGPROBS_MAX, TOP_AFTER_LOGPROB, TOP_AFTER_TRUNCATED = 20, 0, 1
 # token automata: the state words of a released row and of a row that was fed a token outside its state's edges; the columns one
 # workgroup of umv_logit_constrain_bf16 masks (UMV_CONSTRAIN_CHUNK)
 CONSTRAINT_FREE, CONSTRAINT_LEFT, CONSTRAIN_CHUNK = -1, -2, 4096
+# no-repeat n-grams: the largest size a row can ask for, and the length word of a row whose history ran full (UMV_NGRAM_FULL)
+NGRAM_MAX, NGRAM_FULL = 16, -2
 
 
 _SIGS = {
@@ -201,6 +213,7 @@ _SIGS = {
     "umv_logit_penalty_bf16": (C.c_int, [C.POINTER(LogitPenaltyArgs), C.c_void_p]),
     "umv_logit_constrain_bf16": (C.c_int, [C.POINTER(LogitConstrainArgs), C.c_void_p]),
     "umv_constraint_advance": (C.c_int, [C.POINTER(TokenAutomatonArgs), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "umv_logit_ngram_ban_bf16": (C.c_int, [C.POINTER(NgramBanArgs), C.c_void_p]),
     "umv_decode_step_end_speculative": (C.c_int, [C.POINTER(SpecStepArgs), C.c_void_p]),
     "umv_decode_pick_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -319,7 +319,7 @@ class Bagel(BagelPrep):
                       repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
                       logit_bias=None, penalty_context_ids=None, draft_len: int = 0, draft_ngram=(2, 4), draft_context_ids=None,
                       predicted_ids=None, sampling=None, top_logprobs: int = 0, constraint=None, constraint_states=None,
-                      top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+                      no_repeat_ngram_size=0, ngram_context_ids=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """Greedy decode (bagel.py:1236-1317).  Returns [steps, B] int64 whose row 0 holds the
         start tokens.  Like the reference, the batch stops when SAMPLE 0 emits end_token_id
         (bagel.py:1313); per_sample_eos=True is the batched extension (stops when every sample
@@ -353,7 +353,18 @@ class Bagel(BagelPrep):
         call), while return_logits, top_logprobs, penalised params and logit_bias raise.
         constraint (a constraints.TokenAutomaton) / constraint_states (one start state per sample, default 0, -1 = free): constrained
         decoding in the captured step (DecodeSession) - a sample is only ever fed tokens its automaton state has an edge for; ids,
-        logits, logprobs and top_logprobs are those of the masked logits.  With draft_len > 0 it raises."""
+        logits, logprobs and top_logprobs are those of the masked logits.  With draft_len > 0 it raises.
+        no_repeat_ngram_size (n, 0 = off, at most 16; an int or one per sample): no sample is fed a token that would repeat an n-gram
+        of its history - HF's NoRepeatNGramLogitsProcessor, in the captured step (DecodeSession; include/unimedvl_hip.h, no-repeat
+        n-grams), after the penalties and before the constraint mask; ids, logits, logprobs and top_logprobs are those of the banned
+        logits.  The history is the start token and what is fed after it; ngram_context_ids (per sample a token list, the prompt)
+        puts tokens in front of that - this call has no token ids of its own.  HF counts the prompt.  With sampling= a sample's size
+        is its SamplingParams.no_repeat_ngram_size and the keyword stays 0.  With draft_len > 0 it raises."""
+        sizes = [ops.check_ngram(v) for v in no_repeat_ngram_size] if isinstance(no_repeat_ngram_size, (list, tuple)) else \
+            [ops.check_ngram(no_repeat_ngram_size)]
+        if draft_len and (any(sizes) or (sampling is not None and any(p.no_repeat_ngram_size for p in per_sample(
+                sampling, len(past_key_values.lens))))):
+            raise ValueError("no_repeat_ngram_size is not available with draft_len > 0 (speculative decode)")
         if constraint is None and constraint_states is not None:
             raise ValueError("constraint_states goes with constraint")
         if constraint is not None and draft_len:
@@ -410,7 +421,8 @@ class Bagel(BagelPrep):
         sess = DecodeSession(self.language_model, past_key_values, packed_start_tokens, packed_query_position_ids,
                              max_length, use_graph=self.decode_use_graph and not return_logits, seed=seed, logprobs=return_logprobs,
                              logit_bias=logit_bias, penalty_context_ids=penalty_context_ids, top_logprobs=top_logprobs,
-                             constraint=constraint, constraint_states=constraint_states, **sampler)
+                             constraint=constraint, constraint_states=constraint_states, no_repeat_ngram_size=no_repeat_ngram_size,
+                             ngram_context_ids=ngram_context_ids, **sampler)
         logits = []
         steps = 0
         stop = None
@@ -486,6 +498,7 @@ class Bagel(BagelPrep):
              repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None,
              penalize_prompt: bool = False, draft_len: int = 0, draft_ngram=(2, 4), predicted_ids=None,
              sampling=None, top_logprobs: int = 0, choices=None, choices_after: str = "stop",
+             no_repeat_ngram_size: int = 0, no_repeat_ngram_prompt: bool = False,
              top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """ViT-only VQA convenience path (bagel.py:1321-1392).  return_logprobs=True: returns (answer, token_ids, token_logprobs) -
         the generated tokens behind the answer (the end token excluded) and the log-probability of each (generate_text).
@@ -502,7 +515,11 @@ class Bagel(BagelPrep):
         choices (strings, tokenised as `score` tokenises its candidates, or lists of token ids): guided choice - the answer is one of
         them (constraints.TokenAutomaton.from_choices; generate_text(constraint=)), picked by the sampler the other keywords set, the
         end token after it.  choices_after="free": the answer STARTS with one of them and goes on as free text.  `score` ranks a closed
-        set exactly at one forced row per candidate; choices costs one row, samples, and returns the sampler's pick."""
+        set exactly at one forced row per candidate; choices costs one row, samples, and returns the sampler's pick.
+        no_repeat_ngram_size (0 = off): the answer repeats no n-gram of that size (generate_text); with sampling= the size is the
+        SamplingParams'.  no_repeat_ngram_prompt=True seeds the history with the prompt's text tokens - the list penalize_prompt
+        uses, without the bos / eos wrapper - so that an n-gram of the prompt is not repeated either; the default counts generated
+        tokens only.  (HF's generate counts the prompt.)"""
         constraint = None
         if choices is not None:
             from .constraints import TokenAutomaton
@@ -536,7 +553,8 @@ class Bagel(BagelPrep):
                                  return_logprobs=return_logprobs, top_k=top_k, top_p=top_p, min_p=min_p, top_logprobs=top_logprobs,
                                  repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                                  frequency_penalty=frequency_penalty, logit_bias=logit_bias, penalty_context_ids=prompt_ids,
-                                 sampling=sampling, constraint=constraint, **draft, **gi)
+                                 sampling=sampling, constraint=constraint, no_repeat_ngram_size=no_repeat_ngram_size,
+                                 ngram_context_ids=[text_ids] if no_repeat_ngram_prompt else None, **draft, **gi)
         top = None
         if top_logprobs:
             ids, lp, top = ids

@@ -17,9 +17,9 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libunimedvl_hip.so")
 # the product library (include/unimedvl_hip.h): everything the entry points call.  The kernels that were measured and not adopted
 # live in experimental/ with a build target of their own (python -m experimental.build).  (top_logprobs.hip and, behind it,
-# logit_constrain.hip are linked last: the code objects of the plain decode step's kernels load in the order they had before
-# those two existed.)
-SOURCES = ["host_error.hip", "elementwise.hip", "norm.hip", "qkv_post.hip", "token_pick.hip", "logit_penalty.hip", "pack.hip", "gemm.hip", "gemm_w4.hip", "gemm_fp8mfma.hip", "gemm_mxfp4.hip", "gemm_mxfp4t.hip", "gemm_z13.hip", "attention.hip", "attention_prefill.hip", "image_head.hip", "vae_conv.hip", "vae.hip", "top_logprobs.hip", "logit_constrain.hip"]
+# logit_ngram.hip and logit_constrain.hip are linked last: the code objects of the plain decode step's kernels load in the order they
+# had before those three existed.)
+SOURCES = ["host_error.hip", "elementwise.hip", "norm.hip", "qkv_post.hip", "token_pick.hip", "logit_penalty.hip", "pack.hip", "gemm.hip", "gemm_w4.hip", "gemm_fp8mfma.hip", "gemm_mxfp4.hip", "gemm_mxfp4t.hip", "gemm_z13.hip", "attention.hip", "attention_prefill.hip", "image_head.hip", "vae_conv.hip", "vae.hip", "top_logprobs.hip", "logit_ngram.hip", "logit_constrain.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-Wno-unused-result", "-fgpu-rdc" if False else "-fno-gpu-rdc"]
 # per-file additions.  attention_prefill: MFMA destinations stay in VGPRs (the compiler's default parks the 64 O accumulators in

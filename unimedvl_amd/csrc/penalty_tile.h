@@ -1,5 +1,6 @@
 // One 16-column tile of a row of stored logits, recomputed by ONE thread with the bits the lm_head epilogue leaves for it: what the
-// kernels that rewrite stored logits between the lm_head call and the step end share (logit_penalty.hip, logit_constrain.hip).
+// kernels that rewrite stored logits between the lm_head call and the step end share (logit_penalty.hip, logit_ngram.hip,
+// logit_constrain.hip).
 #pragma once
 #include "gemm_epilogue.h"
 

@@ -42,7 +42,8 @@ class DecodeSession:
                  do_sample=False, temperature=1.0, seed=0, logprobs=False, forced_ids=None, *,
                  repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, penalty_context_ids=None,
                  penalty_context_room=None, penalty_history=None, row_sampling=None, row_streams=None, row_penalties=False,
-                 top_logprobs=0, constraint=None, constraint_states=None, top_k=0, top_p=1.0, min_p=0.0):
+                 top_logprobs=0, constraint=None, constraint_states=None, no_repeat_ngram_size=0, ngram_context_ids=None,
+                 ngram_context_room=None, ngram_history=None, top_k=0, top_p=1.0, min_p=0.0):
         """logprobs: also record pred_logprobs (fp32 [max_length, B]) - row s is the log-probability of in_ids[s + 1], the token step s
         picked (include/unimedvl_hip.h, token log-probabilities: of softmax(logits) in greedy decoding, of softmax(bf16(logits / T))
         when sampling).  forced_ids (int64 [max_length, B]): where an entry is >= 0 that token is fed to the next step instead of the
@@ -86,7 +87,20 @@ class DecodeSession:
         constraint_states: one start state per sample (default: state 0 for all), -1 leaves a sample free - its step is today's, bit
         for bit.  The session owns the device tables and the words: set_slot(constraint_state=) rewrites one, rewind_outputs keeps
         them.  Works on the fused and the unfused step and with every keyword above; not with draft_len > 0 (ValueError).  None:
-        today's step, launch for launch, no buffer allocated."""
+        today's step, launch for launch, no buffer allocated.
+        no_repeat_ngram_size (n, 0 = off, at most 16; an int, or a list of one per sample): no sample is fed a token that would repeat
+        an n-gram of its history (include/unimedvl_hip.h, no-repeat n-grams; HF's NoRepeatNGramLogitsProcessor) - one
+        umv_logit_ngram_ban_bf16 launch behind the lm_head call and the penalty kernel, before the constraint mask, records the token
+        the step is fed and sets the banned columns of the stored logits to -inf, their tiles' keys and statistics with them; picks,
+        pred_logprobs, truncation, top_logprobs and `logits` are those of the banned logits.  With row_sampling a row's size is its
+        SamplingParams.no_repeat_ngram_size and the scalar keyword stays 0.  ngram_context_ids: per sample the tokens that precede
+        the start token in its history (the prompt; negative entries are separators nothing matches) - default: generated tokens only.
+        The session owns the history: set_slot starts a slot's over, rewind_outputs keeps it.  ngram_context_room: context tokens per
+        slot to reserve for later set_slot calls (default: the longest list given); ngram_history: fed tokens per slot to reserve
+        (default max_length - more when requests outlive a round of max_length steps; with row_sampling, giving it reserves the
+        buffers even while every row's size is 0).  A slot whose history runs full stops banning.  Works on the fused and the unfused
+        step and with every keyword above; not with draft_len > 0 (ValueError).  Off: today's step, launch for launch, no buffer
+        allocated."""
         if constraint is None and constraint_states is not None:
             raise ValueError("constraint_states goes with constraint")
         if constraint is not None and self.draft_len:
@@ -107,7 +121,8 @@ class DecodeSession:
                        logit_bias=logit_bias, penalty_context_ids=penalty_context_ids, penalty_context_room=penalty_context_room,
                        penalty_history=penalty_history, row_sampling=row_sampling, row_streams=row_streams, row_penalties=row_penalties,
                        top_logprobs=top_logprobs, constraint=constraint, constraint_states=constraint_states, top_k=top_k, top_p=top_p,
-                       min_p=min_p)
+                       min_p=min_p, no_repeat_ngram_size=no_repeat_ngram_size, ngram_context_ids=ngram_context_ids,
+                       ngram_context_room=ngram_context_room, ngram_history=ngram_history)
 
     @property
     def device(self):
@@ -116,7 +131,8 @@ class DecodeSession:
     def _init(self, llm, cache, start_tokens, positions, max_length, *, use_graph, nsplit=None, do_sample=False, temperature=1.0, seed=0,
               logprobs=False, forced_ids=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None,
               penalty_context_ids=None, penalty_context_room=None, penalty_history=None, row_sampling=None, row_streams=None,
-              row_penalties=False, top_logprobs=0, constraint=None, constraint_states=None, top_k=0, top_p=1.0, min_p=0.0):
+              row_penalties=False, top_logprobs=0, constraint=None, constraint_states=None, top_k=0, top_p=1.0, min_p=0.0,
+              no_repeat_ngram_size=0, ngram_context_ids=None, ngram_context_room=None, ngram_history=None):
         """the constructor's keywords under the constructor's names, already checked against each other (__init__)"""
         cfg, dev = llm.cfg, llm.device
         self.llm, self.cache, self.cfg, self.dev = llm, cache, cfg, dev
@@ -318,6 +334,7 @@ class DecodeSession:
         force = self.row_table is not None and (bool(row_penalties) or any(p.penalised for p in self.row_params))
         self._init_penalties(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, penalty_context_ids,
                              penalty_context_room, penalty_history, force)
+        self._init_ngram(no_repeat_ngram_size, ngram_context_ids, ngram_context_room, ngram_history)
         self._init_constraint(constraint, constraint_states)
         self.steps_done = 0
         self.graph = None
@@ -354,6 +371,79 @@ class DecodeSession:
         self.pen_bias = torch.zeros((B, self.pen_static), dtype=torch.float32, device=dev) if self.pen_static else None
         for b in range(B):
             self._reset_penalty_slot(b, context[b])
+
+    # ---- no-repeat n-grams (include/unimedvl_hip.h): per slot the ordered history - context, start token, then every token fed - and
+    # its length; the sizes as one scalar, or one word per slot
+    def _init_ngram(self, size, context_ids, context_room, history):
+        dev, B = self.dev, self.B
+        self.ng_hist = self.ng_len = self.ng_row_n = None
+        self.ng_n = 0
+        if self.row_params is not None:
+            if not (isinstance(size, int) and not isinstance(size, bool) and size == 0):
+                raise ValueError(f"row_sampling excludes the scalar no_repeat_ngram_size (got {size!r}): a row's size is its SamplingParams'")
+            sizes = [p.no_repeat_ngram_size for p in self.row_params]
+            on = any(sizes) or history is not None
+        elif isinstance(size, (list, tuple)):
+            sizes = [ops.check_ngram(v) for v in size]
+            if len(sizes) != B:
+                raise ValueError(f"no_repeat_ngram_size must be one integer or one per sample ({B}), got {len(sizes)}")
+            on = any(sizes)
+        else:
+            self.ng_n = ops.check_ngram(size)
+            sizes, on = None, self.ng_n > 0
+        if not on:
+            return                                  # off (a context alone changes nothing): today's step
+        if self.draft_len:
+            raise ValueError("no_repeat_ngram_size is not available with draft_len > 0 (speculative decode)")
+        context = [[] for _ in range(B)] if context_ids is None else [self._ngram_context(c) for c in context_ids]
+        if len(context) != B:
+            raise ValueError(f"ngram_context_ids must hold one token list per sample ({B}), got {len(context)}")
+        room = max([len(c) for c in context] + [0]) if context_room is None else int(context_room)
+        history = self.max_length if history is None else int(history)
+        if room < 0 or history < 0:
+            raise ValueError(f"ngram_context_room / ngram_history must be >= 0 (got {context_room!r} / {history!r})")
+        self.ng_room = room
+        self.ng_hist = torch.zeros((B, room + max(1, history)), dtype=torch.int32, device=dev)
+        self.ng_len = torch.zeros((B,), dtype=torch.int32, device=dev)
+        if sizes is not None:
+            self.ng_row_n = torch.tensor(sizes, dtype=torch.int32).to(dev)
+        for b in range(B):
+            self._reset_ngram_slot(b, context[b])
+
+    @staticmethod
+    def _ngram_context(tokens):
+        """a context list as ints (negative entries are separators), every one an int32"""
+        out = [int(t) for t in (tokens.tolist() if hasattr(tokens, "tolist") else tokens or ())]
+        if out and (max(out) >= 1 << 31 or min(out) < -(1 << 31)):
+            raise ValueError("ngram_context_ids holds a token that is no int32")
+        return out
+
+    def _reset_ngram_slot(self, b, context):
+        """Slot b starts a request: `context` is its whole history (the step appends the start token)."""
+        if len(context) > self.ng_room:
+            raise ValueError(f"slot {b}: {len(context)} context tokens, the session reserved room for {self.ng_room} (ngram_context_room)")
+        if context:
+            self.ng_hist[b, :len(context)] = torch.tensor(context, dtype=torch.int32, device=self.dev)
+        self.ng_len[b:b + 1].fill_(len(context))
+
+    @ops.on_device
+    def copy_ngram_history(self, other, slots=None):
+        """Take over another session's n-gram histories (and per-slot sizes) for `slots` (default: all) - a re-captured step goes on
+        with those requests.  This session's rows hold at least what the other's hold."""
+        if self.ng_hist is None:
+            return
+        if other.ng_hist is None or other.ng_hist.shape[0] != self.ng_hist.shape[0] or other.ng_hist.shape[1] > self.ng_hist.shape[1] or \
+                (self.ng_row_n is None) != (other.ng_row_n is None):
+            raise ValueError("copy_ngram_history: the sessions do not share an n-gram layout")
+        rows, at = self._slot_index(slots)
+        if not rows:
+            return
+        hist = torch.zeros((len(rows), self.ng_hist.shape[1]), dtype=torch.int32, device=self.dev)
+        hist[:, :other.ng_hist.shape[1]] = other.ng_hist[at]
+        self.ng_hist[at] = hist
+        self.ng_len[at] = other.ng_len[at]
+        if self.ng_row_n is not None:
+            self.ng_row_n[at] = other.ng_row_n[at]
 
     # ---- constrained decoding (include/unimedvl_hip.h, token automata): the automaton's tables and one state word per sample
     def _init_constraint(self, automaton, states):
@@ -499,6 +589,10 @@ class DecodeSession:
             r, p, f = self.pen
             ops.logit_penalty(self.logits, self.ids, self.pen_count, self.pen_list, self.pen_len, self.pen_static, bias=self.pen_bias,
                               repetition_penalty=r, presence_penalty=p, frequency_penalty=f, **self.step_kw)
+        if self.ng_hist is not None:
+            # record the token this step is fed in every sample's history and set the columns that would repeat an n-gram of it to
+            # -inf, their tiles' keys and statistics with them - again with what the lm_head call got
+            ops.logit_ngram_ban(self.logits, self.ids, self.ng_hist, self.ng_len, n=self.ng_n, row_n=self.ng_row_n, **self.step_kw)
         if self.con_state is not None:
             # mask the (adjusted) logits of every constrained sample to its state's tokens and rewrite its tiles' keys and statistics,
             # again with what the lm_head call got: the step end picks from, and normalises over, the allowed set
@@ -552,6 +646,8 @@ class DecodeSession:
             state += (self.row_table,)
         if self.con_state is not None:              # ... and the constraint states
             state += (self.con_state,)
+        if self.ng_hist is not None:                # ... and appends to the n-gram histories
+            state += (self.ng_hist, self.ng_len)
         return state
 
     def _capture(self):
@@ -587,14 +683,17 @@ class DecodeSession:
     # ---- continuous batching support (serving.py): the captured step reads these from device memory, so a slot can be
     # re-pointed at a new request between replays without re-capturing
     @ops.on_device
-    def set_slot(self, b, token, kv_len, pos, penalty_context_ids=None, sampling=None, stream=None, draw=0, constraint_state=None):
+    def set_slot(self, b, token, kv_len, pos, penalty_context_ids=None, sampling=None, stream=None, draw=0, constraint_state=None,
+                 ngram_context_ids=None):
         """Sample b continues from `token` with `kv_len` tokens already in its cache segment and rope position `pos`.  With penalties
         on, the slot's history starts over: no generated tokens, penalty_context_ids as its context set, `token` as its start token.
         sampling (a SamplingParams; sessions with row_sampling): row b of the table is rewritten - the slot decodes with these
         parameters from the next replay on, its key words (seed, stream - default: the slot's current one -, draw); without it the
         row, its draw counter included, stays as it is.
         constraint_state (sessions with constraint): the slot's state word becomes this state of the automaton (-1 = unconstrained)
-        from the next replay on; without it the word stays as it is."""
+        from the next replay on; without it the word stays as it is.
+        With no_repeat_ngram_size on, the slot's n-gram history starts over as well: ngram_context_ids (default: nothing) is what
+        precedes `token` in it; with row_sampling, `sampling` also brings the slot's size."""
         if constraint_state is not None:
             if self.con_state is None:
                 raise ValueError("set_slot(constraint_state=...) needs a session built with constraint")
@@ -603,6 +702,8 @@ class DecodeSession:
             self._set_row(b, sampling, stream, draw)
         if self.pen is not None:
             self._reset_penalty_slot(b, self._penalty_context(penalty_context_ids))
+        if self.ng_hist is not None:
+            self._reset_ngram_slot(b, self._ngram_context(ngram_context_ids))
         self.ids[b:b + 1].fill_(int(token))
         self.tok_slot[b:b + 1].fill_(int(kv_len))
         self.kv_len[b:b + 1].fill_(int(kv_len) + 1)
@@ -613,6 +714,10 @@ class DecodeSession:
             raise ValueError("set_slot(sampling=...) needs a session built with row_sampling")
         if self.pen is None and params.penalised:
             raise ValueError("this session reserved no penalty buffers: build it with row_penalties=True (or a penalised row)")
+        if params.no_repeat_ngram_size and self.ng_hist is None:
+            raise ValueError("this session reserved no n-gram history: build it with ngram_history= (or a row with a size)")
+        if self.ng_row_n is not None:
+            self.ng_row_n[b:b + 1].fill_(params.no_repeat_ngram_size)
         stream = self.row_streams[b] if stream is None else int(stream)
         row = sampling_mod.to_tensor(sampling_mod.pack_row(params, seed=self.seed, stream=stream, draw=draw), self.dev)
         self.row_table[b:b + 1].copy_(row)
@@ -622,7 +727,8 @@ class DecodeSession:
     def rewind_outputs(self):
         """Start writing in_ids / pred_ids (and pred_logprobs) at row 0 again (the caller has harvested the previous rows).  The
         penalty history is NOT touched: a request lives across rounds - and neither are the rows' draw counters (row_sampling): a
-        request's noise does not repeat from round to round - nor the constraint states: a request is where it is in its automaton."""
+        request's noise does not repeat from round to round - nor the constraint states: a request is where it is in its automaton -
+        nor the n-gram histories."""
         self.step_idx.zero_()
         self.in_ids[0].copy_(self.ids)      # the tokens the next step is fed (set_slot may have changed them)
         self.steps_done = 0

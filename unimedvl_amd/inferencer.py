@@ -146,8 +146,11 @@ class InterleaveInferencer:
     @torch.no_grad()
     def gen_text(self, gen_context, max_length: int = 500, do_sample: bool = True, temperature: float = 1.0, *,
                  repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None,
-                 draft_len: int = 0, draft_ngram=(2, 4), predicted_ids=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+                 draft_len: int = 0, draft_ngram=(2, 4), predicted_ids=None, no_repeat_ngram_size: int = 0,
+                 top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         # top_k / top_p / min_p: truncated sampling (Bagel.generate_text), off by default as in the reference
+        # no_repeat_ngram_size: no n-gram of that size is generated twice (Bagel.generate_text), off by default; a context holds no
+        # token ids, so the history is the generated tokens only
         # draft_len > 0 (with do_sample=False): speculative greedy decode (Bagel.generate_text) - the same text from fewer passes over
         # the weights; a context holds no token ids, so the drafts come from predicted_ids (a string or token ids) or from the
         # generated text's own repetitions
@@ -161,7 +164,8 @@ class InterleaveInferencer:
         try:
             ids = self.model.generate_text(past_key_values=cache, max_length=max_length, do_sample=do_sample,
                                            temperature=temperature, end_token_id=self.new_token_ids["eos_token_id"],
-                                           top_k=top_k, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
+                                           top_k=top_k, top_p=top_p, min_p=min_p, no_repeat_ngram_size=no_repeat_ngram_size,
+                                           repetition_penalty=repetition_penalty,
                                            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
                                            logit_bias=logit_bias, **self._draft_kw(draft_len, draft_ngram, predicted_ids, 1), **gi)
         finally:
@@ -190,11 +194,12 @@ class InterleaveInferencer:
                              cfg_renorm_min=0.0, cfg_renorm_type="global", image_shapes=(1024, 1024), *,
                              text_repetition_penalty=1.0, text_presence_penalty=0.0, text_frequency_penalty=0.0, text_logit_bias=None,
                              text_draft_len=0, text_draft_ngram=(2, 4), text_predicted_ids=None,
+                             text_no_repeat_ngram_size=0,
                              text_top_k=0, text_top_p=1.0, text_min_p=0.0) -> List[Union[str, Image.Image]]:
         """inferencer.py:552-638.  text_top_k / text_top_p / text_min_p: truncated sampling of the text passes (gen_text);
         text_repetition_penalty / text_presence_penalty / text_frequency_penalty / text_logit_bias: their logit penalties;
         text_draft_len / text_draft_ngram / text_predicted_ids: their speculative greedy decode (do_sample=False)."""
-        filters = dict(top_k=text_top_k, top_p=text_top_p, min_p=text_min_p,
+        filters = dict(top_k=text_top_k, top_p=text_top_p, min_p=text_min_p, no_repeat_ngram_size=text_no_repeat_ngram_size,
                        **_penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias),
                        **_drafts(text_draft_len, text_draft_ngram, text_predicted_ids))
         output_list = []
@@ -253,6 +258,7 @@ class InterleaveInferencer:
             cfg_renorm_min: float = 0.0, cfg_renorm_type: str = "global", image_shapes: tuple = (1024, 1024),
             *, text_repetition_penalty: float = 1.0, text_presence_penalty: float = 0.0, text_frequency_penalty: float = 0.0,
             text_logit_bias=None, text_draft_len: int = 0, text_draft_ngram=(2, 4), text_predicted_ids=None,
+            text_no_repeat_ngram_size: int = 0,
             text_top_k: int = 0, text_top_p: float = 1.0, text_min_p: float = 0.0
     ) -> List[Union[str, Image.Image]]:
         """VQA, then optionally reconstruct every input image from the answer (inferencer.py:282-362)."""
@@ -270,6 +276,7 @@ class InterleaveInferencer:
                 raise ValueError(f"Unsupported input type: {type(input_term)}")
         vqa_answer = self.gen_text(vqa_context, do_sample=do_sample, temperature=text_temperature,
                                    max_length=max_think_token_n, top_k=text_top_k, top_p=text_top_p, min_p=text_min_p,
+                                   no_repeat_ngram_size=text_no_repeat_ngram_size,
                                    **_penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias),
                                    **_drafts(text_draft_len, text_draft_ngram, text_predicted_ids))
         output_list.append(vqa_answer)
@@ -338,6 +345,7 @@ class InterleaveInferencer:
             cfg_renorm_min: float = 0.0, cfg_renorm_type: str = "global", image_shapes: tuple = (1024, 1024),
             *, text_repetition_penalty: float = 1.0, text_presence_penalty: float = 0.0, text_frequency_penalty: float = 0.0,
             text_logit_bias=None, text_draft_len: int = 0, text_draft_ngram=(2, 4), text_predicted_ids=None,
+            text_no_repeat_ngram_size: int = 0,
             text_top_k: int = 0, text_top_p: float = 1.0, text_min_p: float = 0.0
     ) -> List[Union[str, Image.Image]]:
         """inferencer.py:366-463: VQA, then one reconstruction per input image.  (cfg_*_scale / think / image_shapes are
@@ -346,6 +354,7 @@ class InterleaveInferencer:
                                       cfg_interval, timestep_shift, num_timesteps, cfg_renorm_min, cfg_renorm_type,
                                       text_top_k, text_top_p, text_min_p,
                                       dict(_penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias),
+                                           no_repeat_ngram_size=text_no_repeat_ngram_size,
                                            **_drafts(text_draft_len, text_draft_ngram, text_predicted_ids)))
 
     @torch.no_grad()
@@ -357,6 +366,7 @@ class InterleaveInferencer:
             cfg_renorm_min: float = 0.0, cfg_renorm_type: str = "global", image_shapes: tuple = (1024, 1024),
             *, text_repetition_penalty: float = 1.0, text_presence_penalty: float = 0.0, text_frequency_penalty: float = 0.0,
             text_logit_bias=None, text_draft_len: int = 0, text_draft_ngram=(2, 4), text_predicted_ids=None,
+            text_no_repeat_ngram_size: int = 0,
             text_top_k: int = 0, text_top_p: float = 1.0, text_min_p: float = 0.0
     ) -> List[Union[str, Image.Image]]:
         """inferencer.py:466-549: VQA, then a reconstruction of the FIRST input image only."""
@@ -364,6 +374,7 @@ class InterleaveInferencer:
                                       cfg_interval, timestep_shift, num_timesteps, cfg_renorm_min, cfg_renorm_type,
                                       text_top_k, text_top_p, text_min_p,
                                       dict(_penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias),
+                                           no_repeat_ngram_size=text_no_repeat_ngram_size,
                                            **_drafts(text_draft_len, text_draft_ngram, text_predicted_ids)))
 
     # ------------------------------------------------------------------ batch extension (additive)
@@ -398,7 +409,7 @@ class InterleaveInferencer:
     def gen_text_batch(self, ctx, max_length: int = 500, do_sample: bool = True, temperature: float = 1.0, *,
                        repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None,
                        draft_len: int = 0, draft_ngram=(2, 4), predicted_ids=None,
-                       top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0) -> List[str]:
+                       no_repeat_ngram_size=0, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0) -> List[str]:
         """gen_text for every sample of a batched context; each answer ends at that sample's own EOS.  draft_len / draft_ngram /
         predicted_ids (one entry per sample): speculative greedy decode as in gen_text, B * (draft_len + 1) <= 64."""
         cache = ctx["past_key_values"]
@@ -408,7 +419,8 @@ class InterleaveInferencer:
         try:        # decode in place beyond the committed lengths, then put the lengths back (see gen_text)
             ids = self.model.generate_text(past_key_values=cache, max_length=max_length, do_sample=do_sample,
                                            temperature=temperature, end_token_id=eos, per_sample_eos=True,
-                                           top_k=top_k, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
+                                           top_k=top_k, top_p=top_p, min_p=min_p, no_repeat_ngram_size=no_repeat_ngram_size,
+                                           repetition_penalty=repetition_penalty,
                                            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
                                            logit_bias=logit_bias,
                                            **self._draft_kw(draft_len, draft_ngram, predicted_ids, len(cache.lens)), **gi).cpu()
@@ -459,6 +471,7 @@ class InterleaveInferencer:
                                    num_timesteps=50, cfg_renorm_min=0.0, cfg_renorm_type="global", image_shapes=(1024, 1024),
                                    *, text_repetition_penalty=1.0, text_presence_penalty=0.0, text_frequency_penalty=0.0,
                                    text_logit_bias=None, text_draft_len=0, text_draft_ngram=(2, 4), text_predicted_ids=None,
+                                   text_no_repeat_ngram_size=0,
                                    text_top_k=0, text_top_p=1.0, text_min_p=0.0) -> List[List[Union[str, Image.Image]]]:
         """interleave_inference (inferencer.py:552-638) over B samples at once.  Every sample must have the same
         sequence of item types; lengths (prompt tokens, image sizes) may differ.  Returns one output list per sample."""
@@ -495,6 +508,7 @@ class InterleaveInferencer:
                     cfg_text_ctx = self._snap(ctx)
         outputs = [[] for _ in range(n)]
         penalties = dict(_penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias),
+                         no_repeat_ngram_size=text_no_repeat_ngram_size,
                          **_drafts(text_draft_len, text_draft_ngram, text_predicted_ids))
         if understanding_output:
             for o, t in zip(outputs, self.gen_text_batch(ctx, do_sample=do_sample, temperature=text_temperature,

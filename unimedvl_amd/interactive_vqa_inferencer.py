@@ -45,6 +45,10 @@ DEFAULT_CONFIG = {
     "frequency_penalty": 0.0,
     "logit_bias": None,
     "penalize_prompt": False,       # True: the prompt's own tokens (not the bos / eos wrapper) count as seen for repetition_penalty
+    # no-repeat n-grams (not reference keys; 0 = off): the answer repeats no n-gram of that size (Bagel.chat); "no_repeat_ngram_prompt":
+    # True also counts the n-grams of the prompt's own tokens (HF's generate does), False the generated tokens only
+    "no_repeat_ngram_size": 0,
+    "no_repeat_ngram_prompt": False,
     # speculative greedy decode (not reference keys; off = one token per step): Bagel.chat - needs "do_sample": False
     "draft_len": 0,                 # drafted tokens verified per step (prompt lookup over the question and the answer so far)
     "draft_ngram": (2, 4),
@@ -204,6 +208,10 @@ class VQAInferencer:
         choices = choices if choices is not None else self.config.get("choices")
         if choices is not None:     # the answer is one of these (this call's list, else the config's); not with drafts (Bagel.generate_text)
             extra.update(choices=choices, choices_after=self.config.get("choices_after", "stop"))
+        if self.config.get("no_repeat_ngram_size", 0):
+            extra.update(no_repeat_ngram_size=self.config["no_repeat_ngram_size"])
+        if self.config.get("no_repeat_ngram_prompt", False):      # (with "sampling" the size is the SamplingParams')
+            extra.update(no_repeat_ngram_prompt=True)
         sampler = dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, **penalties)
         sampling = self.config.get("sampling")
         if sampling is not None:    # the config's scalar sampler keys step aside; one given to this call explicitly is passed on (and refused)

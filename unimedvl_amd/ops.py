@@ -8,7 +8,7 @@ import torch
 
 from . import _lib
 from ._lib import (EPI_BIAS, EPI_GELU_TANH, EPI_OUT_F32, EPI_RESIDUAL, EPI_SILU, EPI_SWIGLU, AttnArgs, GemmArgs,
-                   LogitConstrainArgs, LogitPenaltyArgs, QkvPostArgs, TokenAutomatonArgs, check)
+                   LogitConstrainArgs, LogitPenaltyArgs, NgramBanArgs, QkvPostArgs, TokenAutomatonArgs, check)
 
 BF16 = torch.bfloat16
 
@@ -623,6 +623,49 @@ def constraint_advance(automaton, state, ids):
     t = _automaton_args(automaton, "constraint_advance")
     check(lib.umv_constraint_advance(C.byref(t), _p(state), _p(ids), M, _stream()), "umv_constraint_advance")
     return state
+
+
+NGRAM_MAX = _lib.NGRAM_MAX      # the largest no_repeat_ngram_size (UMV_NGRAM_MAX)
+
+
+def check_ngram(n, what="no_repeat_ngram_size"):
+    """A no_repeat_ngram_size (include/unimedvl_hip.h, no-repeat n-grams) as an int, ValueError unless it is an integer in
+    [0, NGRAM_MAX] (0 = off)."""
+    if isinstance(n, bool) or not isinstance(n, (int, float)) or not 0 <= n <= NGRAM_MAX or int(n) != n:
+        raise ValueError(f"{what} must be an integer in [0, {NGRAM_MAX}] (0 = off), got {n!r}")
+    return int(n)
+
+
+def logit_ngram_ban(logits, ids, hist, hist_len, n=0, row_n=None, temperature=0.0, seed=0, step=None, argmax_partial=None,
+                    lse_partial=None, sample_rows=None):
+    """umv_logit_ngram_ban_bf16 on bf16 logits [M, V], in place: append ids (int64 [M], the tokens this step is fed) to the rows'
+    histories (hist int32 [M, hist_ld], hist_len int32 [M]: negative = the row is off) and set to -inf every column that would repeat
+    an n-gram of the row's history - n the scalar size, or row_n (int32 [M]) one per row; a size outside 1..NGRAM_MAX records only.
+    With argmax_partial ([M, n_tiles] int64, lse_partial [M, n_tiles, 2] fp32) the tiles of the banned columns are recomputed as the
+    lm_head call with sample=(temperature, seed, step) leaves them (temperature 0: greedy); sample_rows (the per-row table, int64
+    [M, 6]): with every row's own temperature and key, the scalar temperature left at 0.  Runs after logit_penalty and before
+    logit_constrain when those run, before whatever picks."""
+    lib = _lib.load()
+    _req(logits, BF16, "logits")
+    _req(ids, torch.int64, "ids")
+    _req(hist, torch.int32, "hist")
+    _req(hist_len, torch.int32, "hist_len")
+    M, V = _logits_shape("logit_ngram_ban", logits)
+    if not (ids.is_contiguous() and ids.numel() == M and hist_len.is_contiguous() and hist_len.numel() == M and hist.is_contiguous()
+            and hist.dim() == 2 and hist.shape[0] == M):
+        raise _lib.UmvError("logit_ngram_ban: ids [M], hist [M, hist_ld], hist_len [M], all contiguous")
+    if row_n is not None:
+        _req(row_n, torch.int32, "row_n")
+        if not (row_n.is_contiguous() and row_n.numel() == M):
+            raise _lib.UmvError("logit_ngram_ban: row_n must be a contiguous int32 [M] tensor")
+    a = NgramBanArgs()
+    a.logits, a.ld, a.ids = logits.data_ptr(), logits.stride(0), ids.data_ptr()
+    a.hist, a.hist_ld, a.hist_len = hist.data_ptr() or None, hist.shape[1], hist_len.data_ptr()
+    a.row_n = None if row_n is None else row_n.data_ptr()
+    a.M, a.V, a.n = M, V, int(n)
+    _fill_tile_keys(a, "logit_ngram_ban", M, temperature, seed, step, argmax_partial, lse_partial, sample_rows)
+    check(lib.umv_logit_ngram_ban_bf16(C.byref(a), _stream()), "umv_logit_ngram_ban_bf16")
+    return logits
 
 
 def cast_pad(x, Kp):

@@ -38,6 +38,8 @@ class SamplingParams:
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
     seed: Optional[int] = None
+    no_repeat_ngram_size: int = 0       # (include/unimedvl_hip.h, no-repeat n-grams; 0 = off) - not part of the packed table: the
+                                        # sizes travel in an int32 array of their own
 
     def __post_init__(self):
         if not isinstance(self.do_sample, (bool, np.bool_)):
@@ -53,6 +55,7 @@ class SamplingParams:
             raise ValueError("top_k / top_p / min_p truncate the sampler: they need do_sample=True")
         if self.seed is not None and (isinstance(self.seed, bool) or not isinstance(self.seed, int)):
             raise ValueError(f"seed must be an integer or None, got {self.seed!r}")
+        object.__setattr__(self, "no_repeat_ngram_size", ops.check_ngram(self.no_repeat_ngram_size))
         for name, v in (("temperature", float(t)), ("top_k", k), ("top_p", p), ("min_p", m), ("repetition_penalty", r),
                         ("presence_penalty", pr), ("frequency_penalty", fr)):
             object.__setattr__(self, name, v)
@@ -66,8 +69,8 @@ class SamplingParams:
         return self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
 
 
-# the scalar sampler keywords of DecodeSession, Bagel.generate_text and ContinuousBatcher: SamplingParams' own fields but the seed
-_NEUTRAL = {f.name: f.default for f in fields(SamplingParams) if f.name != "seed"}
+# the scalar sampler keywords of DecodeSession, Bagel.generate_text and ContinuousBatcher: SamplingParams' own fields but the seed and the n-gram size (a keyword of its own)
+_NEUTRAL = {f.name: f.default for f in fields(SamplingParams) if f.name not in ("seed", "no_repeat_ngram_size")}
 
 
 def off_neutral(given):

@@ -54,6 +54,7 @@ class ContinuousBatcher:
                  pool_pages: Optional[int] = None, logprobs: bool = False, *, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, penalize_prompt: bool = False,
                  per_request_sampling: bool = False, seed: Optional[int] = None, top_logprobs: int = 0, constraints=None,
+                 no_repeat_ngram_size: int = 0, no_repeat_ngram_prompt: bool = False,
                  top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """max_context: the context (prompt + images) the slots are RESERVED for; with growable=True longer requests enlarge
         the cache (up to context_limit tokens of context when given), with growable=False they are refused.
@@ -85,7 +86,14 @@ class ContinuousBatcher:
         batcher without constraints.  The automata are merged ONCE, here (TokenAutomaton.union), so the device tables have a captured
         size and never move; admission writes the request's start state into its slot's state word, and a re-captured session takes
         the live slots' words over as it takes the penalty histories over.  An automaton per request, compiled at submit, is not
-        offered: the tables would have to grow under a captured step."""
+        offered: the tables would have to grow under a captured step.
+        no_repeat_ngram_size (0 = off): no request repeats an n-gram of that size (DecodeSession; HF's NoRepeatNGramLogitsProcessor) -
+        batcher-wide like temperature, and under per_request_sampling the default of the requests whose SamplingParams give none.  A
+        slot's history starts over when a request is admitted to it and lives across the rounds of that request; the session reserves
+        it as the penalty context room is reserved - for the longest prompt and token budget admitted so far - and the step is
+        re-captured, histories carried over, when a longer one arrives.  no_repeat_ngram_prompt=True seeds a request's history with
+        its prompt's token ids (the text between the bos / eos wrapper, exactly the list penalize_prompt uses), so that an n-gram of
+        the prompt is not repeated either; the default counts generated tokens only.  (HF's generate counts the prompt.)"""
         self.constraint, self.constraint_start = None, {}
         if constraints:
             from .constraints import TokenAutomaton
@@ -94,7 +102,10 @@ class ContinuousBatcher:
         # requests that give none under per_request_sampling
         self.default_sampling = from_keywords(do_sample, temperature, top_k=top_k, top_p=top_p, min_p=min_p,
                                               repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-                                              frequency_penalty=frequency_penalty)
+                                              frequency_penalty=frequency_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
+        self.ngram_prompt = bool(no_repeat_ngram_prompt)
+        self._ng_on = self.default_sampling.no_repeat_ngram_size > 0      # does any request (or the default) carry a size?
+        self._ng_room = self._ng_hist = 0                                  # context / fed tokens per slot the decode session reserves
         self.top_k, self.top_p, self.min_p = self.default_sampling.top_k, self.default_sampling.top_p, self.default_sampling.min_p
         self.model, self.tokenizer, self.new_token_ids, self.image_transform = model, tokenizer, new_token_ids, image_transform
         self.device = model.device
@@ -150,6 +161,7 @@ class ContinuousBatcher:
             if not isinstance(sampling, SamplingParams):
                 raise ValueError(f"sampling must be a SamplingParams, got {type(sampling).__name__}")
             self._row_pen = self._row_pen or sampling.penalised
+            self._ng_on = self._ng_on or sampling.no_repeat_ngram_size > 0
         imgs = [] if images is None else (list(images) if isinstance(images, (list, tuple)) else [images])
         budget = self.default_new if max_new_tokens is None else int(max_new_tokens)
         if budget > self.default_new and not self.growable:
@@ -188,7 +200,10 @@ class ContinuousBatcher:
             return p if p.seed is not None else dataclasses.replace(p, seed=derive_seed(self.seed, req.rid))
 
         def context_of(b):
-            return active[b].prompt_ids if active[b] is not None else None
+            return active[b].prompt_ids if active[b] is not None and self.penalize_prompt else None
+
+        def ngram_context_of(b):
+            return active[b].prompt_ids if active[b] is not None and self.ngram_prompt else None
 
         def guided(b):            # set_slot's keyword for slot b: its request's start state, -1 for a free request or an idle slot
             if self.constraint is None:
@@ -203,6 +218,19 @@ class ContinuousBatcher:
             self._pen_room = max(32, 1 << (need - 1).bit_length())
             return True
 
+        def ngram_short(slots):   # ... or a longer prompt, or a larger token budget, than the n-gram histories reserve?
+            if not self._ng_on:
+                return False
+            room = max([len(ngram_context_of(b) or ()) for b in slots] + [0])
+            # a request is fed its start token, then its tokens round by round: up to a whole round beyond its budget
+            fed = max([active[b].max_new_tokens for b in slots if active[b] is not None] + [self.default_new]) + 2 * self.check_every + 2
+            if room <= self._ng_room and fed <= self._ng_hist:
+                return False
+            if room > self._ng_room:
+                self._ng_room = max(32, 1 << (room - 1).bit_length())
+            self._ng_hist = max(self._ng_hist, fed)
+            return True
+
         def new_session(prev=None, keep=()):
             # (re-)capture the decode step on the cache's current slabs; every slot continues from `state`, the slots in `keep` with the
             # penalty history they had in `prev` (the others start a request: the constructor seeds their context sets)
@@ -214,7 +242,10 @@ class ContinuousBatcher:
                                logit_bias=self.penalties["logit_bias"])
             else:
                 sampler = dict(do_sample=self.do_sample, temperature=self.temperature, seed=seed, top_k=self.top_k, top_p=self.top_p,
-                               min_p=self.min_p, **self.penalties)
+                               min_p=self.min_p, no_repeat_ngram_size=self.default_sampling.no_repeat_ngram_size, **self.penalties)
+            if self._ng_on:
+                sampler.update(ngram_context_ids=[ngram_context_of(b) for b in range(B)], ngram_context_room=self._ng_room,
+                               ngram_history=self._ng_hist)
             sn = DecodeSession(m.language_model, cache, start, pos, self.check_every, use_graph=self.use_graph,
                                logprobs=self.want_logprobs, top_logprobs=self.n_top, penalty_context_ids=[context_of(b) for b in range(B)],
                                penalty_context_room=self._pen_room, penalty_history=m.cfg.vocab, constraint=self.constraint,
@@ -223,10 +254,12 @@ class ContinuousBatcher:
             if prev is not None:                        # the requests go on: so do their penalty histories and constraint states
                 sn.copy_penalty_history(prev, keep)
                 sn.copy_constraint_states(prev, keep)
+                sn.copy_ngram_history(prev, keep)
             cache.lens = lens_now                       # the session only reads them; this loop owns the bookkeeping
             self._grew = False
             return sn
         room_short(range(B))
+        ngram_short(range(B))
         sess = new_session()
         while any(r is not None for r in active) or self._other_work():
             if not any(r is not None for r in active):  # only the other kind of work is left (MixedBatcher: flow passes)
@@ -244,6 +277,13 @@ class ContinuousBatcher:
             lps = sess.pred_logprobs[:k].cpu() if self.want_logprobs else None
             if self.n_top:
                 tids, tlps, rks = sess.pred_top_ids[:k].cpu(), sess.pred_top_logprobs[:k].cpu(), sess.pred_rank[:k].cpu()
+            # n-gram histories: a negative length word is a history that ran full and stopped banning (UMV_NGRAM_FULL).  ngram_short sizes
+            # the rows so that a live request never gets there - a sizing slip must not pass as a silent loss of the ban.  (An idle slot
+            # records its parked start token every step and is started over by the set_slot below every round: check_every entries.)
+            if sess.ng_len is not None:
+                full = [b for b, n in enumerate(sess.ng_len.tolist()) if n < 0 and active[b] is not None]
+                if full:
+                    raise RuntimeError(f"the n-gram history of slot(s) {full} ran full: {sess.ng_hist.shape[1]} entries reserved")
             freed = []
             for b in range(B):
                 req = active[b]
@@ -284,12 +324,15 @@ class ContinuousBatcher:
             # ViT and LLM forward; the other slots take part with zero query tokens)
             for b, st in zip(freed, self._prefill_many(freed, [active[b] for b in freed])):
                 state[b] = st
-            if room_short(freed) or self._grew:         # an admitted request enlarged the cache (new slabs) or brought a prompt longer
-                sess = new_session(sess, [b for b in range(B) if b not in freed])       # than the penalty reservation: new captured step
+            # an admitted request enlarged the cache (new slabs) or brought a prompt longer than the penalty reservation, or a prompt or
+            # budget beyond the n-gram histories': new captured step (a list: each of the checks also enlarges its reservation)
+            if any([room_short(freed), ngram_short(freed), self._grew]):
+                sess = new_session(sess, [b for b in range(B) if b not in freed])
             else:
                 for b in freed:
                     row = dict(sampling=params_of(b), stream=0, draw=0) if self.per_request else {}
-                    sess.set_slot(b, *state[b], penalty_context_ids=context_of(b), **row, **guided(b))
+                    sess.set_slot(b, *state[b], penalty_context_ids=context_of(b), ngram_context_ids=ngram_context_of(b), **row,
+                                  **guided(b))
         return dict(self.results)
 
     # ------------------------------------------------------------------ hooks (MixedBatcher)
@@ -330,7 +373,7 @@ class ContinuousBatcher:
             room(kvl[0])
             view = m.forward_cache_update_vit(view, **gi)
         gi, kvl, rope = m.prepare_prompts(kvl, rope, [req.prompt], self.tokenizer, self.new_token_ids)
-        if self.penalize_prompt:
+        if self.penalize_prompt or self.ngram_prompt:
             req.prompt_ids = gi["packed_text_ids"].tolist()[1:-1]        # without the bos / eos wrapper
         room(kvl[0])
         view = m.forward_cache_update_text(view, **gi)
@@ -372,7 +415,7 @@ class ContinuousBatcher:
         gi, kvl, rope = m.prepare_prompts(kvl, rope, [r.prompt for r in reqs], self.tokenizer, self.new_token_ids)
         for n, r in zip(kvl, reqs):
             cap = self._check_room(n, r, cap)
-        if self.penalize_prompt:
+        if self.penalize_prompt or self.ngram_prompt:
             for r, ids in zip(reqs, gi["packed_text_ids"].split(gi["text_token_lens"].tolist())):
                 r.prompt_ids = ids.tolist()[1:-1]                        # without the bos / eos wrapper
         gi["text_token_lens"] = spread(gi["text_token_lens"])

@@ -67,8 +67,8 @@ class SpeculativeDecodeSession(DecodeSession):
         (default: the sample index, DecodeSession's default); seed: the seed of the params that carry none.  Greedy entries
         (SamplingParams()) are legal and may be mixed with sampled ones.  logprobs=True (with sampling): out_logprobs (fp32
         [B, max_length]) holds every emitted token's log-probability next to out_ids.  Penalised params, logit_bias, forced_ids,
-        top_logprobs and constraint raise ValueError.
-        Without sampling, any sampler, log-probability, forced-token, penalty, per-row or constraint keyword raises ValueError."""
+        top_logprobs, constraint and no_repeat_ngram_size (the keyword, or a size in a SamplingParams) raise ValueError.
+        Without sampling, any sampler, log-probability, forced-token, penalty, per-row, constraint or n-gram keyword raises ValueError."""
         k = int(draft_len)
         B = len(cache.lens)
         params, logprobs, seed = None, False, 0
@@ -76,6 +76,8 @@ class SpeculativeDecodeSession(DecodeSession):
             params = per_sample(sampling, B)
             if any(p.penalised for p in params):
                 raise ValueError("sampled speculative decode takes no penalties (a penalised SamplingParams)")
+            if any(p.no_repeat_ngram_size for p in params):
+                raise ValueError("speculative decode takes no no_repeat_ngram_size (a SamplingParams with a size)")
             logprobs, seed = bool(plain.pop("logprobs", False)), int(plain.get("seed", 0))
         elif sampling_streams is not None:
             raise ValueError("sampling_streams goes with sampling")
