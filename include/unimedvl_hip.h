@@ -791,6 +791,80 @@ typedef struct {
 } umv_spec_rows_step_args;
 int umv_decode_step_end_speculative_rows(const umv_spec_rows_step_args* a, umv_stream_t stream);
 
+/* ------------------------------------------------------------------ beam search decode
+ * K beams per request, 2 <= K <= UMV_BEAM_K_MAX (K = 1 is greedy decode and runs the plain step): a step has R = B * K ordinary rows,
+ * row b * K + i beam i of request b, each its own segment of a paged KV cache.  tests/beam_ref.py is this text in plain Python.
+ * Each live beam has an fp32 score s_i, [0, -inf, ..., -inf] at the start: all K rows start from one prompt and one start token.
+ * Step t = 0, 1, ... works on the rows' logits in this order:
+ *  1. Candidates.  The first n = 2K columns of every row in the top-n order above - y descending, column ascending, y the bf16 logit
+ *     (greedy definition) - each with lp = (y - ref) - logf(S) as the top-n alternatives define it, (ref, S) merged from lse_partial
+ *     in the greedy step end's order (umv_decode_step_end_logprob): a row's list is its umv_decode_top_logprobs list bit for bit.
+ *     total = s_i + lp, one fp32 add.  A beam whose s_i is not above -inf contributes nothing, nor does an id of -1 (a NaN row).
+ *  2. Order.  All candidates of the request by (total descending, beam ascending, place in the beam's own list ascending); r is a
+ *     candidate's place in that order.  Restricting each beam to its own 2K best does not change the first 2K of the full K * V order.
+ *  3. Walk in that order until K live successors are found.  A candidate whose token is end_token_id is a finished hypothesis if
+ *     r < K and is skipped otherwise; it never becomes a live beam.  Every other candidate becomes the next live beam, in order,
+ *     with (token, parent beam, total, lp).  V > 2K, so that K other candidates exist (a beam's list holds the end token once).
+ *     At the LAST step, t + 1 == max_len, every candidate with r < K is a finished hypothesis, whatever its token: this is how the
+ *     live beams are offered at max_length (HF generate: the length criterion ends every candidate of that step; only the first K
+ *     count).  A hypothesis' normalised score is total / norm[t], norm[t] = powf(t + 1, length_penalty) computed by the host in
+ *     fp32 (len_norm): t + 1 is its number of generated tokens, the end token counted; the one fp32 division is the device's.
+ *  4. Finished list, at most K entries.  While there is room an entry is appended; a full list replaces its worst entry - lowest
+ *     score, the latest among equals - only for a strictly better one.  An entry is fin_f (score, total, lp of its last token, 0)
+ *     and fin_i (step, parent beam = back-pointer into step - 1, last token, sequence number of the entry).
+ *  5. Done.  early_stopping: the request is done when its list is full.  Otherwise: when the list is full AND its worst score is
+ *     >= (best new live total) / norm[t] (HF's early_stopping=False heuristic, current length).  A done request's words are never
+ *     written again: its workgroup returns at once, its rows go on computing and are ignored.
+ *  6. The host takes the best hypothesis: highest score, the earlier entry among equals.
+ *
+ * KV plan.  L = the request's committed length after the step (tok_slot + 1), j0 = prompt length / 256.  Entries below j0 of a row's
+ * table row are the shared prompt pages.  From j0 on every row owns TWO private pages per page index (own [R][n_own][2], index
+ * j0 + q): the one its table row names and a spare.  Child c of parent p: entries j0 <= j < L / 256 (full pages) become
+ * table_old[p][j], a pointer only; if L % 256 != 0 and p != c, copies[c] = (table_old[p][L / 256], c's spare of that index,
+ * L % 256 rounded up to 8) and c's entry flips to the spare - sources are current pages, destinations spares, so a swap of two beams
+ * never overwrites its own source; slots at or above L hold nothing committed.  Otherwise copies[c] = (0, 0, 0).  The workgroup reads
+ * every table word it changes, barriers, then writes; no other workgroup touches its rows.  In the step that sets done, the table
+ * stays and the copies are (0, 0, 0).  So: the page a row appends to next is referenced by no other row; no page below a live row's
+ * length is written; only the fork's private pages are written.
+ *
+ * umv_beam_candidates: one workgroup of 512 threads per row, cand_ids (int32) / cand_lp (fp32) [R][n], rank [R] scratch (0).
+ * umv_beam_step_end: one workgroup per request, steps 2-5, the next ids, the back-pointers beam_tok / beam_parent / beam_lp row t, the
+ *   scores, slot / position / kv_len / step counter + 1 for the request's rows, the table rows and the copy list.  hdr [B][4] =
+ *   (entries in the list, entries ever, done, 0).  K * n_own <= UMV_BEAM_TABLE_ENTRIES.  UMV_ERR_ARG: a NULL pointer, K outside
+ *   [1, UMV_BEAM_K_MAX], misaligned copies / hdr.
+ * umv_beam_kv_copy: grid (chunk, layer, row); pools [2 * layers] device pointers, K pool then V^T pool of each layer; for each kv head
+ *   K [tokens][hd] and V^T [hd][tokens] go from the source page to the destination page in 16-byte accesses (hd % 8 == 0).  A row
+ *   with tokens = 0 leaves at its first branch; a page outside [0, npages) copies nothing. */
+#define UMV_BEAM_K_MAX 10
+#define UMV_BEAM_TABLE_ENTRIES 1024
+typedef struct {
+    int32_t* tok_slot;               /* [R] */
+    int32_t* tok_pos;                /* [R] */
+    int32_t* kv_len;                 /* [R] */
+    int64_t* ids;                    /* [R]: the tokens the next step is fed */
+    int64_t* step_idx;               /* [R]: one counter per row, all equal */
+    const int32_t* cand_ids;         /* [R][2K] */
+    const float* cand_lp;            /* [R][2K] */
+    float* scores;                   /* [R] */
+    int32_t* beam_tok;               /* [max_len][R] */
+    int32_t* beam_parent;            /* [max_len][R] */
+    float* beam_lp;                  /* [max_len][R] */
+    float* fin_f;                    /* [B][K][4] */
+    int32_t* fin_i;                  /* [B][K][4] */
+    int32_t* hdr;                    /* [B][4] */
+    const float* len_norm;           /* [max_len] */
+    int32_t* table;                  /* the page table rows of the R segments */
+    const int32_t* own;              /* [R][n_own][2] */
+    const int32_t* j0;               /* [B] */
+    int32_t* copies;                 /* [R][4]: source page, destination page, tokens, 0 */
+    int32_t table_stride, n_own, B, K, max_len, end_token_id, early_stopping;
+} umv_beam_step_args;
+int umv_beam_candidates(const uint16_t* logits, int64_t ldo, int V, const float* lse_partial, int n_tiles, int R, int n, int32_t* cand_ids,
+                        float* cand_lp, int32_t* rank, umv_stream_t stream);
+int umv_beam_step_end(const umv_beam_step_args* a, umv_stream_t stream);
+int umv_beam_kv_copy(const int32_t* copies, const void* const* pools, int R, int layers, int nkv, int hd, int npages, int chunks,
+                     umv_stream_t stream);
+
 
 /* TimestepEmbedder.timestep_embedding (modeling_utils.py:87-109): out[r] = bf16(cat(cos(t[r] * freqs), sin(t[r] * freqs))),
  * out [n, 2*half]; freqs [half] fp32 = exp(-ln(10000) * i / half) from the caller.  The two linears + SiLU of the embedder

@@ -332,6 +332,42 @@ static void bad_arguments() {
     EXPECT_ERR(umv_logit_ngram_ban_bf16(&ng, nullptr));
     ng.rows = nullptr; ng.temperature = 0.f; ng.M = 0;
     EXPECT_OK(umv_logit_ngram_ban_bf16(&ng, nullptr));           // no rows
+    // beam search decode
+    alignas(16) static int32_t beam_words[8];
+    EXPECT_ERR(umv_beam_candidates(nullptr, 64, 64, dummyf, 4, 1, 4, dummyi, dummyf, dummyi, nullptr));
+    EXPECT_ERR(umv_beam_candidates(dummy16, 64, 64, nullptr, 4, 1, 4, dummyi, dummyf, dummyi, nullptr));          // no statistics
+    EXPECT_ERR(umv_beam_candidates(dummy16, 64, 64, dummyf, 4, 1, 4, nullptr, dummyf, dummyi, nullptr));          // no id list
+    EXPECT_ERR(umv_beam_candidates(dummy16, 64, 64, dummyf, 4, 1, 5, dummyi, dummyf, dummyi, nullptr));           // 2K is even
+    EXPECT_ERR(umv_beam_candidates(dummy16, 64, 64, dummyf, 4, 1, 22, dummyi, dummyf, dummyi, nullptr));          // K above the maximum
+    EXPECT_ERR(umv_beam_candidates(dummy16, 64, 4, dummyf, 1, 1, 4, dummyi, dummyf, dummyi, nullptr));            // V must exceed 2K
+    EXPECT_ERR(umv_beam_candidates(dummy16, 64, 64, dummyf, 3, 1, 4, dummyi, dummyf, dummyi, nullptr));           // 64 columns are not 3 tiles
+    EXPECT_OK(umv_beam_candidates(dummy16, 64, 64, dummyf, 4, 0, 4, dummyi, dummyf, dummyi, nullptr));            // no rows
+    EXPECT_ERR(umv_beam_step_end(nullptr, nullptr));
+    umv_beam_step_args bs;
+    std::memset(&bs, 0, sizeof bs);
+    EXPECT_ERR(umv_beam_step_end(&bs, nullptr));
+    bs.tok_slot = dummyi; bs.tok_pos = dummyi; bs.kv_len = dummyi; bs.ids = dummyl; bs.step_idx = dummyl; bs.cand_ids = dummyi;
+    bs.cand_lp = dummyf; bs.scores = dummyf; bs.beam_tok = dummyi; bs.beam_parent = dummyi; bs.beam_lp = dummyf; bs.fin_f = dummyf;
+    bs.fin_i = dummyi; bs.hdr = beam_words; bs.len_norm = dummyf; bs.table = dummyi; bs.own = dummyi; bs.j0 = dummyi; bs.copies = beam_words + 4;
+    bs.table_stride = 8; bs.n_own = 2; bs.B = 0; bs.K = 3; bs.max_len = 4; bs.end_token_id = -1;
+    EXPECT_OK(umv_beam_step_end(&bs, nullptr));                  // no requests
+    bs.K = 0;
+    EXPECT_ERR(umv_beam_step_end(&bs, nullptr));
+    bs.K = UMV_BEAM_K_MAX + 1;
+    EXPECT_ERR(umv_beam_step_end(&bs, nullptr));
+    bs.K = 3; bs.n_own = UMV_BEAM_TABLE_ENTRIES;                 // K * n_own above what a workgroup carries
+    EXPECT_ERR(umv_beam_step_end(&bs, nullptr));
+    bs.n_own = 2; bs.copies = beam_words + 1;                    // misaligned copy list
+    EXPECT_ERR(umv_beam_step_end(&bs, nullptr));
+    bs.copies = beam_words + 4; bs.own = nullptr;
+    EXPECT_ERR(umv_beam_step_end(&bs, nullptr));
+    const void* beam_pools[2] = {dummy16, dummy16};
+    EXPECT_ERR(umv_beam_kv_copy(nullptr, beam_pools, 0, 1, 2, 128, 4, 1, nullptr));
+    EXPECT_ERR(umv_beam_kv_copy(beam_words, nullptr, 0, 1, 2, 128, 4, 1, nullptr));
+    EXPECT_ERR(umv_beam_kv_copy(beam_words, beam_pools, 0, 1, 2, 100, 4, 1, nullptr));    // hd is a multiple of 8
+    EXPECT_ERR(umv_beam_kv_copy(beam_words, beam_pools, 0, 1, 2, 128, 4, 0, nullptr));    // no chunks
+    EXPECT_ERR(umv_beam_kv_copy(beam_words + 1, beam_pools, 0, 1, 2, 128, 4, 1, nullptr));   // misaligned copy list
+    EXPECT_OK(umv_beam_kv_copy(beam_words, beam_pools, 0, 1, 2, 128, 4, 1, nullptr));     // no rows
     // speculative step end
     EXPECT_ERR(umv_decode_step_end_speculative(nullptr, nullptr));
     umv_spec_step_args sp;

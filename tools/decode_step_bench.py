@@ -22,6 +22,9 @@ about 5 us) in a kernel trace of a decode run: --trace-arm NAME runs that arm of
                 nearly flat logits: c drops the untruncated pick on almost every step (the slow branch), b keeps it with probability
                 about 0.9.  The branch shares are counted on --probe further steps per arm, outside the timing: a step took the fast
                 branch iff its token is the column of the largest lm_head key.
+  beam          beam search decode (beam.BeamDecodeSession on a PagedCache, random weights and no end token, so every step reorders):
+                b_beam_1x4 / c_beam_8x4 = 1 / 8 requests of 4 beams, each next to the plain greedy session with logprobs at the same
+                row count (a_rows4 / a_rows32) - what the three launches that end a beam step add over the plain step end
   per_request   greedy / do_sample / top_p / all (top_p, logprobs, the three penalties), each as a scalar session and as the session
                 whose per-row table holds the same parameters in every row, and mixed_rows: the four samplers, two rows each
   all           every suite, the model loaded once
@@ -29,7 +32,7 @@ about 5 us) in a kernel trace of a decode run: --trace-arm NAME runs that arm of
 The JSON of a suite keeps the keys of the tool it replaces (profiles/*_bench.json).  Only the public session API is used, so the tool
 runs against another checkout of the package on PYTHONPATH as well.
 
-    python tools/decode_step_bench.py SUITE [--steps 64] [--warmup 8] [--repeats 3] [--probe 32] [--trace-arm ARM] [--out FILE]"""
+    python tools/decode_step_bench.py SUITE [--steps 64] [--warmup 8] [--repeats 3] [--probe 32] [--trace-arm ARM] [--context 1060] [--out FILE]"""
 import argparse
 import contextlib
 import json
@@ -75,16 +78,27 @@ def _environ(env):
 
 
 def _session(llm, kw, total):
+    """rows (default B): the samples of the session; num_beams: a beam session of that many beams over `rows` requests on a paged cache"""
     from unimedvl_amd.decode import DecodeSession
     from unimedvl_amd.kvcache import NaiveCache
     cfg, dev = llm.cfg, llm.device
     kw = dict(kw(cfg) if callable(kw) else kw)
+    n, beams = kw.pop("rows", B), kw.pop("num_beams", 0)
+    start = torch.randint(1000, 100000, (n,), generator=torch.Generator().manual_seed(5))
+    pos = torch.full((n,), CONTEXT, dtype=torch.int64)
+    if beams:
+        from unimedvl_amd.beam import BeamDecodeSession
+        from unimedvl_amd.kvcache import PagedCache
+        pages = (CONTEXT + total + 8) // 256 + 2
+        cache = PagedCache(cfg.layers, pool_pages=n * pages * (1 + 2 * beams) + 1, max_context=pages * 256)
+        cache.ensure_tokens([CONTEXT] * n, cfg.kv_heads, cfg.head_dim, dev)
+        cache.lens = [CONTEXT] * n
+        return BeamDecodeSession(llm, cache, start, pos, total + 2, beams, use_graph=True, **kw)
     cache = NaiveCache(cfg.layers)
-    cache.ensure(B, CONTEXT + total + 8, cfg.kv_heads, cfg.head_dim, dev)
-    cache.lens = [CONTEXT] * B           # a context of zero keys / values: timing depends on lengths only
-    start = torch.randint(1000, 100000, (B,), generator=torch.Generator().manual_seed(5))
+    cache.ensure(n, CONTEXT + total + 8, cfg.kv_heads, cfg.head_dim, dev)
+    cache.lens = [CONTEXT] * n           # a context of zero keys / values: timing depends on lengths only
     with _environ(kw.pop("env", {})):
-        return DecodeSession(llm, cache, start, torch.full((B,), CONTEXT, dtype=torch.int64), total + 1, use_graph=True, **kw)
+        return DecodeSession(llm, cache, start, pos, total + 1, use_graph=True, **kw)
 
 
 def _diff(out, arm, base, key):
@@ -332,8 +346,25 @@ PER_REQUEST = Suite(arms=_per_request_arms(), over=[(name + "_rows", name + "_sc
                     + [("mixed_rows", "all_scalar", "over_all_scalar_us"), ("mixed_rows", "greedy_scalar", "over_greedy_scalar_us")],
                     spread=[], head=dict(table_bytes=48 * B), hook=_same_tokens)
 
+# ---- beam search decode
+def _beam_reorders(run, res):
+    for arm, s in run.sessions.items():
+        if hasattr(s, "beam"):
+            n, K = s.steps_done, s.K
+            own = torch.arange(K, dtype=torch.int32, device=s.beam.beam_parent.device).repeat(s.requests)
+            res[arm].update(rows=s.rows, nsplit=s.nsplit, done=s.done(),
+                            rows_that_changed_parent=round(float((s.beam.beam_parent[:n] != own).float().mean()), 3))
+        else:
+            res[arm].update(rows=s.rows, nsplit=s.nsplit)
+
+
+BEAM = Suite(arms={"a_rows4": dict(rows=4, logprobs=True), "b_beam_1x4": dict(rows=1, num_beams=4),
+                   "a_rows32": dict(rows=32, logprobs=True), "c_beam_8x4": dict(rows=8, num_beams=4)},
+             over=[("b_beam_1x4", "a_rows4", "over_plain_us"), ("c_beam_8x4", "a_rows32", "over_plain_us")],
+             spread=[("a_rows4", "a_rows4_spread_us"), ("a_rows32", "a_rows32_spread_us")], hook=_beam_reorders)
+
 SUITES = {"penalties": PENALTIES, "constraint": CONSTRAINT, "ngram": NGRAM_SUITE, "logprobs": LOGPROBS, "top_logprobs": TOP_LOGPROBS, "truncated": TRUNCATED,
-          "per_request": PER_REQUEST}
+          "per_request": PER_REQUEST, "beam": BEAM}
 
 
 def main():
@@ -345,8 +376,10 @@ def main():
     ap.add_argument("--probe", type=int, default=32, help="truncated: further steps per arm on which the branch shares are counted")
     ap.add_argument("--legs", default="step,score", help="logprobs: which of its two legs to run")
     ap.add_argument("--trace-arm", default=None, help="run this arm of the suite alone, for a kernel trace of this tool")
+    ap.add_argument("--context", type=int, default=CONTEXT, help="tokens of context per sample (beam: L mod 256 sets what a reorder copies)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    globals()["CONTEXT"] = args.context
     if not torch.cuda.is_available():
         raise SystemExit("decode_step_bench needs a GPU")
     from unimedvl_amd.bagel import Bagel

@@ -128,6 +128,20 @@ class SpecRowsStepArgs(C.Structure):
     ]
 
 
+class BeamStepArgs(C.Structure):
+    """umv_beam_step_args: the step end of a beam search step (umv_beam_step_end)"""
+    _fields_ = [
+        ("tok_slot", C.c_void_p), ("tok_pos", C.c_void_p), ("kv_len", C.c_void_p), ("ids", C.c_void_p), ("step_idx", C.c_void_p),
+        ("cand_ids", C.c_void_p), ("cand_lp", C.c_void_p), ("scores", C.c_void_p), ("beam_tok", C.c_void_p), ("beam_parent", C.c_void_p),
+        ("beam_lp", C.c_void_p), ("fin_f", C.c_void_p), ("fin_i", C.c_void_p), ("hdr", C.c_void_p), ("len_norm", C.c_void_p),
+        ("table", C.c_void_p), ("own", C.c_void_p), ("j0", C.c_void_p), ("copies", C.c_void_p),
+        ("table_stride", C.c_int32), ("n_own", C.c_int32), ("B", C.c_int32), ("K", C.c_int32), ("max_len", C.c_int32),
+        ("end_token_id", C.c_int32), ("early_stopping", C.c_int32),
+    ]
+
+
+# beam search decode: the most beams a request can have, and the full-page table entries one request's step end can carry (K * n_own)
+BEAM_K_MAX, BEAM_TABLE_ENTRIES = 10, 1024
 # umv_logit_penalty_args.count words: bits 0..29 the count, then "in the context set" and "in the row's visit list"
 PENALTY_COUNT_MASK, PENALTY_CONTEXT, PENALTY_LISTED = 0x3FFFFFFF, 0x40000000, 0x80000000
 # umv_decode_top_logprobs: the most alternatives a row can ask for, and the step end whose merge order the statistics take
@@ -218,6 +232,10 @@ _SIGS = {
     "umv_decode_pick_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "umv_decode_step_end_speculative_rows": (C.c_int, [C.POINTER(SpecRowsStepArgs), C.c_void_p]),
+    "umv_beam_candidates": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
+    "umv_beam_step_end": (C.c_int, [C.POINTER(BeamStepArgs), C.c_void_p]),
+    "umv_beam_kv_copy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "umv_timestep_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "umv_cfg_renorm_euler": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.c_void_p]),

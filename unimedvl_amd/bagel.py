@@ -25,7 +25,7 @@ from .data_utils import (PackedVitImages, get_flattened_position_ids_extrapolate
 from .decode import DecodeSession
 from .sampling import off_neutral, per_sample
 from .prep import BagelPrep
-from .kvcache import NaiveCache
+from .kvcache import NaiveCache, PagedCache
 from .llm import Qwen2MoT
 from .vit import SiglipVisionModel
 from .weights import GlueWeights, LLMWeights, ViTWeights
@@ -77,6 +77,7 @@ class Bagel(BagelPrep):
         self.device_patchify = os.environ.get("UMV_DEVICE_PATCHIFY", "1") not in ("0", "")
         self._vit_graphs = {}
         self.prefill_graph_max = 8          # captured image-span graphs kept (one per cache and patch grid; ~0.1 GB of activations each)
+        self.beam_context_tokens = 8192     # chat(num_beams > 1): the longest context its paged cache is sized for
         self.chat_cache_tokens = 0          # > 0: chat() prefills / decodes in one pooled, reserved cache of that capacity
         self._chat_cache = None
 
@@ -319,7 +320,8 @@ class Bagel(BagelPrep):
                       repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
                       logit_bias=None, penalty_context_ids=None, draft_len: int = 0, draft_ngram=(2, 4), draft_context_ids=None,
                       predicted_ids=None, sampling=None, top_logprobs: int = 0, constraint=None, constraint_states=None,
-                      no_repeat_ngram_size=0, ngram_context_ids=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+                      no_repeat_ngram_size=0, ngram_context_ids=None, num_beams: int = 1, length_penalty: float = 1.0,
+                      early_stopping: bool = False, num_return_sequences: int = 1, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """Greedy decode (bagel.py:1236-1317).  Returns [steps, B] int64 whose row 0 holds the
         start tokens.  Like the reference, the batch stops when SAMPLE 0 emits end_token_id
         (bagel.py:1313); per_sample_eos=True is the batched extension (stops when every sample
@@ -359,7 +361,26 @@ class Bagel(BagelPrep):
         n-grams), after the penalties and before the constraint mask; ids, logits, logprobs and top_logprobs are those of the banned
         logits.  The history is the start token and what is fed after it; ngram_context_ids (per sample a token list, the prompt)
         puts tokens in front of that - this call has no token ids of its own.  HF counts the prompt.  With sampling= a sample's size
-        is its SamplingParams.no_repeat_ngram_size and the keyword stays 0.  With draft_len > 0 it raises."""
+        is its SamplingParams.no_repeat_ngram_size and the keyword stays 0.  With draft_len > 0 it raises.
+        num_beams = K > 1 (at most 10, B * K <= 64): beam search decode (beam.BeamDecodeSession; include/unimedvl_hip.h, beam search
+        decode) as HF's generate(num_beams=K, do_sample=False) defines it, with length_penalty and early_stopping (True / False) as
+        there.  past_key_values must be a PagedCache (ValueError otherwise): the beams decode on a throwaway fork that shares the
+        prompt's pages, and the cache itself is left as it was - nothing is committed to it.  Returns the usual matrix holding every
+        sample's BEST hypothesis: row 0 the start tokens, then its tokens, the end token included; rows after a sample's end token
+        are filled with the end token.  return_logprobs=True adds fp32 [rows - 1, B]: row s the log-probability of ids[s + 1] (0
+        behind a sample's end).  self.last_beam_hypotheses keeps, per sample, the num_return_sequences (<= K) best hypotheses as
+        dicts (tokens, tokens_no_end, score - the length-normalised one -, total, logprobs).  Excludes do_sample, sampling,
+        draft_len, top_logprobs, return_logits, constraint, the penalties, logit_bias, no_repeat_ngram_size and top_k / top_p /
+        min_p (ValueError before any launch); 1 = off: today's call."""
+        num_beams = ops.check_beams(num_beams, self.cfg.vocab, len(past_key_values.lens))
+        if num_beams > 1:
+            from .beam import check_beam_keywords
+            check_beam_keywords(num_beams, do_sample=do_sample, sampling=sampling, draft_len=draft_len, top_logprobs=top_logprobs,
+                                return_logits=return_logits, constraint=constraint, repetition_penalty=repetition_penalty,
+                                presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, logit_bias=logit_bias,
+                                no_repeat_ngram_size=no_repeat_ngram_size, top_k=top_k, top_p=top_p, min_p=min_p)
+            return self._generate_text_beams(past_key_values, packed_start_tokens, packed_query_position_ids, max_length, end_token_id,
+                                             return_logprobs, num_beams, length_penalty, early_stopping, num_return_sequences)
         sizes = [ops.check_ngram(v) for v in no_repeat_ngram_size] if isinstance(no_repeat_ngram_size, (list, tuple)) else \
             [ops.check_ngram(no_repeat_ngram_size)]
         if draft_len and (any(sizes) or (sampling is not None and any(p.no_repeat_ngram_size for p in per_sample(
@@ -454,6 +475,33 @@ class Bagel(BagelPrep):
             res += (TopLogprobs(sess.pred_top_ids[:rows].clone(), sess.pred_top_logprobs[:rows].clone(), sess.pred_rank[:rows].clone()),)
         return res if len(res) > 1 else out
 
+    def _generate_text_beams(self, cache, start_tokens, positions, max_length, end_token_id, return_logprobs, num_beams, length_penalty,
+                             early_stopping, num_return_sequences):
+        """generate_text with num_beams > 1: one beam search on a fork of `cache`, the best hypotheses as the usual matrix"""
+        from .beam import beam_generate, check_beam_options
+        check_beam_options(num_beams, length_penalty, early_stopping, num_return_sequences)
+        if not hasattr(cache, "fork_beams"):
+            raise ValueError(f"num_beams > 1 needs past_key_values to be a PagedCache, got {type(cache).__name__}")
+        B = len(cache.lens)
+        starts = start_tokens.to(device=self.device, dtype=torch.int64).reshape(1, -1)
+        if max_length <= 0:
+            self.last_beam_hypotheses = [[] for _ in range(B)]
+            out = torch.zeros((0, B), dtype=torch.int64, device=self.device)
+            return (out, torch.zeros((0, B), dtype=torch.float32, device=self.device)) if return_logprobs else out
+        hyps = beam_generate(self.language_model, cache, start_tokens, positions, max_length, num_beams, end_token_id=end_token_id,
+                             length_penalty=length_penalty, early_stopping=early_stopping, num_return_sequences=num_return_sequences,
+                             use_graph=self.decode_use_graph, eos_check_every=self.eos_check_every)
+        self.last_beam_hypotheses = hyps
+        n = max(len(h[0]["tokens"]) for h in hyps)
+        fill = 0 if end_token_id is None else int(end_token_id)
+        ids = torch.full((n, B), fill, dtype=torch.int64)
+        lps = torch.zeros((n, B), dtype=torch.float32)
+        for b, h in enumerate(hyps):
+            ids[:len(h[0]["tokens"]), b] = torch.tensor(h[0]["tokens"], dtype=torch.int64)
+            lps[:len(h[0]["logprobs"]), b] = torch.tensor(h[0]["logprobs"], dtype=torch.float32)
+        out = torch.cat([starts, ids.to(self.device)], 0)
+        return (out, lps.to(self.device)) if return_logprobs else out
+
     def _generate_text_speculative(self, cache, start_tokens, positions, max_length, end_token_id, per_sample_eos, draft_len,
                                    draft_ngram, draft_context_ids, predicted_ids, plain):
         """generate_text with drafts: the plain call's matrix row s + 1 is a sample's emitted token s.  The plain call stops at row
@@ -499,6 +547,7 @@ class Bagel(BagelPrep):
              penalize_prompt: bool = False, draft_len: int = 0, draft_ngram=(2, 4), predicted_ids=None,
              sampling=None, top_logprobs: int = 0, choices=None, choices_after: str = "stop",
              no_repeat_ngram_size: int = 0, no_repeat_ngram_prompt: bool = False,
+             num_beams: int = 1, length_penalty: float = 1.0, early_stopping: bool = False, num_return_sequences: int = 1,
              top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """ViT-only VQA convenience path (bagel.py:1321-1392).  return_logprobs=True: returns (answer, token_ids, token_logprobs) -
         the generated tokens behind the answer (the end token excluded) and the log-probability of each (generate_text).
@@ -519,13 +568,25 @@ class Bagel(BagelPrep):
         no_repeat_ngram_size (0 = off): the answer repeats no n-gram of that size (generate_text); with sampling= the size is the
         SamplingParams'.  no_repeat_ngram_prompt=True seeds the history with the prompt's text tokens - the list penalize_prompt
         uses, without the bos / eos wrapper - so that an n-gram of the prompt is not repeated either; the default counts generated
-        tokens only.  (HF's generate counts the prompt.)"""
+        tokens only.  (HF's generate counts the prompt.)
+        num_beams > 1: beam search decode (generate_text) - the context is prefilled into a PagedCache of its own
+        (self.beam_context_tokens bounds the prompt) and the best hypothesis is the answer; length_penalty / early_stopping as HF's.
+        With num_return_sequences > 1 the call returns a list of (answer, score), best first.  It excludes what generate_text
+        excludes, and `choices`."""
+        if num_beams > 1:
+            from .beam import check_beam_keywords
+            check_beam_keywords(ops.check_beams(num_beams, self.cfg.vocab, 1), choices=choices, draft_len=draft_len, sampling=sampling)
         constraint = None
         if choices is not None:
             from .constraints import TokenAutomaton
             constraint = TokenAutomaton.from_choices([tokenizer.encode(c) if isinstance(c, str) else [int(v) for v in c] for c in choices],
                                                      int(new_token_ids["eos_token_id"]), after=choices_after)
-        if self.chat_cache_tokens > 0:       # serving: one reserved cache reused by every request (stable slabs -> graph prefill)
+        if num_beams > 1:                    # the beams fork the prompt's pages: pages for the context, and two per beam and page index
+            P = ops.KV_PAGE
+            private = 2 * num_beams * ((max_length + 1 + P - 1) // P + 1)
+            cache = PagedCache(self.cfg.layers, pool_pages=(self.beam_context_tokens + P - 1) // P + private + 1,
+                               max_context=self.beam_context_tokens + max_length + 1 + P)
+        elif self.chat_cache_tokens > 0:       # serving: one reserved cache reused by every request (stable slabs -> graph prefill)
             if self._chat_cache is None or self._chat_cache.cap < self.chat_cache_tokens:
                 self._chat_cache = NaiveCache(self.cfg.layers)
                 self._chat_cache.reserve(1, self.chat_cache_tokens, self.cfg.kv_heads, self.cfg.head_dim, self.device)
@@ -554,7 +615,13 @@ class Bagel(BagelPrep):
                                  repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                                  frequency_penalty=frequency_penalty, logit_bias=logit_bias, penalty_context_ids=prompt_ids,
                                  sampling=sampling, constraint=constraint, no_repeat_ngram_size=no_repeat_ngram_size,
-                                 ngram_context_ids=[text_ids] if no_repeat_ngram_prompt else None, **draft, **gi)
+                                 ngram_context_ids=[text_ids] if no_repeat_ngram_prompt else None, num_beams=num_beams,
+                                 length_penalty=length_penalty, early_stopping=early_stopping, num_return_sequences=num_return_sequences,
+                                 **draft, **gi)
+        if num_beams > 1 and num_return_sequences > 1:
+            def text(tokens):
+                return tokenizer.decode(torch.tensor([int(gi["packed_start_tokens"][0])] + tokens)).split("<|im_end|>")[0].split("<|im_start|>")[1]
+            return [(text(h["tokens"]), h["score"]) for h in self.last_beam_hypotheses[0]]
         top = None
         if top_logprobs:
             ids, lp, top = ids
@@ -562,6 +629,9 @@ class Bagel(BagelPrep):
             ids, lp = ids
         output = tokenizer.decode(ids[:, 0].cpu())
         answer = output.split("<|im_end|>")[0].split("<|im_start|>")[1]
+        if num_beams > 1 and return_logprobs:           # the best hypothesis' own lists, the end token excluded
+            best = self.last_beam_hypotheses[0][0]
+            return answer, best["tokens_no_end"], best["logprobs"][:len(best["tokens_no_end"])]
         if return_logprobs or top is not None:          # lp[s] belongs to ids[s + 1]
             n = max(ids.shape[0] - 1, 0)
             res = (answer, ids[1:, 0].tolist(), lp[:n, 0].tolist())

@@ -61,6 +61,13 @@ DEFAULT_CONFIG = {
     # ranks the same closed set exactly, at one forced row per candidate; this costs one row and returns the sampler's pick
     "choices": None,
     "choices_after": "stop",
+    # beam search decode (not reference keys; "num_beams": 1 = off): HF's generate(num_beams=K, do_sample=False) with its
+    # "length_penalty" and "early_stopping" (Bagel.chat) - needs "do_sample": False and none of the sampler, penalty, n-gram, draft and
+    # choice keys above.  "num_return_sequences" > 1: the result also carries "answers", a list of (answer, score), best first
+    "num_beams": 1,
+    "length_penalty": 1.0,
+    "early_stopping": False,
+    "num_return_sequences": 1,
 }
 
 # codes/data/default.yaml vlm_sft.image_transform_args (read by eval/vlm/utils.py:486-502)
@@ -220,8 +227,16 @@ class VQAInferencer:
             sampler = {k: v for k, v in passed.items() if v is not None and k not in ("logit_bias", "penalize_prompt")}
             sampler.update(sampling=sampling if isinstance(sampling, SamplingParams) else SamplingParams(**sampling),
                            logit_bias=penalties["logit_bias"], penalize_prompt=penalties["penalize_prompt"])
+        answers = None
+        if int(self.config.get("num_beams", 1) or 1) > 1:
+            extra.update({k: self.config.get(k, DEFAULT_CONFIG[k]) for k in ("num_beams", "length_penalty", "early_stopping", "num_return_sequences")})
+            if extra["num_return_sequences"] > 1:           # several answers: each comes with its score, not with per-token values
+                extra.pop("return_logprobs", None)
+                want_lp = False
         answer = self.model.chat(self.tokenizer, self.new_token_ids, self.image_transform, images=images,
                                  prompt=conversation, max_length=max_new_tokens, **sampler, **extra)
+        if extra.get("num_return_sequences", 1) > 1:        # (answer, score) pairs, best first
+            answers, answer = answer, answer[0][0]
         top = None
         if n_top:
             answer, token_ids, token_logprobs, top = answer
@@ -229,6 +244,8 @@ class VQAInferencer:
             answer, token_ids, token_logprobs = answer
         result = {"answer": answer, "input_image": input_image, "time": time.time() - start, "image_path": image_path,
                   "prompt": prompt, "timestamp": datetime.now().strftime("%Y-%m-%d %H:%M:%S")}
+        if answers is not None:
+            result.update(answers=answers)
         if want_lp:
             result.update(token_ids=token_ids, token_logprobs=token_logprobs)
         if top is not None:

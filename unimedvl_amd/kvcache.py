@@ -329,25 +329,97 @@ class PagedCache:
         c.lens = list(self.lens)
         c.nkv, c.hd, c.device = self.nkv, self.hd, self.device
         if self.pool is not None:
-            src = self.pool
-            c.pool = _PagePool.__new__(_PagePool)
+            c.pool = self._over_same_pools(len(self.lens)).pool
             c.pool.host_table = [list(self._pages(s)[:(n + ops.KV_PAGE - 1) // ops.KV_PAGE]) for s, n in enumerate(self.lens)]
-            c.pool.table = torch.zeros_like(src.table[self._seg0:self._seg0 + len(self.lens)])
             rows = torch.zeros(c.pool.table.shape, dtype=torch.int32)
             for s, pages in enumerate(c.pool.host_table):
                 rows[s, :len(pages)] = torch.tensor(pages, dtype=torch.int32)
             c.pool.table.copy_(rows)
-            c.pool.free, c.pool.refs = src.free, src.refs            # ONE allocator: shared lists
-            c.pool.npages, c.pool.nkv, c.pool.hd, c.pool.device = src.npages, src.nkv, src.hd, src.device
-            c.pool.slabs = []
-            for sl in src.slabs:
-                v = ops.PagedSlab.__new__(ops.PagedSlab)
-                v.k, v.vt, v.table, v.nkv, v.hd, v.cap = sl.k, sl.vt, c.pool.table, sl.nkv, sl.hd, sl.cap
-                c.pool.slabs.append(v)
             for pages in c.pool.host_table:
                 for p in pages:
-                    src.refs[p] += 1
+                    self.pool.refs[p] += 1
         return c
+
+    def _over_same_pools(self, nrows):
+        """An empty cache with a table of `nrows` rows of its own over this cache's pools and allocator (snapshot(), fork_beams())."""
+        src = self.pool
+        c = PagedCache(self._num_layers, self.pool_pages, self.max_pages * ops.KV_PAGE)
+        c.nkv, c.hd, c.device = self.nkv, self.hd, self.device
+        c.pool = _PagePool.__new__(_PagePool)
+        c.pool.host_table = [[] for _ in range(nrows)]
+        c.pool.table = torch.zeros((nrows, src.table.shape[1]), dtype=torch.int32, device=src.table.device)
+        c.pool.free, c.pool.refs = src.free, src.refs            # ONE allocator: shared lists
+        c.pool.npages, c.pool.nkv, c.pool.hd, c.pool.device = src.npages, src.nkv, src.hd, src.device
+        c.pool.slabs = []
+        for sl in src.slabs:
+            v = ops.PagedSlab.__new__(ops.PagedSlab)
+            v.k, v.vt, v.table, v.nkv, v.hd, v.cap = sl.k, sl.vt, c.pool.table, sl.nkv, sl.hd, sl.cap
+            c.pool.slabs.append(v)
+        return c
+
+    def fork_beams(self, K, horizon):
+        """The KV plan of beam search decode (include/unimedvl_hip.h, beam search decode; beam.BeamDecodeSession): a throwaway cache
+        over the same pools and allocator with K table rows per segment, row b * K + i for beam i of segment b.  Every row shares
+        segment b's FULL prompt pages (reference counts) and owns, for every page index from j0 = lens[b] // 256 up to the one slot
+        lens[b] + horizon - 1 falls in, TWO private pages: a current one, which its table row names, and a spare.  The partially
+        filled prompt page is copied into every row's current page at j0.  beam_own (int32 [rows, NP, 2] on the device: the pair of
+        row r and page index j0 + q) and beam_j0 (int32 [segments]) are what the step end reads.  The device rewrites the table rows
+        while it decodes; nothing is ever read back: release_all() returns every page by the host lists, each exactly once.
+        All or nothing: a refused fork (RuntimeError: pool exhausted; ValueError: past the table's reach) takes no page."""
+        if self.pool is None:
+            raise ValueError("fork_beams: the cache holds no context")
+        if isinstance(K, bool) or int(K) != K or K < 1 or horizon < 1:
+            raise ValueError(f"fork_beams: K (got {K!r}) and horizon (got {horizon!r}) must be positive integers")
+        P, K = ops.KV_PAGE, int(K)
+        B = len(self.lens)
+        j0 = [n // P for n in self.lens]
+        npg = [(n + horizon - 1) // P - j + 1 for n, j in zip(self.lens, j0)]
+        if max(j + m for j, m in zip(j0, npg)) > self.max_pages:
+            raise ValueError(f"fork_beams: {max(self.lens) + horizon} tokens exceed the page table's reach of {self.cap} (max_context)")
+        want = 2 * K * sum(npg)
+        if want > len(self.pool.free):
+            raise RuntimeError(f"paged KV pool exhausted: {want} pages wanted, {len(self.pool.free)} of {self.pool.npages - 1} free "
+                               f"({P} tokens each): raise pool_pages")
+        c = self._over_same_pools(B * K)
+        c.lens = [n for n in self.lens for _ in range(K)]
+        NP = max(npg)
+        rows = torch.zeros(c.pool.table.shape, dtype=torch.int32)
+        own = torch.zeros((B * K, NP, 2), dtype=torch.int32)
+        c.beam_spares = [[] for _ in range(B * K)]
+        for b in range(B):
+            shared = list(self._pages(b)[:j0[b]])
+            for r in range(b * K, (b + 1) * K):
+                for p in shared:
+                    self.pool.refs[p] += 1
+                cur = [self.pool.alloc() for _ in range(npg[b])]
+                c.beam_spares[r] = [self.pool.alloc() for _ in range(npg[b])]
+                c.pool.host_table[r] = shared + cur
+                rows[r, :len(shared) + len(cur)] = torch.tensor(shared + cur, dtype=torch.int32)
+                own[r, :npg[b], 0] = torch.tensor(cur, dtype=torch.int32)
+                own[r, :npg[b], 1] = torch.tensor(c.beam_spares[r], dtype=torch.int32)
+            if self.lens[b] % P:                     # the partially filled prompt page: every row's current page at j0 starts as a copy
+                at = own[b * K:(b + 1) * K, 0, 0].to(device=self.device, dtype=torch.int64)
+                old = self._pages(b)[j0[b]]
+                for sl in self.pool.slabs:
+                    sl.k[at] = sl.k[old].clone()
+                    sl.vt[at] = sl.vt[old].clone()
+        c.pool.table.copy_(rows)
+        c.beam_own = own.to(self.device)
+        c.beam_j0 = torch.tensor(j0, dtype=torch.int32).to(self.device)
+        c.beam_K = K
+        return c
+
+    def release_all(self):
+        """Return every page this cache holds to the pool by the host lists - a fork's spares included -, each exactly once, and
+        zero the device table."""
+        for seg in range(len(self.lens)):
+            for p in self._pages(seg) + (self.beam_spares[seg] if getattr(self, "beam_spares", None) else []):
+                self.pool.unref(p)
+            self._pages(seg).clear()
+            if getattr(self, "beam_spares", None):
+                self.beam_spares[seg] = []
+            self.lens[seg] = 0
+        self.pool.table[self._seg0:self._seg0 + len(self.lens)].zero_()
 
     def view_segments(self, start, end):
         """A cache over segments [start, end) of the same table and pools (no copy)."""

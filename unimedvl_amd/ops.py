@@ -1158,6 +1158,118 @@ def top_logprobs(logits, ids, n, temperature=0.0):
     return top_ids, top_lp, rank
 
 
+# ----------------------------------------------------------------------------- beam search decode (include/unimedvl_hip.h)
+def check_beams(num_beams, vocab=None, rows=None):
+    """The beams per request as an int: 1 = off, at most _lib.BEAM_K_MAX, the vocabulary larger than 2K and - rows the request count -
+    at most 64 rows in all; ValueError otherwise."""
+    if isinstance(num_beams, bool) or int(num_beams) != num_beams or not 1 <= num_beams <= _lib.BEAM_K_MAX:
+        raise ValueError(f"num_beams must be an integer in [1, {_lib.BEAM_K_MAX}] (1 = off), got {num_beams!r}")
+    K = int(num_beams)
+    if K > 1 and vocab is not None and vocab <= 2 * K:
+        raise ValueError(f"num_beams = {K} needs a vocabulary of more than {2 * K} tokens (got {vocab})")
+    if K > 1 and rows is not None and rows * K > 64:
+        raise ValueError(f"beam search decode serves at most 64 rows per step: {rows} requests x {K} beams")
+    return K
+
+
+def beam_candidates(logits, lse_partial, cand_ids, cand_lp, rank):
+    """cand_ids (int32) / cand_lp (fp32) [R, 2K]: every row's 2K best columns by (bf16 logit descending, column ascending) with their
+    log-probabilities - the greedy top-n list of decode_top_logprobs, bit for bit.  rank: int32 [R] scratch."""
+    lib = _lib.load()
+    _req(logits, BF16, "logits")
+    _req(cand_ids, torch.int32, "cand_ids")
+    _req(cand_lp, torch.float32, "cand_lp")
+    _req(rank, torch.int32, "rank")
+    if cand_ids.dim() != 2 or cand_lp.shape != cand_ids.shape or not (cand_ids.is_contiguous() and cand_lp.is_contiguous()):
+        raise _lib.UmvError("beam_candidates: cand_ids / cand_lp must be contiguous [R, 2K] tensors of one shape")
+    R, n = cand_ids.shape
+    _, V = _logits_shape("beam_candidates", logits, R)
+    if n % 2 or not 2 <= n <= 2 * _lib.BEAM_K_MAX or V <= n or rank.numel() < R or not rank.is_contiguous():
+        raise _lib.UmvError(f"beam_candidates: 2K = {n} must be even, at most {2 * _lib.BEAM_K_MAX} and below V = {V}; rank holds R entries")
+    _, lse, _, n_tiles = _tile_keys("beam_candidates", R, None, _req(lse_partial, torch.float32, "lse_partial"))
+    check(lib.umv_beam_candidates(_p(logits), logits.stride(0), V, lse, n_tiles, R, n, _p(cand_ids), _p(cand_lp), _p(rank), _stream()),
+          "umv_beam_candidates")
+
+
+class BeamState:
+    """The device words of a beam search (umv_beam_step_args) for B requests of K beams: scores, back-pointers, finished list, done
+    words and copy list - allocated here - next to the decode session's counters and the forked cache's table."""
+
+    def __init__(self, B, K, max_length, device, length_penalty=1.0):
+        R = B * K
+        self.B, self.K, self.max_length = B, K, max_length
+        self.cand_ids = torch.zeros((R, 2 * K), dtype=torch.int32, device=device)
+        self.cand_lp = torch.zeros((R, 2 * K), dtype=torch.float32, device=device)
+        self.rank = torch.zeros((R,), dtype=torch.int32, device=device)
+        scores = torch.full((B, K), float("-inf"), dtype=torch.float32)
+        scores[:, 0] = 0.0
+        self.scores = scores.reshape(R).to(device)
+        self.beam_tok = torch.zeros((max_length, R), dtype=torch.int32, device=device)
+        self.beam_parent = torch.zeros((max_length, R), dtype=torch.int32, device=device)
+        self.beam_lp = torch.zeros((max_length, R), dtype=torch.float32, device=device)
+        self.fin_f = torch.zeros((B, K, 4), dtype=torch.float32, device=device)
+        self.fin_i = torch.zeros((B, K, 4), dtype=torch.int32, device=device)
+        self.hdr = torch.zeros((B, 4), dtype=torch.int32, device=device)
+        self.copies = torch.zeros((R, 4), dtype=torch.int32, device=device)
+        # norm[t] = powf(t + 1, length_penalty) in fp32, once, on the host: the device divides by it
+        import numpy as np
+        norm = np.power(np.arange(1, max_length + 1, dtype=np.float32), np.float32(length_penalty)).astype(np.float32)
+        self.len_norm = torch.from_numpy(norm).to(device)
+
+    def written(self):
+        """every tensor a step end writes that a later one (or the copy launch) reads"""
+        return (self.scores, self.fin_f, self.fin_i, self.hdr, self.copies)
+
+
+def beam_step_end(tok_slot, tok_pos, kv_len, ids, step_idx, st, table, own, j0, end_token_id, early_stopping):
+    """The step end of a beam search step (include/unimedvl_hip.h, beam search decode) over st (a BeamState, its candidate lists
+    filled by beam_candidates): orders and walks the candidates of every request, keeps its finished list and done word, writes the
+    next ids, back-pointers and scores, advances the counters, rewrites the request's rows of `table` (int32 [R, stride]) by the KV plan
+    and leaves st.copies.  own (int32 [R, n_own, 2]) / j0 (int32 [B]): kvcache.PagedCache.fork_beams."""
+    lib = _lib.load()
+    R = st.B * st.K
+    for t, dt, name, numel in ((tok_slot, torch.int32, "tok_slot", R), (tok_pos, torch.int32, "tok_pos", R), (kv_len, torch.int32, "kv_len", R),
+                               (ids, torch.int64, "ids", R), (step_idx, torch.int64, "step_idx", R), (j0, torch.int32, "j0", st.B)):
+        _req(t, dt, name)
+        if not (t.is_contiguous() and t.numel() >= numel):
+            raise _lib.UmvError(f"beam_step_end: {name} must be a contiguous tensor of {numel} entries")
+    _req(table, torch.int32, "table")
+    _req(own, torch.int32, "own")
+    if not (table.dim() == 2 and table.shape[0] == R and table.stride(1) == 1 and own.is_contiguous() and own.dim() == 3
+            and own.shape[0] == R and own.shape[2] == 2):
+        raise _lib.UmvError(f"beam_step_end: table must be int32 [{R}, stride] and own a contiguous int32 [{R}, n_own, 2]")
+    if st.K * own.shape[1] > _lib.BEAM_TABLE_ENTRIES:
+        raise _lib.UmvError(f"beam_step_end: K * n_own = {st.K * own.shape[1]} exceeds {_lib.BEAM_TABLE_ENTRIES}: shorten the decode horizon")
+    a = _lib.BeamStepArgs()
+    a.tok_slot, a.tok_pos, a.kv_len, a.ids, a.step_idx = (t.data_ptr() for t in (tok_slot, tok_pos, kv_len, ids, step_idx))
+    a.cand_ids, a.cand_lp, a.scores = st.cand_ids.data_ptr(), st.cand_lp.data_ptr(), st.scores.data_ptr()
+    a.beam_tok, a.beam_parent, a.beam_lp = st.beam_tok.data_ptr(), st.beam_parent.data_ptr(), st.beam_lp.data_ptr()
+    a.fin_f, a.fin_i, a.hdr, a.len_norm = st.fin_f.data_ptr(), st.fin_i.data_ptr(), st.hdr.data_ptr(), st.len_norm.data_ptr()
+    a.table, a.own, a.j0, a.copies = table.data_ptr(), own.data_ptr(), j0.data_ptr(), st.copies.data_ptr()
+    a.table_stride, a.n_own, a.B, a.K, a.max_len = table.stride(0), own.shape[1], st.B, st.K, st.max_length
+    a.end_token_id, a.early_stopping = -1 if end_token_id is None else int(end_token_id), int(bool(early_stopping))
+    check(lib.umv_beam_step_end(C.byref(a), _stream()), "umv_beam_step_end")
+
+
+def beam_pool_pointers(slabs):
+    """the device array umv_beam_kv_copy takes: per layer the K pool's and the V^T pool's base address (int64 [2 * layers])"""
+    ptrs = [p for sl in slabs for p in (sl.k.data_ptr(), sl.vt.data_ptr())]
+    return torch.tensor(ptrs, dtype=torch.int64).to(slabs[0].k.device)
+
+
+def beam_kv_copy(copies, pools, slabs, chunks=4):
+    """Carry out a step end's copy list (int32 [R, 4]) in every layer's pools: the first `tokens` slots of the source page into the
+    destination page, K and V^T of every kv head.  pools: beam_pool_pointers(slabs)."""
+    lib = _lib.load()
+    _req(copies, torch.int32, "copies")
+    _req(pools, torch.int64, "pools")
+    sl = slabs[0]
+    if not (copies.is_contiguous() and copies.dim() == 2 and copies.shape[1] == 4 and pools.numel() == 2 * len(slabs)):
+        raise _lib.UmvError("beam_kv_copy: copies must be a contiguous int32 [R, 4] and pools hold two pointers per layer")
+    check(lib.umv_beam_kv_copy(_p(copies), _p(pools), copies.shape[0], len(slabs), sl.nkv, sl.hd, sl.k.shape[0], int(chunks), _stream()),
+          "umv_beam_kv_copy")
+
+
 def timestep_embed(t, freqs):
     """[n] fp32 timesteps (device) x [half] fp32 frequencies -> [n, 2*half] bf16 sinusoid (cos | sin)"""
     lib = _lib.load()
