@@ -426,6 +426,28 @@ int umv_decode_step_end_logprob(int32_t* tok_slot, int32_t* tok_pos, int32_t* kv
  * workgroup per row.  temperature = 0: greedy (T = 1 without the rounding step).  An id outside [0, V) gives NaN. */
 int umv_token_logprob_bf16(const uint16_t* logits, int64_t ld, const int64_t* ids, float* out, int M, int V, float temperature,
                            umv_stream_t stream);
+/* Token log-probabilities of given rows, no logits stored (the prefill-time scorer: every row of a teacher-forced pass against the
+ * token that follows it).  The greedy form of the definition above, for ANY number of rows: for row m with hidden state x[m] and
+ * target ids[m],
+ *   y[n]    = float(bf16(lm_head(x[m])[n] (+ bias[n]))), exactly the value umv_gemm_bf16 would store to `out`;
+ *   logprob = y[ids[m]] - logsumexp_n y[n] in fp32, through the per-16-column-tile (m_t, s_t) of lse_partial above, in its order, merged
+ *             in umv_decode_step_end_logprob's order.  A -inf column adds 0, a NaN logit gives NaN, an id outside [0, V) gives NaN.
+ *
+ * umv_lm_head_stats_bf16: the lm_head GEMM on an MFMA tile (every M >= 1; one accumulator chain per output over k in ascending 32-wide
+ * steps, as umv_gemm_bf16 on any of its tiles, so y is the bf16 value that call stores) whose epilogue writes
+ *   lse_partial [M][ceil(N/16)][2] fp32: (m_t, s_t) of every tile of every row - each entry of rows < M is written;
+ *   target_y [M] fp32: y[ids[m]], where ids[m] (int64 [M], device memory) lies in [0, N); otherwise the entry is left alone
+ * and NO logits: a->out may be NULL and is ignored.  The struct is umv_gemm_args unchanged; of its fields the call takes x, ldx, wp (the
+ * umv_pack_weight_bf16 image), M, N, K and bias with UMV_EPI_BIAS.  UMV_ERR_ARG: a NULL x / wp / ids / lse_partial / target_y, a bad
+ * shape, a->lse_partial set.  UMV_ERR_UNSUPPORTED: row_idx, residual, norm_w, k_splits > 1, tile_rows other than 0 / 16, any epilogue
+ * flag but UMV_EPI_BIAS, argmax_partial, sample_temperature != 0.
+ *
+ * umv_token_logprob_from_stats: one workgroup per row merges lse_partial [M][n_tiles][2] as umv_decode_step_end_logprob does and
+ * writes out[m] = (target_y[m] - ref) - logf(S), NaN for ids[m] outside [0, V) - given the same statistics and y, that entry's bits.
+ * UMV_ERR_ARG: a NULL pointer, V that is not the column count behind n_tiles. */
+int umv_lm_head_stats_bf16(const umv_gemm_args* a, const int64_t* ids, float* lse_partial, float* target_y, umv_stream_t stream);
+int umv_token_logprob_from_stats(const float* lse_partial, int n_tiles, const float* target_y, const int64_t* ids, int V, float* out, int M,
+                                 umv_stream_t stream);
 
 /* ------------------------------------------------------------------ truncated sampling: top-k, top-p (nucleus), min-p
  * For one row, y[n] = bf16_round(logit[n] / T), T > 0 - the value the sampling keys and the log-probabilities above use.  A CLASS is the

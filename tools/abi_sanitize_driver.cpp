@@ -174,6 +174,26 @@ static void bad_arguments() {
     EXPECT_ERR(umv_token_logprob_bf16(dummy16, 32, dummyl, dummyf, 1, 64, 0.f, nullptr));         // row stride below V
     EXPECT_ERR(umv_token_logprob_bf16(dummy16, 64, dummyl, dummyf, 1, 64, -1.f, nullptr));        // negative temperature
     EXPECT_OK(umv_token_logprob_bf16(dummy16, 64, dummyl, dummyf, 0, 64, 0.f, nullptr));          // no rows
+    {   // the prefill-time scorer: the lm_head call that stores statistics instead of logits, and its finish
+        umv_gemm_args gs;
+        std::memset(&gs, 0, sizeof gs);
+        gs.x = dummy16; gs.wp = dummy16; gs.ldx = 64; gs.M = 1; gs.N = 64; gs.K = 64;
+        EXPECT_ERR(umv_lm_head_stats_bf16(nullptr, dummyl, dummyf, dummyf, nullptr));
+        EXPECT_ERR(umv_lm_head_stats_bf16(&gs, nullptr, dummyf, dummyf, nullptr));                  // no ids
+        EXPECT_ERR(umv_lm_head_stats_bf16(&gs, dummyl, nullptr, dummyf, nullptr));                  // no lse_partial
+        EXPECT_ERR(umv_lm_head_stats_bf16(&gs, dummyl, dummyf, nullptr, nullptr));                  // no target_y
+        gs.k_splits = 2;
+        EXPECT_ERR(umv_lm_head_stats_bf16(&gs, dummyl, dummyf, dummyf, nullptr));                   // split-K
+        gs.k_splits = 0; gs.epilogue = UMV_EPI_OUT_F32;
+        EXPECT_ERR(umv_lm_head_stats_bf16(&gs, dummyl, dummyf, dummyf, nullptr));                   // an epilogue flag other than BIAS
+        gs.epilogue = 0; gs.argmax_partial = (uint64_t*)dummyl;
+        EXPECT_ERR(umv_lm_head_stats_bf16(&gs, dummyl, dummyf, dummyf, nullptr));                   // argmax_partial
+        gs.argmax_partial = nullptr; gs.M = 0;
+        EXPECT_OK(umv_lm_head_stats_bf16(&gs, dummyl, dummyf, dummyf, nullptr));                    // no rows
+        EXPECT_ERR(umv_token_logprob_from_stats(nullptr, 9504, nullptr, nullptr, 152064, nullptr, 8, nullptr));
+        EXPECT_ERR(umv_token_logprob_from_stats(dummyf, 4, dummyf, dummyl, 100, dummyf, 1, nullptr));   // 100 columns are not 4 tiles
+        EXPECT_OK(umv_token_logprob_from_stats(dummyf, 4, dummyf, dummyl, 64, dummyf, 0, nullptr));     // no rows
+    }
     EXPECT_ERR(umv_decode_top_logprobs(nullptr, 152064, 152064, nullptr, 9504, 0.f, nullptr, UMV_TOP_AFTER_LOGPROB, nullptr, nullptr, nullptr, 8,
                                        16, 5, nullptr, nullptr, nullptr, nullptr));
     EXPECT_ERR(umv_decode_top_logprobs(dummy16, 64, 64, dummyf, 4, 0.f, nullptr, UMV_TOP_AFTER_LOGPROB, dummyl, dummyl, nullptr, 1, 16, 0, dummyi,

@@ -8,8 +8,8 @@ cd "$(dirname "$0")/.."
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 WHAT=${1:-both}
 # one line per source, "name [per-file flags]": the build's own list (unimedvl_amd/build.py), so this script cannot fall behind it
-LIST=$(${PYTHON:-python} -c "from unimedvl_amd.build import SOURCES, FILE_FLAGS
-for s in SOURCES: print(s[:-4], *FILE_FLAGS.get(s, []))")
+LIST=$(${PYTHON:-python} -c "from unimedvl_amd.build import SOURCES, LAST_SOURCES, TAIL_SOURCES, FILE_FLAGS
+for s in SOURCES + LAST_SOURCES + TAIL_SOURCES: print(s[:-4], *FILE_FLAGS.get(s, []))")
 SRCS=$(echo "$LIST" | cut -d' ' -f1 | tr '\n' ' ')
 build_and_run() {
   local name=$1 flags=$2 D=unimedvl_amd/lib/san_$1

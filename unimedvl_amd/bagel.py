@@ -36,6 +36,20 @@ TopLogprobs = namedtuple("TopLogprobs", ["ids", "logprobs", "rank"])
 BF16 = torch.bfloat16
 
 
+def prefill_score_layout(toks, start, pos0):
+    """The rows of Bagel.score_prefill for candidates toks (lists of scored tokens, none empty) behind a context whose start token sits
+    at rope position pos0: candidate c with tokens t_0 .. t_{m-1} is the segment [start, t_0, .., t_{m-2}] at positions pos0 .. pos0 + m - 1
+    and row i is scored against t_i - the rows and targets `score`'s forced session feeds.  -> (fed ids, targets, query lengths, rope
+    positions), the first, second and last one entry per row, candidates back to back."""
+    fed, targets, qlens, pos = [], [], [], []
+    for t in toks:
+        fed += [int(start)] + [int(v) for v in t[:-1]]
+        targets += [int(v) for v in t]
+        qlens.append(len(t))
+        pos += list(range(pos0, pos0 + len(t)))
+    return fed, targets, qlens, pos
+
+
 class Bagel(BagelPrep):
     def __init__(self, cfg: UniMedVLConfig, get, device="cuda", visual_gen=True, visual_und=True,
                  interpolate_pos=False):
@@ -650,9 +664,44 @@ class Bagel(BagelPrep):
         candidate's end.  Greedy definition: log-softmax of the bf16 logits.  Returns one dict per candidate: token_ids (the scored
         tokens, EOS included), token_logprobs (one fp32 value per token) and logprob (their sum, added in fp64 on the host).
         Samples are independent rows of every kernel, so a candidate's values do not depend on the others.
-        Forced decoding costs one decode step per token - the right trade for answers of a few tokens; long continuations want a
-        prefill-time scorer, which this is not.  score_top_logprobs adds every token's rank and alternatives."""
+        Forced decoding costs one decode step per token - the right trade for answers of a few tokens; long continuations want the
+        prefill-time scorer, score_prefill: the same rows and targets in one forward pass.  score_top_logprobs adds every token's rank
+        and alternatives."""
         return self._score(tokenizer, new_token_ids, image_transform, images, prompt, candidates, append_eos, None)
+
+    @torch.no_grad()
+    @ops.on_device
+    def score_prefill(self, tokenizer, new_token_ids, image_transform, images, prompt, candidates, append_eos: bool = True, *,
+                      rows_per_pass: int = 1024, fused: bool = True):
+        """`score` for long candidates - report sentences, long multiple-choice options, the perplexity of a reference text, beam
+        hypotheses to re-rank: the rows `score`'s forced session feeds one step at a time - per candidate the segment [start, t_0, ..,
+        t_{m-2}] at consecutive slots and rope positions behind the context, row i scored against t_i - run through ONE prefill pass
+        over a NaiveCache.merged copy of the context per candidate, and Qwen2MoT.token_logprobs turns the returned rows into
+        log-probabilities without storing logits (rows_per_pass rows of lm_head per launch over one reused workspace; fused=False:
+        the unfused composition over stored logits - what an e4m3 lm_head takes either way).  Same candidates (1..64), same dict per
+        candidate (token_ids, token_logprobs, logprob = the fp64 host sum) and same ValueErrors as `score`, plus one for a candidate
+        that would pass max_position.  The values are the prefill kernels': they agree with `score`'s to the kernels' tolerance, not
+        bit for bit.  Ranks and top-n alternatives stay with score_top_logprobs.  The context cache is left as it was."""
+        toks = self._score_candidates(tokenizer, new_token_ids, candidates, append_eos)
+        cache, gi = self._score_context(tokenizer, new_token_ids, image_transform, images, prompt)
+        cfg, lm, n = self.cfg, self.language_model, len(toks)
+        fed, targets, qlens, pos = prefill_score_layout(toks, int(gi["packed_start_tokens"][0]), int(gi["packed_query_position_ids"][0]))
+        if max(pos) >= cfg.max_position:
+            raise ValueError(f"score_prefill: the longest candidate ({max(qlens)} tokens) would pass max_position ({cfg.max_position}): "
+                             f"its last row sits at rope position {max(pos)}")
+        if min(targets) < 0 or max(targets) >= cfg.vocab:
+            raise ValueError(f"score_prefill: candidate tokens must lie in the vocabulary [0, {cfg.vocab})")
+        many = NaiveCache.merged([cache] * n, [1] * n, max(qlens) + 1, cfg.kv_heads, cfg.head_dim, self.device)
+        out = lm.forward_inference(packed_query_sequence=lm.embed_tokens(torch.tensor(fed, dtype=torch.int64)), query_lens=qlens,
+                                   packed_query_position_ids=torch.tensor(pos, dtype=torch.int32), past_key_values=many,
+                                   update_past_key_values=False, is_causal=True, mode="und")
+        lp = lm.token_logprobs(out.packed_query_sequence, torch.tensor(targets, dtype=torch.int64), rows_per_pass, fused=fused).cpu()
+        res, r0 = [], 0
+        for t in toks:
+            vals = lp[r0:r0 + len(t)]
+            res.append({"token_ids": t, "token_logprobs": vals.tolist(), "logprob": float(vals.double().sum())})
+            r0 += len(t)
+        return res
 
     @torch.no_grad()
     @ops.on_device
@@ -665,9 +714,9 @@ class Bagel(BagelPrep):
         `score`'s parameter list is pinned."""
         return self._score(tokenizer, new_token_ids, image_transform, images, prompt, candidates, append_eos, top_logprobs)
 
-    def _score(self, tokenizer, new_token_ids, image_transform, images, prompt, candidates, append_eos, top_logprobs):
-        ranks = top_logprobs is not None
-        want_top = ops.check_top_logprobs(top_logprobs, self.cfg.vocab) if ranks else 0
+    @staticmethod
+    def _score_candidates(tokenizer, new_token_ids, candidates, append_eos):
+        """the scored tokens of every candidate of score / score_prefill: strings through tokenizer.encode, the end token behind them"""
         cands = list(candidates)
         if not 1 <= len(cands) <= 64:
             raise ValueError(f"score takes 1..64 candidates, got {len(cands)}")
@@ -679,15 +728,25 @@ class Bagel(BagelPrep):
             if not t:
                 raise ValueError("score: an empty candidate (and append_eos=False) has nothing to score")
             toks.append(t)
-        cfg, n, steps = self.cfg, len(toks), max(len(t) for t in toks)
-        cache = NaiveCache(cfg.layers)
+        return toks
+
+    def _score_context(self, tokenizer, new_token_ids, image_transform, images, prompt):
+        """the context of `chat` (images, then the prompt) prefilled once -> (its cache, the start tokens behind it)"""
+        cache = NaiveCache(self.cfg.layers)
         newlens, new_rope = [0], [0]
         for image in images:
             gi, newlens, new_rope = self.prepare_vit_images(newlens, new_rope, [image], image_transform, new_token_ids)
             cache = self.forward_cache_update_vit(cache, **gi)
         gi, newlens, new_rope = self.prepare_prompts(newlens, new_rope, [prompt], tokenizer, new_token_ids)
         cache = self.forward_cache_update_text(cache, **gi)
-        gi = self.prepare_start_tokens(newlens, new_rope, new_token_ids)
+        return cache, self.prepare_start_tokens(newlens, new_rope, new_token_ids)
+
+    def _score(self, tokenizer, new_token_ids, image_transform, images, prompt, candidates, append_eos, top_logprobs):
+        ranks = top_logprobs is not None
+        want_top = ops.check_top_logprobs(top_logprobs, self.cfg.vocab) if ranks else 0
+        toks = self._score_candidates(tokenizer, new_token_ids, candidates, append_eos)
+        cfg, n, steps = self.cfg, len(toks), max(len(t) for t in toks)
+        cache, gi = self._score_context(tokenizer, new_token_ids, image_transform, images, prompt)
         many = NaiveCache.merged([cache] * n, [1] * n, steps + 1, cfg.kv_heads, cfg.head_dim, self.device) if n > 1 else cache
         forced = torch.full((steps, n), -1, dtype=torch.int64)
         for b, t in enumerate(toks):

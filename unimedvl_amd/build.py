@@ -22,6 +22,8 @@ LIB = os.path.join(LIBDIR, "libunimedvl_hip.so")
 SOURCES = ["host_error.hip", "elementwise.hip", "norm.hip", "qkv_post.hip", "token_pick.hip", "logit_penalty.hip", "pack.hip", "gemm.hip", "gemm_w4.hip", "gemm_fp8mfma.hip", "gemm_mxfp4.hip", "gemm_mxfp4t.hip", "gemm_z13.hip", "attention.hip", "attention_prefill.hip", "image_head.hip", "vae_conv.hip", "vae.hip", "top_logprobs.hip", "logit_ngram.hip", "logit_constrain.hip"]
 # linked behind SOURCES, in this order: what came later still (beam.hip), so that every earlier code object keeps its place
 LAST_SOURCES = ["beam.hip"]
+# ... and behind those, for the same reason (beam.hip stays the last of its list): the prefill-time scorer's kernels
+TAIL_SOURCES = ["lm_head_stats.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-Wno-unused-result", "-fgpu-rdc" if False else "-fno-gpu-rdc"]
 # per-file additions.  attention_prefill: MFMA destinations stay in VGPRs (the compiler's default parks the 64 O accumulators in
@@ -62,7 +64,7 @@ def build(force=False, verbose=True):
             hh.update(open(os.path.join(CSRC, f), "rb").read())
     headers = hh.hexdigest()
     obj_stamps = {}
-    for lib, sources, extra, suffix in ((LIB, SOURCES + LAST_SOURCES, [], ""),):
+    for lib, sources, extra, suffix in ((LIB, SOURCES + LAST_SOURCES + TAIL_SOURCES, [], ""),):
         objs = []
         for src in sources:
             sp = os.path.join(CSRC, src)

@@ -592,3 +592,52 @@ __device__ __forceinline__ bool epi_wave_tile_lean_any(int kind, const umv_gemm_
     default: return false;
     }
 }
+
+// ----------------------------------------------------------------------------- statistics-only wave-tile epilogue
+// The lm_head GEMM of the prefill-time scorer (lm_head_stats.hip; include/unimedvl_hip.h, umv_lm_head_stats_bf16): NO logits leave the
+// kernel.  Lane layout as epi_wave_tile_lean documents it - r = lane & 15 the row, g = lane >> 4 the holder of columns 4g .. 4g + 3 of
+// n-tile q - which is what epi_lse_tile expects.  Per accumulator: (+ bias) -> bf16, the value the store epilogues write (`final`);
+// the tile's (m_t, s_t) through epi_lse_tile, in its order; and the lane that holds column ids[m] of row m writes that value to
+// target_y[m].  Rows >= M and tiles >= NTT write nothing; an id outside [0, N) leaves target_y[m] alone (the finish answers NaN).
+// bias_tile: LDS copy of bias[nt_base * 16 ..], zero past N, or nullptr for a call without bias (no + 0: -0 stays -0, as stored).
+template <int TN, int TM>
+__device__ __forceinline__ void epi_wave_tile_stats(f32x4 (&acc)[TN][TM], int lane, int m_wave0, int M, int N, int nt_base, int NTT,
+                                                    const bf16_t* bias_tile, const int64_t* __restrict__ ids, float* __restrict__ lse,
+                                                    float* __restrict__ target_y) {
+    const int r = lane & 15, g = lane >> 4;
+    bool mok[TM];
+    int64_t id[TM];
+#pragma unroll
+    for (int j = 0; j < TM; ++j) {
+        const int m = m_wave0 + j * 16 + r;
+        mok[j] = m < M;
+        id[j] = mok[j] ? ids[m] : -1;
+    }
+    static_for<0, TN>([&](auto Q) {
+        constexpr int q = decltype(Q)::value;
+        const int tile = nt_base + q;              // wave-uniform: every lane of the wave takes the shuffles of epi_lse_tile or none does
+        if (tile < NTT) {
+            const int n0 = tile * 16 + g * 4;
+            float b4[4] = {0.f, 0.f, 0.f, 0.f};
+            if (bias_tile) {
+                const u32x2 pk = *reinterpret_cast<const u32x2*>(bias_tile + q * 16 + g * 4);
+                b4[0] = __uint_as_float(pk.x << 16); b4[1] = __uint_as_float(pk.x & 0xFFFF0000u);
+                b4[2] = __uint_as_float(pk.y << 16); b4[3] = __uint_as_float(pk.y & 0xFFFF0000u);
+            }
+            static_for<0, TM>([&](auto J) {
+                constexpr int j = decltype(J)::value;
+                const int m = m_wave0 + j * 16 + r;
+                float final[4] = {acc[q][j].x, acc[q][j].y, acc[q][j].z, acc[q][j].w};
+                if (bias_tile) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) final[k] += b4[k];
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) final[k] = rbf(final[k]);
+                epi_lse_tile(lse, NTT, m, tile, lane, mok[j], n0, N, final, 0.f);
+                const int64_t k = id[j] - n0;
+                if (mok[j] && k >= 0 && k < 4 && id[j] < N) target_y[m] = k == 0 ? final[0] : k == 1 ? final[1] : k == 2 ? final[2] : final[3];
+            });
+        }
+    });
+}

@@ -265,3 +265,13 @@ class VQAInferencer:
                                                  append_eos=append_eos, top_logprobs=self.config["top_logprobs"])
         return self.model.score(self.tokenizer, self.new_token_ids, self.image_transform, images, conversation, candidates,
                                 append_eos=append_eos)
+
+    def score_prefill(self, image, question, candidates, append_eos=True):
+        """`score` for long candidates (Bagel.score_prefill): the same dicts - token_ids, token_logprobs, logprob - from one prefill pass
+        over all candidates' rows instead of one decode step per token.  No ranks or alternatives (the "top_logprobs" key is `score`'s)."""
+        if not self.loaded:
+            raise RuntimeError("Model not loaded, please call load_model() first")
+        input_image = image.convert("RGB") if isinstance(image, Image.Image) else Image.open(image).convert("RGB")
+        images, conversation = process_conversation([input_image], question)
+        return self.model.score_prefill(self.tokenizer, self.new_token_ids, self.image_transform, images, conversation, candidates,
+                                        append_eos=append_eos)

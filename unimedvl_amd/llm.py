@@ -42,6 +42,25 @@ def _host_list(x):
     return [int(v) for v in x]
 
 
+def row_chunks(T, rows_per_pass):
+    """the lm_head passes of Qwen2MoT.token_logprobs over T rows: [r0, r1) ranges of at most rows_per_pass rows, in order"""
+    if isinstance(rows_per_pass, bool) or int(rows_per_pass) != rows_per_pass or rows_per_pass < 1:
+        raise ValueError(f"rows_per_pass must be a positive integer, got {rows_per_pass!r}")
+    rows_per_pass = int(rows_per_pass)
+    return [(r0, min(r0 + rows_per_pass, T)) for r0 in range(0, T, rows_per_pass)]
+
+
+def fused_lm_head_ok(lin):
+    """whether ops.lm_head_stats takes this lm_head: its plain 16-row bf16 image, and no e4m3 / MXFP4 image beside it"""
+    return lin.wp is not None and lin.th == 16 and not lin.swiglu and lin.w8 is None and lin.w4 is None
+
+
+def token_logprobs_workspace_bytes(rows, V, fused):
+    """bytes Qwen2MoT.token_logprobs holds beside its inputs and output for passes of `rows` rows: the tile statistics and one
+    logit per row, or the logits"""
+    return rows * ((V + 15) // 16 * 8 + 4) if fused else rows * V * 2
+
+
 class Qwen2MoT:
     def __init__(self, cfg: UniMedVLConfig, weights: LLMWeights, device):
         self.cfg = cfg
@@ -72,6 +91,43 @@ class Qwen2MoT:
     @ops.on_device
     def lm_head(self, h):
         return ops.gemm(h, self.w.lm_head)
+
+    @ops.on_device
+    def token_logprobs(self, hidden, target_ids, rows_per_pass=1024, *, fused=True):
+        """log_softmax(lm_head(hidden[t]))[target_ids[t]] for every row: hidden [T, H] bf16 (final-normed rows, forward_inference's
+        output), target_ids [T] -> fp32 [T], by the greedy definition of include/unimedvl_hip.h ("token log-probabilities"; NaN for an
+        id outside the vocabulary).  The lm_head runs rows_per_pass rows at a time over ONE reused workspace, and a row's bits do not
+        depend on its chunk.  With a bf16 lm_head image each chunk is two launches that store no logits (ops.lm_head_stats,
+        ops.token_logprob_from_stats): 8 bytes of statistics per 16 columns and row - 78 MB at 1024 rows of the full vocabulary.
+        fused=False, or an e4m3 lm_head (llm_weight_dtype "fp8" / "fp4"): ops.gemm into a [rows_per_pass, V] logits chunk, then
+        ops.token_logprob - four times the workspace and a second pass over it.  last_token_logprobs records which form ran and its
+        workspace bytes."""
+        lin, dev = self.w.lm_head, self.device
+        if hidden.dim() != 2 or hidden.shape[1] != lin.K or hidden.dtype != BF16:
+            raise ValueError(f"token_logprobs: hidden must be bf16 [T, {lin.K}]")
+        T = hidden.shape[0]
+        ids = torch.as_tensor(target_ids).to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+        if ids.numel() != T:
+            raise ValueError(f"token_logprobs: {ids.numel()} target ids for {T} rows")
+        hidden = hidden.contiguous()
+        fused = bool(fused) and fused_lm_head_ok(lin)
+        plan = row_chunks(T, rows_per_pass)
+        rows = max([r1 - r0 for r0, r1 in plan], default=0)
+        out = torch.empty((T,), dtype=torch.float32, device=dev)
+        if fused:
+            lse = torch.empty((rows, (lin.N + 15) // 16, 2), dtype=torch.float32, device=dev)
+            target_y = torch.empty((rows,), dtype=torch.float32, device=dev)
+        else:
+            logits = torch.empty((rows, lin.N), dtype=BF16, device=dev)
+        self.last_token_logprobs = {"fused": fused, "rows_per_pass": rows, "workspace_bytes": token_logprobs_workspace_bytes(rows, lin.N, fused)}
+        for r0, r1 in plan:
+            if fused:
+                ops.lm_head_stats(hidden[r0:r1], lin, ids[r0:r1], lse, target_y, M=r1 - r0)
+                ops.token_logprob_from_stats(lse, target_y, ids[r0:r1], lin.N, out=out[r0:r1], M=r1 - r0)
+            else:
+                ops.gemm(hidden[r0:r1], lin, out=logits[:r1 - r0])
+                ops.token_logprob(logits[:r1 - r0], ids[r0:r1], out=out[r0:r1])
+        return out
 
     # ------------------------------------------------------------------ per-token bookkeeping of one forward
     @ops.on_device

@@ -1088,6 +1088,53 @@ def token_logprob(logits, ids, temperature=0.0, out=None):
     return out
 
 
+def lm_head_stats(x, lin, ids, lse_partial, target_y, *, M=None, use_bias=True):
+    """The lm_head GEMM of the prefill-time scorer (include/unimedvl_hip.h, umv_lm_head_stats_bf16): for rows [0, M) of x [>= M, K] bf16
+    the softmax statistics of every 16-column tile go to lse_partial (fp32 [>= M, ceil(N/16), 2]) and row m's logit at ids[m] (int64
+    [>= M]) to target_y (fp32 [>= M]); no logits are stored.  Any M >= 1; the linear must hold its plain 16-row bf16 image - an e4m3 or
+    MXFP4 lm_head takes gemm + token_logprob instead (Qwen2MoT.token_logprobs).  Finished by token_logprob_from_stats."""
+    lib = _lib.load()
+    _req(x, BF16, "x")
+    assert x.stride(-1) == 1
+    M = x.shape[0] if M is None else M
+    if lin.wp is None or lin.th != 16 or lin.swiglu or lin.w8 is not None or lin.w4 is not None:
+        raise _lib.UmvError("lm_head_stats needs a plain bf16 linear (16-row image, no SwiGLU, no e4m3 / MXFP4 image)")
+    nt = (lin.N + 15) // 16
+    _req(lse_partial, torch.float32, "lse_partial")
+    if not (lse_partial.is_contiguous() and lse_partial.dim() == 3 and lse_partial.shape[0] >= M and lse_partial.shape[1:] == (nt, 2)):
+        raise _lib.UmvError(f"lm_head_stats: lse_partial must be a contiguous fp32 [>= {M}, {nt}, 2] tensor")
+    for name, t, dt in (("ids", ids, torch.int64), ("target_y", target_y, torch.float32)):
+        _req(t, dt, name)
+        if not (t.is_contiguous() and t.dim() == 1 and t.shape[0] >= M):
+            raise _lib.UmvError(f"lm_head_stats: {name} must be a contiguous {dt} tensor of >= {M} entries")
+    if x.shape[0] < M or x.shape[1] != lin.K:
+        raise _lib.UmvError(f"lm_head_stats: x must be [>= {M}, {lin.K}]")
+    a = GemmArgs(x=x.data_ptr(), ldx=x.stride(0), wp=lin.wp.data_ptr(), M=M, N=lin.N, K=lin.K, tile_rows=lin.th)
+    if lin.bias is not None and use_bias:
+        a.bias, a.epilogue = lin.bias.data_ptr(), EPI_BIAS
+    check(lib.umv_lm_head_stats_bf16(C.byref(a), _p(ids), _p(lse_partial), _p(target_y), _stream()), "umv_lm_head_stats_bf16")
+
+
+def token_logprob_from_stats(lse_partial, target_y, ids, V, out=None, *, M=None):
+    """out[m] = target_y[m] - logsumexp of row m from its tile statistics (lm_head_stats' outputs), merged in decode_step_end_logprob's
+    order: fp32 [M]; NaN where ids[m] lies outside [0, V)."""
+    lib = _lib.load()
+    _req(lse_partial, torch.float32, "lse_partial")
+    if not (lse_partial.is_contiguous() and lse_partial.dim() == 3 and lse_partial.shape[2] == 2):
+        raise _lib.UmvError("token_logprob_from_stats: lse_partial must be a contiguous fp32 [M, n_tiles, 2] tensor")
+    M = lse_partial.shape[0] if M is None else M
+    out = torch.empty((M,), dtype=torch.float32, device=lse_partial.device) if out is None else out
+    for name, t, dt in (("ids", ids, torch.int64), ("target_y", target_y, torch.float32), ("out", out, torch.float32)):
+        _req(t, dt, name)
+        if not (t.is_contiguous() and t.dim() == 1 and t.shape[0] >= M):
+            raise _lib.UmvError(f"token_logprob_from_stats: {name} must be a contiguous {dt} tensor of >= {M} entries")
+    if lse_partial.shape[0] < M:
+        raise _lib.UmvError(f"token_logprob_from_stats: lse_partial holds {lse_partial.shape[0]} rows, M = {M}")
+    check(lib.umv_token_logprob_from_stats(_p(lse_partial), lse_partial.shape[1], _p(target_y), _p(ids), int(V), _p(out), M, _stream()),
+          "umv_token_logprob_from_stats")
+    return out
+
+
 def check_top_logprobs(n, vocab=None):
     """The number of alternatives per token as an int: 0 = off, at most _lib.TOP_LOGPROBS_MAX and the vocabulary; ValueError otherwise."""
     if isinstance(n, bool) or int(n) != n or n < 0 or n > _lib.TOP_LOGPROBS_MAX:
