@@ -199,6 +199,19 @@ class _PagePool:
             self.free.append(p)
 
 
+class PrefixHandle:
+    """A context prefix of n tokens in a page pool (PagedCache.retain_prefix): its n // 256 full pages, shared by reference count, and -
+    n % 256 != 0 - the page that holds its tail.  owned: the handle holds those references and that page (False: live_prefix)."""
+    __slots__ = ("n", "full", "tail", "owned")
+
+    def __init__(self, n, full, tail, owned):
+        self.n, self.full, self.tail, self.owned = n, list(full), tail, owned
+
+    @property
+    def pages(self):
+        return self.full + ([self.tail] if self.tail is not None else [])
+
+
 class PagedCache:
     """Block-table KV cache: every layer owns ONE pool of 256-token pages, K [page][kvh][256][hd] and
     V^T [page][kvh][hd][256], that all segments draw from; a segment's context is the list of its pages (`table` on the device).
@@ -268,14 +281,7 @@ class PagedCache:
         if nseg != len(self.lens):
             raise ValueError(f"cache holds {len(self.lens)} samples, call has {nseg}")
         P = ops.KV_PAGE
-        want = 0                              # all-or-nothing: check the reach and the pool before taking a single page
-        for s, n in enumerate(need):
-            if n > self.cap:
-                raise ValueError(f"segment {s}: {n} tokens exceed the page table's reach of {self.cap} (max_context)")
-            pages = self._pages(s)
-            want += max(0, (n + P - 1) // P - len(pages))
-            if n > self.lens[s]:
-                want += sum(self.pool.refs[p] > 1 for p in pages[self.lens[s] // P:(n + P - 1) // P])
+        want = self.pages_wanted(need)        # all-or-nothing: check the reach and the pool before taking a single page
         if want > len(self.pool.free):
             raise RuntimeError(f"paged KV pool exhausted: {want} pages wanted, {len(self.pool.free)} of {self.pool.npages - 1} free "
                                f"({P} tokens each): raise pool_pages")
@@ -304,6 +310,23 @@ class PagedCache:
             val = torch.tensor([v for _, _, v in changed], dtype=torch.int32)
             self.pool.table.index_put_((idx[:, 0].to(self.device), idx[:, 1].to(self.device)), val.to(self.device))
 
+    def pages_wanted(self, need):
+        """Pure query: the pages ensure_tokens(need) would take from the free list - the pages each segment lacks for need[s] tokens
+        plus one per shared page the call would write (copy-on-write).  ValueError beyond the page table's reach, as ensure_tokens."""
+        P = ops.KV_PAGE
+        want = 0
+        for s, n in enumerate(need):
+            if n > self.cap:
+                raise ValueError(f"segment {s}: {n} tokens exceed the page table's reach of {self.cap} (max_context)")
+            if self.pool is None:
+                want += (n + P - 1) // P
+                continue
+            pages = self._pages(s)
+            want += max(0, (n + P - 1) // P - len(pages))
+            if n > self.lens[s]:
+                want += sum(self.pool.refs[p] > 1 for p in pages[self.lens[s] // P:(n + P - 1) // P])
+        return want
+
     def reserve(self, nseg, cap, nkv, hd, device):
         """NaiveCache.reserve pre-sizes slabs; here it only creates the pool and the table (pages are taken as contexts grow)"""
         self.ensure_tokens([0] * nseg, nkv, hd, device)
@@ -319,6 +342,96 @@ class PagedCache:
 
     def pages_in_use(self):
         return self.pool.npages - 1 - len(self.pool.free)
+
+    # --- prefixes shared at page granularity (serving.ContinuousBatcher(share_prefixes=True))
+    # A partially filled page is never shared: every holder of a prefix - a retained handle, and each segment that adopts one - refers
+    # to the prefix's FULL pages (reference counts) and owns a private copy of the first n % 256 tokens of the partial page.  So no
+    # holder ever writes a shared page (its write position, n, lies in its own tail), and ensure_tokens' copy-on-write has nothing to do.
+    def live_prefix(self, seg):
+        """A handle on segment `seg`'s context as it stands: it owns nothing (no reference, no page), so it is good for an adopt_prefix
+        that is queued before the segment is written or released again, and for nothing else; drop_prefix ignores it."""
+        P, n = ops.KV_PAGE, self.lens[seg]
+        pages = self._pages(seg)
+        return PrefixHandle(n, list(pages[:n // P]), pages[n // P] if n % P else None, False)
+
+    def retain_prefix(self, segs):
+        """Keep the context of a segment (an index -> one handle) or of several (a list -> a list of handles): a reference to each of
+        its lens[seg] // 256 full pages and, with lens[seg] % 256 != 0, one new page holding a copy of the tail.  All the tail copies of
+        the call are one launch.  All or nothing: a refused call (RuntimeError: pool exhausted) takes no page and no reference."""
+        one = not isinstance(segs, (list, tuple))
+        live = [self.live_prefix(s) for s in ([segs] if one else segs)]
+        self._want_free(sum(h.tail is not None for h in live), "retain_prefix")
+        out, copies = [], []
+        for h in live:
+            for p in h.full:
+                self.pool.refs[p] += 1
+            tail = None
+            if h.tail is not None:
+                tail = self.pool.alloc()
+                copies.append((h.tail, tail, h.n % ops.KV_PAGE))
+            out.append(PrefixHandle(h.n, h.full, tail, True))
+        self._copy_tails(copies)
+        return out[0] if one else out
+
+    def adopt_prefix(self, seg, handle=None):
+        """adopt_prefix(seg, handle) or adopt_prefix([(seg, handle), ...]): every segment, which must hold nothing (a released one is
+        fine), becomes a holder of its handle's prefix - a reference to each full page, a private page with a copy of the handle's tail,
+        its table row written and lens[seg] set.  One launch for all the tail copies.  All or nothing against the free list."""
+        pairs = [(seg, handle)] if handle is not None else list(seg)
+        if len({s for s, _ in pairs}) != len(pairs):
+            raise ValueError("adopt_prefix: a segment is named twice")
+        for s, h in pairs:
+            if self.lens[s] or self._pages(s):
+                raise ValueError(f"adopt_prefix: segment {s} holds {self.lens[s]} tokens / {len(self._pages(s))} pages; release it first")
+            if h.n > self.cap:
+                raise ValueError(f"segment {s}: {h.n} tokens exceed the page table's reach of {self.cap} (max_context)")
+        self._want_free(sum(h.tail is not None for _, h in pairs), "adopt_prefix")
+        copies = []
+        for s, h in pairs:
+            pages = self._pages(s)
+            for p in h.full:
+                self.pool.refs[p] += 1
+                pages.append(p)
+            if h.tail is not None:
+                pages.append(self.pool.alloc())
+                copies.append((h.tail, pages[-1], h.n % ops.KV_PAGE))
+            if pages:
+                self.pool.table[self._seg0 + s, :len(pages)] = torch.tensor(pages, dtype=torch.int32).to(self.pool.table.device)
+            self.lens[s] = h.n
+        self._copy_tails(copies)
+
+    def drop_prefix(self, handle):
+        """Give a retained handle's pages back: one reference of each full page and the tail page, each exactly once (a second drop
+        of the same handle, or a drop of a live_prefix handle, does nothing)."""
+        if not handle.owned:
+            return
+        for p in handle.full:
+            self.pool.unref(p)
+        if handle.tail is not None:
+            self.pool.unref(handle.tail)
+        handle.owned = False
+
+    def _want_free(self, want, what):
+        if want > len(self.pool.free):
+            raise RuntimeError(f"paged KV pool exhausted: {what} wants {want} pages, {len(self.pool.free)} of {self.pool.npages - 1} free "
+                               f"({ops.KV_PAGE} tokens each): raise pool_pages")
+
+    def _copy_tails(self, copies):
+        """(source page, destination page, tokens) in every layer, K and V^T: tokens rounded up to 8 (the copy's 16-byte unit; what lies
+        behind a holder's length is never read).  A pool on the GPU: ONE umv_beam_kv_copy launch; a CPU pool: the same range by slices."""
+        if not copies:
+            return
+        rows = [(src, dst, _round_up(t, 8), 0) for src, dst, t in copies]
+        slabs = self.pool.slabs
+        if slabs[0].k.is_cuda:
+            if getattr(self.pool, "prefix_pools", None) is None:
+                self.pool.prefix_pools = ops.beam_pool_pointers(slabs)
+            ops.beam_kv_copy(torch.tensor(rows, dtype=torch.int32).to(slabs[0].k.device), self.pool.prefix_pools, slabs)
+            return
+        for src, dst, t, _ in rows:
+            for sl in slabs:
+                sl.k[dst, :, :t] = sl.k[src, :, :t]
+                sl.vt[dst, :, :, :t] = sl.vt[src, :, :, :t]
 
     def snapshot(self):
         """Logical copy sharing the pages of the current contexts (reference counted): the first ceil(lens[s] / 256) pages of each

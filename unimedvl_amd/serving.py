@@ -29,6 +29,7 @@ from . import ops
 
 from .decode import DecodeSession
 from .kvcache import NaiveCache, PagedCache
+from .prefix import PrefixTable, adopt_point, chunk_keys, plan_group
 from .sampling import SamplingParams, derive_seed, from_keywords
 
 
@@ -45,6 +46,7 @@ class _Request:
     prompt_ids: Optional[List[int]] = None      # penalize_prompt: the prompt's tokens, the repetition penalty's context set
     sampling: Optional[SamplingParams] = None   # per_request_sampling: the request's own parameters (None = the batcher's)
     constraint: Optional[str] = None            # the name of the automaton (ContinuousBatcher(constraints=)) the request decodes under
+    image_keys: Optional[List[Any]] = None      # share_prefixes: the caller's own keys for the images (None = digests of the inputs)
 
 
 class ContinuousBatcher:
@@ -54,8 +56,8 @@ class ContinuousBatcher:
                  pool_pages: Optional[int] = None, logprobs: bool = False, *, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, penalize_prompt: bool = False,
                  per_request_sampling: bool = False, seed: Optional[int] = None, top_logprobs: int = 0, constraints=None,
-                 no_repeat_ngram_size: int = 0, no_repeat_ngram_prompt: bool = False,
-                 top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+                 no_repeat_ngram_size: int = 0, no_repeat_ngram_prompt: bool = False, share_prefixes: bool = False,
+                 prefix_cache_pages: Optional[int] = None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """max_context: the context (prompt + images) the slots are RESERVED for; with growable=True longer requests enlarge
         the cache (up to context_limit tokens of context when given), with growable=False they are refused.
         paged=True: block-table KV (kvcache.PagedCache) instead of slabs - the slots draw 256-token pages from ONE pool of `pool_pages`
@@ -93,7 +95,23 @@ class ContinuousBatcher:
         it as the penalty context room is reserved - for the longest prompt and token budget admitted so far - and the step is
         re-captured, histories carried over, when a longer one arrives.  no_repeat_ngram_prompt=True seeds a request's history with
         its prompt's token ids (the text between the bos / eos wrapper, exactly the list penalize_prompt uses), so that an n-gram of
-        the prompt is not repeated either; the default counts generated tokens only.  (HF's generate counts the prompt.)"""
+        the prompt is not repeated either; the default counts generated tokens only.  (HF's generate counts the prompt.)
+        share_prefixes=True (needs paged=True): requests with the same images share their KV pages.  A request's chunks are its images
+        in order, then its prompt; after every chunk a request computes, its context is retained under the tuple of the chunk keys so
+        far (prefix.chunk_keys: digests of the raw images - or submit(image_keys=) - and the prompt's packed token ids), and a later
+        request whose chain starts with a retained one adopts it - the full pages by reference count, the partially filled page as a
+        private copy (PagedCache.adopt_prefix) - and prefills only the rest; inside one admission group the first request with a new
+        key computes the chunk and the others copy from its slot right after the pass.  Sharing at chunk boundaries is exact: tokens
+        and log-probabilities are those of the batcher with the option off (tests/test_prefix_share_gpu.py) wherever a pass stays on
+        the same side of the 64-row GEMM split as in that run - always, for images of real size.  The entries live across
+        rounds and run() calls, hold at most prefix_cache_pages distinct pages (default: a quarter of the pool), least recently used
+        out first, and give way whenever a call that takes pages would not fit the free list - so sharing never fails a run that the
+        same pool serves without it.  drop_prefixes() empties the table.  stats: prefix_hits (adoptions), prefix_tokens_reused,
+        vit_images (images that went through the ViT), prefix_evictions.  False: nothing changes."""
+        if (share_prefixes or prefix_cache_pages is not None) and not paged:
+            raise ValueError("share_prefixes / prefix_cache_pages need paged=True: prefixes are shared page by page")
+        if prefix_cache_pages is not None and (not share_prefixes or int(prefix_cache_pages) < 0):
+            raise ValueError(f"prefix_cache_pages (got {prefix_cache_pages!r}) is a page count >= 0 and goes with share_prefixes=True")
         self.constraint, self.constraint_start = None, {}
         if constraints:
             from .constraints import TokenAutomaton
@@ -146,11 +164,18 @@ class ContinuousBatcher:
         self.ranks: Dict[int, List[int]] = {}
         self._next_id = 0
         self.stats = {"decode_steps": 0, "prefills": 0, "tokens": 0, "cache_grows": 0}
+        self.prefixes = None                # share_prefixes: the retained prefixes (prefix.PrefixTable)
+        if share_prefixes:
+            self.stats.update({"prefix_hits": 0, "prefix_tokens_reused": 0, "vit_images": 0})
+            bound = (self.cache.pool_pages - 1) // 4 if prefix_cache_pages is None else int(prefix_cache_pages)
+            self.prefixes = PrefixTable(self.cache, bound, self.stats)
 
     # ------------------------------------------------------------------ API
     def submit(self, images, prompt: str, max_new_tokens: Optional[int] = None, sampling: Optional[SamplingParams] = None,
-               constraint: Optional[str] = None) -> int:
+               constraint: Optional[str] = None, image_keys=None) -> int:
         """images: one image / a list of images (PIL or [3,H,W] tensors, as the transform accepts) or None.
+        image_keys (share_prefixes=True; ignored without): one hashable key per image, used instead of a digest of the image's bytes
+        (a study / series id, say).  They are trusted: equal keys must mean equal images.
         sampling (per_request_sampling=True only): the request's own SamplingParams; None = the batcher's defaults.
         constraint: the name of one of the batcher's automata (ContinuousBatcher(constraints=)); None = free text."""
         if constraint is not None and constraint not in self.constraint_start:
@@ -163,13 +188,24 @@ class ContinuousBatcher:
             self._row_pen = self._row_pen or sampling.penalised
             self._ng_on = self._ng_on or sampling.no_repeat_ngram_size > 0
         imgs = [] if images is None else (list(images) if isinstance(images, (list, tuple)) else [images])
+        if image_keys is not None:
+            image_keys = list(image_keys) if isinstance(image_keys, (list, tuple)) else [image_keys]
+            if len(image_keys) != len(imgs):
+                raise ValueError(f"submit(image_keys=...): {len(image_keys)} keys for {len(imgs)} images")
+            for key in image_keys:
+                hash(key)
         budget = self.default_new if max_new_tokens is None else int(max_new_tokens)
         if budget > self.default_new and not self.growable:
             raise ValueError(f"max_new_tokens {budget} exceeds the batcher's reserve of {self.default_new}")
         rid = self._next_id
         self._next_id += 1
-        self.queue.append(_Request(rid, imgs, prompt, budget, sampling=sampling, constraint=constraint))
+        self.queue.append(_Request(rid, imgs, prompt, budget, sampling=sampling, constraint=constraint, image_keys=image_keys))
         return rid
+
+    def drop_prefixes(self):
+        """share_prefixes: forget every retained prefix (its pages go back to the pool unless a live request still shares them)"""
+        if self.prefixes is not None:
+            self.prefixes.clear()
 
     @torch.no_grad()
     @ops.on_device
@@ -237,6 +273,7 @@ class ContinuousBatcher:
             start = torch.tensor([s[0] for s in state], dtype=torch.int64)
             pos = torch.tensor([s[2] for s in state], dtype=torch.int64)
             lens_now = list(cache.lens)
+            self._room_for([n + self.check_every + 1 for n in lens_now])      # (the session takes the pages of its first round)
             if self.per_request:    # one table row per slot: stream 0, draw 0 (the kept slots take theirs over from `prev` below)
                 sampler = dict(row_sampling=[params_of(b) for b in range(B)], row_streams=[0] * B, row_penalties=self._row_pen,
                                logit_bias=self.penalties["logit_bias"])
@@ -268,6 +305,7 @@ class ContinuousBatcher:
             k = self.check_every
             if self.paged:      # pages for this round's tokens (the captured step reads the table from device memory; an idle slot, parked
                 cfg = m.cfg     # at the start of its segment, keeps one page of its own to write to)
+                self._room_for([n + k + 1 for n in cache.lens])
                 cache.ensure_tokens([n + k + 1 for n in cache.lens], cfg.kv_heads, cfg.head_dim, self.device)
             sess.rewind_outputs()
             sess.step(k)
@@ -352,6 +390,8 @@ class ContinuousBatcher:
     # ------------------------------------------------------------------ internals
     def _prefill(self, b: int, req: _Request):
         """Image(s) then the prompt into slot b (Bagel.chat's order, bagel.py:1321-1392); returns the slot's decode state."""
+        if self.prefixes is not None:
+            return self._prefill_shared([b], [req])[0]
         m = self.model
         self._free_slot(b)
         view = self.cache.view_segments(b, b + 1)
@@ -392,6 +432,9 @@ class ContinuousBatcher:
             return []
         if len({len(r.images) for r in reqs}) != 1:
             return [self._prefill(b, r) for b, r in zip(slots, reqs)]
+        if self.prefixes is not None:
+            self.stats["batched_prefills"] = self.stats.get("batched_prefills", 0) + 1
+            return self._prefill_shared(slots, reqs)
         # (a single admission takes this path too: on the whole reserved cache its image span replays from a HIP graph,
         # bagel.Bagel.forward_cache_update_vit)
         m, cache, B = self.model, self.cache, self.slots
@@ -428,6 +471,99 @@ class ContinuousBatcher:
         self.stats["prefills"] += k
         self.stats["batched_prefills"] = self.stats.get("batched_prefills", 0) + 1
         return [(self.new_token_ids["bos_token_id"], n, r) for n, r in zip(kvl, rope)]
+
+    # ------------------------------------------------------------------ share_prefixes
+    def _room_for(self, need):
+        """share_prefixes: a call is about to take the pages of need[s] tokens per slot - retained prefixes give way, least recently
+        used first, until it fits the free list or none is left (then the call fails as it does without sharing).  Off: nothing."""
+        if self.prefixes is not None:
+            self.prefixes.make_room(self.cache.pages_wanted(need))
+
+    def _prefill_shared(self, slots: List[int], reqs: List[_Request]):
+        """_prefill_many with share_prefixes (the requests have the same number of images; a single request takes this path too).
+        Chunk j of the group is ONE batched pass over the whole slot cache for the requests that LEAD it (prefix.plan_group); a request
+        whose chain is retained adopts the deepest entry before the first pass, a follower copies its leader's slot right after the
+        last pass it follows, and both then take part in the passes they do not lead with zero query tokens, as idle slots do.  After
+        a pass every leader's context is retained under its prefix key - when the pool has the page for the tail: an entry is a
+        convenience, never a reason to fail."""
+        m, cache, B, tab, ntid = self.model, self.cache, self.slots, self.prefixes, self.new_token_ids
+        cap = cache.cap
+        for b in slots:
+            self._free_slot(b)
+        k, nimg = len(slots), len(reqs[0].images)
+        # the prompts are packed once for the keys (and the penalty / n-gram context); the leaders' are packed again at their position
+        gi, _, _ = m.prepare_prompts([0] * k, [0] * k, [r.prompt for r in reqs], self.tokenizer, ntid)
+        ids = [t.tolist() for t in gi["packed_text_ids"].split(gi["text_token_lens"].tolist())]
+        if self.penalize_prompt or self.ngram_prompt:
+            for r, t in zip(reqs, ids):
+                r.prompt_ids = t[1:-1]                                   # without the bos / eos wrapper
+        chains = [chunk_keys(r.images, t, r.image_keys) for r, t in zip(reqs, ids)]
+        states, leader = plan_group(chains, tab.__contains__)
+        at = [adopt_point(s) for s in states]
+        kvl, rope = [0] * k, [0] * k
+
+        def spread(per_request, who):     # query lengths of the requests `who` -> [B] with zeros for every other slot
+            full = torch.zeros(B, dtype=per_request.dtype)
+            full[torch.tensor([slots[r] for r in who])] = per_request.cpu()
+            return full
+
+        def adopt(triples, keep=()):      # [(request, handle, rope position)]: one launch for all the tail copies
+            if not triples:
+                return
+            for r, h, _ in triples:
+                self._check_room(h.n, reqs[r], cap)
+            tab.make_room(sum(h.tail is not None for _, h, _ in triples), keep)
+            cache.adopt_prefix([(slots[r], h) for r, h, _ in triples])
+            for r, h, rp in triples:
+                kvl[r], rope[r] = h.n, rp
+                self.stats["prefix_hits"] += 1
+                self.stats["prefix_tokens_reused"] += h.n
+
+        hits = [r for r in range(k) if at[r] >= 0 and states[r][at[r]] == "hit"]
+        adopt([(r,) + tab.get(chains[r][:at[r] + 1]) for r in hits], keep={chains[r][:at[r] + 1] for r in hits})
+        for j in range(nimg + 1):
+            lead = [r for r in range(k) if states[r][j] == "lead"]
+            if not lead:
+                continue
+            at_k, at_r = [kvl[r] for r in lead], [rope[r] for r in lead]
+            if j < nimg:
+                gi, new_k, new_r = m.prepare_vit_images(at_k, at_r, [reqs[r].images[j] for r in lead], self.image_transform, ntid)
+                lens_key, drop = "packed_seqlens", "packed_indexes"
+            else:
+                gi, new_k, new_r = m.prepare_prompts(at_k, at_r, [reqs[r].prompt for r in lead], self.tokenizer, ntid)
+                lens_key, drop = "text_token_lens", "packed_text_indexes"
+            for r, n in zip(lead, new_k):
+                self._check_room(n, reqs[r], cap)
+            gi[lens_key] = spread(gi[lens_key], lead)
+            gi["key_values_lens"] = gi["packed_key_value_indexes"] = gi[drop] = None      # written for a cache of the leaders alone
+            self._room_for([c + q for c, q in zip(cache.lens, gi[lens_key].tolist())])
+            if j < nimg:
+                m.forward_cache_update_vit(cache, **gi)
+                self.stats["vit_images"] += len(lead)
+            else:
+                m.forward_cache_update_text(cache, **gi)
+            for r, n, p in zip(lead, new_k, new_r):
+                kvl[r], rope[r] = n, p
+            adopt([(r, cache.live_prefix(slots[leader[r][j]]), rope[leader[r][j]])
+                   for r in range(k) if states[r][j] == "follow" and at[r] == j])
+            # retain what the pool has a tail page for (after the least recently used entries gave way)
+            new = [r for r in lead if chains[r][:j + 1] not in tab]
+            tails = [int(kvl[r] % ops.KV_PAGE != 0) for r in new]
+            tab.make_room(sum(tails))
+            free, keep = len(cache.pool.free), []
+            for r, t in zip(new, tails):
+                if t <= free:
+                    keep.append(r)
+                    free -= t
+            for r, h in zip(keep, cache.retain_prefix([slots[r] for r in keep])):
+                tab.put(chains[r][:j + 1], h, rope[r])
+            tab.trim()
+        if cache.cap != cap:
+            raise RuntimeError("the slot cache was re-allocated: a request does not fit the reserved capacity")
+        for b, n in zip(slots, kvl):
+            assert cache.lens[b] == n
+        self.stats["prefills"] += k
+        return [(ntid["bos_token_id"], n, r) for n, r in zip(kvl, rope)]
 
     def _check_room(self, ctx_tokens: int, req: _Request, cap: int) -> int:
         """Room for `ctx_tokens` of context + the request's new tokens in a slot?  Returns the capacity to go on with: the
