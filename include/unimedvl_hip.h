@@ -887,6 +887,77 @@ int umv_beam_step_end(const umv_beam_step_args* a, umv_stream_t stream);
 int umv_beam_kv_copy(const int32_t* copies, const void* const* pools, int R, int layers, int nkv, int hd, int npages, int chunks,
                      umv_stream_t stream);
 
+/* ------------------------------------------------------------------ banned sequences
+ * bad_words_ids, suppress_tokens, begin_suppress_tokens and min_new_tokens: a row may not emit a token that would complete a listed
+ * sequence, and some entries hold only for a row's first tokens.  tests/sequence_ban_ref.py is this text in plain Python.
+ *   table       S entries, 0 <= S <= UMV_SEQ_ENTRIES_MAX, in CSR form in device memory: entry s is the token sequence
+ *               w[0..m) = seq_tok[seq_ptr[s] .. seq_ptr[s + 1]), 1 <= m <= UMV_SEQ_MAX, n_tok = seq_ptr[S] tokens in all, with the word
+ *               until = seq_until[s]:  0 = always active;  u > 0 = active only while the row's count <= u;  UMV_SEQ_ROW (-1) = active
+ *               while count <= row_min[b] (a row value of 0 is never active, a NULL row_min is never active).  Any other until
+ *               word, or an entry whose length or offsets are outside the table, is never active (the host validates them: the table
+ *               is caller memory).
+ *   history     row b owns count[b], the number of tokens it has been fed since its slot started, after this step's record, and
+ *               tail [M][UMV_SEQ_MAX - 1], the last 15 tokens fed, most recent last, -1 where there is none.  The kernel records the
+ *               token the step is fed, ids[b] - the start token and forced tokens included; an id outside [0, 2^31) is recorded as
+ *               -1 (the n-gram kernel's rule).  A slot starts with count 0 and a tail of -1; the count stops at 2^31 - 1.
+ *   off         count[b] < 0 is a row switched off: nothing recorded, nothing banned, no byte of the row written.
+ *   banned set  entry s bans column w[m - 1] when it is active, m - 1 <= count, the last m - 1 history tokens equal w[0..m - 1)
+ *               element for element, and w[m - 1] lies in [0, V).  A -1 or out-of-range token - in the history or in w[0..m - 1) -
+ *               matches nothing.
+ *   column      a banned column becomes bf16 -inf (0xFF80), also where it held NaN; every other column keeps its bits.  A row with an
+ *               empty banned set gets no write to its logits, keys or statistics.
+ *   tiles       with argmax_partial (and optionally lse_partial) every tile that holds a banned column carries the bits the lm_head
+ *               epilogue would leave for the banned logits, exactly as umv_logit_ngram_ban_bf16 leaves them: scalar (temperature,
+ *               seed, *step) or the per-row table rows.  argmax_partial = NULL: record and ban only (the unfused step).
+ *   order       a step is lm_head, [penalty], [ngram ban], sequence ban, [constrain], step end, ...  All three bans store -inf and
+ *               commute; the penalties keep -inf.
+ *   HF          bad_words_ids=[w...] = entries (w, 0); suppress_tokens=[t...] = ([t], 0); begin_suppress_tokens=[t...] = ([t], 1);
+ *               min_new_tokens=n with end token e = ([e], UMV_SEQ_ROW) and row_min[b] = n.  The history is the fed tokens only, start
+ *               token first: a bad word that begins in the prompt is out of scope.  (HF skips a word longer than its whole input; here a word
+ *               whose first m - 1 tokens ARE everything fed so far, start token included, bans - a start token no word holds, or
+ *               a prompt in HF's input, makes the two the same.)
+ *   beam form   K >= 1: the same kernel without tail / count, recording nothing.  Row r = b * K + i at step t = step_idx[r] has
+ *               count = t + 1 and the tail ids[r], then beam_tok[u][b * K + i_u] for u = t - 2, t - 3, ..., with
+ *               i_{t-2} = beam_parent[t - 1][r] and i_{u-1} = beam_parent[u][b * K + i_u] (beam_tok / beam_parent [max_len][M] of
+ *               umv_beam_step_end; parents are beam indices inside the request), then the request's start token start_ids[b] before
+ *               u = 0.  The walk reads max_m - 1 tokens, max_m the longest entry's length as the caller states it (longer entries
+ *               see -1 beyond and do not match): max_m = 1 walks nothing.  A step counter outside [0, max_len) or a parent outside
+ *               [0, K) ends the walk (the rest of the tail is -1; the former bans nothing).  The beam form is greedy: rows is NULL.
+ * umv_logit_sequence_ban_bf16: one 256-thread workgroup per row, no word shared between workgroups.  UMV_ERR_ARG: what
+ * umv_logit_ngram_ban_bf16 rejects of the shared fields; S outside [0, UMV_SEQ_ENTRIES_MAX]; NULL seq_ptr / seq_tok / seq_until with
+ * S > 0; n_tok < S or > S * UMV_SEQ_MAX; max_m outside [0, UMV_SEQ_MAX] (or 0 with S > 0); NULL ids; the plain form (K = 0) without
+ * tail / count; the beam form without beam_tok / beam_parent / step_idx / start_ids, with K outside [1, UMV_BEAM_K_MAX], M no
+ * multiple of K, max_len < 1, or with rows.  A rejected call launches nothing. */
+#define UMV_SEQ_MAX 16
+#define UMV_SEQ_ENTRIES_MAX 4096
+#define UMV_SEQ_ROW (-1)
+typedef struct {
+    uint16_t* logits;          /* [M][V] bf16, row stride ld elements; banned in place */
+    int64_t ld;
+    const int64_t* ids;        /* [M]: the token each row is fed at this step */
+    const int32_t* seq_ptr;    /* [S + 1] */
+    const int32_t* seq_tok;    /* [n_tok] */
+    const int32_t* seq_until;  /* [S] */
+    const int32_t* row_min;    /* optional [M] */
+    int32_t* tail;             /* plain form: [M][UMV_SEQ_MAX - 1] */
+    int32_t* count;            /* plain form: [M]; negative = the row is off */
+    const int32_t* beam_tok;   /* beam form: [max_len][M] */
+    const int32_t* beam_parent;/* beam form: [max_len][M] */
+    const int64_t* step_idx;   /* beam form: [M] */
+    const int64_t* start_ids;  /* beam form: [M / K], one per request */
+    int M, V, S, n_tok, max_m;
+    int K;                     /* 0 = the plain form; >= 1 = the beam form with K beams per request */
+    int max_len;               /* beam form */
+    float temperature;         /* as given to the lm_head GEMM: 0 = greedy keys and y = l */
+    uint64_t* argmax_partial;  /* optional [M][n_tiles] */
+    float* lse_partial;        /* optional [M][n_tiles][2], only with argmax_partial */
+    int n_tiles;
+    uint64_t seed;             /* sample_seed / sample_step of the lm_head call (temperature > 0) */
+    const int64_t* step;
+    const umv_row_sampling* rows; /* optional [M]: row b's temperature and (seed, draw, stream); the scalar temperature must be 0 */
+} umv_sequence_ban_args;
+int umv_logit_sequence_ban_bf16(const umv_sequence_ban_args* a, umv_stream_t stream);
+
 
 /* TimestepEmbedder.timestep_embedding (modeling_utils.py:87-109): out[r] = bf16(cat(cos(t[r] * freqs), sin(t[r] * freqs))),
  * out [n, 2*half]; freqs [half] fp32 = exp(-ln(10000) * i / half) from the caller.  The two linears + SiLU of the embedder

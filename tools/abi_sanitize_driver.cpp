@@ -388,6 +388,51 @@ static void bad_arguments() {
     EXPECT_ERR(umv_beam_kv_copy(beam_words, beam_pools, 0, 1, 2, 128, 4, 0, nullptr));    // no chunks
     EXPECT_ERR(umv_beam_kv_copy(beam_words + 1, beam_pools, 0, 1, 2, 128, 4, 1, nullptr));   // misaligned copy list
     EXPECT_OK(umv_beam_kv_copy(beam_words, beam_pools, 0, 1, 2, 128, 4, 1, nullptr));     // no rows
+    // banned sequences
+    EXPECT_ERR(umv_logit_sequence_ban_bf16(nullptr, nullptr));
+    umv_sequence_ban_args sq;
+    std::memset(&sq, 0, sizeof sq);
+    EXPECT_ERR(umv_logit_sequence_ban_bf16(&sq, nullptr));
+    sq.logits = dummy16; sq.ld = 64; sq.ids = dummyl; sq.seq_ptr = dummyi; sq.seq_tok = dummyi; sq.seq_until = dummyi; sq.tail = dummyi;
+    sq.count = dummyi; sq.M = 1; sq.V = 64; sq.S = 1; sq.n_tok = 2; sq.max_m = 2;
+    sq.S = -1;                                                   // a negative entry count
+    EXPECT_ERR(umv_logit_sequence_ban_bf16(&sq, nullptr));
+    sq.S = UMV_SEQ_ENTRIES_MAX + 1; sq.n_tok = sq.S;             // more entries than the maximum
+    EXPECT_ERR(umv_logit_sequence_ban_bf16(&sq, nullptr));
+    sq.S = 1; sq.n_tok = 2; sq.seq_ptr = nullptr;                // entries without a table
+    EXPECT_ERR(umv_logit_sequence_ban_bf16(&sq, nullptr));
+    sq.seq_ptr = dummyi; sq.seq_until = nullptr;
+    EXPECT_ERR(umv_logit_sequence_ban_bf16(&sq, nullptr));
+    sq.seq_until = dummyi; sq.n_tok = UMV_SEQ_MAX + 1;           // more tokens than S entries can hold
+    EXPECT_ERR(umv_logit_sequence_ban_bf16(&sq, nullptr));
+    sq.n_tok = 2; sq.max_m = UMV_SEQ_MAX + 1;                    // a longest entry above the maximum
+    EXPECT_ERR(umv_logit_sequence_ban_bf16(&sq, nullptr));
+    sq.max_m = 2; sq.ids = nullptr;                              // no fed tokens
+    EXPECT_ERR(umv_logit_sequence_ban_bf16(&sq, nullptr));
+    sq.ids = dummyl; sq.tail = nullptr;                          // the plain form without its tail
+    EXPECT_ERR(umv_logit_sequence_ban_bf16(&sq, nullptr));
+    sq.tail = dummyi; sq.count = nullptr;
+    EXPECT_ERR(umv_logit_sequence_ban_bf16(&sq, nullptr));
+    sq.count = dummyi; sq.K = 2; sq.M = 2; sq.max_len = 4;       // the beam form without its back-pointers
+    EXPECT_ERR(umv_logit_sequence_ban_bf16(&sq, nullptr));
+    sq.beam_tok = dummyi; sq.beam_parent = dummyi; sq.step_idx = dummyl; sq.start_ids = dummyl; sq.K = UMV_BEAM_K_MAX + 1;
+    EXPECT_ERR(umv_logit_sequence_ban_bf16(&sq, nullptr));       // K above the maximum
+    sq.K = 2; sq.M = 3;                                          // rows that are no multiple of K
+    EXPECT_ERR(umv_logit_sequence_ban_bf16(&sq, nullptr));
+    sq.M = 2; sq.rows = rows; sq.argmax_partial = (uint64_t*)dummyl; sq.n_tiles = 4;      // the beam form is greedy
+    EXPECT_ERR(umv_logit_sequence_ban_bf16(&sq, nullptr));
+    sq.rows = nullptr; sq.argmax_partial = nullptr; sq.n_tiles = 0; sq.K = 0; sq.M = 1; sq.temperature = -1.f;   // negative temperature
+    EXPECT_ERR(umv_logit_sequence_ban_bf16(&sq, nullptr));
+    sq.temperature = 0.f; sq.lse_partial = dummyf;               // lse_partial without argmax_partial
+    EXPECT_ERR(umv_logit_sequence_ban_bf16(&sq, nullptr));
+    sq.lse_partial = nullptr; sq.argmax_partial = (uint64_t*)dummyl; sq.n_tiles = 3;     // 64 columns are not 3 tiles
+    EXPECT_ERR(umv_logit_sequence_ban_bf16(&sq, nullptr));
+    sq.n_tiles = 4; sq.ld = 32;                                  // a row stride below V
+    EXPECT_ERR(umv_logit_sequence_ban_bf16(&sq, nullptr));
+    sq.ld = 64; sq.M = 0;
+    EXPECT_OK(umv_logit_sequence_ban_bf16(&sq, nullptr));        // no rows
+    sq.S = 0; sq.n_tok = 0; sq.max_m = 0; sq.seq_ptr = nullptr; sq.seq_tok = nullptr; sq.seq_until = nullptr;
+    EXPECT_OK(umv_logit_sequence_ban_bf16(&sq, nullptr));        // an empty table records only
     // speculative step end
     EXPECT_ERR(umv_decode_step_end_speculative(nullptr, nullptr));
     umv_spec_step_args sp;

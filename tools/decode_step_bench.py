@@ -13,6 +13,10 @@ about 5 us) in a kernel trace of a decode run: --trace-arm NAME runs that arm of
   ngram         a off | b greedy, no_repeat_ngram_size 3, generated history only | c b plus a 1024-token seeded context per row (the
                 scan walks about 1.2 k int32 per row) | d do_sample, top_p 0.9, logprobs, repetition_penalty 1.1 and the same n = 3 (d0: that
                 sampler and penalty, n-gram ban off)
+  sequences     a off | b min_new_tokens 1000 alone (one single-token entry, active on every step) | c 64 bad words of 1 to 4 tokens |
+                d a suppress list of 4096 tokens (every thread scans 16 entries and recomputes 16 tiles) | e beam search, 8 requests
+                of 4 beams, with one 16-token bad word next to the 64: max_m = 16, every row walks 14 back-pointers (e0: the same
+                search, stage off)
   logprobs      off | on, greedy; plus a `score` leg: one Bagel.score call (a 448 x 448 image, a 32-token question, four candidates of
                 eight tokens) next to one Bagel.chat call with max_length = 9, each run twice - the warm time is the one to read
   top_logprobs  a greedy logprobs | b a + top 5 | c a + top 20 | s do_sample | d s + top_k 50: the yardstick - the selection runs the
@@ -210,6 +214,40 @@ NGRAM_SUITE = Suite(
     spread=[("a_off", "a_spread_ms"), ("d0_sample_top_p_logprobs_penalty_off", "d0_spread_ms")], hook=_ngram_histories)
 
 
+# ---- banned sequences
+def _bad_words(n, longest=4, extra=()):
+    def build(cfg):
+        g = torch.Generator().manual_seed(9)
+        words = [torch.randint(1000, 100000, (1 + i % longest,), generator=g).tolist() for i in range(n)]
+        return dict(bad_words_ids=words + [list(w) for w in extra])
+    return build
+
+
+def _suppress_list(cfg):
+    return dict(suppress_tokens=torch.randperm(cfg.vocab, generator=torch.Generator().manual_seed(9))[:4096].tolist())
+
+
+def _sequence_tables(run, res):
+    for arm, s in run.sessions.items():
+        if s.seq_table is not None:
+            res[arm].update(entries=s.seq_table.S, table_tokens=s.seq_table.n_tok, max_m=s.seq_table.max_m)
+            if s.seq_count is not None:
+                res[arm]["count_at_end"] = [int(v) for v in s.seq_count.tolist()]
+
+
+def _beamed(kw):
+    return lambda cfg: dict(kw(cfg) if callable(kw) else kw, rows=8, num_beams=4)
+
+
+SEQUENCES = Suite(
+    arms={"a_off": {}, "b_min_new_tokens": dict(min_new_tokens=1000, end_token_id=EOS), "c_64_bad_words": _bad_words(64),
+          "d_suppress_4096": _suppress_list, "e0_beam_8x4_off": _beamed({}),
+          "e_beam_8x4_max_m16": _beamed(_bad_words(64, extra=[range(2000, 2016)]))},
+    over=[(arm, "a_off", "over_a_us") for arm in ("b_min_new_tokens", "c_64_bad_words", "d_suppress_4096")]
+    + [("e_beam_8x4_max_m16", "e0_beam_8x4_off", "over_e0_us")],
+    spread=[("a_off", "a_spread_us"), ("e0_beam_8x4_off", "e0_spread_us")], hook=_sequence_tables)
+
+
 # ---- logprobs
 def _logprob_values(run, res):
     n = run.args.warmup + run.args.repeats * run.args.steps
@@ -363,7 +401,7 @@ BEAM = Suite(arms={"a_rows4": dict(rows=4, logprobs=True), "b_beam_1x4": dict(ro
              over=[("b_beam_1x4", "a_rows4", "over_plain_us"), ("c_beam_8x4", "a_rows32", "over_plain_us")],
              spread=[("a_rows4", "a_rows4_spread_us"), ("a_rows32", "a_rows32_spread_us")], hook=_beam_reorders)
 
-SUITES = {"penalties": PENALTIES, "constraint": CONSTRAINT, "ngram": NGRAM_SUITE, "logprobs": LOGPROBS, "top_logprobs": TOP_LOGPROBS, "truncated": TRUNCATED,
+SUITES = {"penalties": PENALTIES, "constraint": CONSTRAINT, "ngram": NGRAM_SUITE, "sequences": SEQUENCES, "logprobs": LOGPROBS, "top_logprobs": TOP_LOGPROBS, "truncated": TRUNCATED,
           "per_request": PER_REQUEST, "beam": BEAM}
 
 

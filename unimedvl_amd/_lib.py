@@ -140,6 +140,18 @@ class BeamStepArgs(C.Structure):
     ]
 
 
+class SequenceBanArgs(C.Structure):
+    """umv_sequence_ban_args: banned sequences on the stored logits of a step (umv_logit_sequence_ban_bf16)"""
+    _fields_ = [
+        ("logits", C.c_void_p), ("ld", C.c_int64), ("ids", C.c_void_p), ("seq_ptr", C.c_void_p), ("seq_tok", C.c_void_p),
+        ("seq_until", C.c_void_p), ("row_min", C.c_void_p), ("tail", C.c_void_p), ("count", C.c_void_p), ("beam_tok", C.c_void_p),
+        ("beam_parent", C.c_void_p), ("step_idx", C.c_void_p), ("start_ids", C.c_void_p),
+        ("M", C.c_int), ("V", C.c_int), ("S", C.c_int), ("n_tok", C.c_int), ("max_m", C.c_int), ("K", C.c_int), ("max_len", C.c_int),
+        ("temperature", C.c_float), ("argmax_partial", C.c_void_p), ("lse_partial", C.c_void_p), ("n_tiles", C.c_int),
+        ("seed", C.c_uint64), ("step", C.c_void_p), ("rows", C.c_void_p),
+    ]
+
+
 # beam search decode: the most beams a request can have, and the full-page table entries one request's step end can carry (K * n_own)
 BEAM_K_MAX, BEAM_TABLE_ENTRIES = 10, 1024
 # umv_logit_penalty_args.count words: bits 0..29 the count, then "in the context set" and "in the row's visit list"
@@ -151,6 +163,8 @@ TOP_LOGPROBS_MAX, TOP_AFTER_LOGPROB, TOP_AFTER_TRUNCATED = 20, 0, 1
 CONSTRAINT_FREE, CONSTRAINT_LEFT, CONSTRAIN_CHUNK = -1, -2, 4096
 # no-repeat n-grams: the largest size a row can ask for, and the length word of a row whose history ran full (UMV_NGRAM_FULL)
 NGRAM_MAX, NGRAM_FULL = 16, -2
+# banned sequences: the longest entry, the most entries, and the `until` word of an entry that holds while count <= row_min[b]
+SEQ_MAX, SEQ_ENTRIES_MAX, SEQ_ROW = 16, 4096, -1
 
 
 _SIGS = {
@@ -237,6 +251,7 @@ _SIGS = {
     "umv_beam_candidates": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
     "umv_beam_step_end": (C.c_int, [C.POINTER(BeamStepArgs), C.c_void_p]),
+    "umv_logit_sequence_ban_bf16": (C.c_int, [C.POINTER(SequenceBanArgs), C.c_void_p]),
     "umv_beam_kv_copy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "umv_timestep_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "umv_cfg_renorm_euler": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,

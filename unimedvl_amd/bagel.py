@@ -335,7 +335,8 @@ class Bagel(BagelPrep):
                       logit_bias=None, penalty_context_ids=None, draft_len: int = 0, draft_ngram=(2, 4), draft_context_ids=None,
                       predicted_ids=None, sampling=None, top_logprobs: int = 0, constraint=None, constraint_states=None,
                       no_repeat_ngram_size=0, ngram_context_ids=None, num_beams: int = 1, length_penalty: float = 1.0,
-                      early_stopping: bool = False, num_return_sequences: int = 1, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+                      early_stopping: bool = False, num_return_sequences: int = 1, bad_words_ids=None, suppress_tokens=None,
+                      begin_suppress_tokens=None, min_new_tokens=0, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """Greedy decode (bagel.py:1236-1317).  Returns [steps, B] int64 whose row 0 holds the
         start tokens.  Like the reference, the batch stops when SAMPLE 0 emits end_token_id
         (bagel.py:1313); per_sample_eos=True is the batched extension (stops when every sample
@@ -385,8 +386,25 @@ class Bagel(BagelPrep):
         behind a sample's end).  self.last_beam_hypotheses keeps, per sample, the num_return_sequences (<= K) best hypotheses as
         dicts (tokens, tokens_no_end, score - the length-normalised one -, total, logprobs).  Excludes do_sample, sampling,
         draft_len, top_logprobs, return_logits, constraint, the penalties, logit_bias, no_repeat_ngram_size and top_k / top_p /
-        min_p (ValueError before any launch); 1 = off: today's call."""
+        min_p (ValueError before any launch); 1 = off: today's call.
+        bad_words_ids (token lists of at most 16), suppress_tokens, begin_suppress_tokens (token lists) and min_new_tokens (an int or
+        one per sample; bans end_token_id, which it needs): HF's keywords of these names, in the captured step (DecodeSession;
+        include/unimedvl_hip.h, banned sequences) behind the n-gram ban and before the constraint mask; ids, logits, logprobs and
+        top_logprobs are those of the banned logits.  The history is the start token and what is fed after it: a bad word that begins
+        in the prompt is not seen.  They are the one logit stage that also runs with num_beams > 1 (every beam by its own tokens).
+        With draft_len > 0 they raise."""
         num_beams = ops.check_beams(num_beams, self.cfg.vocab, len(past_key_values.lens))
+        words, suppress, begin, mins, _ = ops.check_sequences(bad_words_ids, suppress_tokens, begin_suppress_tokens, min_new_tokens,
+                                                              end_token_id if min_new_tokens else None, vocab=self.cfg.vocab,
+                                                              rows=len(past_key_values.lens))
+        banned = {}                          # what is on, under DecodeSession's names
+        if words or suppress or begin:
+            banned.update(bad_words_ids=words, suppress_tokens=suppress, begin_suppress_tokens=begin)
+        if any(mins) if isinstance(mins, list) else mins:
+            banned.update(min_new_tokens=mins)
+        if banned and draft_len:
+            raise ValueError("bad_words_ids / suppress_tokens / begin_suppress_tokens / min_new_tokens are not available with "
+                             "draft_len > 0 (speculative decode)")
         if num_beams > 1:
             from .beam import check_beam_keywords
             check_beam_keywords(num_beams, do_sample=do_sample, sampling=sampling, draft_len=draft_len, top_logprobs=top_logprobs,
@@ -394,7 +412,9 @@ class Bagel(BagelPrep):
                                 presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, logit_bias=logit_bias,
                                 no_repeat_ngram_size=no_repeat_ngram_size, top_k=top_k, top_p=top_p, min_p=min_p)
             return self._generate_text_beams(past_key_values, packed_start_tokens, packed_query_position_ids, max_length, end_token_id,
-                                             return_logprobs, num_beams, length_penalty, early_stopping, num_return_sequences)
+                                             return_logprobs, num_beams, length_penalty, early_stopping, num_return_sequences, banned)
+        if "min_new_tokens" in banned:
+            banned.update(end_token_id=end_token_id)
         sizes = [ops.check_ngram(v) for v in no_repeat_ngram_size] if isinstance(no_repeat_ngram_size, (list, tuple)) else \
             [ops.check_ngram(no_repeat_ngram_size)]
         if draft_len and (any(sizes) or (sampling is not None and any(p.no_repeat_ngram_size for p in per_sample(
@@ -457,7 +477,7 @@ class Bagel(BagelPrep):
                              max_length, use_graph=self.decode_use_graph and not return_logits, seed=seed, logprobs=return_logprobs,
                              logit_bias=logit_bias, penalty_context_ids=penalty_context_ids, top_logprobs=top_logprobs,
                              constraint=constraint, constraint_states=constraint_states, no_repeat_ngram_size=no_repeat_ngram_size,
-                             ngram_context_ids=ngram_context_ids, **sampler)
+                             ngram_context_ids=ngram_context_ids, **banned, **sampler)
         logits = []
         steps = 0
         stop = None
@@ -490,8 +510,9 @@ class Bagel(BagelPrep):
         return res if len(res) > 1 else out
 
     def _generate_text_beams(self, cache, start_tokens, positions, max_length, end_token_id, return_logprobs, num_beams, length_penalty,
-                             early_stopping, num_return_sequences):
-        """generate_text with num_beams > 1: one beam search on a fork of `cache`, the best hypotheses as the usual matrix"""
+                             early_stopping, num_return_sequences, banned=None):
+        """generate_text with num_beams > 1: one beam search on a fork of `cache`, the best hypotheses as the usual matrix.  banned:
+        the banned-sequence keywords that are on (beam_generate's names)"""
         from .beam import beam_generate, check_beam_options
         check_beam_options(num_beams, length_penalty, early_stopping, num_return_sequences)
         if not hasattr(cache, "fork_beams"):
@@ -504,7 +525,7 @@ class Bagel(BagelPrep):
             return (out, torch.zeros((0, B), dtype=torch.float32, device=self.device)) if return_logprobs else out
         hyps = beam_generate(self.language_model, cache, start_tokens, positions, max_length, num_beams, end_token_id=end_token_id,
                              length_penalty=length_penalty, early_stopping=early_stopping, num_return_sequences=num_return_sequences,
-                             use_graph=self.decode_use_graph, eos_check_every=self.eos_check_every)
+                             use_graph=self.decode_use_graph, eos_check_every=self.eos_check_every, **(banned or {}))
         self.last_beam_hypotheses = hyps
         n = max(len(h[0]["tokens"]) for h in hyps)
         fill = 0 if end_token_id is None else int(end_token_id)
@@ -562,6 +583,7 @@ class Bagel(BagelPrep):
              sampling=None, top_logprobs: int = 0, choices=None, choices_after: str = "stop",
              no_repeat_ngram_size: int = 0, no_repeat_ngram_prompt: bool = False,
              num_beams: int = 1, length_penalty: float = 1.0, early_stopping: bool = False, num_return_sequences: int = 1,
+             bad_words_ids=None, bad_words=None, suppress_tokens=None, begin_suppress_tokens=None, min_new_tokens: int = 0,
              top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """ViT-only VQA convenience path (bagel.py:1321-1392).  return_logprobs=True: returns (answer, token_ids, token_logprobs) -
         the generated tokens behind the answer (the end token excluded) and the log-probability of each (generate_text).
@@ -586,7 +608,12 @@ class Bagel(BagelPrep):
         num_beams > 1: beam search decode (generate_text) - the context is prefilled into a PagedCache of its own
         (self.beam_context_tokens bounds the prompt) and the best hypothesis is the answer; length_penalty / early_stopping as HF's.
         With num_return_sequences > 1 the call returns a list of (answer, score), best first.  It excludes what generate_text
-        excludes, and `choices`."""
+        excludes, and `choices`.
+        bad_words_ids / suppress_tokens / begin_suppress_tokens / min_new_tokens: generate_text's (HF's) keywords - phrases and tokens
+        the answer must not hold, and the number of tokens it holds at the least before the end token may come; also with num_beams.
+        bad_words (strings): each is encoded twice, bare and with a leading space - a word inside a sentence and one at its start
+        are different tokens - and both token sequences join bad_words_ids (ops.encode_bad_words); a phrase is banned as the
+        tokenizer splits it, other spellings (capitals, no space after a bracket) are other phrases."""
         if num_beams > 1:
             from .beam import check_beam_keywords
             check_beam_keywords(ops.check_beams(num_beams, self.cfg.vocab, 1), choices=choices, draft_len=draft_len, sampling=sampling)
@@ -631,7 +658,9 @@ class Bagel(BagelPrep):
                                  sampling=sampling, constraint=constraint, no_repeat_ngram_size=no_repeat_ngram_size,
                                  ngram_context_ids=[text_ids] if no_repeat_ngram_prompt else None, num_beams=num_beams,
                                  length_penalty=length_penalty, early_stopping=early_stopping, num_return_sequences=num_return_sequences,
-                                 **draft, **gi)
+                                 bad_words_ids=list(bad_words_ids or []) + ops.encode_bad_words(tokenizer, bad_words),
+                                 suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
+                                 min_new_tokens=min_new_tokens, **draft, **gi)
         if num_beams > 1 and num_return_sequences > 1:
             def text(tokens):
                 return tokenizer.decode(torch.tensor([int(gi["packed_start_tokens"][0])] + tokens)).split("<|im_end|>")[0].split("<|im_start|>")[1]

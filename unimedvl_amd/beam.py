@@ -66,13 +66,16 @@ class BeamDecodeSession(DecodeSession):
 
     def __new__(cls, llm, cache, start_tokens, positions, max_length, num_beams=1, **kw):
         if ops.check_beams(num_beams) == 1:
-            for k in ("end_token_id", "length_penalty", "early_stopping", "num_return_sequences", "eos_check_every"):
+            for k in ("length_penalty", "early_stopping", "num_return_sequences", "eos_check_every"):
                 kw.pop(k, None)
+            if not kw.get("min_new_tokens"):            # (the plain session takes the end token only to hold it back)
+                kw.pop("end_token_id", None)
             return DecodeSession(llm, cache, start_tokens, positions, max_length, **kw)
         return super().__new__(cls)
 
     def __init__(self, llm, cache, start_tokens, positions, max_length, num_beams=1, *, end_token_id=None, length_penalty=1.0,
-                 early_stopping=False, num_return_sequences=1, use_graph=True, nsplit=None, eos_check_every=8, **excluded):
+                 early_stopping=False, num_return_sequences=1, use_graph=True, nsplit=None, eos_check_every=8, bad_words_ids=None,
+                 suppress_tokens=None, begin_suppress_tokens=None, min_new_tokens=0, **excluded):
         check_beam_keywords(num_beams, **excluded)
         if not hasattr(cache, "fork_beams"):
             raise ValueError(f"num_beams > 1 needs a PagedCache (the beams share the prompt's pages), got {type(cache).__name__}")
@@ -90,6 +93,12 @@ class BeamDecodeSession(DecodeSession):
                 pos = torch.as_tensor(positions).reshape(-1).repeat_interleave(K)
                 self._init(llm, fork, starts, pos, max_length, use_graph=False, nsplit=nsplit, logprobs=True)
                 self.beam = ops.BeamState(self.requests, K, max_length, self.dev, self.length_penalty)
+                # banned sequences (the first logit stage under beams: its state is the step number and the back-pointers): min_new_tokens
+                # one per request; the start tokens are kept aside, ids moves on
+                self._init_sequences(bad_words_ids, suppress_tokens, begin_suppress_tokens, min_new_tokens, self.end_token_id, beams=K)
+                if self.seq_table is not None:
+                    self.seq_start = torch.as_tensor(start_tokens).reshape(-1).to(device=self.dev, dtype=torch.int64).clone()
+                    self.seq_beam = (self.beam.beam_tok, self.beam.beam_parent, self.step_idx, self.seq_start, K)
                 self.pools = ops.beam_pool_pointers(fork.pool.slabs)
                 if use_graph:
                     self._capture()
@@ -167,11 +176,14 @@ class BeamDecodeSession(DecodeSession):
 
 
 def beam_generate(llm, cache, start_tokens, positions, max_length, num_beams, *, end_token_id=None, length_penalty=1.0,
-                  early_stopping=False, num_return_sequences=1, use_graph=True, eos_check_every=8):
-    """One beam search over `cache` (a prefilled PagedCache, left as it was): the session's result()."""
+                  early_stopping=False, num_return_sequences=1, use_graph=True, eos_check_every=8, bad_words_ids=None,
+                  suppress_tokens=None, begin_suppress_tokens=None, min_new_tokens=0):
+    """One beam search over `cache` (a prefilled PagedCache, left as it was): the session's result().  bad_words_ids, suppress_tokens,
+    begin_suppress_tokens, min_new_tokens (an int or one per request): DecodeSession's keywords of these names, per beam."""
     sess = BeamDecodeSession(llm, cache, start_tokens, positions, max_length, num_beams, end_token_id=end_token_id,
                              length_penalty=length_penalty, early_stopping=early_stopping, num_return_sequences=num_return_sequences,
-                             use_graph=use_graph, eos_check_every=eos_check_every)
+                             use_graph=use_graph, eos_check_every=eos_check_every, bad_words_ids=bad_words_ids,
+                             suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens, min_new_tokens=min_new_tokens)
     try:
         return sess.run().result()
     finally:

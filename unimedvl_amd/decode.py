@@ -43,7 +43,8 @@ class DecodeSession:
                  repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, penalty_context_ids=None,
                  penalty_context_room=None, penalty_history=None, row_sampling=None, row_streams=None, row_penalties=False,
                  top_logprobs=0, constraint=None, constraint_states=None, no_repeat_ngram_size=0, ngram_context_ids=None,
-                 ngram_context_room=None, ngram_history=None, top_k=0, top_p=1.0, min_p=0.0):
+                 ngram_context_room=None, ngram_history=None, bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None,
+                 min_new_tokens=0, end_token_id=None, sequence_row_min=False, top_k=0, top_p=1.0, min_p=0.0):
         """logprobs: also record pred_logprobs (fp32 [max_length, B]) - row s is the log-probability of in_ids[s + 1], the token step s
         picked (include/unimedvl_hip.h, token log-probabilities: of softmax(logits) in greedy decoding, of softmax(bf16(logits / T))
         when sampling).  forced_ids (int64 [max_length, B]): where an entry is >= 0 that token is fed to the next step instead of the
@@ -100,7 +101,18 @@ class DecodeSession:
         (default max_length - more when requests outlive a round of max_length steps; with row_sampling, giving it reserves the
         buffers even while every row's size is 0).  A slot whose history runs full stops banning.  Works on the fused and the unfused
         step and with every keyword above; not with draft_len > 0 (ValueError).  Off: today's step, launch for launch, no buffer
-        allocated."""
+        allocated.
+        bad_words_ids (a list of token lists of at most 16), suppress_tokens, begin_suppress_tokens (token lists) and min_new_tokens
+        (an int, or a list of one per sample; needs end_token_id): HF's keywords of these names (include/unimedvl_hip.h, banned
+        sequences) - no sample is fed the last token of a bad word whose other tokens it was just fed, a suppressed token, a
+        begin-suppressed token as its first pick, or end_token_id among its first min_new_tokens picks.  One
+        umv_logit_sequence_ban_bf16 launch behind the n-gram ban and before the constraint mask records the token the step is fed in
+        the sample's count and 15-token tail and sets the banned columns to -inf, their tiles' keys and statistics with them.  The
+        history is the fed tokens, start token first: a bad word that begins in the prompt is not seen.  The session owns the state:
+        set_slot starts a slot's over (min_new_tokens= gives it its own minimum), rewind_outputs keeps it, copy_sequence_state takes
+        another session's.  sequence_row_min=True (with end_token_id) reserves the end-token entry and the per-slot minimums for later
+        set_slot calls while every minimum is 0.  Works on the fused and the unfused step and with every keyword above; not with
+        draft_len > 0 (ValueError).  Off: today's step, launch for launch, no buffer allocated."""
         if constraint is None and constraint_states is not None:
             raise ValueError("constraint_states goes with constraint")
         if constraint is not None and self.draft_len:
@@ -122,7 +134,9 @@ class DecodeSession:
                        penalty_history=penalty_history, row_sampling=row_sampling, row_streams=row_streams, row_penalties=row_penalties,
                        top_logprobs=top_logprobs, constraint=constraint, constraint_states=constraint_states, top_k=top_k, top_p=top_p,
                        min_p=min_p, no_repeat_ngram_size=no_repeat_ngram_size, ngram_context_ids=ngram_context_ids,
-                       ngram_context_room=ngram_context_room, ngram_history=ngram_history)
+                       ngram_context_room=ngram_context_room, ngram_history=ngram_history, bad_words_ids=bad_words_ids,
+                       suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens, min_new_tokens=min_new_tokens,
+                       end_token_id=end_token_id, sequence_row_min=sequence_row_min)
 
     @property
     def device(self):
@@ -132,7 +146,8 @@ class DecodeSession:
               logprobs=False, forced_ids=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None,
               penalty_context_ids=None, penalty_context_room=None, penalty_history=None, row_sampling=None, row_streams=None,
               row_penalties=False, top_logprobs=0, constraint=None, constraint_states=None, top_k=0, top_p=1.0, min_p=0.0,
-              no_repeat_ngram_size=0, ngram_context_ids=None, ngram_context_room=None, ngram_history=None):
+              no_repeat_ngram_size=0, ngram_context_ids=None, ngram_context_room=None, ngram_history=None, bad_words_ids=None,
+              suppress_tokens=None, begin_suppress_tokens=None, min_new_tokens=0, end_token_id=None, sequence_row_min=False):
         """the constructor's keywords under the constructor's names, already checked against each other (__init__)"""
         cfg, dev = llm.cfg, llm.device
         self.llm, self.cache, self.cfg, self.dev = llm, cache, cfg, dev
@@ -335,6 +350,7 @@ class DecodeSession:
         self._init_penalties(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, penalty_context_ids,
                              penalty_context_room, penalty_history, force)
         self._init_ngram(no_repeat_ngram_size, ngram_context_ids, ngram_context_room, ngram_history)
+        self._init_sequences(bad_words_ids, suppress_tokens, begin_suppress_tokens, min_new_tokens, end_token_id, sequence_row_min)
         self._init_constraint(constraint, constraint_states)
         self.steps_done = 0
         self.graph = None
@@ -444,6 +460,68 @@ class DecodeSession:
         self.ng_len[at] = other.ng_len[at]
         if self.ng_row_n is not None:
             self.ng_row_n[at] = other.ng_row_n[at]
+
+    # ---- banned sequences (include/unimedvl_hip.h): one static table for the session; per slot the count of tokens fed, the last 15 of
+    # them and, where min_new_tokens is in play, the slot's minimum.  beams (K > 0): the rows are B / K requests of K beams, the kernel
+    # takes count and tail from the search's back-pointers (self.seq_beam, set by the beam session) and the session owns no history
+    def _init_sequences(self, bad_words_ids, suppress_tokens, begin_suppress_tokens, min_new_tokens, end_token_id, row_entry=False,
+                        beams=0):
+        dev, B = self.dev, self.B
+        self.seq_table = self.seq_tail = self.seq_count = self.seq_row_min = self.seq_beam = None
+        requests = B // beams if beams else B
+        probe = min_new_tokens.tolist() if hasattr(min_new_tokens, "tolist") else min_new_tokens
+        held = any(probe) if isinstance(probe, (list, tuple)) else bool(probe)
+        # (an end token that holds nothing back is not looked at)
+        _, _, _, mins, end = ops.check_sequences(bad_words_ids, suppress_tokens, begin_suppress_tokens, min_new_tokens,
+                                                 end_token_id if held or row_entry else None, vocab=self.cfg.vocab, rows=requests)
+        if row_entry and end is None:
+            raise ValueError("sequence_row_min reserves the end-token entry: it needs end_token_id")
+        ptr, tok, until, _ = ops.sequence_table(bad_words_ids, suppress_tokens, begin_suppress_tokens, mins, end, vocab=self.cfg.vocab,
+                                                row_entry=row_entry)
+        if not len(until):
+            return                                  # off: today's step
+        if self.draft_len:
+            raise ValueError("bad_words_ids / suppress_tokens / begin_suppress_tokens / min_new_tokens are not available with "
+                             "draft_len > 0 (speculative decode)")
+        self.seq_table = ops.SequenceTable(ptr, tok, until, dev)
+        if int(until[-1]) == ops.SEQ_ROW:
+            per = mins if isinstance(mins, list) else [mins] * requests
+            self.seq_row_min = torch.tensor([n for n in per for _ in range(max(1, beams))], dtype=torch.int32).to(dev)
+        if not beams:
+            self.seq_tail = torch.full((B, ops.SEQ_TAIL), -1, dtype=torch.int32, device=dev)
+            self.seq_count = torch.zeros((B,), dtype=torch.int32, device=dev)
+
+    def _reset_sequence_slot(self, b, min_new_tokens=None):
+        """Slot b starts a request: nothing fed yet; min_new_tokens (None: as it is) becomes the slot's minimum."""
+        if min_new_tokens is not None:
+            n = ops.check_sequences(min_new_tokens=min_new_tokens, end_token_id=0)[3]
+            if isinstance(n, list):
+                raise ValueError(f"set_slot(min_new_tokens=...) takes one integer, got {min_new_tokens!r}")
+            if self.seq_row_min is None:
+                if n:
+                    raise ValueError("this session reserved no minimums: build it with min_new_tokens or sequence_row_min=True (and end_token_id)")
+            else:
+                self.seq_row_min[b:b + 1].fill_(n)
+        if self.seq_tail is not None:
+            self.seq_tail[b].fill_(-1)
+            self.seq_count[b:b + 1].fill_(0)
+
+    @ops.on_device
+    def copy_sequence_state(self, other, slots=None):
+        """Take over another session's banned-sequence state (counts, tails, minimums) for `slots` (default: all) - a re-captured step
+        goes on with those requests.  The sessions were built with the same table; one that carried no minimums leaves this one's as
+        they were built."""
+        if self.seq_tail is None or other.seq_tail is None:      # (a session that had no table had nothing banned: nothing to take)
+            return
+        if other.seq_tail.shape != self.seq_tail.shape:
+            raise ValueError("copy_sequence_state: the sessions do not hold the same slots")
+        rows, at = self._slot_index(slots)
+        if not rows:
+            return
+        self.seq_tail[at] = other.seq_tail[at]
+        self.seq_count[at] = other.seq_count[at]
+        if self.seq_row_min is not None and other.seq_row_min is not None:
+            self.seq_row_min[at] = other.seq_row_min[at]
 
     # ---- constrained decoding (include/unimedvl_hip.h, token automata): the automaton's tables and one state word per sample
     def _init_constraint(self, automaton, states):
@@ -593,6 +671,11 @@ class DecodeSession:
             # record the token this step is fed in every sample's history and set the columns that would repeat an n-gram of it to
             # -inf, their tiles' keys and statistics with them - again with what the lm_head call got
             ops.logit_ngram_ban(self.logits, self.ids, self.ng_hist, self.ng_len, n=self.ng_n, row_n=self.ng_row_n, **self.step_kw)
+        if self.seq_table is not None:
+            # record the token this step is fed in every sample's count and tail (a beam search: read them off its back-pointers) and set
+            # the columns the table bans to -inf, their tiles' keys and statistics with them - again with what the lm_head call got
+            ops.logit_sequence_ban(self.logits, self.ids, self.seq_table, tail=self.seq_tail, count=self.seq_count,
+                                   row_min=self.seq_row_min, beam=self.seq_beam, **self.step_kw)
         if self.con_state is not None:
             # mask the (adjusted) logits of every constrained sample to its state's tokens and rewrite its tiles' keys and statistics,
             # again with what the lm_head call got: the step end picks from, and normalises over, the allowed set
@@ -648,6 +731,8 @@ class DecodeSession:
             state += (self.con_state,)
         if self.ng_hist is not None:                # ... and appends to the n-gram histories
             state += (self.ng_hist, self.ng_len)
+        if self.seq_tail is not None:               # ... and records in the banned-sequence counts and tails
+            state += (self.seq_tail, self.seq_count)
         return state
 
     def _capture(self):
@@ -684,7 +769,7 @@ class DecodeSession:
     # re-pointed at a new request between replays without re-capturing
     @ops.on_device
     def set_slot(self, b, token, kv_len, pos, penalty_context_ids=None, sampling=None, stream=None, draw=0, constraint_state=None,
-                 ngram_context_ids=None):
+                 ngram_context_ids=None, min_new_tokens=None):
         """Sample b continues from `token` with `kv_len` tokens already in its cache segment and rope position `pos`.  With penalties
         on, the slot's history starts over: no generated tokens, penalty_context_ids as its context set, `token` as its start token.
         sampling (a SamplingParams; sessions with row_sampling): row b of the table is rewritten - the slot decodes with these
@@ -693,7 +778,9 @@ class DecodeSession:
         constraint_state (sessions with constraint): the slot's state word becomes this state of the automaton (-1 = unconstrained)
         from the next replay on; without it the word stays as it is.
         With no_repeat_ngram_size on, the slot's n-gram history starts over as well: ngram_context_ids (default: nothing) is what
-        precedes `token` in it; with row_sampling, `sampling` also brings the slot's size."""
+        precedes `token` in it; with row_sampling, `sampling` also brings the slot's size.
+        With banned sequences on, the slot's count and tail start over too; min_new_tokens (sessions built with min_new_tokens or
+        sequence_row_min) becomes the slot's own minimum, without it the minimum stays as it is."""
         if constraint_state is not None:
             if self.con_state is None:
                 raise ValueError("set_slot(constraint_state=...) needs a session built with constraint")
@@ -704,6 +791,8 @@ class DecodeSession:
             self._reset_penalty_slot(b, self._penalty_context(penalty_context_ids))
         if self.ng_hist is not None:
             self._reset_ngram_slot(b, self._ngram_context(ngram_context_ids))
+        if self.seq_table is not None or min_new_tokens is not None:
+            self._reset_sequence_slot(b, min_new_tokens)
         self.ids[b:b + 1].fill_(int(token))
         self.tok_slot[b:b + 1].fill_(int(kv_len))
         self.kv_len[b:b + 1].fill_(int(kv_len) + 1)
@@ -728,7 +817,7 @@ class DecodeSession:
         """Start writing in_ids / pred_ids (and pred_logprobs) at row 0 again (the caller has harvested the previous rows).  The
         penalty history is NOT touched: a request lives across rounds - and neither are the rows' draw counters (row_sampling): a
         request's noise does not repeat from round to round - nor the constraint states: a request is where it is in its automaton -
-        nor the n-gram histories."""
+        nor the n-gram histories, nor the banned-sequence counts, tails and minimums."""
         self.step_idx.zero_()
         self.in_ids[0].copy_(self.ids)      # the tokens the next step is fed (set_slot may have changed them)
         self.steps_done = 0

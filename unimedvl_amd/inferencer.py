@@ -40,6 +40,13 @@ def _drafts(draft_len, draft_ngram, predicted_ids):
     return dict(draft_len=draft_len, draft_ngram=draft_ngram, predicted_ids=predicted_ids) if draft_len else {}
 
 
+def _banned(bad_words_ids, suppress_tokens, begin_suppress_tokens, min_new_tokens):
+    """the text_bad_words_ids / text_suppress_tokens / text_begin_suppress_tokens / text_min_new_tokens keywords of a pipeline as
+    gen_text's keywords"""
+    return dict(bad_words_ids=bad_words_ids, suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
+                min_new_tokens=min_new_tokens)
+
+
 class InterleaveInferencer:
     def __init__(self, model, vae_model, tokenizer, vae_transform, vit_transform, new_token_ids):
         self.model = model
@@ -147,8 +154,11 @@ class InterleaveInferencer:
     def gen_text(self, gen_context, max_length: int = 500, do_sample: bool = True, temperature: float = 1.0, *,
                  repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None,
                  draft_len: int = 0, draft_ngram=(2, 4), predicted_ids=None, no_repeat_ngram_size: int = 0,
+                 bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, min_new_tokens: int = 0,
                  top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         # top_k / top_p / min_p: truncated sampling (Bagel.generate_text), off by default as in the reference
+        # bad_words_ids / suppress_tokens / begin_suppress_tokens / min_new_tokens: HF's keywords of these names (Bagel.generate_text),
+        # off by default; min_new_tokens holds the eos token back, and a bad word that begins in the context is not seen
         # no_repeat_ngram_size: no n-gram of that size is generated twice (Bagel.generate_text), off by default; a context holds no
         # token ids, so the history is the generated tokens only
         # draft_len > 0 (with do_sample=False): speculative greedy decode (Bagel.generate_text) - the same text from fewer passes over
@@ -165,6 +175,8 @@ class InterleaveInferencer:
             ids = self.model.generate_text(past_key_values=cache, max_length=max_length, do_sample=do_sample,
                                            temperature=temperature, end_token_id=self.new_token_ids["eos_token_id"],
                                            top_k=top_k, top_p=top_p, min_p=min_p, no_repeat_ngram_size=no_repeat_ngram_size,
+                                           bad_words_ids=bad_words_ids, suppress_tokens=suppress_tokens,
+                                           begin_suppress_tokens=begin_suppress_tokens, min_new_tokens=min_new_tokens,
                                            repetition_penalty=repetition_penalty,
                                            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
                                            logit_bias=logit_bias, **self._draft_kw(draft_len, draft_ngram, predicted_ids, 1), **gi)
@@ -195,11 +207,13 @@ class InterleaveInferencer:
                              text_repetition_penalty=1.0, text_presence_penalty=0.0, text_frequency_penalty=0.0, text_logit_bias=None,
                              text_draft_len=0, text_draft_ngram=(2, 4), text_predicted_ids=None,
                              text_no_repeat_ngram_size=0,
+                             text_bad_words_ids=None, text_suppress_tokens=None, text_begin_suppress_tokens=None, text_min_new_tokens=0,
                              text_top_k=0, text_top_p=1.0, text_min_p=0.0) -> List[Union[str, Image.Image]]:
         """inferencer.py:552-638.  text_top_k / text_top_p / text_min_p: truncated sampling of the text passes (gen_text);
         text_repetition_penalty / text_presence_penalty / text_frequency_penalty / text_logit_bias: their logit penalties;
         text_draft_len / text_draft_ngram / text_predicted_ids: their speculative greedy decode (do_sample=False)."""
         filters = dict(top_k=text_top_k, top_p=text_top_p, min_p=text_min_p, no_repeat_ngram_size=text_no_repeat_ngram_size,
+                           **_banned(text_bad_words_ids, text_suppress_tokens, text_begin_suppress_tokens, text_min_new_tokens),
                        **_penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias),
                        **_drafts(text_draft_len, text_draft_ngram, text_predicted_ids))
         output_list = []
@@ -259,6 +273,7 @@ class InterleaveInferencer:
             *, text_repetition_penalty: float = 1.0, text_presence_penalty: float = 0.0, text_frequency_penalty: float = 0.0,
             text_logit_bias=None, text_draft_len: int = 0, text_draft_ngram=(2, 4), text_predicted_ids=None,
             text_no_repeat_ngram_size: int = 0,
+            text_bad_words_ids=None, text_suppress_tokens=None, text_begin_suppress_tokens=None, text_min_new_tokens: int = 0,
             text_top_k: int = 0, text_top_p: float = 1.0, text_min_p: float = 0.0
     ) -> List[Union[str, Image.Image]]:
         """VQA, then optionally reconstruct every input image from the answer (inferencer.py:282-362)."""
@@ -277,6 +292,7 @@ class InterleaveInferencer:
         vqa_answer = self.gen_text(vqa_context, do_sample=do_sample, temperature=text_temperature,
                                    max_length=max_think_token_n, top_k=text_top_k, top_p=text_top_p, min_p=text_min_p,
                                    no_repeat_ngram_size=text_no_repeat_ngram_size,
+                           **_banned(text_bad_words_ids, text_suppress_tokens, text_begin_suppress_tokens, text_min_new_tokens),
                                    **_penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias),
                                    **_drafts(text_draft_len, text_draft_ngram, text_predicted_ids))
         output_list.append(vqa_answer)
@@ -346,6 +362,7 @@ class InterleaveInferencer:
             *, text_repetition_penalty: float = 1.0, text_presence_penalty: float = 0.0, text_frequency_penalty: float = 0.0,
             text_logit_bias=None, text_draft_len: int = 0, text_draft_ngram=(2, 4), text_predicted_ids=None,
             text_no_repeat_ngram_size: int = 0,
+            text_bad_words_ids=None, text_suppress_tokens=None, text_begin_suppress_tokens=None, text_min_new_tokens: int = 0,
             text_top_k: int = 0, text_top_p: float = 1.0, text_min_p: float = 0.0
     ) -> List[Union[str, Image.Image]]:
         """inferencer.py:366-463: VQA, then one reconstruction per input image.  (cfg_*_scale / think / image_shapes are
@@ -355,6 +372,7 @@ class InterleaveInferencer:
                                       text_top_k, text_top_p, text_min_p,
                                       dict(_penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias),
                                            no_repeat_ngram_size=text_no_repeat_ngram_size,
+                           **_banned(text_bad_words_ids, text_suppress_tokens, text_begin_suppress_tokens, text_min_new_tokens),
                                            **_drafts(text_draft_len, text_draft_ngram, text_predicted_ids)))
 
     @torch.no_grad()
@@ -367,6 +385,7 @@ class InterleaveInferencer:
             *, text_repetition_penalty: float = 1.0, text_presence_penalty: float = 0.0, text_frequency_penalty: float = 0.0,
             text_logit_bias=None, text_draft_len: int = 0, text_draft_ngram=(2, 4), text_predicted_ids=None,
             text_no_repeat_ngram_size: int = 0,
+            text_bad_words_ids=None, text_suppress_tokens=None, text_begin_suppress_tokens=None, text_min_new_tokens: int = 0,
             text_top_k: int = 0, text_top_p: float = 1.0, text_min_p: float = 0.0
     ) -> List[Union[str, Image.Image]]:
         """inferencer.py:466-549: VQA, then a reconstruction of the FIRST input image only."""
@@ -375,6 +394,7 @@ class InterleaveInferencer:
                                       text_top_k, text_top_p, text_min_p,
                                       dict(_penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias),
                                            no_repeat_ngram_size=text_no_repeat_ngram_size,
+                           **_banned(text_bad_words_ids, text_suppress_tokens, text_begin_suppress_tokens, text_min_new_tokens),
                                            **_drafts(text_draft_len, text_draft_ngram, text_predicted_ids)))
 
     # ------------------------------------------------------------------ batch extension (additive)
@@ -409,7 +429,8 @@ class InterleaveInferencer:
     def gen_text_batch(self, ctx, max_length: int = 500, do_sample: bool = True, temperature: float = 1.0, *,
                        repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None,
                        draft_len: int = 0, draft_ngram=(2, 4), predicted_ids=None,
-                       no_repeat_ngram_size=0, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0) -> List[str]:
+                       no_repeat_ngram_size=0, bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, min_new_tokens=0,
+                       top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0) -> List[str]:
         """gen_text for every sample of a batched context; each answer ends at that sample's own EOS.  draft_len / draft_ngram /
         predicted_ids (one entry per sample): speculative greedy decode as in gen_text, B * (draft_len + 1) <= 64."""
         cache = ctx["past_key_values"]
@@ -420,6 +441,8 @@ class InterleaveInferencer:
             ids = self.model.generate_text(past_key_values=cache, max_length=max_length, do_sample=do_sample,
                                            temperature=temperature, end_token_id=eos, per_sample_eos=True,
                                            top_k=top_k, top_p=top_p, min_p=min_p, no_repeat_ngram_size=no_repeat_ngram_size,
+                                           bad_words_ids=bad_words_ids, suppress_tokens=suppress_tokens,
+                                           begin_suppress_tokens=begin_suppress_tokens, min_new_tokens=min_new_tokens,
                                            repetition_penalty=repetition_penalty,
                                            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
                                            logit_bias=logit_bias,
@@ -472,6 +495,7 @@ class InterleaveInferencer:
                                    *, text_repetition_penalty=1.0, text_presence_penalty=0.0, text_frequency_penalty=0.0,
                                    text_logit_bias=None, text_draft_len=0, text_draft_ngram=(2, 4), text_predicted_ids=None,
                                    text_no_repeat_ngram_size=0,
+                                   text_bad_words_ids=None, text_suppress_tokens=None, text_begin_suppress_tokens=None, text_min_new_tokens=0,
                                    text_top_k=0, text_top_p=1.0, text_min_p=0.0) -> List[List[Union[str, Image.Image]]]:
         """interleave_inference (inferencer.py:552-638) over B samples at once.  Every sample must have the same
         sequence of item types; lengths (prompt tokens, image sizes) may differ.  Returns one output list per sample."""
@@ -509,6 +533,7 @@ class InterleaveInferencer:
         outputs = [[] for _ in range(n)]
         penalties = dict(_penalties(text_repetition_penalty, text_presence_penalty, text_frequency_penalty, text_logit_bias),
                          no_repeat_ngram_size=text_no_repeat_ngram_size,
+                           **_banned(text_bad_words_ids, text_suppress_tokens, text_begin_suppress_tokens, text_min_new_tokens),
                          **_drafts(text_draft_len, text_draft_ngram, text_predicted_ids))
         if understanding_output:
             for o, t in zip(outputs, self.gen_text_batch(ctx, do_sample=do_sample, temperature=text_temperature,

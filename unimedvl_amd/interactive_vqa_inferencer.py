@@ -49,6 +49,14 @@ DEFAULT_CONFIG = {
     # True also counts the n-grams of the prompt's own tokens (HF's generate does), False the generated tokens only
     "no_repeat_ngram_size": 0,
     "no_repeat_ngram_prompt": False,
+    # banned sequences (not reference keys; None / 0 = off): HF's generate keywords of these names (Bagel.chat) - token lists the answer
+    # must not hold, tokens it never / never first emits, and the number of tokens it holds before the end token may come; they also
+    # run with "num_beams" > 1.  "bad_words": strings, each banned as the tokenizer encodes it bare and behind a space
+    "bad_words_ids": None,
+    "bad_words": None,
+    "suppress_tokens": None,
+    "begin_suppress_tokens": None,
+    "min_new_tokens": 0,
     # speculative greedy decode (not reference keys; off = one token per step): Bagel.chat - needs "do_sample": False
     "draft_len": 0,                 # drafted tokens verified per step (prompt lookup over the question and the answer so far)
     "draft_ngram": (2, 4),
@@ -219,6 +227,9 @@ class VQAInferencer:
             extra.update(no_repeat_ngram_size=self.config["no_repeat_ngram_size"])
         if self.config.get("no_repeat_ngram_prompt", False):      # (with "sampling" the size is the SamplingParams')
             extra.update(no_repeat_ngram_prompt=True)
+        for key in ("bad_words_ids", "bad_words", "suppress_tokens", "begin_suppress_tokens", "min_new_tokens"):
+            if self.config.get(key):
+                extra[key] = self.config[key]
         sampler = dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, **penalties)
         sampling = self.config.get("sampling")
         if sampling is not None:    # the config's scalar sampler keys step aside; one given to this call explicitly is passed on (and refused)

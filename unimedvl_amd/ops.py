@@ -668,6 +668,197 @@ def logit_ngram_ban(logits, ids, hist, hist_len, n=0, row_n=None, temperature=0.
     return logits
 
 
+# ----------------------------------------------------------------------------- banned sequences (include/unimedvl_hip.h)
+SEQ_MAX, SEQ_ENTRIES_MAX, SEQ_ROW = _lib.SEQ_MAX, _lib.SEQ_ENTRIES_MAX, _lib.SEQ_ROW
+SEQ_TAIL = SEQ_MAX - 1          # history words a row keeps: what the longest entry compares
+
+
+def _token_list(tokens, what, vocab):
+    """a list of token ids as ints, each in [0, vocab) (vocab None: below 2^31); ValueError otherwise"""
+    if tokens is None:
+        return []
+    if hasattr(tokens, "tolist"):
+        tokens = tokens.tolist()
+    if isinstance(tokens, (str, bytes)) or not isinstance(tokens, (list, tuple)):
+        raise ValueError(f"{what} must be a list of token ids, got {tokens!r}")
+    top = (1 << 31) if vocab is None else int(vocab)
+    out = []
+    for t in tokens:
+        if isinstance(t, bool) or not isinstance(t, (int, float)) or int(t) != t or not 0 <= t < top:
+            raise ValueError(f"{what} holds {t!r}: a token id is an integer in [0, {top})")
+        out.append(int(t))
+    return out
+
+
+def check_sequences(bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, min_new_tokens=0, end_token_id=None,
+                    vocab=None, rows=None):
+    """The banned-sequence keywords checked and normalised: (bad_words_ids as a list of int lists, suppress_tokens and
+    begin_suppress_tokens as int lists, min_new_tokens as an int - or, where a list of one per sample (`rows` of them) was given, as a
+    list of ints -, end_token_id as an int or None).  ValueError: a bad word that is no non-empty list of at most SEQ_MAX token ids,
+    a token outside [0, vocab), a negative or fractional min_new_tokens, min_new_tokens > 0 without end_token_id, more than
+    SEQ_ENTRIES_MAX entries in all."""
+    if bad_words_ids is None:
+        bad_words_ids = []
+    if hasattr(bad_words_ids, "tolist"):
+        bad_words_ids = bad_words_ids.tolist()
+    if isinstance(bad_words_ids, (str, bytes)) or not isinstance(bad_words_ids, (list, tuple)):
+        raise ValueError(f"bad_words_ids must be a list of token id lists, got {bad_words_ids!r}")
+    words = []
+    for w in bad_words_ids:
+        if isinstance(w, (int, float)):
+            raise ValueError(f"bad_words_ids must be a list of token id LISTS, got the entry {w!r}")
+        w = _token_list(w, "a bad_words_ids entry", vocab)
+        if not 1 <= len(w) <= SEQ_MAX:
+            raise ValueError(f"a bad_words_ids entry holds 1 to {SEQ_MAX} tokens, got {len(w)}")
+        words.append(w)
+    suppress = _token_list(suppress_tokens, "suppress_tokens", vocab)
+    begin = _token_list(begin_suppress_tokens, "begin_suppress_tokens", vocab)
+
+    def one_min(n):
+        if isinstance(n, bool) or not isinstance(n, (int, float)) or int(n) != n or not 0 <= n < (1 << 31):
+            raise ValueError(f"min_new_tokens must be a non-negative integer (0 = off), got {n!r}")
+        return int(n)
+    if min_new_tokens is None:
+        min_new_tokens = 0
+    if hasattr(min_new_tokens, "tolist"):
+        min_new_tokens = min_new_tokens.tolist()
+    if isinstance(min_new_tokens, (list, tuple)):
+        mins = [one_min(n) for n in min_new_tokens]
+        if rows is not None and len(mins) != rows:
+            raise ValueError(f"min_new_tokens must be one integer or one per sample ({rows}), got {len(mins)}")
+        any_min = any(mins)
+    else:
+        mins = one_min(min_new_tokens)
+        any_min = mins > 0
+    end = None
+    if end_token_id is not None:
+        end = _token_list([end_token_id], "end_token_id", vocab)[0]
+    if any_min and end is None:
+        raise ValueError("min_new_tokens needs end_token_id: it is the end token that is banned")
+    if len(words) + len(suppress) + len(begin) + bool(any_min) > SEQ_ENTRIES_MAX:
+        raise ValueError(f"at most {SEQ_ENTRIES_MAX} banned sequences and suppressed tokens in all (min_new_tokens takes one), got "
+                         f"{len(words) + len(suppress) + len(begin) + bool(any_min)}")
+    return words, suppress, begin, mins, end
+
+
+def sequence_table(bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, min_new_tokens=0, end_token_id=None,
+                   vocab=None, row_entry=False):
+    """The CSR table of the banned-sequence stage from HF's keywords: (seq_ptr int32 [S + 1], seq_tok int32 [n_tok], seq_until int32
+    [S], max_m) as numpy arrays and an int - entries (w, 0) for every bad word, ([t], 0) for every suppressed token, ([t], 1) for every
+    token suppressed at the beginning and, where min_new_tokens is on for any sample (or row_entry asks for it: rows that come later
+    bring their own minimum), ([end_token_id], SEQ_ROW).  S = 0 (max_m 0) when everything is off."""
+    import numpy as np
+    words, suppress, begin, mins, end = check_sequences(bad_words_ids, suppress_tokens, begin_suppress_tokens, min_new_tokens, end_token_id,
+                                                        vocab)
+    entries = [(w, 0) for w in words] + [([t], 0) for t in suppress] + [([t], 1) for t in begin]
+    if (any(mins) if isinstance(mins, list) else mins > 0) or (row_entry and end is not None):
+        entries.append(([end], SEQ_ROW))
+    ptr, tok = [0], []
+    for w, _ in entries:
+        tok += w
+        ptr.append(len(tok))
+    return (np.array(ptr, dtype=np.int32), np.array(tok, dtype=np.int32), np.array([u for _, u in entries], dtype=np.int32),
+            max([len(w) for w, _ in entries] + [0]))
+
+
+def encode_bad_words(tokenizer, bad_words):
+    """bad_words (strings) as bad_words_ids: every string encoded bare and with a leading space - inside a sentence a word follows a
+    space, and most tokenizers give that another first token - both kept, duplicates and empty encodings dropped.  ValueError for
+    what is no list of non-empty strings."""
+    if bad_words is None:
+        return []
+    if isinstance(bad_words, str) or not isinstance(bad_words, (list, tuple)):
+        raise ValueError(f"bad_words must be a list of strings, got {bad_words!r}")
+    out = []
+    for w in bad_words:
+        if not isinstance(w, str) or not w.strip():
+            raise ValueError(f"bad_words holds {w!r}: a bad word is a non-empty string")
+        for text in (w, " " + w):
+            ids = [int(t) for t in tokenizer.encode(text)]
+            if ids and ids not in out:
+                out.append(ids)
+    return out
+
+
+class SequenceTable:
+    """A banned-sequence table in device memory (umv_sequence_ban_args: seq_ptr / seq_tok / seq_until, S, n_tok, max_m).  The entry
+    lengths and offsets are validated here, on the host: the kernel entry cannot read them."""
+
+    def __init__(self, seq_ptr, seq_tok, seq_until, device, max_m=None):
+        import numpy as np
+        ptr, tok, until = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (seq_ptr, seq_tok, seq_until))
+        S = until.size
+        if not 0 <= S <= SEQ_ENTRIES_MAX or ptr.size != S + 1 or ptr[0] != 0 or ptr[-1] != tok.size:
+            raise ValueError(f"a sequence table holds 0 to {SEQ_ENTRIES_MAX} entries, seq_ptr [S + 1] from 0 to len(seq_tok)")
+        lens = np.diff(ptr)
+        if S and (lens.min() < 1 or lens.max() > SEQ_MAX):
+            raise ValueError(f"a sequence table entry holds 1 to {SEQ_MAX} tokens")
+        if S and (until.min() < SEQ_ROW or until.max() >= 1 << 31 or np.abs(tok).max() >= 1 << 31):
+            raise ValueError("a sequence table's until words are SEQ_ROW, 0 or a positive int32; its tokens are int32")
+        longest = int(lens.max()) if S else 0
+        if max_m is not None and int(max_m) != longest:
+            raise ValueError(f"max_m = {max_m}, the longest entry holds {longest} tokens")
+        self.S, self.n_tok, self.max_m = S, int(tok.size), longest
+        self.ptr = torch.tensor(ptr.tolist(), dtype=torch.int32).to(device)
+        self.tok = torch.tensor(tok.tolist() or [0], dtype=torch.int32).to(device)
+        self.until = torch.tensor(until.tolist() or [0], dtype=torch.int32).to(device)
+
+
+def logit_sequence_ban(logits, ids, table, tail=None, count=None, row_min=None, beam=None, temperature=0.0, seed=0, step=None,
+                       argmax_partial=None, lse_partial=None, sample_rows=None):
+    """umv_logit_sequence_ban_bf16 on bf16 logits [M, V], in place, against `table` (a SequenceTable).  Plain form: record ids (int64
+    [M], the tokens this step is fed) in tail (int32 [M, SEQ_TAIL]) and count (int32 [M]: negative = the row is off), then set to -inf
+    the last token's column of every entry that is active for the row's count - row_min (int32 [M], optional) for SEQ_ROW entries -
+    and whose first tokens are the row's last.  Beam form: beam = (beam_tok, beam_parent, step_idx, start_ids, K), the back-pointers
+    (int32 [max_len, M]) and row counters (int64 [M]) of a beam search and one start token per request (int64 [M / K]); nothing is
+    recorded.  With argmax_partial ([M, n_tiles] int64, lse_partial [M, n_tiles, 2] fp32) the banned columns' tiles are recomputed as
+    the lm_head call with sample=(temperature, seed, step) leaves them; sample_rows: with every row's own temperature and key.  Runs
+    after logit_penalty and logit_ngram_ban and before logit_constrain when those run, before whatever picks."""
+    lib = _lib.load()
+    _req(logits, BF16, "logits")
+    _req(ids, torch.int64, "ids")
+    M, V = _logits_shape("logit_sequence_ban", logits)
+    if not isinstance(table, SequenceTable):
+        raise _lib.UmvError("logit_sequence_ban: table must be an ops.SequenceTable")
+    if not (ids.is_contiguous() and ids.numel() == M):
+        raise _lib.UmvError("logit_sequence_ban: ids must be a contiguous int64 [M] tensor")
+    a = _lib.SequenceBanArgs()
+    a.logits, a.ld, a.ids = logits.data_ptr(), logits.stride(0), ids.data_ptr()
+    if table.S:
+        a.seq_ptr, a.seq_tok, a.seq_until = table.ptr.data_ptr(), table.tok.data_ptr(), table.until.data_ptr()
+    a.M, a.V, a.S, a.n_tok, a.max_m = M, V, table.S, table.n_tok, table.max_m
+    if row_min is not None:
+        _row_outputs("logit_sequence_ban", M, row_min=(row_min, torch.int32))
+        a.row_min = row_min.data_ptr()
+    if beam is None:
+        if tail is None or count is None:
+            raise _lib.UmvError("logit_sequence_ban: the plain form needs tail and count")
+        _req(tail, torch.int32, "tail")
+        _req(count, torch.int32, "count")
+        if not (tail.is_contiguous() and tuple(tail.shape) == (M, SEQ_TAIL) and count.is_contiguous() and count.numel() == M):
+            raise _lib.UmvError(f"logit_sequence_ban: tail [M, {SEQ_TAIL}] and count [M], both contiguous")
+        a.tail, a.count = tail.data_ptr() or None, count.data_ptr() or None
+    else:
+        beam_tok, beam_parent, step_idx, start_ids, K = beam
+        K = int(K)
+        if tail is not None or count is not None:
+            raise _lib.UmvError("logit_sequence_ban: the beam form keeps no tail / count")
+        if not 1 <= K <= _lib.BEAM_K_MAX or M % K:
+            raise _lib.UmvError(f"logit_sequence_ban: K = {K} must be in [1, {_lib.BEAM_K_MAX}] and divide M = {M}")
+        _req(beam_tok, torch.int32, "beam_tok")
+        _req(beam_parent, torch.int32, "beam_parent")
+        if not (beam_tok.is_contiguous() and beam_tok.dim() == 2 and beam_tok.shape[1] == M and beam_tok.shape[0] >= 1
+                and beam_parent.is_contiguous() and beam_parent.shape == beam_tok.shape):
+            raise _lib.UmvError("logit_sequence_ban: beam_tok / beam_parent must be contiguous int32 [max_len, M] tensors of one shape")
+        _row_outputs("logit_sequence_ban", M, step_idx=(step_idx, torch.int64))
+        _row_outputs("logit_sequence_ban", M // K, start_ids=(start_ids, torch.int64))
+        a.beam_tok, a.beam_parent, a.step_idx, a.start_ids = (t.data_ptr() for t in (beam_tok, beam_parent, step_idx, start_ids))
+        a.K, a.max_len = K, beam_tok.shape[0]
+    _fill_tile_keys(a, "logit_sequence_ban", M, temperature, seed, step, argmax_partial, lse_partial, sample_rows)
+    check(lib.umv_logit_sequence_ban_bf16(C.byref(a), _stream()), "umv_logit_sequence_ban_bf16")
+    return logits
+
+
 def cast_pad(x, Kp):
     lib = _lib.load()
     _req(x, torch.float32, "x")

@@ -47,6 +47,7 @@ class _Request:
     sampling: Optional[SamplingParams] = None   # per_request_sampling: the request's own parameters (None = the batcher's)
     constraint: Optional[str] = None            # the name of the automaton (ContinuousBatcher(constraints=)) the request decodes under
     image_keys: Optional[List[Any]] = None      # share_prefixes: the caller's own keys for the images (None = digests of the inputs)
+    min_new_tokens: Optional[int] = None        # the request's own minimum before the end token may come (None = the batcher's)
 
 
 class ContinuousBatcher:
@@ -57,7 +58,8 @@ class ContinuousBatcher:
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, penalize_prompt: bool = False,
                  per_request_sampling: bool = False, seed: Optional[int] = None, top_logprobs: int = 0, constraints=None,
                  no_repeat_ngram_size: int = 0, no_repeat_ngram_prompt: bool = False, share_prefixes: bool = False,
-                 prefix_cache_pages: Optional[int] = None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+                 prefix_cache_pages: Optional[int] = None, bad_words_ids=None, bad_words=None, suppress_tokens=None,
+                 begin_suppress_tokens=None, min_new_tokens: int = 0, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """max_context: the context (prompt + images) the slots are RESERVED for; with growable=True longer requests enlarge
         the cache (up to context_limit tokens of context when given), with growable=False they are refused.
         paged=True: block-table KV (kvcache.PagedCache) instead of slabs - the slots draw 256-token pages from ONE pool of `pool_pages`
@@ -107,7 +109,16 @@ class ContinuousBatcher:
         rounds and run() calls, hold at most prefix_cache_pages distinct pages (default: a quarter of the pool), least recently used
         out first, and give way whenever a call that takes pages would not fit the free list - so sharing never fails a run that the
         same pool serves without it.  drop_prefixes() empties the table.  stats: prefix_hits (adoptions), prefix_tokens_reused,
-        vit_images (images that went through the ViT), prefix_evictions.  False: nothing changes."""
+        vit_images (images that went through the ViT), prefix_evictions.  False: nothing changes.
+        bad_words_ids / suppress_tokens / begin_suppress_tokens (HF's keywords; DecodeSession, include/unimedvl_hip.h banned sequences):
+        ONE batcher-wide table of token sequences no request may emit, tokens it never emits and tokens it does not emit first - the
+        table has a captured size, so a table per request is not offered.  bad_words (strings): each is encoded bare and with a
+        leading space (a word at the start of a text and inside a sentence are different tokens) and both join bad_words_ids
+        (ops.encode_bad_words).  min_new_tokens: the end token is banned for a request's first that many tokens - the batcher-wide
+        default, submit(..., min_new_tokens=) gives a request its own (one word per slot on the device, no re-capture: run() builds
+        its step for what has been submitted).  A slot's count and last tokens start over
+        when a request is admitted to it and live across its rounds.  The history is the fed tokens: a bad word that begins in the
+        prompt is not seen.  All off: nothing changes."""
         if (share_prefixes or prefix_cache_pages is not None) and not paged:
             raise ValueError("share_prefixes / prefix_cache_pages need paged=True: prefixes are shared page by page")
         if prefix_cache_pages is not None and (not share_prefixes or int(prefix_cache_pages) < 0):
@@ -122,6 +133,16 @@ class ContinuousBatcher:
                                               repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                                               frequency_penalty=frequency_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
         self.ngram_prompt = bool(no_repeat_ngram_prompt)
+        # banned sequences: the batcher-wide table (DecodeSession's keywords) and the default minimum; _min_on: does any request (or the
+        # default) hold the end token back?  Then the session carries the end-token entry and one minimum per slot
+        eos_id = int(new_token_ids["eos_token_id"])
+        words, suppress, begin, self.min_new, _ = ops.check_sequences(
+            list(bad_words_ids or []) + ops.encode_bad_words(tokenizer, bad_words), suppress_tokens, begin_suppress_tokens, min_new_tokens,
+            eos_id, vocab=model.cfg.vocab)
+        if isinstance(self.min_new, list):
+            raise ValueError("min_new_tokens is one integer, the batcher-wide default: submit(..., min_new_tokens=) gives a request its own")
+        self.banned = dict(bad_words_ids=words, suppress_tokens=suppress, begin_suppress_tokens=begin) if words or suppress or begin else {}
+        self._min_on = self.min_new > 0
         self._ng_on = self.default_sampling.no_repeat_ngram_size > 0      # does any request (or the default) carry a size?
         self._ng_room = self._ng_hist = 0                                  # context / fed tokens per slot the decode session reserves
         self.top_k, self.top_p, self.min_p = self.default_sampling.top_k, self.default_sampling.top_p, self.default_sampling.min_p
@@ -172,12 +193,18 @@ class ContinuousBatcher:
 
     # ------------------------------------------------------------------ API
     def submit(self, images, prompt: str, max_new_tokens: Optional[int] = None, sampling: Optional[SamplingParams] = None,
-               constraint: Optional[str] = None, image_keys=None) -> int:
+               constraint: Optional[str] = None, image_keys=None, min_new_tokens: Optional[int] = None) -> int:
         """images: one image / a list of images (PIL or [3,H,W] tensors, as the transform accepts) or None.
         image_keys (share_prefixes=True; ignored without): one hashable key per image, used instead of a digest of the image's bytes
         (a study / series id, say).  They are trusted: equal keys must mean equal images.
         sampling (per_request_sampling=True only): the request's own SamplingParams; None = the batcher's defaults.
-        constraint: the name of one of the batcher's automata (ContinuousBatcher(constraints=)); None = free text."""
+        constraint: the name of one of the batcher's automata (ContinuousBatcher(constraints=)); None = free text.
+        min_new_tokens: the end token is banned for the request's first that many tokens; None = the batcher's default."""
+        if min_new_tokens is not None:
+            min_new_tokens = ops.check_sequences(min_new_tokens=min_new_tokens, end_token_id=0)[3]
+            if isinstance(min_new_tokens, list):
+                raise ValueError("submit(min_new_tokens=...) takes one integer")
+            self._min_on = self._min_on or min_new_tokens > 0
         if constraint is not None and constraint not in self.constraint_start:
             raise ValueError(f"submit(constraint={constraint!r}): the batcher holds {sorted(self.constraint_start) or 'no automata'}")
         if sampling is not None:
@@ -199,7 +226,8 @@ class ContinuousBatcher:
             raise ValueError(f"max_new_tokens {budget} exceeds the batcher's reserve of {self.default_new}")
         rid = self._next_id
         self._next_id += 1
-        self.queue.append(_Request(rid, imgs, prompt, budget, sampling=sampling, constraint=constraint, image_keys=image_keys))
+        self.queue.append(_Request(rid, imgs, prompt, budget, sampling=sampling, constraint=constraint, image_keys=image_keys,
+                                   min_new_tokens=min_new_tokens))
         return rid
 
     def drop_prefixes(self):
@@ -240,6 +268,13 @@ class ContinuousBatcher:
 
         def ngram_context_of(b):
             return active[b].prompt_ids if active[b] is not None and self.ngram_prompt else None
+
+        def min_of(b):            # the minimum slot b decodes with: its request's own, else the batcher's; 0 when idle
+            req = active[b]
+            return 0 if req is None else self.min_new if req.min_new_tokens is None else req.min_new_tokens
+
+        def held(b):              # set_slot's keyword for slot b on a session that carries minimums
+            return dict(min_new_tokens=min_of(b)) if sess.seq_row_min is not None else {}
 
         def guided(b):            # set_slot's keyword for slot b: its request's start state, -1 for a free request or an idle slot
             if self.constraint is None:
@@ -283,6 +318,9 @@ class ContinuousBatcher:
             if self._ng_on:
                 sampler.update(ngram_context_ids=[ngram_context_of(b) for b in range(B)], ngram_context_room=self._ng_room,
                                ngram_history=self._ng_hist)
+            sampler.update(self.banned)
+            if self._min_on:
+                sampler.update(min_new_tokens=[min_of(b) for b in range(B)], end_token_id=eos, sequence_row_min=True)
             sn = DecodeSession(m.language_model, cache, start, pos, self.check_every, use_graph=self.use_graph,
                                logprobs=self.want_logprobs, top_logprobs=self.n_top, penalty_context_ids=[context_of(b) for b in range(B)],
                                penalty_context_room=self._pen_room, penalty_history=m.cfg.vocab, constraint=self.constraint,
@@ -292,6 +330,7 @@ class ContinuousBatcher:
                 sn.copy_penalty_history(prev, keep)
                 sn.copy_constraint_states(prev, keep)
                 sn.copy_ngram_history(prev, keep)
+                sn.copy_sequence_state(prev, keep)
             cache.lens = lens_now                       # the session only reads them; this loop owns the bookkeeping
             self._grew = False
             return sn
@@ -370,7 +409,7 @@ class ContinuousBatcher:
                 for b in freed:
                     row = dict(sampling=params_of(b), stream=0, draw=0) if self.per_request else {}
                     sess.set_slot(b, *state[b], penalty_context_ids=context_of(b), ngram_context_ids=ngram_context_of(b), **row,
-                                  **guided(b))
+                                  **guided(b), **held(b))
         return dict(self.results)
 
     # ------------------------------------------------------------------ hooks (MixedBatcher)
