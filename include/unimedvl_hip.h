@@ -958,6 +958,70 @@ typedef struct {
 } umv_sequence_ban_args;
 int umv_logit_sequence_ban_bf16(const umv_sequence_ban_args* a, umv_stream_t stream);
 
+/* ------------------------------------------------------------------ classifier-free guidance for text
+ * HF's guidance_scale (UnbatchedClassifierFreeGuidanceLogitsProcessor) on the stored logits of a decode step: a CONDITIONAL row is
+ * contrasted with an UNCONDITIONAL row of the same step - the same prompt without its images (visual contrastive decoding), or a
+ * negative prompt.  A step has M rows; pair [M] (int32, device memory) names for a guided row c its unconditional row u = pair[c].
+ *   active    row c is ACTIVE when u = pair[c] lies in [0, M), u != c, scale[c] is finite, >= 0 and not exactly 1 (HF returns
+ *             log_softmax there: the same distribution), pair[u] does not itself name a row of [0, M) other than u (a row is never
+ *             both guided and read), and no row c' < c has pair[c'] == u (an unconditional row serves one guided row).  Every other
+ *             row - pair[r] = -1 is the way to say so - is left untouched in every bit, its keys and statistics included.  The
+ *             host refuses tables that break the last two rules; the kernels only hold to them.
+ *   lse       a row r TAKES PART when it is active or the u of an active row.  For such a row lse[r] = M_r + logf(S_r) and
+ *             row_max[r] = M_r, where (M_r, S_r) is the merge, in the order of the step ends (one 256-thread workgroup: thread-strided,
+ *             the wave tree, waves 0..3), of the per-tile (max, sum exp) of the stored bf16 logits l at temperature 0 - the tile
+ *             pairs in the lm_head epilogue's order.  HF runs this processor before the temperature warper, so no temperature is
+ *             applied here.  Where the lm_head call left lse_partial at temperature 0 (or 1: y = l there too) those ARE the tile
+ *             pairs; otherwise the call first writes them to `stats` [M][n_tiles][2].  A -inf column adds 0; a NaN logit makes
+ *             lse[r] NaN; M_r is the maximum over the columns that are not NaN.  Rows that take no part get no write to lse / row_max.
+ *   column    for an active row c with g = scale[c], in fp32, one rounding per operation, nothing contracted to an FMA:
+ *                 if l_c[n] == -inf or l_c[n] < M_c + log_beta[c]:   l'[n] = -inf      (banned stays banned; the plausibility floor)
+ *                 else  cc = l_c[n] - lse[c]
+ *                       if l_u[n] == -inf:                           l'[n] = bf16(cc)  (the unconditional row has no opinion)
+ *                       else  uu = l_u[n] - lse[u];  d = cc - uu;  a = g * d;  a = a + uu;  l'[n] = bf16(a)
+ *             = HF's scale * (cond - uncond) + uncond on log-softmaxes.  A NaN in either operand gives NaN through the arithmetic.
+ *             log_beta[c] = logf(beta), beta in [0, 1) the plausibility floor of contrastive decoding (-inf = off = HF exactly): the
+ *             columns the conditional row itself finds implausible are dropped, the maximum column always survives.  An active row
+ *             whose M_c is -inf is left as it is.  l' REPLACES l in the conditional row; the unconditional row is only read.
+ *   tiles     with argmax_partial (and lse_partial when given) EVERY tile of a rewritten row holds the bits the lm_head epilogue
+ *             leaves for l': greedy keys at temperature 0, the sampling keys of (temperature, seed, *step) otherwise, the statistics
+ *             of pick_value(l', temperature).  Whatever follows - penalties, bans, the step ends, the top-n alternatives - is
+ *             defined on l'.  argmax_partial = NULL: the logits only.
+ *   order     the stage is the FIRST behind the lm_head call: lm_head, guidance, [penalty], [bans], [constrain], step end, ...,
+ *             guidance feed (HF's processor order).
+ * umv_logit_guidance_bf16: up to three launches on one stream - the tile pairs (grid (UMV_CONSTRAIN_CHUNK columns, row), only when
+ * lse_partial cannot serve), the merge (one workgroup per row), the combine (grid (UMV_CONSTRAIN_CHUNK columns, row), one tile per
+ * thread).  No word is shared between workgroups of a launch; a pair's result does not depend on the batch it sits in.  UMV_ERR_ARG:
+ * NULL logits / pair / scale / log_beta / lse / row_max, ld < V, temperature < 0 or not finite, lse_partial without argmax_partial,
+ * n_tiles that is not ceil(V / 16), no lse_partial at temperature 0 or 1 and no stats either, M > 65535.  M = 0 is UMV_OK.  The
+ * per-row arrays live in device memory so that a slot can be re-pointed between replays of a captured step.
+ *
+ * umv_guidance_feed: one launch BEHIND the step end (umv_decode_step_end_argmax / _logprob / _truncated), one thread per row.  For
+ * every row c whose pair word passes the rules above (the scale is not looked at: a pair at scale 1 still decodes in lockstep) the
+ * token the step end left for c becomes u's: ids[u] = ids[c], and with s = step_idx[c] - 1 the step just ended, pred_ids[s][u] =
+ * pred_ids[s][c] (s in [0, max_len)) and in_ids[s + 1][u] = in_ids[s + 1][c] (s + 1 in [0, max_len)).  Nothing else is written:
+ * u's slot, position, length and step counter advanced on their own. */
+typedef struct {
+    uint16_t* logits;          /* [M][V] bf16, row stride ld elements; active rows rewritten in place */
+    int64_t ld;
+    int M, V;
+    const int32_t* pair;       /* [M]: the unconditional row of row c, -1 = not guided */
+    const float* scale;        /* [M]: guidance_scale of row c */
+    const float* log_beta;     /* [M]: logf(guidance_plausibility) of row c, -inf = off */
+    float* lse;                /* [M] out: lse[r] of the rows that take part */
+    float* row_max;            /* [M] out: M_r of the rows that take part */
+    float* stats;              /* [M][n_tiles][2] workspace for the temperature-0 tile pairs; may be NULL where lse_partial serves */
+    float temperature;         /* as given to the lm_head GEMM: 0 = greedy keys and y = l' */
+    uint64_t* argmax_partial;  /* optional [M][n_tiles] */
+    float* lse_partial;        /* optional [M][n_tiles][2], only with argmax_partial */
+    int n_tiles;
+    uint64_t seed;             /* sample_seed / sample_step of the lm_head call (temperature > 0) */
+    const int64_t* step;
+} umv_logit_guidance_args;
+int umv_logit_guidance_bf16(const umv_logit_guidance_args* a, umv_stream_t stream);
+int umv_guidance_feed(const int32_t* pair, int64_t* ids, int64_t* in_ids, int64_t* pred_ids, const int64_t* step_idx, int M, int max_len,
+                      umv_stream_t stream);
+
 
 /* TimestepEmbedder.timestep_embedding (modeling_utils.py:87-109): out[r] = bf16(cat(cos(t[r] * freqs), sin(t[r] * freqs))),
  * out [n, 2*half]; freqs [half] fp32 = exp(-ln(10000) * i / half) from the caller.  The two linears + SiLU of the embedder

@@ -352,6 +352,36 @@ static void bad_arguments() {
     EXPECT_ERR(umv_logit_ngram_ban_bf16(&ng, nullptr));
     ng.rows = nullptr; ng.temperature = 0.f; ng.M = 0;
     EXPECT_OK(umv_logit_ngram_ban_bf16(&ng, nullptr));           // no rows
+    // classifier-free guidance for text
+    EXPECT_ERR(umv_logit_guidance_bf16(nullptr, nullptr));
+    umv_logit_guidance_args lg;
+    std::memset(&lg, 0, sizeof lg);
+    EXPECT_ERR(umv_logit_guidance_bf16(&lg, nullptr));
+    lg.logits = dummy16; lg.ld = 64; lg.M = 1; lg.V = 64; lg.pair = dummyi; lg.scale = dummyf; lg.log_beta = dummyf; lg.lse = dummyf;
+    lg.row_max = dummyf; lg.stats = dummyf; lg.n_tiles = 4;
+    lg.pair = nullptr;                                           // no pair table
+    EXPECT_ERR(umv_logit_guidance_bf16(&lg, nullptr));
+    lg.pair = dummyi; lg.lse = nullptr;                          // no lse words
+    EXPECT_ERR(umv_logit_guidance_bf16(&lg, nullptr));
+    lg.lse = dummyf; lg.temperature = -1.f;                      // negative temperature
+    EXPECT_ERR(umv_logit_guidance_bf16(&lg, nullptr));
+    lg.temperature = 0.f; lg.lse_partial = dummyf;               // lse_partial without argmax_partial
+    EXPECT_ERR(umv_logit_guidance_bf16(&lg, nullptr));
+    lg.lse_partial = nullptr; lg.n_tiles = 3;                    // 64 columns are not 3 tiles
+    EXPECT_ERR(umv_logit_guidance_bf16(&lg, nullptr));
+    lg.n_tiles = 4; lg.ld = 32;                                  // a row stride below V
+    EXPECT_ERR(umv_logit_guidance_bf16(&lg, nullptr));
+    lg.ld = 64; lg.stats = nullptr;                              // no statistics that serve and no workspace
+    EXPECT_ERR(umv_logit_guidance_bf16(&lg, nullptr));
+    lg.stats = dummyf; lg.M = 65536;                             // too many rows
+    EXPECT_ERR(umv_logit_guidance_bf16(&lg, nullptr));
+    lg.M = 0;
+    EXPECT_OK(umv_logit_guidance_bf16(&lg, nullptr));            // no rows
+    EXPECT_ERR(umv_guidance_feed(nullptr, dummyl, dummyl, dummyl, dummyl, 1, 4, nullptr));
+    EXPECT_ERR(umv_guidance_feed(dummyi, nullptr, dummyl, dummyl, dummyl, 1, 4, nullptr));
+    EXPECT_ERR(umv_guidance_feed(dummyi, dummyl, dummyl, dummyl, nullptr, 1, 4, nullptr));
+    EXPECT_ERR(umv_guidance_feed(dummyi, dummyl, dummyl, dummyl, dummyl, -1, 4, nullptr));
+    EXPECT_OK(umv_guidance_feed(dummyi, dummyl, dummyl, dummyl, dummyl, 0, 4, nullptr));          // no rows
     // beam search decode
     alignas(16) static int32_t beam_words[8];
     EXPECT_ERR(umv_beam_candidates(nullptr, 64, 64, dummyf, 4, 1, 4, dummyi, dummyf, dummyi, nullptr));

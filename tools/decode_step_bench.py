@@ -29,6 +29,10 @@ about 5 us) in a kernel trace of a decode run: --trace-arm NAME runs that arm of
   beam          beam search decode (beam.BeamDecodeSession on a PagedCache, random weights and no end token, so every step reorders):
                 b_beam_1x4 / c_beam_8x4 = 1 / 8 requests of 4 beams, each next to the plain greedy session with logprobs at the same
                 row count (a_rows4 / a_rows32) - what the three launches that end a beam step add over the plain step end
+  guidance      classifier-free guidance for text (guidance.GuidedDecodeSession): a_plain_8 plain, 8 rows | b_plain_16 plain, 16 rows (the
+                same rows without the stage; logprobs on, as a guided session always runs with statistics) | c_guided_8x2 8 guided pairs,
+                greedy, scale 3 | d_guided_8x2_sample_top_p_logprobs as c with do_sample, T = 0.7, top_p 0.9 and log-probabilities (d0: that
+                sampler on 16 plain rows).  c - b is the stage's cost, b - a the price of the second row set
   per_request   greedy / do_sample / top_p / all (top_p, logprobs, the three penalties), each as a scalar session and as the session
                 whose per-row table holds the same parameters in every row, and mixed_rows: the four samplers, two rows each
   all           every suite, the model loaded once
@@ -87,7 +91,7 @@ def _session(llm, kw, total):
     from unimedvl_amd.kvcache import NaiveCache
     cfg, dev = llm.cfg, llm.device
     kw = dict(kw(cfg) if callable(kw) else kw)
-    n, beams = kw.pop("rows", B), kw.pop("num_beams", 0)
+    n, beams, guided = kw.pop("rows", B), kw.pop("num_beams", 0), kw.pop("guidance_scale", None)
     start = torch.randint(1000, 100000, (n,), generator=torch.Generator().manual_seed(5))
     pos = torch.full((n,), CONTEXT, dtype=torch.int64)
     if beams:
@@ -101,6 +105,10 @@ def _session(llm, kw, total):
     cache = NaiveCache(cfg.layers)
     cache.ensure(n, CONTEXT + total + 8, cfg.kv_heads, cfg.head_dim, dev)
     cache.lens = [CONTEXT] * n           # a context of zero keys / values: timing depends on lengths only
+    if guided is not None:               # n rows = n / 2 pairs: the conditional rows, then their partners
+        from unimedvl_amd.guidance import GuidedDecodeSession
+        return GuidedDecodeSession(llm, cache, start[:n // 2], pos[:n // 2], total + 1, guided, guidance_positions=pos[n // 2:],
+                                   use_graph=True, **kw)
     with _environ(kw.pop("env", {})):
         return DecodeSession(llm, cache, start, pos, total + 1, use_graph=True, **kw)
 
@@ -401,8 +409,29 @@ BEAM = Suite(arms={"a_rows4": dict(rows=4, logprobs=True), "b_beam_1x4": dict(ro
              over=[("b_beam_1x4", "a_rows4", "over_plain_us"), ("c_beam_8x4", "a_rows32", "over_plain_us")],
              spread=[("a_rows4", "a_rows4_spread_us"), ("a_rows32", "a_rows32_spread_us")], hook=_beam_reorders)
 
+# ---- classifier-free guidance for text
+def _guidance_rows(run, res):
+    for arm, s in run.sessions.items():
+        res[arm].update(rows=s.rows, nsplit=s.nsplit, step_end=s.step_end)
+        if getattr(s, "guid", None) is not None:
+            res[arm].update(stage_launches=2 if s.guid["stats"] is None else 3, lse_finite=bool(torch.isfinite(s.lse).all()))
+    res["stage_cost_us"] = _diff(run.out, "c_guided_8x2", "b_plain_16", "_us")
+    res["second_row_set_us"] = _diff(run.out, "b_plain_16", "a_plain_8", "_us")
+    res["sampled_stage_cost_us"] = _diff(run.out, "d_guided_8x2_sample_top_p_logprobs", "d0_plain_16_sample_top_p_logprobs", "_us")
+
+
+GUIDED_SAMPLED = dict(do_sample=True, temperature=0.7, seed=SEED, top_p=0.9, logprobs=True)
+GUIDANCE = Suite(
+    arms={"a_plain_8": {}, "b_plain_16": dict(rows=16, logprobs=True), "c_guided_8x2": dict(rows=16, guidance_scale=3.0),
+          "d_guided_8x2_sample_top_p_logprobs": dict(GUIDED_SAMPLED, rows=16, guidance_scale=3.0),
+          "d0_plain_16_sample_top_p_logprobs": dict(GUIDED_SAMPLED, rows=16)},
+    over=[("b_plain_16", "a_plain_8", "over_a_us"), ("c_guided_8x2", "b_plain_16", "over_b_us"),
+          ("d_guided_8x2_sample_top_p_logprobs", "d0_plain_16_sample_top_p_logprobs", "over_d0_us")],
+    spread=[("a_plain_8", "a_spread_us"), ("b_plain_16", "b_spread_us"), ("d0_plain_16_sample_top_p_logprobs", "d0_spread_us")],
+    hook=_guidance_rows)
+
 SUITES = {"penalties": PENALTIES, "constraint": CONSTRAINT, "ngram": NGRAM_SUITE, "sequences": SEQUENCES, "logprobs": LOGPROBS, "top_logprobs": TOP_LOGPROBS, "truncated": TRUNCATED,
-          "per_request": PER_REQUEST, "beam": BEAM}
+          "per_request": PER_REQUEST, "beam": BEAM, "guidance": GUIDANCE}
 
 
 def main():

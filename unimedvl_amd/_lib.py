@@ -152,6 +152,15 @@ class SequenceBanArgs(C.Structure):
     ]
 
 
+class LogitGuidanceArgs(C.Structure):
+    """umv_logit_guidance_args: classifier-free guidance for text on the stored logits of a step (umv_logit_guidance_bf16)"""
+    _fields_ = [
+        ("logits", C.c_void_p), ("ld", C.c_int64), ("M", C.c_int), ("V", C.c_int), ("pair", C.c_void_p), ("scale", C.c_void_p),
+        ("log_beta", C.c_void_p), ("lse", C.c_void_p), ("row_max", C.c_void_p), ("stats", C.c_void_p), ("temperature", C.c_float),
+        ("argmax_partial", C.c_void_p), ("lse_partial", C.c_void_p), ("n_tiles", C.c_int), ("seed", C.c_uint64), ("step", C.c_void_p),
+    ]
+
+
 # beam search decode: the most beams a request can have, and the full-page table entries one request's step end can carry (K * n_own)
 BEAM_K_MAX, BEAM_TABLE_ENTRIES = 10, 1024
 # umv_logit_penalty_args.count words: bits 0..29 the count, then "in the context set" and "in the row's visit list"
@@ -252,6 +261,8 @@ _SIGS = {
                                       C.c_void_p, C.c_void_p]),
     "umv_beam_step_end": (C.c_int, [C.POINTER(BeamStepArgs), C.c_void_p]),
     "umv_logit_sequence_ban_bf16": (C.c_int, [C.POINTER(SequenceBanArgs), C.c_void_p]),
+    "umv_logit_guidance_bf16": (C.c_int, [C.POINTER(LogitGuidanceArgs), C.c_void_p]),
+    "umv_guidance_feed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "umv_beam_kv_copy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "umv_timestep_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "umv_cfg_renorm_euler": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,

@@ -336,7 +336,9 @@ class Bagel(BagelPrep):
                       predicted_ids=None, sampling=None, top_logprobs: int = 0, constraint=None, constraint_states=None,
                       no_repeat_ngram_size=0, ngram_context_ids=None, num_beams: int = 1, length_penalty: float = 1.0,
                       early_stopping: bool = False, num_return_sequences: int = 1, bad_words_ids=None, suppress_tokens=None,
-                      begin_suppress_tokens=None, min_new_tokens=0, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+                      begin_suppress_tokens=None, min_new_tokens=0, guidance_scale: float = 1.0, guidance_past_key_values=None,
+                      guidance_query_position_ids=None, guidance_plausibility: float = 0.0,
+                      top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """Greedy decode (bagel.py:1236-1317).  Returns [steps, B] int64 whose row 0 holds the
         start tokens.  Like the reference, the batch stops when SAMPLE 0 emits end_token_id
         (bagel.py:1313); per_sample_eos=True is the batched extension (stops when every sample
@@ -392,7 +394,32 @@ class Bagel(BagelPrep):
         include/unimedvl_hip.h, banned sequences) behind the n-gram ban and before the constraint mask; ids, logits, logprobs and
         top_logprobs are those of the banned logits.  The history is the start token and what is fed after it: a bad word that begins
         in the prompt is not seen.  They are the one logit stage that also runs with num_beams > 1 (every beam by its own tokens).
-        With draft_len > 0 they raise."""
+        With draft_len > 0 they raise.
+        guidance_scale = g != 1 (finite, >= 0): classifier-free guidance for text - HF's guidance_scale
+        (UnbatchedClassifierFreeGuidanceLogitsProcessor), in the captured step (guidance.GuidedDecodeSession; include/unimedvl_hip.h,
+        classifier-free guidance for text).  guidance_past_key_values: the unconditional contexts, a second NaiveCache with the same
+        number of segments (the prompt without its images - visual contrastive decoding -, or a negative prompt);
+        guidance_query_position_ids: their rope positions.  Every step the logits become g * (log_softmax(cond) -
+        log_softmax(uncond)) + log_softmax(uncond), before temperature and truncation; ids, logprobs and top_logprobs are those of the
+        guided distribution.  guidance_plausibility = beta in [0, 1): tokens whose conditional probability is below beta times the
+        most likely token's are dropped first (the adaptive plausibility constraint of contrastive decoding; 0 = HF exactly).  The
+        call decodes on a merged copy of the two caches (2 B <= 64 rows) and leaves BOTH as they were - nothing is committed.  Slab
+        caches only.  Combines with do_sample / temperature, top_k / top_p / min_p, return_logprobs, top_logprobs and
+        per_sample_eos; everything else (ops.GUIDANCE_EXCLUDES: beams, drafts, sampling=, penalties, logit_bias, bans, constraint,
+        return_logits) raises ValueError before any launch.  1.0 = off: today's call."""
+        guidance_scale, guidance_plausibility = ops.check_guidance(
+            guidance_scale, guidance_plausibility, num_beams=num_beams, draft_len=draft_len, sampling=sampling,
+            repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+            logit_bias=logit_bias, no_repeat_ngram_size=no_repeat_ngram_size, constraint=constraint, bad_words_ids=bad_words_ids,
+            suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens, min_new_tokens=min_new_tokens,
+            return_logits=return_logits)
+        if guidance_scale != 1.0:
+            return self._generate_text_guided(past_key_values, key_values_lens, packed_start_tokens, packed_query_position_ids, max_length,
+                                              end_token_id, per_sample_eos, return_logprobs, top_logprobs, guidance_scale,
+                                              guidance_past_key_values, guidance_query_position_ids, guidance_plausibility,
+                                              dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p))
+        if guidance_past_key_values is not None or guidance_query_position_ids is not None:
+            raise ValueError("guidance_past_key_values / guidance_query_position_ids go with guidance_scale != 1")
         num_beams = ops.check_beams(num_beams, self.cfg.vocab, len(past_key_values.lens))
         words, suppress, begin, mins, _ = ops.check_sequences(bad_words_ids, suppress_tokens, begin_suppress_tokens, min_new_tokens,
                                                               end_token_id if min_new_tokens else None, vocab=self.cfg.vocab,
@@ -509,6 +536,67 @@ class Bagel(BagelPrep):
             res += (TopLogprobs(sess.pred_top_ids[:rows].clone(), sess.pred_top_logprobs[:rows].clone(), sess.pred_rank[:rows].clone()),)
         return res if len(res) > 1 else out
 
+    def _generate_text_guided(self, cache, key_values_lens, start_tokens, positions, max_length, end_token_id, per_sample_eos,
+                              return_logprobs, top_logprobs, scale, uncond, uncond_positions, beta, sampler):
+        """generate_text with guidance_scale != 1: one guided decode on a merged copy of `cache` and `uncond`, the conditional rows as
+        the usual matrix.  Both caches are read, never written."""
+        from .guidance import GuidedDecodeSession
+        if hasattr(cache, "ensure_tokens") or hasattr(uncond, "ensure_tokens"):
+            raise ValueError("guidance_scale != 1 decodes on slab caches (NaiveCache): a PagedCache is not available")
+        if uncond is None or uncond_positions is None:
+            raise ValueError("guidance_scale != 1 needs guidance_past_key_values and guidance_query_position_ids (the unconditional contexts)")
+        B = len(cache.lens)
+        if len(uncond.lens) != B or uncond.slabs is None or cache.slabs is None:
+            raise ValueError(f"guidance_past_key_values must hold the same number of prefilled segments as past_key_values ({B}), "
+                             f"got {len(uncond.lens)}")
+        if 2 * B > 64:
+            raise ValueError(f"guidance_scale != 1 decodes two rows per sample: at most 32 samples, got {B}")
+        if key_values_lens is not None and [int(v) for v in key_values_lens.tolist()] != list(cache.lens):
+            raise ValueError("key_values_lens disagree with the cache")
+        sampler["top_k"], sampler["top_p"], sampler["min_p"] = ops.check_truncation(sampler["top_k"], sampler["top_p"], sampler["min_p"])
+        top_logprobs = ops.check_top_logprobs(top_logprobs, self.cfg.vocab)
+        return_logprobs = bool(return_logprobs) or top_logprobs > 0
+        if max_length <= 0:
+            out = torch.zeros((0, B), dtype=torch.int64, device=self.device)
+            res = (out,)
+            if return_logprobs:
+                res += (torch.zeros((0, B), dtype=torch.float32, device=self.device),)
+            if top_logprobs:
+                shape = (0, B, top_logprobs)
+                res += (TopLogprobs(torch.zeros(shape, dtype=torch.int32, device=self.device),
+                                    torch.zeros(shape, dtype=torch.float32, device=self.device),
+                                    torch.zeros(shape[:2], dtype=torch.int32, device=self.device)),)
+            return res if len(res) > 1 else out
+        seed = self._sampling_seed() if sampler["do_sample"] else 0
+        cfg = self.cfg
+        both = NaiveCache.merged([cache, uncond], [B, B], max_length + 1, cfg.kv_heads, cfg.head_dim, self.device)
+        sess = GuidedDecodeSession(self.language_model, both, start_tokens, positions, max_length, scale,
+                                   guidance_positions=uncond_positions, guidance_plausibility=beta, use_graph=self.decode_use_graph,
+                                   seed=seed, logprobs=return_logprobs, top_logprobs=top_logprobs, **sampler)
+        steps, stop = 0, None
+        while steps < max_length:
+            n = min(self.eos_check_every, max_length - steps)
+            sess.step(n)
+            steps += n
+            if end_token_id is not None:
+                hit = sess.tokens(steps).cpu() == end_token_id
+                if per_sample_eos:
+                    if bool(hit.any(0).all()):
+                        stop = int(hit.float().argmax(0).max()) + 1
+                        break
+                elif bool(hit[:, 0].any()):
+                    stop = int(hit[:, 0].float().argmax()) + 1
+                    break
+        rows = stop if stop is not None else steps
+        self.last_guidance_lse = sess.lse.clone()
+        out = sess.fed(rows).clone()
+        res = (out,)
+        if return_logprobs:
+            res += (sess.token_logprobs(rows).clone(),)
+        if top_logprobs:
+            res += (TopLogprobs(*(t.clone() for t in sess.top(rows))),)
+        return res if len(res) > 1 else out
+
     def _generate_text_beams(self, cache, start_tokens, positions, max_length, end_token_id, return_logprobs, num_beams, length_penalty,
                              early_stopping, num_return_sequences, banned=None):
         """generate_text with num_beams > 1: one beam search on a fork of `cache`, the best hypotheses as the usual matrix.  banned:
@@ -584,6 +672,7 @@ class Bagel(BagelPrep):
              no_repeat_ngram_size: int = 0, no_repeat_ngram_prompt: bool = False,
              num_beams: int = 1, length_penalty: float = 1.0, early_stopping: bool = False, num_return_sequences: int = 1,
              bad_words_ids=None, bad_words=None, suppress_tokens=None, begin_suppress_tokens=None, min_new_tokens: int = 0,
+             guidance_scale: float = 1.0, negative_prompt=None, guidance_plausibility: float = 0.0,
              top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """ViT-only VQA convenience path (bagel.py:1321-1392).  return_logprobs=True: returns (answer, token_ids, token_logprobs) -
         the generated tokens behind the answer (the end token excluded) and the log-probability of each (generate_text).
@@ -613,7 +702,21 @@ class Bagel(BagelPrep):
         the answer must not hold, and the number of tokens it holds at the least before the end token may come; also with num_beams.
         bad_words (strings): each is encoded twice, bare and with a leading space - a word inside a sentence and one at its start
         are different tokens - and both token sequences join bad_words_ids (ops.encode_bad_words); a phrase is banned as the
-        tokenizer splits it, other spellings (capitals, no space after a bracket) are other phrases."""
+        tokenizer splits it, other spellings (capitals, no space after a bracket) are other phrases.
+        guidance_scale != 1: classifier-free guidance for text (generate_text) - the answer is decoded from the contrast of the
+        context above with an UNCONDITIONAL context prefilled into a cache of its own: negative_prompt (a string) as its only text,
+        or - negative_prompt=None - the same prompt with its images dropped (visual contrastive decoding: what the answer owes to
+        the language prior alone is pushed down).  Without images and without a negative_prompt there is nothing to contrast:
+        ValueError.  guidance_plausibility: generate_text's.  It excludes what generate_text excludes, and `choices`."""
+        guidance_scale, guidance_plausibility = ops.check_guidance(
+            guidance_scale, guidance_plausibility, num_beams=num_beams, draft_len=draft_len, sampling=sampling, choices=choices,
+            repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+            logit_bias=logit_bias, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids, bad_words=bad_words,
+            suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens, min_new_tokens=min_new_tokens)
+        if guidance_scale == 1.0 and negative_prompt is not None:
+            raise ValueError("negative_prompt goes with guidance_scale != 1")
+        if guidance_scale != 1.0 and negative_prompt is None and not images:
+            raise ValueError("guidance_scale != 1 without images and without a negative_prompt: there is nothing to contrast")
         if num_beams > 1:
             from .beam import check_beam_keywords
             check_beam_keywords(ops.check_beams(num_beams, self.cfg.vocab, 1), choices=choices, draft_len=draft_len, sampling=sampling)
@@ -650,7 +753,15 @@ class Bagel(BagelPrep):
                          predicted_ids=None if predicted_ids is None else [list(predicted_ids)])
         cache = self.forward_cache_update_text(cache, **gi)
         gi = self.prepare_start_tokens(newlens, new_rope, new_token_ids)
-        ids = self.generate_text(past_key_values=cache, max_length=max_length, do_sample=do_sample,
+        guided = {}
+        if guidance_scale != 1.0:            # the unconditional context: a text-only prefill into a cache of its own
+            ulens, urope = [0], [0]
+            ugi, ulens, urope = self.prepare_prompts(ulens, urope, [prompt if negative_prompt is None else negative_prompt], tokenizer,
+                                                     new_token_ids)
+            ucache = self.forward_cache_update_text(NaiveCache(self.cfg.layers), **ugi)
+            guided = dict(guidance_scale=guidance_scale, guidance_plausibility=guidance_plausibility, guidance_past_key_values=ucache,
+                          guidance_query_position_ids=self.prepare_start_tokens(ulens, urope, new_token_ids)["packed_query_position_ids"])
+        ids = self.generate_text(past_key_values=cache, max_length=max_length, do_sample=do_sample, **guided,
                                  temperature=temperature, end_token_id=new_token_ids["eos_token_id"],
                                  return_logprobs=return_logprobs, top_k=top_k, top_p=top_p, min_p=min_p, top_logprobs=top_logprobs,
                                  repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,

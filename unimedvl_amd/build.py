@@ -26,6 +26,8 @@ LAST_SOURCES = ["beam.hip"]
 TAIL_SOURCES = ["lm_head_stats.hip"]
 # ... and behind that one, again for the same reason: the banned-sequence stage of the decode step
 END_SOURCES = ["logit_sequence.hip"]
+# ... and behind that one, once more: the text-guidance stage of the decode step
+GUIDANCE_SOURCES = ["logit_guidance.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-Wno-unused-result", "-fgpu-rdc" if False else "-fno-gpu-rdc"]
 # per-file additions.  attention_prefill: MFMA destinations stay in VGPRs (the compiler's default parks the 64 O accumulators in
@@ -66,7 +68,7 @@ def build(force=False, verbose=True):
             hh.update(open(os.path.join(CSRC, f), "rb").read())
     headers = hh.hexdigest()
     obj_stamps = {}
-    for lib, sources, extra, suffix in ((LIB, SOURCES + LAST_SOURCES + TAIL_SOURCES + END_SOURCES, [], ""),):
+    for lib, sources, extra, suffix in ((LIB, SOURCES + LAST_SOURCES + TAIL_SOURCES + END_SOURCES + GUIDANCE_SOURCES, [], ""),):
         objs = []
         for src in sources:
             sp = os.path.join(CSRC, src)

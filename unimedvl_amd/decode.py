@@ -352,6 +352,7 @@ class DecodeSession:
         self._init_ngram(no_repeat_ngram_size, ngram_context_ids, ngram_context_room, ngram_history)
         self._init_sequences(bad_words_ids, suppress_tokens, begin_suppress_tokens, min_new_tokens, end_token_id, sequence_row_min)
         self._init_constraint(constraint, constraint_states)
+        self.guid = None                            # the tables of classifier-free guidance (guidance.GuidedDecodeSession sets them)
         self.steps_done = 0
         self.graph = None
         if use_graph:
@@ -661,6 +662,11 @@ class DecodeSession:
                 ops.gemm(self.act, down_w, out=self.seq, residual=self.seq)
                 ops.rmsnorm(self.seq, nxt, cfg.rms_eps, out=dst)
         ops.gemm(self.hn, w.lm_head, out=self.logits, **self.lm_head_kw)
+        if self.guid is not None:
+            # first behind the lm_head call (HF's processor order): every guided row becomes the contrast of its log-softmax with its
+            # unconditional row's, its tiles' keys and statistics rewritten with what the lm_head call got
+            ops.logit_guidance(self.logits, temperature=self.step_kw["temperature"], seed=self.seed, step=self.step_idx,
+                               argmax_partial=self.amax_part, lse_partial=self.lse_part, **self.guid)
         if self.pen is not None:
             # record the token this step was fed, patch the logits of the seen / biased columns, recompute the tiles they sit in - with
             # the (temperature, seed, step) the lm_head call got, so whichever step end follows reads the adjusted distribution
@@ -681,6 +687,8 @@ class DecodeSession:
             # again with what the lm_head call got: the step end picks from, and normalises over, the allowed set
             ops.logit_constrain(self.logits, self.con_dev, self.con_state, **self.step_kw)
         self._step_end()
+        if self.guid is not None:
+            ops.guidance_feed(self.guid["pair"], self.ids, self.in_ids, self.pred_ids, self.step_idx)   # the pick of a guided row is its partner's too
         if self.top_logprobs:
             # the n best columns of the (adjusted) logits and the rank of the token just fed, with the statistics merged as the step end did
             ops.decode_top_logprobs(self.logits, self.lse_part, self.ids, self.step_idx, self.pred_top_ids, self.pred_top_logprobs,

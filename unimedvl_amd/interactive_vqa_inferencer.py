@@ -76,6 +76,13 @@ DEFAULT_CONFIG = {
     "length_penalty": 1.0,
     "early_stopping": False,
     "num_return_sequences": 1,
+    # classifier-free guidance for text (not reference keys; "guidance_scale": 1.0 = off): HF's guidance_scale (Bagel.chat) - the answer
+    # is decoded from the contrast of the question about the image with the same question WITHOUT the image ("negative_prompt": None;
+    # visual contrastive decoding) or with a negative prompt (a string); "guidance_plausibility" (beta in [0, 1), 0 = off) first drops
+    # the tokens the conditional distribution itself finds implausible.  Not with beams, drafts, "sampling", penalties, bans or choices
+    "guidance_scale": 1.0,
+    "negative_prompt": None,
+    "guidance_plausibility": 0.0,
 }
 
 # codes/data/default.yaml vlm_sft.image_transform_args (read by eval/vlm/utils.py:486-502)
@@ -230,6 +237,8 @@ class VQAInferencer:
         for key in ("bad_words_ids", "bad_words", "suppress_tokens", "begin_suppress_tokens", "min_new_tokens"):
             if self.config.get(key):
                 extra[key] = self.config[key]
+        if float(self.config.get("guidance_scale", 1.0)) != 1.0 or self.config.get("negative_prompt") is not None:
+            extra.update({k: self.config.get(k, DEFAULT_CONFIG[k]) for k in ("guidance_scale", "negative_prompt", "guidance_plausibility")})
         sampler = dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, **penalties)
         sampling = self.config.get("sampling")
         if sampling is not None:    # the config's scalar sampler keys step aside; one given to this call explicitly is passed on (and refused)

@@ -625,6 +625,124 @@ def constraint_advance(automaton, state, ids):
     return state
 
 
+# what guidance_scale != 1 does not combine with, by keyword -> the value that leaves it off (beam.BEAM_EXCLUDES' precedent: refused by
+# ValueError before any launch).  The later logit stages would work on the conditional row as they do today: DESIGN.md section 7.
+GUIDANCE_EXCLUDES = dict(num_beams=1, draft_len=0, sampling=None, row_sampling=None, repetition_penalty=1.0, presence_penalty=0.0,
+                         frequency_penalty=0.0, logit_bias=None, no_repeat_ngram_size=0, constraint=None, choices=None,
+                         bad_words_ids=None, bad_words=None, suppress_tokens=None, begin_suppress_tokens=None, min_new_tokens=0,
+                         forced_ids=None, return_logits=False)
+
+
+def check_guidance(guidance_scale=1.0, guidance_plausibility=0.0, **kw):
+    """Classifier-free guidance for text (include/unimedvl_hip.h) as (scale, beta) floats: guidance_scale finite and >= 0 (1.0 = off),
+    guidance_plausibility in [0, 1) (0.0 = off), ValueError otherwise.  kw: the other keywords of the call by name (names outside
+    GUIDANCE_EXCLUDES are a TypeError); with guidance on (scale != 1) one that is not off is a ValueError, and so is the unfused
+    step end (UMV_DECODE_FUSED_ARGMAX=0).  guidance_plausibility without guidance is a ValueError too: there is nothing to floor."""
+    import math
+    import os
+    unknown = set(kw) - set(GUIDANCE_EXCLUDES)
+    if unknown:
+        raise TypeError(f"check_guidance: unknown keywords {sorted(unknown)}")
+    for v, name in ((guidance_scale, "guidance_scale"), (guidance_plausibility, "guidance_plausibility")):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"{name} must be a number, got {v!r}")
+    g, beta = float(guidance_scale), float(guidance_plausibility)
+    if not (math.isfinite(g) and g >= 0.0):
+        raise ValueError(f"guidance_scale must be finite and >= 0 (1.0 = off), got {guidance_scale!r}")
+    if not 0.0 <= beta < 1.0:
+        raise ValueError(f"guidance_plausibility must be in [0, 1) (0.0 = off), got {guidance_plausibility!r}")
+    if g == 1.0:
+        if beta != 0.0:
+            raise ValueError("guidance_plausibility floors the guided distribution: it needs guidance_scale != 1")
+        return g, beta
+
+    def off(value, neutral):
+        if isinstance(value, (list, tuple)):
+            return all(off(v, neutral) for v in value) if neutral is not None or len(value) == 0 else False
+        if neutral is None:
+            return value is None or value == {}
+        return value == neutral
+    on = [k for k, v in kw.items() if not off(v, GUIDANCE_EXCLUDES[k])]
+    if on:
+        raise ValueError(f"guidance_scale != 1 (classifier-free guidance for text) excludes {', '.join(sorted(on))}")
+    if os.environ.get("UMV_DECODE_FUSED_ARGMAX", "1") in ("0", ""):
+        raise ValueError("guidance_scale != 1 rides on the fused step end: UMV_DECODE_FUSED_ARGMAX must not be 0")
+    return g, beta
+
+
+def check_guidance_pairs(pair, rows=None):
+    """A pair table (include/unimedvl_hip.h: pair[c] = the unconditional row of guided row c, -1 = not guided) as a list of ints,
+    ValueError for what the kernels would only ignore: an entry outside [-1, rows), a row paired with itself, a row that is both
+    guided and someone's unconditional row, two guided rows that share one."""
+    pair = [int(v) for v in (pair.tolist() if hasattr(pair, "tolist") else pair)]
+    rows = len(pair) if rows is None else int(rows)
+    if len(pair) != rows:
+        raise ValueError(f"the pair table must hold one entry per row ({rows}), got {len(pair)}")
+    taken = {}
+    for c, u in enumerate(pair):
+        if u == -1:
+            continue
+        if not 0 <= u < rows or u == c:
+            raise ValueError(f"pair[{c}] = {u}: an unconditional row is another row of [0, {rows}), or -1")
+        if u in taken:
+            raise ValueError(f"rows {taken[u]} and {c} share the unconditional row {u}")
+        taken[u] = c
+    for c, u in enumerate(pair):
+        if u != -1 and c in taken:
+            raise ValueError(f"row {c} is guided (by row {u}) and the unconditional row of row {taken[c]}")
+    return pair
+
+
+def logit_guidance(logits, pair, scale, log_beta, lse, row_max, stats=None, temperature=0.0, seed=0, step=None, argmax_partial=None,
+                   lse_partial=None):
+    """umv_logit_guidance_bf16 on bf16 logits [M, V], in place: every active row c (pair int32 [M], scale / log_beta fp32 [M]) becomes
+    bf16(scale[c] * (log_softmax(l_c) - log_softmax(l_u)) + log_softmax(l_u)), u = pair[c], under the plausibility floor log_beta[c]
+    (include/unimedvl_hip.h, classifier-free guidance for text); lse / row_max (fp32 [M]) receive the log-sum-exp and the maximum of
+    the rows that took part.  With argmax_partial ([M, n_tiles] int64, lse_partial [M, n_tiles, 2] fp32) every tile of a rewritten row
+    is recomputed as the lm_head call with sample=(temperature, seed, step) leaves it.  stats (fp32 [M, n_tiles, 2]): the workspace of
+    the temperature-0 tile pairs, needed unless lse_partial holds them (temperature 0 or 1).  Runs first behind the lm_head call."""
+    lib = _lib.load()
+    _req(logits, BF16, "logits")
+    M, V = _logits_shape("logit_guidance", logits)
+    _req(pair, torch.int32, "pair")
+    if not (pair.is_contiguous() and pair.numel() == M):
+        raise _lib.UmvError("logit_guidance: pair must be a contiguous int32 [M] tensor")
+    _row_outputs("logit_guidance", M, scale=(scale, torch.float32), log_beta=(log_beta, torch.float32), lse=(lse, torch.float32),
+                 row_max=(row_max, torch.float32))
+    n_tiles = (V + 15) // 16
+    if stats is not None:
+        _req(stats, torch.float32, "stats")
+        if not (stats.is_contiguous() and tuple(stats.shape) == (M, n_tiles, 2)):
+            raise _lib.UmvError(f"logit_guidance: stats must be a contiguous fp32 [{M}, {n_tiles}, 2] tensor")
+    a = _lib.LogitGuidanceArgs()
+    a.logits, a.ld, a.M, a.V = logits.data_ptr(), logits.stride(0), M, V
+    a.pair, a.scale, a.log_beta, a.lse, a.row_max = (None if t is None else t.data_ptr() for t in (pair, scale, log_beta, lse, row_max))
+    a.stats = None if stats is None else stats.data_ptr()
+    a.temperature, a.seed, a.step = float(temperature), _seed64(seed), None if step is None else step.data_ptr()
+    a.argmax_partial, a.lse_partial, _, _ = _tile_keys("logit_guidance", M, argmax_partial, lse_partial, None, n_tiles=n_tiles)
+    a.n_tiles = n_tiles
+    check(lib.umv_logit_guidance_bf16(C.byref(a), _stream()), "umv_logit_guidance_bf16")
+    return logits
+
+
+def guidance_feed(pair, ids, in_ids, pred_ids, step_idx):
+    """umv_guidance_feed, behind the step end: for every guided row c (pair int32 [M]) the token the step end left for c - ids[c] and
+    this step's pred_ids / in_ids words ([max_len, M] int64) - is copied into the words of its unconditional row pair[c]; step_idx
+    (int64 [M]) as the step end left it."""
+    lib = _lib.load()
+    _req(pair, torch.int32, "pair")
+    for t, name in ((ids, "ids"), (in_ids, "in_ids"), (pred_ids, "pred_ids"), (step_idx, "step_idx")):
+        _req(t, torch.int64, name)
+    M = pair.numel()
+    if not (pair.is_contiguous() and ids.is_contiguous() and ids.numel() == M and step_idx.is_contiguous() and step_idx.numel() >= M
+            and in_ids.is_contiguous() and pred_ids.is_contiguous() and in_ids.dim() == 2 and in_ids.shape == pred_ids.shape
+            and in_ids.shape[1] == M):
+        raise _lib.UmvError("guidance_feed: pair int32 [M], ids / step_idx int64 [M], in_ids / pred_ids int64 [max_len, M], all contiguous")
+    check(lib.umv_guidance_feed(_p(pair), _p(ids), _p(in_ids), _p(pred_ids), _p(step_idx), M, in_ids.shape[0], _stream()),
+          "umv_guidance_feed")
+    return ids
+
+
 NGRAM_MAX = _lib.NGRAM_MAX      # the largest no_repeat_ngram_size (UMV_NGRAM_MAX)
 
 
